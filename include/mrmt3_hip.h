@@ -426,6 +426,11 @@ int mrmt3_decoder_graph_captured(const mrmt3_decoder* dec);
  * which the last row finished (or -1); [0] counts prefix positions too, [2] counts token steps only.  Copies 3 int32 asynchronously to caller-owned PINNED host
  * memory; the caller synchronises the stream before reading. */
 int mrmt3_decoder_poll(mrmt3_decoder* dec, int32_t* state_out_pinned, void* stream);
+/* Stream-ordered device-to-device copy of the logits of the last step run: rows [0, rows) of the
+ * f32 [B][vocab] lm_head output (prefix steps included), into caller-owned device memory dst.
+ * Errors (MRMT3_ERR_INVALID_ARG) if rows is not in 1..B, before mrmt3_decoder_begin, or inside a
+ * stream capture.  For tests: call after mrmt3_decoder_run(dec, 1, stream). */
+int mrmt3_decoder_logits(mrmt3_decoder* dec, float* dst, int rows, void* stream);
 
 /* ---- gradient exchange (data parallel, one process per GPU): RCCL communicators as opaque handles ----------------
  * Replaces what the reference gets from Lightning's `ddp_find_unused_parameters_false` strategy (config/config.yaml:45,

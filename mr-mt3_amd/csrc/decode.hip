@@ -382,6 +382,17 @@ __device__ __forceinline__ void dec_step_close(int* state, int B, int p, int t, 
   state[ST_T] = p + 1;
 }
 
+// torch.argmax order: NaN above every number (the first NaN wins), then the larger value, then the lower index;
+// index -1 = no candidate.  For finite logits this is the first maximum.
+__device__ __forceinline__ bool argmax_beats(float v, int i, float bv, int bi) {
+  if (i < 0) return false;
+  if (bi < 0) return true;
+  const bool vn = v != v, bn = bv != bv;
+  if (vn != bn) return vn;
+  if (!vn && v != bv) return v > bv;
+  return i < bi;
+}
+
 __global__ __launch_bounds__(512) void dec_argmax(const float* __restrict__ logits, int V, int B, int64_t* __restrict__ tokens,
                                                   int tok_ld, const float* __restrict__ embed, const float* __restrict__ pos,
                                                   float* __restrict__ x, int* __restrict__ state, int eos, int pad,
@@ -413,21 +424,24 @@ __global__ __launch_bounds__(512) void dec_argmax(const float* __restrict__ logi
 #pragma unroll
     for (int c = 0; c < DMODEL / 64; ++c) pv[c] = pr[c * 64 + lane];
     float best = -INFINITY;
-    int idx = 0x7fffffff;
+    int idx = -1;                        // -1: this lane has seen no logit yet (lanes >= V when V < 64)
     for (int c0 = lane; c0 < V; c0 += 512) {
       float lv[8];
 #pragma unroll
       for (int u = 0; u < 8; ++u) lv[u] = (c0 + 64 * u < V) ? logits[(size_t)b * V + c0 + 64 * u] : -INFINITY;
 #pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (lv[u] > best) { best = lv[u]; idx = c0 + 64 * u; }   // ascending c per lane: first maximum wins
+      for (int u = 0; u < 8; ++u) {
+        const int c = c0 + 64 * u;
+        if (argmax_beats(lv[u], c < V ? c : -1, best, idx)) { best = lv[u]; idx = c; }   // ascending c per lane
+      }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
       const float ov = __shfl_xor(best, off, 64);
       const int oi = __shfl_xor(idx, off, 64);
-      if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
+      if (argmax_beats(ov, oi, best, idx)) { best = ov; idx = oi; }
     }
+    // lane 0 always holds index 0 (V > 0), so idx is in [0, V) here whatever the logits hold
     const int nxt = was_done ? pad : idx;
     const float* er = embed + (size_t)nxt * DMODEL;
 #pragma unroll
@@ -675,6 +689,18 @@ extern "C" int mrmt3_decoder_run(mrmt3_decoder* D, int n_steps, void* stream) {
 }
 
 extern "C" int mrmt3_decoder_graph_captured(const mrmt3_decoder* D) { return D ? D->captured : 0; }
+
+extern "C" int mrmt3_decoder_logits(mrmt3_decoder* D, float* dst, int rows, void* stream) {
+  MR_CHECK_ARG(D && dst, "decoder_logits: null pointer");
+  MR_CHECK_ARG(D->tokens, "decoder_logits: call decoder_begin first");
+  MR_CHECK_ARG(rows > 0 && rows <= D->B, "decoder_logits: need 0 < rows <= batch (%d), got %d", D->B, rows);
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  MR_CHECK_HIP(hipStreamIsCapturing((hipStream_t)stream, &st));
+  MR_CHECK_ARG(st == hipStreamCaptureStatusNone, "decoder_logits: not allowed inside a stream capture");
+  MR_CHECK_HIP(hipMemcpyAsync(dst, D->logits, sizeof(float) * (size_t)rows * D->V, hipMemcpyDeviceToDevice,
+                              (hipStream_t)stream));
+  return MRMT3_OK;
+}
 
 extern "C" int mrmt3_decoder_poll(mrmt3_decoder* D, int32_t* state_out_pinned, void* stream) {
   MR_CHECK_ARG(D && state_out_pinned, "decoder_poll: null pointer");

@@ -97,21 +97,28 @@ class Decoder:
             lib.gemm_nt(enc_cat, eng.W(f"decoder.{i}.ckv"), out=out[i])
         return out
 
-    def run(self, ckv, B, Lc, max_steps, poll_every=64, prefix=None):
+    def run(self, ckv, B, Lc, max_steps, poll_every=64, prefix=None, logits_out=None):
         """Decode up to max_steps tokens for B rows; returns (tokens [B, max_len+1] view, steps run,
-        finish_step or -1).  `prefix` [B, n, d] f32: memory rows fed as decoder positions 0..n-1."""
+        finish_step or -1).  `prefix` [B, n, d] f32: memory rows fed as decoder positions 0..n-1.
+        `logits_out` [>= n + max_steps, B, V] f32 device tensor (tests): row s receives step s's lm_head
+        output, prefix steps included; steps are then replayed one at a time, each followed by a copy."""
         cfg = self.model.cfg
         l = lib.load()
         w = self._weights()
         self._ckv = ckv
+        if logits_out is not None:
+            n_pre = 0 if prefix is None else prefix.shape[1]
+            assert logits_out.dtype == torch.float32 and logits_out.is_contiguous() and logits_out.is_cuda
+            assert logits_out.dim() == 3 and logits_out.shape[0] >= n_pre + max_steps and \
+                tuple(logits_out.shape[1:]) == (B, cfg["vocab_size"]), tuple(logits_out.shape)
         cur = torch.cuda.current_stream()
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
-            out = self._run_on_stream(l, w, ckv, B, Lc, max_steps, poll_every, cfg, prefix)
+            out = self._run_on_stream(l, w, ckv, B, Lc, max_steps, poll_every, cfg, prefix, logits_out)
         cur.wait_stream(self.stream)
         return out
 
-    def _run_on_stream(self, l, w, ckv, B, Lc, max_steps, poll_every, cfg, prefix=None):
+    def _run_on_stream(self, l, w, ckv, B, Lc, max_steps, poll_every, cfg, prefix=None, logits_out=None):
         lib._check(l.mrmt3_decoder_begin(self.h, C.byref(w), lib._p(ckv), B, Lc, lib._p(self.tokens),
                                          cfg["decoder_start_token_id"], cfg["eos_token_id"], cfg["pad_token_id"],
                                          lib._stream()), "decoder_begin")
@@ -125,7 +132,13 @@ class Decoder:
         done, fin = 0, -1
         while done < max_steps:
             n = min(poll_every, max_steps - done)
-            lib._check(l.mrmt3_decoder_run(self.h, n, lib._stream()), "decoder_run")
+            if logits_out is None:
+                lib._check(l.mrmt3_decoder_run(self.h, n, lib._stream()), "decoder_run")
+            else:
+                for i in range(n):
+                    lib._check(l.mrmt3_decoder_run(self.h, 1, lib._stream()), "decoder_run")
+                    lib._check(l.mrmt3_decoder_logits(self.h, lib._p(logits_out[done + i]), B, lib._stream()),
+                               "decoder_logits")
             done += n
             lib._check(l.mrmt3_decoder_poll(self.h, C.c_void_p(self.pinned.data_ptr()), lib._stream()), "decoder_poll")
             torch.cuda.current_stream().synchronize()

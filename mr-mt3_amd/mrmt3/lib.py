@@ -85,6 +85,7 @@ _SIGS = {
     "mrmt3_decoder_graph_captured": (ci, [vp]),
     "mrmt3_decoder_run": (ci, [vp, ci, vp]),
     "mrmt3_decoder_poll": (ci, [vp, vp, vp]),
+    "mrmt3_decoder_logits": (ci, [vp, vp, ci, vp]),
     "mrmt3_comm_unique_id": (ci, [vp]),
     "mrmt3_comm_create": (ci, [vp, ci, ci, C.POINTER(vp)]),
     "mrmt3_comm_destroy": (ci, [vp]),
@@ -141,7 +142,7 @@ def load():
     return lib
 
 
-MIN_VERSION = 110
+MIN_VERSION = 111
 COUNTER_NAMES = ("gemm_nt_tile", "gemm_nt8", "gemm_nt_geglu", "tn_group", "tn8", "tn_tile", "attn_fwd", "attn_bwd",
                  "attn_bwd_onepass", "attn_f32", "tn_f32", "gemm_nt_splitk", "gemm_nt_addnorm", "gemm_nt_normbwd",
                  "gemm_nt_geglubwd")

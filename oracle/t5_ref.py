@@ -34,9 +34,14 @@ import torch.nn.functional as F
 # building blocks (HF 4.18 T5 arithmetic)
 # ----------------------------------------------------------------------------------------------
 
+def _f32(t):
+    """The reference's `.float()` / `.to(torch.float32)` upcasts; float64 stays float64 (the fp64 references)."""
+    return t if t.dtype == torch.float64 else t.float()
+
+
 def rms_norm(x, w, eps=1e-6):
     """T5LayerNorm: x * rsqrt(mean(x^2) + eps) * w; no mean subtraction, no bias."""
-    var = x.float().pow(2).mean(-1, keepdim=True)
+    var = _f32(x).pow(2).mean(-1, keepdim=True)
     return w * (x * torch.rsqrt(var + eps))
 
 
@@ -57,7 +62,7 @@ def attention(xq, xkv, wq, wk, wv, wo, n_heads, mask=None):
     scores = q @ k.transpose(2, 3)
     if mask is not None:
         scores = scores + mask
-    p = F.softmax(scores.float(), dim=-1).type_as(scores)
+    p = F.softmax(_f32(scores), dim=-1).type_as(scores)
     o = (p @ v).transpose(1, 2).reshape(B, Lq, n_heads * dk)
     return o @ wo.t()
 
@@ -261,6 +266,56 @@ def generate_t5_cached(sd, cfg, mel, max_length=1024):
         if unfinished.max() == 0:
             break
     return ids
+
+
+def decode_step_logits(sd, cfg, ids, ck, cv, prefix=None, rnd=None):
+    """Teacher-forced restatement of one KV-cached greedy decode (`generate_t5_cached`'s structure) in float64: the
+    lm_head logits of EVERY step, [B, n_prefix + T, V], for decoder inputs `ids` [B, T] (start token first) after
+    `prefix` [B, n_prefix, d] memory rows (`generate_2`; fed without the positional term, which is added here).
+
+    The cross-attention K/V are inputs, `ck` / `cv` [layers][B, Lc, inner] (the decoder's own buffer in the GPU tests,
+    so only the token loop is under test).  The inputs of every step are known, so the self-attention cache is filled
+    for all positions at once and a causal mask stands for "keys 0..t"; the arithmetic per step is the cached
+    decode's.  `rnd` (None = exact) is applied where csrc/decode.hip rounds to the weights' dtype: the normed
+    activation entering every projection (lm_head included), the attention output before an O projection, the gated
+    GELU output before wo, and each self-attention K/V cache entry.  The residual stream, q, the scores and the
+    softmax stay unrounded."""
+    H, eps, L = cfg["num_heads"], cfg["layer_norm_epsilon"], cfg["num_decoder_layers"]
+    r = (lambda t: t) if rnd is None else rnd
+    W = lambda k: sd[k].double()
+    blk = lambda i, n: W(f"decoder.block.{i}.layer.{n}.weight")
+    x = W("decoder_embed_tokens.weight")[ids]
+    if prefix is not None:
+        x = torch.cat([prefix.double(), x], dim=1)
+    B, T, d = x.shape
+    x = x + pos_emb(T, d)[0].double()
+    dk = blk(0, "0.SelfAttention.q").shape[0] // H
+    heads = lambda t: t.reshape(B, -1, H, dk).transpose(1, 2)
+    causal = torch.ones(T, T, dtype=torch.bool).tril()
+
+    def attend(q, k, v, wo, mask):
+        # batch chunks keep the [chunk, H, T, Lk] score block near 16 M elements
+        step = max(1, (1 << 24) // (H * T * k.shape[2]))
+        o = []
+        for b0 in range(0, B, step):
+            sc = q[b0:b0 + step] @ k[b0:b0 + step].transpose(2, 3)
+            if mask is not None:
+                sc = sc.masked_fill(~mask, float("-inf"))
+            o.append(F.softmax(sc, dim=-1) @ v[b0:b0 + step])
+        return r(torch.cat(o).transpose(1, 2).reshape(B, T, H * dk)) @ wo.t()
+
+    for i in range(L):
+        xn = r(rms_norm(x, blk(i, "0.layer_norm"), eps))
+        k, v = r(xn @ blk(i, "0.SelfAttention.k").t()), r(xn @ blk(i, "0.SelfAttention.v").t())
+        x = x + attend(heads(xn @ blk(i, "0.SelfAttention.q").t()), heads(k), heads(v), blk(i, "0.SelfAttention.o"),
+                       causal)
+        xn = r(rms_norm(x, blk(i, "1.layer_norm"), eps))
+        x = x + attend(heads(xn @ blk(i, "1.EncDecAttention.q").t()), heads(ck[i].double()), heads(cv[i].double()),
+                       blk(i, "1.EncDecAttention.o"), None)
+        xn = r(rms_norm(x, blk(i, "2.layer_norm"), eps))
+        g = r(gelu_new(xn @ blk(i, "2.DenseReluDense.wi_0").t()) * (xn @ blk(i, "2.DenseReluDense.wi_1").t()))
+        x = x + g @ blk(i, "2.DenseReluDense.wo").t()
+    return r(rms_norm(x, W("decoder.final_layer_norm.weight"), eps)) @ W("lm_head.weight").t()
 
 
 def generate_segmem_v2(sd, cfg, mel, max_length=1024, segmem_length=64, with_prev=True,

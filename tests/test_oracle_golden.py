@@ -165,3 +165,36 @@ def test_oracle_at_the_long_context_shape_matches_what_the_reference_recorded():
         assert abs(g.double().norm().item() - norm) <= 1e-4 * norm + 1e-9, n
         np.testing.assert_allclose(g.reshape(-1)[torch.from_numpy(si)].numpy(), sv, rtol=0,
                                    atol=2e-4 * float(np.abs(sv).max()) + 1e-9, err_msg=n)
+
+
+@pytest.mark.parametrize("with_prefix", [False, True])
+def test_decode_step_logits_equals_the_full_decoder_in_fp64(with_prefix):
+    """`decode_step_logits` (teacher-forced, cross K/V given, the reference the GPU decode tests score against) with
+    rnd=None is the plain decoder: every step's logits equal `decode_logits` + lm_head over the same ids (memory rows
+    through `dec_embeds`, as `generate_segmem_v1` feeds them), in float64."""
+    torch.set_num_threads(8)
+    cfg, L = T5_SMALL, T5_SMALL["num_decoder_layers"]
+    sd = {k: v.double() for k, v in _sd("t5").items()}
+    B, Le, T, n_pre = 2, 24, 11, 5
+    enc = t5_ref.encode(sd, cfg, torch.from_numpy(synth_mel(B, frames=Le, seed=3)).double())
+    ids = torch.from_numpy(synth_labels(B, T, seed=4)).clamp(min=0)
+    ids[:, 0] = cfg["decoder_start_token_id"]
+    ck = [enc @ sd[f"decoder.block.{i}.layer.1.EncDecAttention.k.weight"].t() for i in range(L)]
+    cv = [enc @ sd[f"decoder.block.{i}.layer.1.EncDecAttention.v.weight"].t() for i in range(L)]
+    prefix = torch.randn(B, n_pre, cfg["d_model"], generator=torch.Generator().manual_seed(5), dtype=torch.float64)
+    with torch.no_grad():
+        if with_prefix:
+            emb = torch.cat([prefix, sd["decoder_embed_tokens.weight"][ids]], dim=1)
+            ref = t5_ref.decode_logits(sd, cfg, None, enc, dec_embeds=emb) @ sd["lm_head.weight"].t()
+            got = t5_ref.decode_step_logits(sd, cfg, ids, ck, cv, prefix=prefix)
+        else:
+            ref = t5_ref.decode_logits(sd, cfg, ids, enc) @ sd["lm_head.weight"].t()
+            got = t5_ref.decode_step_logits(sd, cfg, ids, ck, cv)
+        rounded = t5_ref.decode_step_logits(sd, cfg, ids, ck, cv, prefix=prefix if with_prefix else None,
+                                            rnd=lambda t: t.float().bfloat16().double())
+    assert got.dtype == torch.float64 and got.shape == (B, T + (n_pre if with_prefix else 0), cfg["vocab_size"])
+    err = (got - ref).abs().max().item()
+    assert err < 1e-12 * ref.abs().max().item(), err
+    # the rounding hook is applied: bf16 rounding moves the logits by far more than fp64 noise, but not wildly
+    gap = (rounded - got).abs().max().item()
+    assert 1e-4 < gap < 0.5, gap
