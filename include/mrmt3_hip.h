@@ -70,7 +70,9 @@ void mrmt3_host_free(void* p);
 #define MRMT3_CNT_GEMM_NT_ADDNORM 12  /* projection + residual add + RMS norm in one launch (mrmt3_gemm_nt_addnorm) */
 #define MRMT3_CNT_GEMM_NT_NORMBWD 13  /* data gradient + norm backward in one launch (mrmt3_gemm_nt_normbwd) */
 #define MRMT3_CNT_GEMM_NT_GEGLUBWD 14 /* wo data gradient + gated-GELU backward in one launch (mrmt3_gemm_nt_geglubwd) */
-#define MRMT3_CNT_N 15
+#define MRMT3_CNT_ATTN_FWD_VARLEN 15  /* packed-row attention forward, bf16 or exact f32 (mrmt3_attn_fwd_varlen) */
+#define MRMT3_CNT_ATTN_BWD_VARLEN 16  /* packed-row attention backward, bf16 or exact f32 (mrmt3_attn_bwd_varlen) */
+#define MRMT3_CNT_N 17
 int mrmt3_dispatch_counts(unsigned long long* out, int n, int reset);
 
 /* Dispatch / tuning switches ("knobs").  Which kernel or tile shape a call takes is a function of its arguments; a few
@@ -254,6 +256,43 @@ int mrmt3_attn_bwd_bias(const void* q, int ldq, const void* k, int ldk, const vo
                         long long bias_batch_stride, void* dq, int lddq, void* dk, int lddk, void* dv, int lddv,
                         float* dbias, int B, int H, int Lq, int Lk, int causal, int dtype, float p_drop, uint64_t seed,
                         const int32_t* step_dev, uint32_t stream_id, void* stream);
+
+/* ---- packed decoder rows (training on padded target rows; csrc/pack.hip) ---------------------------------------------
+ * A target row padded with -100 (tasks/mt3_net.py:32-35 ignores those positions) only needs its prefix
+ * len_b = 1 + (last t with labels[b][t] != -100), 0 for a row without one: under the causal decoder the positions after it
+ * reach no scored position and get no gradient.  The prefixes are laid end to end: row b owns packed rows
+ * [row_off[b], row_off[b+1]), T = row_off[B], padded to a capacity Tcap >= T (rows [T, Tcap) are the tail).
+ * mrmt3_pack_lengths: len [B] int32 from labels [B][L] int64.
+ * mrmt3_pack_plan (three small launches, all on the device): len [B], row_off [B+1] int32, per packed row tok_row / tok_pos
+ * [Tcap] int32 (row -1 in the tail), dec_ids [Tcap] int64 (the shifted decoder input: start_id at t = 0, labels[b][t-1]
+ * otherwise, -100 -> pad_id; pad_id in the tail), targets [Tcap] int64 (labels of the prefix, -100 in the tail), and the
+ * tile list of the varlen attention kernels, tiles [2 + 2 * mrmt3_pack_tile_entries(B, Tcap)] int32.  *err (int32) = 1 when
+ * T > Tcap: the offsets are then clamped to Tcap and nothing is written past Tcap. */
+int mrmt3_pack_tile_entries(int B, int Tcap);
+int mrmt3_pack_lengths(const int64_t* labels, int B, int L, int32_t* len, void* stream);
+int mrmt3_pack_plan(const int64_t* labels, int B, int L, int Tcap, int start_id, int pad_id, int32_t* len, int32_t* row_off,
+                    int32_t* tok_row, int32_t* tok_pos, int64_t* dec_ids, int64_t* targets, int32_t* tiles, int32_t* err,
+                    void* stream);
+/* embedding of packed rows: x[i] = table[ids[i]] + pos[tok_pos[i]] (ids already shifted: the dec_ids of the plan), dropout
+ * keyed by the packed row.  Its backward is mrmt3_embed_bwd with shift = 0 on the same ids. */
+int mrmt3_embed_fwd_packed(const int64_t* ids, const int32_t* tok_pos, const float* table, const float* pos, float* x,
+                           int rows, int d, int vocab, float p_drop, uint64_t seed, const int32_t* step_dev,
+                           uint32_t stream_id, void* stream);
+/* attention over packed rows: q / o / dq [Tcap][*] packed by row_off; k / v / dk / dv packed the same way (Lk = 0:
+ * self-attention, causal or not) or dense [B][Lk][*] (Lk > 0: cross-attention).  lse / delta [H][Tcap] f32.  Lmax = the
+ * longest possible row (the dense L).  For every row the results are those of mrmt3_attn_fwd / mrmt3_attn_bwd (bf16) or the
+ * exact-f32 kernels on that row's prefix, with the same dropout masks (keyed by the in-row coordinates (b, h, t_q, t_k));
+ * the tail rows of o, o_lo, lse, dq, delta (and dk, dv for self-attention) are written as zeros.  The grid depends on
+ * (B, H, Tcap) alone. */
+int mrmt3_attn_fwd_varlen(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo,
+                          void* o_lo, float* lse, const int32_t* row_off, const int32_t* tiles, int B, int H, int Tcap,
+                          int Lmax, int Lk, int causal, int dtype, float p_drop, uint64_t seed, const int32_t* step_dev,
+                          uint32_t stream_id, void* stream);
+int mrmt3_attn_bwd_varlen(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* o, int ldo,
+                          const void* o_lo, const void* d_o, int lddo, const float* lse, float* delta, void* dq, int lddq,
+                          void* dk, int lddk, void* dv, int lddv, const int32_t* row_off, const int32_t* tiles, int B, int H,
+                          int Tcap, int Lmax, int Lk, int causal, int dtype, float p_drop, uint64_t seed,
+                          const int32_t* step_dev, uint32_t stream_id, void* stream);
 
 /* ---- K7: gated-GELU (HF T5DenseGatedGeluDense: gelu_new(h0) * h1, then dropout) ----------------
  * h [rows][2*dff] = [wi_0 x | wi_1 x] -> g [rows][dff] */

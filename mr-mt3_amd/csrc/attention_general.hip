@@ -237,6 +237,225 @@ int check_bias(const float* bias, long long bias_bs, int H, int Lq, int Lk, cons
   return MRMT3_OK;
 }
 
+
+// ---- variable-length (packed) rows: the kernels above, one packed query (key) row per workgroup.  Row b of the batch owns
+// packed rows [row_off[b], row_off[b+1]); the keys of self-attention are packed the same way, those of cross-attention are
+// dense [B][Lk].  Same arithmetic in the same order as the dense kernels on the row's prefix, so the results are theirs bit for
+// bit; the tail rows [T, Tcap) come back as zeros.  Statistics are [H][Tcap].
+struct VarP {
+  const int* row_off;
+  int Tcap, self;      // self = 1: keys packed like the queries (Lk = the row's length)
+};
+
+__device__ __forceinline__ int varlen_row_of(const int* row_off, int B, int i) {     // the b with row_off[b] <= i < row_off[b+1]
+  int lo = 0, hi = B - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (row_off[mid] <= i) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void attn_gen_fwd_varlen_kernel(GenP P, VarP V) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];  // scores[Lk] | q[64] | red[8] | part[4][64]
+  const int H = P.H, i = blockIdx.x, h = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (i >= V.row_off[P.B]) {                                  // tail row
+    if (tid < 64) st1((T*)P.out + (size_t)i * P.ldo + h * HD + tid, 0.f);
+    if (tid == 0 && P.lse) P.lse[(size_t)h * V.Tcap + i] = 0.f;
+    return;
+  }
+  const int b = varlen_row_of(V.row_off, P.B, i);
+  const int o0 = V.row_off[b], qi = i - o0;
+  const int Lk = V.self ? V.row_off[b + 1] - o0 : P.Lk;
+  float* sc = sm;
+  float* qs = sm + (V.self ? P.Lq : Lk);
+  float* red = qs + 64;
+  float* part = red + 8;
+  const T* qp = (const T*)P.q + (size_t)i * P.ldq + h * HD;
+  const size_t kr0 = V.self ? (size_t)o0 : (size_t)b * Lk;
+  const T* kb = (const T*)P.k + kr0 * P.ldk + h * HD;
+  const T* vb = (const T*)P.v + kr0 * P.ldv + h * HD;
+  if (tid < 64) qs[tid] = ld1(qp + tid);
+  __syncthreads();
+  const int nk = P.causal ? min(Lk, qi + 1) : Lk;
+  float mx = -INFINITY;
+  for (int key = tid; key < nk; key += 256) {
+    const T* kr = kb + (size_t)key * P.ldk;
+    float s = 0.f;
+#pragma unroll
+    for (int d = 0; d < HD; d += 4) {
+      const f32x4 kv = ld4(kr + d);
+      s = fmaf(qs[d], kv.x, s); s = fmaf(qs[d + 1], kv.y, s); s = fmaf(qs[d + 2], kv.z, s); s = fmaf(qs[d + 3], kv.w, s);
+    }
+    sc[key] = s;
+    mx = fmaxf(mx, s);
+  }
+  mx = wave_max(mx);
+  if (lane == 0) red[wave] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  float se = 0.f;
+  for (int key = tid; key < nk; key += 256) {
+    const float p = expf(sc[key] - mx);
+    sc[key] = p;
+    se += p;
+  }
+  se = wave_sum(se);
+  if (lane == 0) red[4 + wave] = se;
+  __syncthreads();
+  se = red[4] + red[5] + red[6] + red[7];
+  if (P.drop.thresh8) {
+    const unsigned drop_bh = P.drop.seed + step_salt(P.drop.step) + (unsigned)(b * H + h) * DROP_CB;
+    for (int key = tid; key < nk; key += 256)
+      if (!attn_keep1(P.drop, drop_bh, qi, key)) sc[key] = 0.f;
+    __syncthreads();
+  }
+  float acc = 0.f;
+  for (int key = wave; key < nk; key += 4) acc = fmaf(sc[key], ld1(vb + (size_t)key * P.ldv + lane), acc);
+  part[wave * 64 + lane] = acc;
+  __syncthreads();
+  if (tid < 64) {
+    const float r = (part[tid] + part[64 + tid]) + (part[128 + tid] + part[192 + tid]);
+    st1((T*)P.out + (size_t)i * P.ldo + h * HD + tid, r * P.drop.scale / se);
+  }
+  if (tid == 0 && P.lse) P.lse[(size_t)h * V.Tcap + i] = mx + logf(se);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void attn_gen_bwd_dq_varlen_kernel(GenP P, VarP V) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];  // ds[Lk] | q[64] | dO[64] | red[4] | part[4][64]
+  const int H = P.H, i = blockIdx.x, h = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (i >= V.row_off[P.B]) {
+    if (tid < 64) st1((T*)P.dq + (size_t)i * P.lddq + h * HD + tid, 0.f);
+    if (tid == 0) P.delta[(size_t)h * V.Tcap + i] = 0.f;
+    return;
+  }
+  const int b = varlen_row_of(V.row_off, P.B, i);
+  const int o0 = V.row_off[b], qi = i - o0;
+  const int Lk = V.self ? V.row_off[b + 1] - o0 : P.Lk;
+  float* sc = sm;
+  float* qs = sm + (V.self ? P.Lq : Lk);
+  float* dos = qs + 64;
+  float* red = dos + 64;
+  float* part = red + 4;
+  const int nk = P.causal ? min(Lk, qi + 1) : Lk;
+  const size_t qrow = (size_t)i;
+  const size_t kr0 = V.self ? (size_t)o0 : (size_t)b * Lk;
+  const T* kb = (const T*)P.k + kr0 * P.ldk + h * HD;
+  const T* vb = (const T*)P.v + kr0 * P.ldv + h * HD;
+  const unsigned drop_bh = P.drop.seed + step_salt(P.drop.step) + (unsigned)(b * H + h) * DROP_CB;
+  if (tid < 64) {
+    qs[tid] = ld1((const T*)P.q + qrow * P.ldq + h * HD + tid);
+    dos[tid] = ld1((const T*)P.d_o + qrow * P.lddo + h * HD + tid);
+  }
+  __syncthreads();
+  float dl = 0.f;
+  if (wave == 0) {
+    dl = wave_sum(dos[lane] * ld1((const T*)P.o + qrow * P.ldo + h * HD + lane));
+    if (lane == 0) { red[0] = dl; P.delta[(size_t)h * V.Tcap + i] = dl; }
+  }
+  __syncthreads();
+  dl = red[0];
+  const float l = P.lse[(size_t)h * V.Tcap + i];
+  for (int key = tid; key < nk; key += 256) {
+    const T* kr = kb + (size_t)key * P.ldk;
+    const T* vr = vb + (size_t)key * P.ldv;
+    float sv = 0.f, dp = 0.f;
+#pragma unroll
+    for (int d = 0; d < HD; d += 4) {
+      const f32x4 kv = ld4(kr + d), vv = ld4(vr + d);
+      sv = fmaf(qs[d], kv.x, sv); sv = fmaf(qs[d + 1], kv.y, sv); sv = fmaf(qs[d + 2], kv.z, sv); sv = fmaf(qs[d + 3], kv.w, sv);
+      dp = fmaf(dos[d], vv.x, dp); dp = fmaf(dos[d + 1], vv.y, dp); dp = fmaf(dos[d + 2], vv.z, dp); dp = fmaf(dos[d + 3], vv.w, dp);
+    }
+    const float pr = expf(sv - l);
+    if (P.drop.thresh8) dp = attn_keep1(P.drop, drop_bh, qi, key) ? dp * P.drop.scale : 0.f;
+    sc[key] = pr * (dp - dl);
+  }
+  __syncthreads();
+  float acc = 0.f;
+  for (int key = wave; key < nk; key += 4) acc = fmaf(sc[key], ld1(kb + (size_t)key * P.ldk + lane), acc);
+  part[wave * 64 + lane] = acc;
+  __syncthreads();
+  if (tid < 64)
+    st1((T*)P.dq + qrow * P.lddq + h * HD + tid, (part[tid] + part[64 + tid]) + (part[128 + tid] + part[192 + tid]));
+}
+
+// self: one workgroup per packed key row (grid Tcap x H); cross: per dense key row (grid Lk x H x B)
+template <typename T>
+__global__ __launch_bounds__(256) void attn_gen_bwd_dkdv_varlen_kernel(GenP P, VarP V) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];  // pd[Lmax] | ds[Lmax] | k[64] | v[64] | part[2][4][64]
+  const int H = P.H, h = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int b, key;
+  size_t krow;
+  if (V.self) {
+    const int i = blockIdx.x;
+    if (i >= V.row_off[P.B]) {
+      if (tid < 64) {
+        st1((T*)P.dv + (size_t)i * P.lddv + h * HD + tid, 0.f);
+        st1((T*)P.dk + (size_t)i * P.lddk + h * HD + tid, 0.f);
+      }
+      return;
+    }
+    b = varlen_row_of(V.row_off, P.B, i);
+    key = i - V.row_off[b];
+    krow = (size_t)i;
+  } else {
+    b = blockIdx.z;
+    key = blockIdx.x;
+    krow = (size_t)b * P.Lk + key;
+  }
+  const int o0 = V.row_off[b], Lq = V.row_off[b + 1] - o0;
+  float* pd = sm;
+  float* ds = sm + P.Lq;
+  float* ks = ds + P.Lq;
+  float* vs = ks + 64;
+  float* part = vs + 64;
+  const T* qb = (const T*)P.q + (size_t)o0 * P.ldq + h * HD;
+  const T* dob = (const T*)P.d_o + (size_t)o0 * P.lddo + h * HD;
+  const float* lseb = P.lse + (size_t)h * V.Tcap + o0;
+  const float* dltb = P.delta + (size_t)h * V.Tcap + o0;
+  const unsigned drop_bh = P.drop.seed + step_salt(P.drop.step) + (unsigned)(b * H + h) * DROP_CB;
+  if (tid < 64) {
+    ks[tid] = ld1((const T*)P.k + krow * P.ldk + h * HD + tid);
+    vs[tid] = ld1((const T*)P.v + krow * P.ldv + h * HD + tid);
+  }
+  __syncthreads();
+  const int q_lo = P.causal ? key : 0;
+  for (int qi = q_lo + tid; qi < Lq; qi += 256) {
+    const T* qr = qb + (size_t)qi * P.ldq;
+    const T* dr = dob + (size_t)qi * P.lddo;
+    float sv = 0.f, dp = 0.f;
+#pragma unroll
+    for (int d = 0; d < HD; d += 4) {
+      const f32x4 qv = ld4(qr + d), dv4 = ld4(dr + d);
+      sv = fmaf(qv.x, ks[d], sv); sv = fmaf(qv.y, ks[d + 1], sv); sv = fmaf(qv.z, ks[d + 2], sv); sv = fmaf(qv.w, ks[d + 3], sv);
+      dp = fmaf(dv4.x, vs[d], dp); dp = fmaf(dv4.y, vs[d + 1], dp); dp = fmaf(dv4.z, vs[d + 2], dp); dp = fmaf(dv4.w, vs[d + 3], dp);
+    }
+    const float pr = expf(sv - lseb[qi]);
+    float keep = 1.f;
+    if (P.drop.thresh8) keep = attn_keep1(P.drop, drop_bh, qi, key) ? P.drop.scale : 0.f;
+    pd[qi] = pr * keep;
+    ds[qi] = pr * (dp * keep - dltb[qi]);
+  }
+  __syncthreads();
+  float av = 0.f, ak = 0.f;
+  for (int qi = q_lo + wave; qi < Lq; qi += 4) {
+    av = fmaf(pd[qi], ld1(dob + (size_t)qi * P.lddo + lane), av);
+    ak = fmaf(ds[qi], ld1(qb + (size_t)qi * P.ldq + lane), ak);
+  }
+  part[wave * 64 + lane] = av;
+  part[256 + wave * 64 + lane] = ak;
+  __syncthreads();
+  if (tid < 64) {
+    st1((T*)P.dv + krow * P.lddv + h * HD + tid, (part[tid] + part[64 + tid]) + (part[128 + tid] + part[192 + tid]));
+    st1((T*)P.dk + krow * P.lddk + h * HD + tid, (part[256 + tid] + part[320 + tid]) + (part[384 + tid] + part[448 + tid]));
+  }
+}
+
 }  // namespace
 
 int mrmt3_attn_general_fwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const float* bias,
@@ -313,4 +532,48 @@ extern "C" int mrmt3_attn_bwd_bias(const void* q, int ldq, const void* k, int ld
   return mrmt3_attn_general_bwd(q, ldq, k, ldk, v, ldv, o, ldo, d_o, lddo, lse, delta, bias, bias_batch_stride, dq, lddq, dk,
                                 lddk, dv, lddv, dbias, B, H, Lq, Lk, causal, dtype,
                                 make_attn_drop(p_drop, seed, stream_id, step_dev), (hipStream_t)stream);
+}
+
+// varlen entry points of the exact-f32 path (called by mrmt3_attn_fwd_varlen / mrmt3_attn_bwd_varlen): P.Lq carries the longest
+// row (shared-memory sizing), Lk > 0 the dense key length of cross-attention, Lk = 0 packed self-attention keys
+int mrmt3_attn_general_fwd_varlen(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo,
+                                  float* lse, const int* row_off, int B, int H, int Tcap, int Lmax, int Lk, int causal,
+                                  const AttnDrop& drop, hipStream_t s) {
+  MR_CHECK_ARG(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0, "attn_fwd_varlen (f32): strides must be multiples of 4");
+  const int Lsc = Lk > 0 ? Lk : Lmax;
+  const size_t shm = (size_t)(Lsc + 64 + 8 + 256) * sizeof(float);
+  MR_CHECK_ARG(shm <= 160 * 1024, "attn_fwd_varlen (f32): rows too long");
+  GenP P;
+  memset(&P, 0, sizeof(P));
+  P.q = q; P.k = k; P.v = v; P.out = o; P.lse = lse;
+  P.ldq = ldq; P.ldk = ldk; P.ldv = ldv; P.ldo = ldo;
+  P.B = B; P.H = H; P.Lq = Lmax; P.Lk = Lk; P.causal = causal; P.bloop = 1; P.drop = drop;
+  VarP V{row_off, Tcap, Lk > 0 ? 0 : 1};
+  hipLaunchKernelGGL(attn_gen_fwd_varlen_kernel<float>, dim3(Tcap, H), dim3(256), shm, s, P, V);
+  MR_CHECK_LAUNCH("attn_fwd_varlen (f32)");
+  return MRMT3_OK;
+}
+
+int mrmt3_attn_general_bwd_varlen(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* o,
+                                  int ldo, const void* d_o, int lddo, const float* lse, float* delta, void* dq, int lddq,
+                                  void* dk, int lddk, void* dv, int lddv, const int* row_off, int B, int H, int Tcap, int Lmax,
+                                  int Lk, int causal, const AttnDrop& drop, hipStream_t s) {
+  MR_CHECK_ARG(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && lddo % 4 == 0,
+               "attn_bwd_varlen (f32): strides must be multiples of 4");
+  const int Lsc = Lk > 0 ? Lk : Lmax;
+  const size_t shm_q = (size_t)(Lsc + 64 + 64 + 4 + 256) * sizeof(float), shm_k = (size_t)(2 * Lmax + 128 + 512) * sizeof(float);
+  MR_CHECK_ARG(shm_q <= 160 * 1024 && shm_k <= 160 * 1024, "attn_bwd_varlen (f32): rows too long");
+  GenP P;
+  memset(&P, 0, sizeof(P));
+  P.q = q; P.k = k; P.v = v; P.o = o; P.d_o = d_o; P.lse = (float*)lse; P.delta = delta;
+  P.dq = dq; P.dk = dk; P.dv = dv;
+  P.ldq = ldq; P.ldk = ldk; P.ldv = ldv; P.ldo = ldo; P.lddo = lddo; P.lddq = lddq; P.lddk = lddk; P.lddv = lddv;
+  P.B = B; P.H = H; P.Lq = Lmax; P.Lk = Lk; P.causal = causal; P.bloop = 1; P.drop = drop;
+  VarP V{row_off, Tcap, Lk > 0 ? 0 : 1};
+  hipLaunchKernelGGL(attn_gen_bwd_dq_varlen_kernel<float>, dim3(Tcap, H), dim3(256), shm_q, s, P, V);
+  MR_CHECK_LAUNCH("attn_bwd_varlen dq (f32)");
+  const dim3 gk = Lk > 0 ? dim3(Lk, H, B) : dim3(Tcap, H);
+  hipLaunchKernelGGL(attn_gen_bwd_dkdv_varlen_kernel<float>, gk, dim3(256), shm_k, s, P, V);
+  MR_CHECK_LAUNCH("attn_bwd_varlen dkdv (f32)");
+  return MRMT3_OK;
 }

@@ -116,6 +116,33 @@ struct AttnParams {
   AttnDrop drop;
 };
 
+// Variable-length (packed) rows, built on the device by mrmt3_pack_plan (pack.hip).  Row b of the batch owns packed rows
+// [row_off[b], row_off[b+1]); packed rows [T, Tcap) with T = row_off[B] are the tail.  `tiles` is the launch list of the varlen
+// kernels: tiles[0] = entries in use, tiles[1] = T, then n_ent (row, 64-row tile) pairs, heaviest causal tile first (tile index
+// descending), row = -1 for a surplus entry.  n_ent = mrmt3_pack_tile_entries(B, Tcap) = ceil(Tcap/64) + B + 1 depends on the
+// shapes alone (a captured launch replays for any batch with the same Tcap) and always leaves at least ceil((Tcap-T)/64) surplus
+// entries: those write the tail rows' zeros.
+#define VARLEN_TILE 64
+struct AttnVarlen {
+  const int* row_off;
+  const int* tiles;
+  int n_ent, Tcap;
+};
+// VL: 0 dense (the original kernels), 1 self-attention (queries and keys packed), 2 cross-attention (queries packed, keys dense)
+// surplus entry e of a varlen launch -> the 64 tail rows it zeroes: [r0, r1)
+__device__ __forceinline__ bool varlen_tail_rows(const AttnVarlen& V, int e, int& r0, int& r1) {
+  const int k = e - V.tiles[0], T = V.tiles[1];
+  r0 = T + k * VARLEN_TILE;
+  r1 = min(r0 + VARLEN_TILE, V.Tcap);
+  return k >= 0 && r0 < r1;
+}
+// zero rows [r0, r1) of head h in a [rows][ld] bf16 tensor (workgroup of 256: a 16-byte chunk per thread and pass)
+__device__ __forceinline__ void varlen_zero_rows(bf16_t* base, int ld, int h, int r0, int r1) {
+  if (!base) return;
+  for (int i = threadIdx.x; i < (r1 - r0) * 8; i += 256)
+    *(u32x4*)(base + (size_t)(r0 + (i >> 3)) * ld + h * HD + (i & 7) * 8) = u32x4{0u, 0u, 0u, 0u};
+}
+
 // ---- LDS tiles: [rows][64] bf16 = 128-B rows, the 16-B chunk index XOR-ed with (row & 7).  Tiles are
 // filled by buffer_load ... lds (memory -> LDS, no VGPR round trip, see blds_rows8 below): one wave-instruction
 // covers 8 rows x 128 B linearly, so the swizzle is applied to each lane's SOURCE chunk.  The same image
@@ -206,3 +233,11 @@ int mrmt3_attn_general_bwd(const void* q, int ldq, const void* k, int ldk, const
                            const void* d_o, int lddo, const float* lse, float* delta, const float* bias, long long bias_bs,
                            void* dq, int lddq, void* dk, int lddk, void* dv, int lddv, float* dbias, int B, int H, int Lq,
                            int Lk, int causal, int dtype, const AttnDrop& drop, hipStream_t s);
+// attention_general.hip: the varlen exact-f32 kernels (Lk > 0: dense cross-attention keys [B][Lk]; Lk = 0: packed self keys)
+int mrmt3_attn_general_fwd_varlen(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo,
+                                  float* lse, const int* row_off, int B, int H, int Tcap, int Lmax, int Lk, int causal,
+                                  const AttnDrop& drop, hipStream_t s);
+int mrmt3_attn_general_bwd_varlen(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* o,
+                                  int ldo, const void* d_o, int lddo, const float* lse, float* delta, void* dq, int lddq,
+                                  void* dk, int lddk, void* dv, int lddv, const int* row_off, int B, int H, int Tcap, int Lmax,
+                                  int Lk, int causal, const AttnDrop& drop, hipStream_t s);

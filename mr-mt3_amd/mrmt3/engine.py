@@ -246,10 +246,11 @@ class Engine:
             self._wt32 = {}
 
     # ---- one T5Stack (models/t5.py:507-702) ----------------------------------------------------------
-    def stack_fwd(self, prefix, x, B, L, n_layers, is_decoder, enc=None, Le=0, p=0.0, tape=None, out_dtype=None):
+    def stack_fwd(self, prefix, x, B, L, n_layers, is_decoder, enc=None, Le=0, p=0.0, tape=None, out_dtype=None, pack=None):
         """x: [B*L, d] fp32 (embeddings + sinusoid, dropout already applied).
         enc: [B*Le, d] compute-dtype encoder states for cross-attention.  Returns the final-normed
-        (and dropped) states [B*L, d] in the compute dtype."""
+        (and dropped) states [B*L, d] in the compute dtype.  pack (a lib.PackPlan): x is [Tcap, d], rows packed end to end —
+        every row-wise kernel runs on the Tcap rows, the attention sites on the varlen kernels (encoder states stay dense)."""
         f, dt, H, inner, eps = self.flat, self.dt, self.H, self.inner, self.eps
         keep = tape is not None
         pend = None          # the projection of the sublayer above, not yet added to the residual stream: (operand, weight)
@@ -264,9 +265,14 @@ class Engine:
                                              p=p, seed=self.seed, step=self.step_dev, stream_y=s_in, x1=None if keep else x)
             qkv = lib.gemm_nt(xn, self.W(f"{prefix}.{i}.qkv"))
             s_att = self._sid()
-            o, lse, o_lo = lib.attn_fwd(qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:], B, H, L, L,
-                                        is_decoder, p=p, seed=self.seed, step=self.step_dev, stream_id=s_att,
-                                        want_lse=keep, want_lo=keep and self.lo_sites == "all")
+            if pack is not None:
+                o, lse, o_lo = lib.attn_fwd_varlen(qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:], pack, H, 0,
+                                                   is_decoder, p=p, seed=self.seed, step=self.step_dev, stream_id=s_att,
+                                                   want_lse=keep, want_lo=keep and self.lo_sites == "all")
+            else:
+                o, lse, o_lo = lib.attn_fwd(qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:], B, H, L, L,
+                                            is_decoder, p=p, seed=self.seed, step=self.step_dev, stream_id=s_att,
+                                            want_lse=keep, want_lo=keep and self.lo_sites == "all")
             pend = (o, self.W(f"{prefix}.{i}.o"))
             sy = self._sid()
             if keep:
@@ -280,8 +286,12 @@ class Engine:
                 q = lib.gemm_nt(xn, self.W(f"{prefix}.{i}.cq"))
                 kv = kv_all[:, i * 2 * inner:(i + 1) * 2 * inner]        # this layer's K | V columns (row stride n_layers * 768)
                 s_att = self._sid()
-                o, lse, o_lo = lib.attn_fwd(q, kv[:, :inner], kv[:, inner:], B, H, L, Le, False, p=p, seed=self.seed,
-                                            step=self.step_dev, stream_id=s_att, want_lse=keep, want_lo=keep)
+                if pack is not None:
+                    o, lse, o_lo = lib.attn_fwd_varlen(q, kv[:, :inner], kv[:, inner:], pack, H, Le, False, p=p, seed=self.seed,
+                                                       step=self.step_dev, stream_id=s_att, want_lse=keep, want_lo=keep)
+                else:
+                    o, lse, o_lo = lib.attn_fwd(q, kv[:, :inner], kv[:, inner:], B, H, L, Le, False, p=p, seed=self.seed,
+                                                step=self.step_dev, stream_id=s_att, want_lse=keep, want_lo=keep)
                 pend = (o, self.W(f"{prefix}.{i}.co"))
                 sy = self._sid()
                 if keep:
@@ -308,7 +318,7 @@ class Engine:
                                           x1=None if keep else x)
         if keep:
             tape.push(kind="final", x1=x, rstd=rstd, s_in=sy, s_out=s_out, prefix=prefix, n_layers=n_layers,
-                      is_decoder=is_decoder, B=B, L=L, Le=Le, enc=enc, p=p)
+                      is_decoder=is_decoder, B=B, L=L, Le=Le, enc=enc, p=p, pack=pack)
         return out
 
     def stack_bwd(self, tape, d_out, d_enc=None, on_layer_done=None):
@@ -319,7 +329,7 @@ class Engine:
         fin = tape.pop()
         assert fin["kind"] == "final"
         prefix, n_layers, is_dec = fin["prefix"], fin["n_layers"], fin["is_decoder"]
-        B, L, Le, enc, p = fin["B"], fin["L"], fin["Le"], fin["enc"], fin["p"]
+        B, L, Le, enc, p, pack = fin["B"], fin["L"], fin["Le"], fin["enc"], fin["p"], fin.get("pack")
         H, inner, seed = self.H, self.inner, self.seed
         has_y = n_layers > 0
         rg = self.res_grad_dtype if has_y else torch.float32
@@ -350,9 +360,14 @@ class Engine:
                 dq = torch.empty_like(t["q"])
                 dkv = dkv_all[:, i * 2 * inner:(i + 1) * 2 * inner]
                 kv = t["kv"]
-                lib.attn_bwd(t["q"], kv[:, :inner], kv[:, inner:], t["o"], do, t["lse"], dq, dkv[:, :inner],
-                             dkv[:, inner:], B, H, L, Le, False, p=p, seed=seed, step=self.step_dev,
-                             stream_id=t["s_att"], o_lo=t["o_lo"])
+                if pack is not None:
+                    lib.attn_bwd_varlen(t["q"], kv[:, :inner], kv[:, inner:], t["o"], do, t["lse"], dq, dkv[:, :inner],
+                                        dkv[:, inner:], pack, H, Le, False, p=p, seed=seed, step=self.step_dev,
+                                        stream_id=t["s_att"], o_lo=t["o_lo"])
+                else:
+                    lib.attn_bwd(t["q"], kv[:, :inner], kv[:, inner:], t["o"], do, t["lse"], dq, dkv[:, :inner],
+                                 dkv[:, inner:], B, H, L, Le, False, p=p, seed=seed, step=self.step_dev,
+                                 stream_id=t["s_att"], o_lo=t["o_lo"])
                 self.wgrad(dq, t["xn"], f.GW(f"{prefix}.{i}.cq"))
                 self.wgrad(dkv, enc, f.GW(f"{prefix}.{i}.ckv"))
                 dx, dy = self._proj_norm_bwd(dq, self.WT(f"{prefix}.{i}.cq"), dx, t["x1"], t["rstd"],
@@ -364,9 +379,14 @@ class Engine:
             do = lib.gemm_nt(dy, self.WT(f"{prefix}.{i}.o"))
             qkv = t["qkv"]
             dqkv = torch.empty_like(qkv)
-            lib.attn_bwd(qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:], t["o"], do, t["lse"],
-                         dqkv[:, :inner], dqkv[:, inner:2 * inner], dqkv[:, 2 * inner:], B, H, L, L, is_dec, p=p,
-                         seed=seed, step=self.step_dev, stream_id=t["s_att"], o_lo=t["o_lo"])
+            if pack is not None:
+                lib.attn_bwd_varlen(qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:], t["o"], do, t["lse"],
+                                    dqkv[:, :inner], dqkv[:, inner:2 * inner], dqkv[:, 2 * inner:], pack, H, 0, is_dec, p=p,
+                                    seed=seed, step=self.step_dev, stream_id=t["s_att"], o_lo=t["o_lo"])
+            else:
+                lib.attn_bwd(qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:], t["o"], do, t["lse"],
+                             dqkv[:, :inner], dqkv[:, inner:2 * inner], dqkv[:, 2 * inner:], B, H, L, L, is_dec, p=p,
+                             seed=seed, step=self.step_dev, stream_id=t["s_att"], o_lo=t["o_lo"])
             self.wgrad(dqkv, t["xn"], f.GW(f"{prefix}.{i}.qkv"))
             last = i == 0                                     # the stack's input gradient leaves in f32
             dx, dy = self._proj_norm_bwd(dqkv, self.WT(f"{prefix}.{i}.qkv"), dx, t["x1"], t["rstd"],
@@ -514,12 +534,18 @@ class Engine:
         return torch.cat([dummy, seg[:-1]], 0).contiguous()
 
     # ---- full forward / backward --------------------------------------------------------------------------
-    def forward(self, mel, labels, targets_prev=None, training=False, need_grad=False, want_logits=True):
+    def forward(self, mel, labels, targets_prev=None, training=False, need_grad=False, want_logits=True, pack=None):
         """Returns (logits [B, Ld, V] fp32, tape or None) — or, with want_logits=False, the final-normed decoder states
         [B*Ld, d] in the compute dtype instead of the logits (the trainer feeds them to the fused lm_head + CE call, so
         the 403 MB of f32 logits of a 64-segment batch never exist).  Mirrors get_model_outputs of the four
         reference model classes (models/t5.py:99-180, t5_segmem.py:68-170, t5_segmem_v2.py:64-167,
-        t5_segmem_v2_with_prev.py:60-153)."""
+        t5_segmem_v2_with_prev.py:60-153).
+
+        pack (a lib.PackPlan of these labels, lib.pack_plan): the decoder runs on each row's scored prefix only, its rows packed
+        end to end — logits / decoder states come back as [Tcap, ...] rows in packed order, scored against plan.targets.  The
+        encoder, the memory encoder and its ids (built from the full labels) stay dense.  Same loss and gradients as the dense
+        step (causality: nothing after a row's last scored label reaches a scored position); with dropout on, the row-wise
+        masks are keyed by the packed row, so they differ from the dense step's but are drawn the same way."""
         cfg, f = self.cfg, self.flat
         if not mel.is_cuda:
             raise RuntimeError("MR-MT3 MI355X path needs device tensors (no CPU fallback)")
@@ -552,6 +578,9 @@ class Engine:
             mem = self.segmem(ids, B, Lm, tape=tape)                             # [B, Ls, d]
             Ls = mem.shape[1]
         s_emb = self._sid()
+        if variant == "segmem_v1" and pack is not None:
+            raise ValueError("packed decoder rows are not supported for segmem_v1 (its memory slots are prepended to the "
+                             "decoder input)")
         if variant == "segmem_v1":
             # memory is PREPENDED to the decoder input embeddings (t5_segmem.py:138-160)
             emb = lib.embed_fwd(labels.view(-1), table, None, Ld, shift=True, start_id=start, pad_id=pad)
@@ -561,8 +590,11 @@ class Engine:
             enc_cat, Lc = enc, Le
         else:
             Lx = Ld
-            x = lib.embed_fwd(labels.view(-1), table, pos, Ld, shift=True, start_id=start, pad_id=pad, p=p,
-                              seed=self.seed, step=self.step_dev, stream_id=s_emb)
+            if pack is not None:
+                x = lib.embed_fwd_packed(pack, table, pos, p=p, seed=self.seed, step=self.step_dev, stream_id=s_emb)
+            else:
+                x = lib.embed_fwd(labels.view(-1), table, pos, Ld, shift=True, start_id=start, pad_id=pad, p=p,
+                                  seed=self.seed, step=self.step_dev, stream_id=s_emb)
             if mem is not None:
                 enc_cat = torch.cat([enc.view(B, Le, d), mem], 1).contiguous().view(-1, d)
                 Lc = Le + Ls
@@ -570,10 +602,10 @@ class Engine:
                 enc_cat, Lc = enc, Le
         if tape is not None:
             tape.push(kind="dec_in", s_emb=s_emb, p=p, labels=labels, B=B, Le=Le, Ld=Ld, Lx=Lx, Lc=Lc, Ls=Ls,
-                      Lm=(ids.shape[1] if variant != "t5" else 0), variant=variant)
+                      Lm=(ids.shape[1] if variant != "t5" else 0), variant=variant, pack=pack)
         head_f32 = self.head_dtype == "f32" and tape is None and self.dt == torch.bfloat16
         dec = self.stack_fwd("decoder", x, B, Lx, cfg["num_decoder_layers"], True, enc=enc_cat, Le=Lc, p=p, tape=tape,
-                             out_dtype=torch.float32 if head_f32 else None)
+                             out_dtype=torch.float32 if head_f32 else None, pack=pack)
         if variant == "segmem_v1":
             dec = dec.view(B, Lx, d)[:, Ls:].contiguous().view(B * Ld, d)
         if tape is not None:
@@ -582,6 +614,8 @@ class Engine:
             return dec, tape
         w_head = f.W("lm_head", torch.float32) if head_f32 else self.W("lm_head")
         logits = lib.gemm_nt(dec, w_head, out_dtype=torch.float32)               # [B*Ld, V]
+        if pack is not None:
+            return logits, tape                                                   # [Tcap, V], packed rows
         return logits.view(B, Ld, self.V), tape
 
     def backward(self, tape, dlogits, on_layer_done=None):
@@ -622,8 +656,12 @@ class Engine:
                           start_id=start, pad_id=pad)
             d_enc = d_enc_cat
         else:
-            lib.embed_bwd(t["labels"].view(-1), dx, table_g, Ld, shift=True, start_id=start, pad_id=pad, p=t["p"],
-                          seed=self.seed, step=self.step_dev, stream_id=t["s_emb"])
+            if t["pack"] is not None:          # the packed inputs are already shifted: a plain scatter-add over the Tcap rows
+                lib.embed_bwd(t["pack"].dec_ids, dx, table_g, t["pack"].Tcap, shift=False, pad_id=pad, p=t["p"],
+                              seed=self.seed, step=self.step_dev, stream_id=t["s_emb"])
+            else:
+                lib.embed_bwd(t["labels"].view(-1), dx, table_g, Ld, shift=True, start_id=start, pad_id=pad, p=t["p"],
+                              seed=self.seed, step=self.step_dev, stream_id=t["s_emb"])
             if variant != "t5":
                 dcat = d_enc_cat.view(B, Lc, d)
                 d_enc = dcat[:, :Le].contiguous().view(-1, d)

@@ -98,6 +98,14 @@ _SIGS = {
     "mrmt3_stream_create": (ci, [C.POINTER(vp), ci]),
     "mrmt3_stream_destroy": (ci, [vp]),
     "mrmt3_abort_trace_install": (ci, [C.c_char_p]),
+    "mrmt3_pack_tile_entries": (ci, [ci, ci]),
+    "mrmt3_pack_lengths": (ci, [vp, ci, ci, vp, vp]),
+    "mrmt3_pack_plan": (ci, [vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "mrmt3_embed_fwd_packed": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, cf, cu64, vp, cu32, vp]),
+    "mrmt3_attn_fwd_varlen": (ci, [vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, cu64, vp,
+                                   cu32, vp]),
+    "mrmt3_attn_bwd_varlen": (ci, [vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, ci, vp, ci, vp, ci, vp, vp, ci, ci,
+                                   ci, ci, ci, ci, ci, cf, cu64, vp, cu32, vp]),
 }
 
 
@@ -142,10 +150,10 @@ def load():
     return lib
 
 
-MIN_VERSION = 111
+MIN_VERSION = 112
 COUNTER_NAMES = ("gemm_nt_tile", "gemm_nt8", "gemm_nt_geglu", "tn_group", "tn8", "tn_tile", "attn_fwd", "attn_bwd",
                  "attn_bwd_onepass", "attn_f32", "tn_f32", "gemm_nt_splitk", "gemm_nt_addnorm", "gemm_nt_normbwd",
-                 "gemm_nt_geglubwd")
+                 "gemm_nt_geglubwd", "attn_fwd_varlen", "attn_bwd_varlen")
 
 
 def set_knob(name: str, value: int):
@@ -665,6 +673,99 @@ def attn_bwd(q, k, v, o, d_o, lse, dq, dk, dv, B, H, Lq, Lk, causal, p=0.0, seed
                                      _p(o_lo), _p(d_o), d_o.stride(0), _p(lse), _p(delta), _p(dq), dq.stride(0), _p(dk),
                                      dk.stride(0), _p(dv), dv.stride(0), B, H, Lq, Lk, int(causal), p, seed,
                                      _p(step), stream_id, _stream()), "attn_bwd")
+    return dq, dk, dv
+
+
+class PackPlan:
+    """Device tensors of one packed batch (mrmt3_pack_plan, csrc/pack.hip): row b of the [B, L] labels owns packed rows
+    [row_off[b], row_off[b+1]) of Tcap."""
+
+    def __init__(self, B, L, Tcap, device):
+        i32 = dict(device=device, dtype=torch.int32)
+        self.B, self.L, self.Tcap = B, L, Tcap
+        self.n_ent = load().mrmt3_pack_tile_entries(B, Tcap)
+        self.len = torch.empty(B, **i32)
+        self.row_off = torch.empty(B + 1, **i32)
+        self.tok_row = torch.empty(Tcap, **i32)
+        self.tok_pos = torch.empty(Tcap, **i32)
+        self.dec_ids = torch.empty(Tcap, device=device, dtype=torch.int64)
+        self.targets = torch.empty(Tcap, device=device, dtype=torch.int64)
+        self.tiles = torch.empty(2 + 2 * self.n_ent, **i32)
+        self.err = torch.empty(1, **i32)
+
+
+def pack_lengths(labels):
+    """len [B] int32 on the device: 1 + the last position of each row whose label is not -100 (0 for none)."""
+    _dev(labels)
+    assert labels.dtype == torch.int64 and labels.dim() == 2 and labels.is_contiguous()
+    B, L = labels.shape
+    out = torch.empty(B, device=labels.device, dtype=torch.int32)
+    _check(load().mrmt3_pack_lengths(_p(labels), B, L, _p(out), _stream()), "pack_lengths")
+    return out
+
+
+def pack_plan(labels, Tcap, start_id, pad_id, plan=None):
+    """The packing plan of labels [B, L] int64 (device) at capacity Tcap: a PackPlan (its `err` is 1 when the rows do not fit)."""
+    _dev(labels)
+    assert labels.dtype == torch.int64 and labels.dim() == 2 and labels.is_contiguous()
+    B, L = labels.shape
+    pl = plan if plan is not None else PackPlan(B, L, Tcap, labels.device)
+    _check(load().mrmt3_pack_plan(_p(labels), B, L, Tcap, start_id, pad_id, _p(pl.len), _p(pl.row_off), _p(pl.tok_row),
+                                  _p(pl.tok_pos), _p(pl.dec_ids), _p(pl.targets), _p(pl.tiles), _p(pl.err), _stream()),
+           "pack_plan")
+    return pl
+
+
+def embed_fwd_packed(plan, table, pos, p=0.0, seed=0, stream_id=0, step=None):
+    """Embedding of the packed decoder inputs: table[dec_ids] + pos[tok_pos], dropout keyed by the packed row.  [Tcap, d] f32."""
+    _dev(table, pos)
+    V, d = table.shape
+    x = torch.empty(plan.Tcap, d, device=table.device, dtype=torch.float32)
+    _check(load().mrmt3_embed_fwd_packed(_p(plan.dec_ids), _p(plan.tok_pos), _p(table), _p(pos), _p(x), plan.Tcap, d, V, p, seed,
+                                         _p(step), stream_id, _stream()), "embed_fwd_packed")
+    return x
+
+
+def packed_attn_pairs(lengths, Lk, causal):
+    """(query, key) pairs of a packed launch from the host-side row lengths: the algorithmic work of the varlen kernels."""
+    if Lk:
+        return float(sum(lengths)) * Lk
+    if causal:
+        return float(sum(n * (n + 1) // 2 for n in lengths))
+    return float(sum(n * n for n in lengths))
+
+
+def attn_fwd_varlen(q, k, v, plan, H, Lk, causal, p=0.0, seed=0, stream_id=0, step=None, want_lse=True, want_lo=False,
+                    lengths=None):
+    """Attention over packed rows: q [Tcap, *] (head h at columns h*64..), k / v packed like q (Lk = 0, self-attention) or dense
+    [B*Lk, *] (cross-attention).  Returns (o [Tcap, H*64], lse [H, Tcap] or None, o_lo or None).  `lengths` (host list, optional)
+    only prices the launch for the profile."""
+    _dev(q, k, v)
+    T = plan.Tcap
+    assert q.shape[0] == T and (k.shape[0] == (T if Lk == 0 else plan.B * Lk))
+    o = torch.empty(T, H * 64, device=q.device, dtype=q.dtype)
+    o_lo = torch.empty_like(o) if want_lo and q.dtype == torch.bfloat16 else None
+    lse = torch.empty(H, T, device=q.device, dtype=torch.float32) if want_lse else None
+    work = 4.0 * H * 64 * packed_attn_pairs(lengths, Lk, causal) if lengths is not None else 0.0
+    with _Timed("attn_fwd_varlen", work, "FLOP"):
+        _check(load().mrmt3_attn_fwd_varlen(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(o), o.stride(0),
+                                            _p(o_lo), _p(lse), _p(plan.row_off), _p(plan.tiles), plan.B, H, T, plan.L, Lk,
+                                            int(causal), _dt(q), p, seed, _p(step), stream_id, _stream()), "attn_fwd_varlen")
+    return o, lse, o_lo
+
+
+def attn_bwd_varlen(q, k, v, o, d_o, lse, dq, dk, dv, plan, H, Lk, causal, p=0.0, seed=0, stream_id=0, step=None, o_lo=None,
+                    lengths=None):
+    """Backward of attn_fwd_varlen into caller-owned dq (packed like q) and dk / dv (laid out like k / v)."""
+    _dev(q, k, v, o, d_o, lse, dq, dk, dv, o_lo)
+    delta = torch.empty(H, plan.Tcap, device=q.device, dtype=torch.float32)
+    work = 8.0 * H * 64 * packed_attn_pairs(lengths, Lk, causal) if lengths is not None else 0.0
+    with _Timed("attn_bwd_varlen", work, "FLOP"):
+        _check(load().mrmt3_attn_bwd_varlen(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(o), o.stride(0),
+                                            _p(o_lo), _p(d_o), d_o.stride(0), _p(lse), _p(delta), _p(dq), dq.stride(0), _p(dk),
+                                            dk.stride(0), _p(dv), dv.stride(0), _p(plan.row_off), _p(plan.tiles), plan.B, H,
+                                            plan.Tcap, plan.L, Lk, int(causal), _dt(q), p, seed, _p(step), stream_id,
+                                            _stream()), "attn_bwd_varlen")
     return dq, dk, dv
 
 

@@ -33,6 +33,13 @@ the default generator's state but BEFORE that state has noted the graph, and des
 capture never begins on a stream whose status is not "none" (mrmt3_stream_capture_status); after a failure every participating
 stream is taken out of capture mode (mrmt3_stream_abandon_capture), the capture stream is replaced by a fresh one, and a graph
 object whose capture_begin raised is never destroyed (`_retire`).
+
+Packed decoder rows (`pack_targets=True`, MRMT3_PACK_TARGETS=1; mrmt3/packing.py).  The step reads each row's length on the
+host (from CPU labels directly, else one device-to-host copy of B int32 — the one place a packed step waits for the device),
+picks the capacity Tcap, and runs the decoder, the lm_head and the CE on Tcap packed rows; Tcap = B*L takes the dense step
+unchanged.  The signature of a captured step gains Tcap; the pack kernel runs inside the graph on the static label buffer.
+Captured packed signatures are kept in a small LRU (MRMT3_PACK_GRAPHS, default 4).  Eviction follows the rules above: the
+device is drained and the graph dropped OUTSIDE any capture, and the garbage is collected before the next capture begins.
 """
 from __future__ import annotations
 
@@ -74,7 +81,13 @@ class _CapturedStep:
 class Trainer:
     def __init__(self, model, lr: float = 2e-4, lr_lambda=None, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.01, weighted_loss: bool = False, layers_per_bucket: int = 4,
-                 graph: bool = None, grad_exchange_dtype=None):
+                 graph: bool = None, grad_exchange_dtype=None, pack_targets: bool = None):
+        if pack_targets is None:
+            pack_targets = os.environ.get("MRMT3_PACK_TARGETS", "0") != "0"
+        self.pack_targets = bool(pack_targets)
+        if self.pack_targets and model.engine.variant == "segmem_v1":
+            raise ValueError("pack_targets is not supported for segmem_v1: its memory slots are prepended to the decoder input, "
+                             "so the decoder rows cannot be cut to the scored prefix")
         self.model, self.flat, self.engine = model, model.flat, model.engine
         assert model.device.type == "cuda", "the trainer drives the HIP kernels: move the model to the GPU first"
         self.base_lr, self.lr_lambda = lr, lr_lambda
@@ -113,6 +126,8 @@ class Trainer:
         self._eager_seen = {}
         self._cap_stream = None
         self._cap_owner = None
+        self.pack_graphs = max(1, int(os.environ.get("MRMT3_PACK_GRAPHS", "4")))
+        self._pack_lru = []              # captured packed signatures, least recently used first
 
     def mel_from_audio(self, audio):
         """[B, n_samples] f32 device audio -> [B, frames, 512] mel in the compute dtype."""
@@ -120,21 +135,44 @@ class Trainer:
         return sp.logmel_segments(audio, out_bf16=(self.engine.dt == torch.bfloat16))
 
     # ---- one step's device work (identical in eager mode, under capture and — by replay — afterwards) ------------
-    def _step_body(self, inputs, labels, targets_prev, audio, cut=None):
+    def _pack_plan(self, labels, tcap):
+        """The device packing plan of `labels` at capacity `tcap` (None: the dense step)."""
+        if tcap is None:
+            return None
+        cfg = self.model.cfg
+        return lib.pack_plan(labels.contiguous(), tcap, cfg["decoder_start_token_id"], cfg["pad_token_id"])
+
+    def pack_capacity(self, labels):
+        """Tcap of this batch, or None for the dense step (packing off, or nothing to save).  Device labels cost one
+        device-to-host copy of B int32 (a wait for the device)."""
+        if not self.pack_targets:
+            return None
+        from . import packing
+        B, L = labels.shape
+        if labels.is_cuda:
+            lengths = lib.pack_lengths(labels.contiguous()).cpu().numpy()
+        else:
+            lengths = packing.row_lengths(labels.numpy())
+        tcap = packing.capacity(lengths, B, L)
+        return None if tcap == B * L else tcap
+
+    def _step_body(self, inputs, labels, targets_prev, audio, cut=None, tcap=None):
         """Enqueues one optimizer step.  `cut(bucket_indices)` is called where a gradient bucket is complete (only
-        when collectives will run): under capture it closes the current graph segment."""
+        when collectives will run): under capture it closes the current graph segment.  tcap: packed decoder rows."""
         eng, flat = self.engine, self.flat
         eng.reset_deferred()                                 # nothing of an aborted capture / failed step leaks into this one
         eng._stream_ctr = 0                                  # dropout site ids are per-step (step_dev salts them)
         mel = self.mel_from_audio(inputs) if audio else inputs
+        plan = self._pack_plan(labels, tcap)
+        targets = labels.reshape(-1) if plan is None else plan.targets
         if eng.dt == torch.bfloat16:
-            dec, tape = eng.forward(mel, labels, targets_prev, training=True, need_grad=True, want_logits=False)
+            dec, tape = eng.forward(mel, labels, targets_prev, training=True, need_grad=True, want_logits=False, pack=plan)
             # lm_head + CE over row chunks: the f32 logits exist one chunk at a time in a cache-sized workspace (SURVEY K9)
-            loss, dl = lib.lmhead_cross_entropy(dec, eng.W("lm_head"), labels.reshape(-1), want_grad=True,
+            loss, dl = lib.lmhead_cross_entropy(dec, eng.W("lm_head"), targets, want_grad=True,
                                                 grad_dtype=torch.bfloat16, weighted=self.weighted)
         else:                                                # fp32 engine (`precision: 32`): exact-f32 lm_head, then CE
-            logits, tape = eng.forward(mel, labels, targets_prev, training=True, need_grad=True)
-            loss, dl = lib.cross_entropy(logits.view(-1, logits.shape[-1]), labels.reshape(-1), want_grad=True,
+            logits, tape = eng.forward(mel, labels, targets_prev, training=True, need_grad=True, pack=plan)
+            loss, dl = lib.cross_entropy(logits.reshape(-1, logits.shape[-1]), targets, want_grad=True,
                                          grad_dtype=torch.float32, weighted=self.weighted)
         flat.G.zero_()
         self.buckets.reset()
@@ -174,10 +212,13 @@ class Trainer:
         if targets_prev is not None and eng.variant == "segmem_v2_with_prev":
             # in place on the caller's tensor, like the reference (t5_segmem_v2_with_prev.py:119)
             targets_prev.masked_fill_(targets_prev == -100, m.cfg["pad_token_id"])
+        tcap = self.pack_capacity(labels)
+        if self.pack_targets and not labels.is_cuda:
+            labels = labels.to(self.flat.G.device)          # CPU labels: lengths taken above, copied once
         if self.use_graph:
-            loss = self._graph_step(inputs, labels, targets_prev, audio)
+            loss = self._graph_step(inputs, labels, targets_prev, audio, tcap)
         else:
-            loss = self._step_body(inputs, labels, targets_prev, audio)
+            loss = self._step_body(inputs, labels, targets_prev, audio, tcap=tcap)
         self.host_step += 1
         if self.world > 1:   # C4: logged loss, reduced without blocking the host
             loss = loss.clone()
@@ -187,17 +228,21 @@ class Trainer:
         return loss
 
     # ---- hipGraph capture / replay of the step ---------------------------------------------------------------
-    def _graph_step(self, inputs, labels, targets_prev, audio):
+    def _graph_step(self, inputs, labels, targets_prev, audio, tcap=None):
         sig = (bool(audio), tuple(inputs.shape), inputs.dtype, tuple(labels.shape),
                None if targets_prev is None else tuple(targets_prev.shape))
+        if tcap is not None:
+            sig = sig + (tcap,)
         cap = self._graphs.get(sig)
         if cap is None:
             seen = self._eager_seen.get(sig, 0)
             if seen < self.graph_warmup:
                 self._eager_seen[sig] = seen + 1
-                return self._step_body(inputs, labels, targets_prev, audio)
+                return self._step_body(inputs, labels, targets_prev, audio, tcap=tcap)
+            if tcap is not None:
+                self._evict_packed(self.pack_graphs - 1)
             try:
-                cap = self._capture(sig, inputs, labels, targets_prev, audio)
+                cap = self._capture(sig, inputs, labels, targets_prev, audio, tcap)
             except Exception as e:     # noqa: BLE001 — whatever a capture trips over, the eager step is still correct
                 # (nothing executed during the failed capture: the step below is the first to run; the launches the
                 # aborted capture had deferred are dropped — _after_failed_capture and _step_body reset them)
@@ -206,7 +251,12 @@ class Trainer:
                 warnings.warn("hipGraph capture of the training step failed (%s: %s)%s; continuing with eager launches"
                               % (type(e).__name__, _first_line(e), state))
                 self.use_graph = False
-                return self._step_body(inputs, labels, targets_prev, audio)
+                return self._step_body(inputs, labels, targets_prev, audio, tcap=tcap)
+            if tcap is not None:
+                self._pack_lru.append(sig)
+        elif tcap is not None:
+            self._pack_lru.remove(sig)
+            self._pack_lru.append(sig)
         self.engine.prepare(True)          # weights written through torch since the last step? rebuild the shadows
         cap.inputs.copy_(inputs, non_blocking=True)
         cap.labels.copy_(labels, non_blocking=True)
@@ -220,6 +270,21 @@ class Trainer:
         self.buckets.wait()
         cap.tail.replay()
         return cap.loss.clone()            # the graph's own loss scalar is overwritten by the next replay
+
+    def _evict_packed(self, keep: int):
+        """Drop the least recently used captured packed steps until at most `keep` remain.  Called outside any capture: the
+        device is drained first (no replay of the graph may be in flight) and the garbage collected here, while HIP calls are
+        legal, not by the collector at some later moment."""
+        if len(self._pack_lru) <= keep:
+            return
+        import gc
+        torch.cuda.synchronize()
+        while len(self._pack_lru) > keep:
+            sig = self._pack_lru.pop(0)
+            self._graphs.pop(sig, None)
+            self._eager_seen.pop(sig, None)
+        gc.collect()
+        torch.cuda.synchronize()
 
     # ---- a capture that failed: leave nothing behind -----------------------------------------------------------------
     def _capture_streams(self):
@@ -319,7 +384,7 @@ class Trainer:
                 return True
         return False
 
-    def _capture(self, sig, inputs, labels, targets_prev, audio):
+    def _capture(self, sig, inputs, labels, targets_prev, audio, tcap=None):
         """Record the step once (nothing executes during capture); `train_step` then replays it, this step included."""
         import gc
         eng = self.engine
@@ -385,7 +450,7 @@ class Trainer:
             with torch.cuda.stream(cs):
                 begin()
                 try:
-                    cap.loss = self._step_body(cap.inputs, cap.labels, cap.prev, audio, cut=cut)
+                    cap.loss = self._step_body(cap.inputs, cap.labels, cap.prev, audio, cut=cut, tcap=tcap)
                     g, state["g"] = state["g"], None
                     g.capture_end()
                     cap.tail = g
@@ -416,6 +481,7 @@ class Trainer:
         torch.cuda.synchronize()
         self._graphs.clear()
         self._eager_seen.clear()
+        self._pack_lru.clear()
         gc.collect()
         torch.cuda.synchronize()
         self._drop_capture_stream()
@@ -463,11 +529,16 @@ class Trainer:
     def eval_loss(self, inputs, labels, targets_prev=None, audio: bool = False):
         self.model.eval()
         mel = self.mel_from_audio(inputs) if audio else inputs
+        tcap = self.pack_capacity(labels)
+        if self.pack_targets and not labels.is_cuda:
+            labels = labels.to(self.flat.G.device)
+        plan = self._pack_plan(labels, tcap)
+        targets = labels.reshape(-1) if plan is None else plan.targets
         if self.engine.dt != torch.bfloat16:
-            logits, _ = self.engine.forward(mel, labels, targets_prev, training=False, need_grad=False)
-            return lib.cross_entropy(logits.view(-1, logits.shape[-1]), labels.reshape(-1), want_grad=False,
+            logits, _ = self.engine.forward(mel, labels, targets_prev, training=False, need_grad=False, pack=plan)
+            return lib.cross_entropy(logits.reshape(-1, logits.shape[-1]), targets, want_grad=False,
                                      weighted=self.weighted)[0]
-        dec, _ = self.engine.forward(mel, labels, targets_prev, training=False, need_grad=False, want_logits=False)
-        loss, _ = lib.lmhead_cross_entropy(dec, self.engine.W("lm_head"), labels.reshape(-1), want_grad=False,
+        dec, _ = self.engine.forward(mel, labels, targets_prev, training=False, need_grad=False, want_logits=False, pack=plan)
+        loss, _ = lib.lmhead_cross_entropy(dec, self.engine.W("lm_head"), targets, want_grad=False,
                                            weighted=self.weighted)
         return loss

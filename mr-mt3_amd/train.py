@@ -161,8 +161,11 @@ def main(argv=None):
     lam = None if finetune else cosine_warmup_lambda(int(cfg.optim.warmup_steps),
                                                      int(cfg.optim.num_steps_per_epoch) * int(cfg.optim.num_epochs),
                                                      min_lr=float(cfg.optim.min_lr))
+    # packed decoder rows (mrmt3/packing.py): `+pack_targets=true`; absent, MRMT3_PACK_TARGETS decides (default off)
+    pack = cfg.get("pack_targets")
+    pack = None if pack is None else str(pack).lower() in ("1", "true", "yes", "on")
     trainer = Trainer(task.model, lr=float(cfg.optim.lr), lr_lambda=lam,
-                      weighted_loss=type(task).__name__ == "MT3NetWeightedLoss")
+                      weighted_loss=type(task).__name__ == "MT3NetWeightedLoss", pack_targets=pack)
     task.model.engine.seed = int(cfg.seed)
     with_prev = "WithPrev" in type(task).__name__
     synthetic = bool(cfg.get("synthetic", False))
