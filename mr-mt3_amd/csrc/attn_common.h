@@ -128,7 +128,8 @@ struct AttnVarlen {
   const int* tiles;
   int n_ent, Tcap;
 };
-// VL: 0 dense (the original kernels), 1 self-attention (queries and keys packed), 2 cross-attention (queries packed, keys dense)
+// VL, the layout parameter of the attention kernel templates: 0 dense rows (a dense launch passes AttnVarlen{}), 1 packed
+// self-attention (queries and keys packed), 2 packed cross-attention (queries packed, keys dense); only the prologue differs
 // surplus entry e of a varlen launch -> the 64 tail rows it zeroes: [r0, r1)
 __device__ __forceinline__ bool varlen_tail_rows(const AttnVarlen& V, int e, int& r0, int& r1) {
   const int k = e - V.tiles[0], T = V.tiles[1];
