@@ -21,7 +21,8 @@
  *  - Dropout: every entry point that draws a mask takes (p_drop, seed, step_dev, stream id): the mask is a pure function
  *    of (seed, stream id, element index) salted, when step_dev is not NULL, by the int32 it points to in DEVICE memory —
  *    read by the kernel at run time, so a captured hipGraph draws new masks every optimizer step (mrmt3_adamw_step
- *    increments the counter).  Forward and backward of a site must pass the same four values.
+ *    increments the counter; with gradient accumulation the trainer passes a micro-batch counter of its own instead,
+ *    bumped by mrmt3_counter_add).  Forward and backward of a site must pass the same four values.
  *  - Return value: 0 = MRMT3_OK, otherwise an error code; mrmt3_last_error() returns a
  *    thread-local message.  Nothing aborts or throws across this ABI.
  */
@@ -403,6 +404,10 @@ int mrmt3_lmhead_ce_fwd_bwd(const void* dec, int ld_dec, const void* W, int ldw,
 int mrmt3_adamw_step(float* p, const float* g, float* m, float* v, size_t n, const float* lr_dev,
                      int32_t* step_dev, float beta1, float beta2, float eps, float weight_decay,
                      float grad_scale, void* shadow_bf16, void* stream);
+/* ctr[0] += delta on the device (int32, one thread, stream-ordered).  The trainer's gradient accumulation keeps its
+ * per-micro-batch dropout salt in such a counter: it is passed as the step_dev of the dropout entry points and bumped
+ * once per micro-batch, inside the captured step, so replays draw new masks per micro-batch. */
+int mrmt3_counter_add(int32_t* ctr, int32_t delta, void* stream);
 /* out[c][r] = in[r][c] (2-D transpose, with optional f32->bf16 cast) for the pre-transposed dgrad
  * weights. */
 int mrmt3_transpose(const void* in, int in_dtype, void* out, int out_dtype, int rows, int cols,

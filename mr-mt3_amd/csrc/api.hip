@@ -100,7 +100,7 @@ extern "C" int mrmt3_reset_knobs(void) {
   return MRMT3_OK;
 }
 
-extern "C" int mrmt3_version(void) { return 112; /* 0.1.12: packed decoder rows (mrmt3_pack_*, mrmt3_embed_fwd_packed, mrmt3_attn_*_varlen); 111: mrmt3_decoder_logits, torch.argmax NaN order in the decoder; 110: round 6 (capture hygiene entry points, owned streams, abort trace, pair bf16 conversion); 108: round 5 (knobs read once per process + mrmt3_set_knob; kernel diagnostics only in the -DMRMT3_DIAG build); 107: round 4 */ }
+extern "C" int mrmt3_version(void) { return 113; /* 0.1.13: mrmt3_counter_add (per-micro-batch dropout salt of gradient accumulation); 112: packed decoder rows (mrmt3_pack_*, mrmt3_embed_fwd_packed, mrmt3_attn_*_varlen); 111: mrmt3_decoder_logits, torch.argmax NaN order in the decoder; 110: round 6 (capture hygiene entry points, owned streams, abort trace, pair bf16 conversion); 108: round 5 (knobs read once per process + mrmt3_set_knob; kernel diagnostics only in the -DMRMT3_DIAG build); 107: round 4 */ }
 extern "C" const char* mrmt3_last_error(void) { return g_err; }
 
 // Page-locked host memory for tables the device reads through an async copy (the grouped weight-gradient plan): owned by

@@ -1098,6 +1098,15 @@ extern "C" int mrmt3_adamw_step(float* p, const float* g, float* m, float* v, si
   return MRMT3_OK;
 }
 
+__global__ void counter_add_kernel(int32_t* ctr, int32_t delta) { ctr[0] += delta; }
+
+extern "C" int mrmt3_counter_add(int32_t* ctr, int32_t delta, void* stream) {
+  MR_CHECK_ARG(ctr, "counter_add: bad args");
+  hipLaunchKernelGGL(counter_add_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, ctr, delta);
+  MR_CHECK_LAUNCH("counter_add");
+  return MRMT3_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // cast / transpose helpers (bf16 shadow weights and their pre-transposed dgrad copies)
 // ------------------------------------------------------------------------------------------------

@@ -141,6 +141,8 @@ def lightning_checkpoint(model, trainer=None, epoch: int = 0) -> dict:
         out["global_step"] = trainer.host_step
         # not part of Lightning's layout (ignored by it): lets a resumed run draw the same dropout masks
         out["mrmt3"] = {"dropout_seed": model.engine.seed, "dropout_stream_ctr": model.engine._stream_ctr}
+        if getattr(trainer, "accumulate", 1) > 1:      # gradient accumulation's micro-batch dropout salt
+            out["mrmt3"]["dropout_salt"] = int(trainer.salt_dev.item())
         if trainer.lr_lambda is not None:       # LambdaLR.state_dict() (the lambda itself is not pickled)
             out["lr_schedulers"] = [{"base_lrs": [trainer.base_lr], "last_epoch": trainer.host_step,
                                      "verbose": False, "_step_count": trainer.host_step + 1,

@@ -75,6 +75,7 @@ _SIGS = {
     "mrmt3_ce_fwd_bwd": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, cf, vp]),
     "mrmt3_lmhead_ce_fwd_bwd": (ci, [vp, ci, vp, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, vp, csz, ci, vp]),
     "mrmt3_adamw_step": (ci, [vp, vp, vp, vp, csz, vp, vp, cf, cf, cf, cf, cf, vp, vp]),
+    "mrmt3_counter_add": (ci, [vp, ci, vp]),
     "mrmt3_transpose": (ci, [vp, ci, vp, ci, ci, ci, vp]),
     "mrmt3_cast": (ci, [vp, ci, vp, ci, csz, vp]),
     "mrmt3_transpose_batched": (ci, [vp, vp, vp, vp, ci, ci, vp]),
@@ -150,7 +151,7 @@ def load():
     return lib
 
 
-MIN_VERSION = 112
+MIN_VERSION = 113
 COUNTER_NAMES = ("gemm_nt_tile", "gemm_nt8", "gemm_nt_geglu", "tn_group", "tn8", "tn_tile", "attn_fwd", "attn_bwd",
                  "attn_bwd_onepass", "attn_f32", "tn_f32", "gemm_nt_splitk", "gemm_nt_addnorm", "gemm_nt_normbwd",
                  "gemm_nt_geglubwd", "attn_fwd_varlen", "attn_bwd_varlen")
@@ -1028,6 +1029,13 @@ def adamw_step(p, g, m, v, lr_dev, step_dev, beta1=0.9, beta2=0.999, eps=1e-8, w
     _dev(p, g, m, v, lr_dev, step_dev)
     _check(load().mrmt3_adamw_step(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(lr_dev), _p(step_dev), beta1, beta2,
                                    eps, weight_decay, grad_scale, _p(shadow), _stream()), "adamw_step")
+
+
+def counter_add(ctr, delta=1):
+    """ctr[0] += delta on the device (int32 [1]), stream-ordered: graph-capture safe."""
+    _dev(ctr)
+    assert ctr.dtype == torch.int32 and ctr.numel() >= 1
+    _check(load().mrmt3_counter_add(_p(ctr), int(delta), _stream()), "counter_add")
 
 
 def transpose(src, out):

@@ -40,6 +40,18 @@ picks the capacity Tcap, and runs the decoder, the lm_head and the CE on Tcap pa
 unchanged.  The signature of a captured step gains Tcap; the pack kernel runs inside the graph on the static label buffer.
 Captured packed signatures are kept in a small LRU (MRMT3_PACK_GRAPHS, default 4).  Eviction follows the rules above: the
 device is drained and the graph dropped OUTSIDE any capture, and the garbage is collected before the next capture begins.
+
+Gradient accumulation (`accumulate_grad_batches=N`, Lightning's automatic-optimisation semantics).  `train_step` consumes one
+micro-batch; the optimizer steps after every N-th, or at `finish_accumulation()` for a partial cycle (an epoch's end).  With
+N > 1 a step has three phases, each its own part of the captured signature: "first" zeroes G and runs forward + backward,
+"middle" runs forward + backward, "last" runs forward + backward with the bucket cuts and exchanges, then AdamW.  N = 1 is
+the single phase of before (signature, graphs and launches unchanged).  The gradient producers all add into `flat.G`, so
+after the last micro-batch G holds the SUM over micro-batches (and, after the exchange, over ranks) of the per-micro-batch
+mean gradients; AdamW takes grad_scale = 1/(world*N), which is Lightning's loss/N per micro-batch — also for a partial cycle.
+Dropout salt: `step_dev` counts optimizer steps (AdamW's bias correction); with N > 1 the dropout kernels read `salt_dev`
+instead, a device counter of micro-batches bumped at the end of every micro-batch inside the step (mrmt3_counter_add), so
+the micro-batches of one cycle and every replay draw their own masks, the same in eager and replayed steps.  With N = 1
+`salt_dev` IS `step_dev`: the masks are those of the plain step.
 """
 from __future__ import annotations
 
@@ -81,7 +93,13 @@ class _CapturedStep:
 class Trainer:
     def __init__(self, model, lr: float = 2e-4, lr_lambda=None, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.01, weighted_loss: bool = False, layers_per_bucket: int = 4,
-                 graph: bool = None, grad_exchange_dtype=None, pack_targets: bool = None):
+                 graph: bool = None, grad_exchange_dtype=None, pack_targets: bool = None,
+                 accumulate_grad_batches: int = 1):
+        n_acc = int(accumulate_grad_batches)
+        if n_acc < 1 or n_acc != accumulate_grad_batches:
+            raise ValueError("accumulate_grad_batches must be an integer >= 1, got %r" % (accumulate_grad_batches,))
+        self.accumulate = n_acc
+        self._micro = 0                  # micro-batches of the current accumulation cycle already run
         if pack_targets is None:
             pack_targets = os.environ.get("MRMT3_PACK_TARGETS", "0") != "0"
         self.pack_targets = bool(pack_targets)
@@ -117,8 +135,10 @@ class Trainer:
         if self.world > 1:   # C2: identical replicas
             dist.broadcast(self.flat.P, src=0)
         self.last_loss = None
-        # every dropout mask of a step is salted in-kernel by the device step counter (see module docstring)
-        self.engine.step_dev = self.step_dev
+        # every dropout mask of a step is salted in-kernel by a device counter (see module docstring): the optimizer step
+        # counter itself, or with accumulation a micro-batch counter of its own
+        self.salt_dev = self.step_dev if n_acc == 1 else torch.zeros(1, device=dev, dtype=torch.int32)
+        self.engine.step_dev = self.salt_dev
         self.use_graph = (os.environ.get("MRMT3_TRAIN_GRAPH", "1") != "0") if graph is None else bool(graph)
         self._collective_stream_checked = False
         self.graph_warmup = 2            # eager steps per input signature before capture (tables, workspaces)
@@ -156,9 +176,19 @@ class Trainer:
         tcap = packing.capacity(lengths, B, L)
         return None if tcap == B * L else tcap
 
-    def _step_body(self, inputs, labels, targets_prev, audio, cut=None, tcap=None):
-        """Enqueues one optimizer step.  `cut(bucket_indices)` is called where a gradient bucket is complete (only
-        when collectives will run): under capture it closes the current graph segment.  tcap: packed decoder rows."""
+    def _phase(self):
+        """Phase of the next micro-batch: None without accumulation (the whole optimizer step), else "first" / "middle" /
+        "last" of its cycle."""
+        if self.accumulate == 1:
+            return None
+        if self._micro == 0:
+            return "first"
+        return "last" if self._micro == self.accumulate - 1 else "middle"
+
+    def _step_body(self, inputs, labels, targets_prev, audio, cut=None, tcap=None, phase=None):
+        """Enqueues one optimizer step, or with accumulation one micro-batch of it (`phase`, see _phase).  `cut(bucket_indices)`
+        is called where a gradient bucket is complete (only when collectives will run, only in a step that ends with AdamW):
+        under capture it closes the current graph segment.  tcap: packed decoder rows."""
         eng, flat = self.engine, self.flat
         eng.reset_deferred()                                 # nothing of an aborted capture / failed step leaks into this one
         eng._stream_ctr = 0                                  # dropout site ids are per-step (step_dev salts them)
@@ -174,9 +204,12 @@ class Trainer:
             logits, tape = eng.forward(mel, labels, targets_prev, training=True, need_grad=True, pack=plan)
             loss, dl = lib.cross_entropy(logits.reshape(-1, logits.shape[-1]), targets, want_grad=True,
                                          grad_dtype=torch.float32, weighted=self.weighted)
-        flat.G.zero_()
+        if phase in (None, "first"):
+            flat.G.zero_()
         self.buckets.reset()
-        if cut is None:
+        if phase in ("first", "middle"):                   # no exchange: the gradients keep accumulating in G
+            eng.backward(tape, dl)
+        elif cut is None:
             eng.backward(tape, dl, on_layer_done=self.buckets.on_layer_done)
             self.buckets.finish()
         else:
@@ -191,12 +224,17 @@ class Trainer:
             active = self.buckets.active
             eng.backward(tape, dl, on_layer_done=layer_done if active else None)     # ends with join_wgrad()
             cut([j for j in range(len(self.buckets.buckets)) if j not in sent] if active else [])
-        flat.adamw_step(self.lr_dev, self.step_dev, self.betas, self.eps, self.wd, grad_scale=1.0 / self.world)
+        if phase in (None, "last"):
+            flat.adamw_step(self.lr_dev, self.step_dev, self.betas, self.eps, self.wd,
+                            grad_scale=1.0 / (self.world * self.accumulate))
+        if self.accumulate > 1:
+            lib.counter_add(self.salt_dev, 1)               # the next micro-batch draws other masks
         return loss
 
     def train_step(self, inputs, labels, targets_prev=None, audio: bool = False):
-        """One optimizer step.  `inputs` is mel [B,Le,512] or, with audio=True, raw audio [B,n].
-        Returns the (device, un-synchronised) mean loss of this rank."""
+        """One optimizer step, or with accumulate_grad_batches = N > 1 one micro-batch (the optimizer steps after every N-th).
+        `inputs` is mel [B,Le,512] or, with audio=True, raw audio [B,n].  Returns the (device, un-synchronised) mean loss of
+        this rank over this (micro-)batch, undivided by N."""
         m, eng = self.model, self.engine
         m.train()
         if self.buckets.active and not self._collective_stream_checked:
@@ -215,11 +253,15 @@ class Trainer:
         tcap = self.pack_capacity(labels)
         if self.pack_targets and not labels.is_cuda:
             labels = labels.to(self.flat.G.device)          # CPU labels: lengths taken above, copied once
+        phase = self._phase()
         if self.use_graph:
-            loss = self._graph_step(inputs, labels, targets_prev, audio, tcap)
+            loss = self._graph_step(inputs, labels, targets_prev, audio, tcap, phase)
         else:
-            loss = self._step_body(inputs, labels, targets_prev, audio, tcap=tcap)
-        self.host_step += 1
+            loss = self._step_body(inputs, labels, targets_prev, audio, tcap=tcap, phase=phase)
+        self._micro += 1
+        if self._micro == self.accumulate:
+            self._micro = 0
+            self.host_step += 1
         if self.world > 1:   # C4: logged loss, reduced without blocking the host
             loss = loss.clone()
             dist.all_reduce(loss, op=dist.ReduceOp.SUM, async_op=True).wait()   # stream-level wait only
@@ -227,22 +269,50 @@ class Trainer:
         self.last_loss = loss
         return loss
 
+    def finish_accumulation(self) -> bool:
+        """Run the optimizer step of a partial accumulation cycle (the micro-batches left at an epoch's end, like Lightning):
+        exchange the accumulated gradients (not overlapped: backward is over), then AdamW with the same grad_scale
+        1/(world*N) as a full cycle.  Nothing happens when no micro-batch is pending.  Returns whether a step ran."""
+        if self._micro == 0:
+            return False
+        if self.lr_lambda is not None:
+            self.lr_dev.fill_(self.base_lr * self.lr_lambda(self.host_step))
+        self.buckets.reset()
+        self.buckets.finish()
+        self.flat.adamw_step(self.lr_dev, self.step_dev, self.betas, self.eps, self.wd,
+                             grad_scale=1.0 / (self.world * self.accumulate))
+        self._micro = 0
+        self.host_step += 1
+        return True
+
+    @property
+    def pending_micro_batches(self) -> int:
+        """Micro-batches run since the last optimizer step (0 <= n < accumulate_grad_batches)."""
+        return self._micro
+
+    @property
+    def optimizer_steps(self) -> int:
+        """Optimizer steps taken (what the LR schedule, max_steps and checkpoints count); same as host_step."""
+        return self.host_step
+
     # ---- hipGraph capture / replay of the step ---------------------------------------------------------------
-    def _graph_step(self, inputs, labels, targets_prev, audio, tcap=None):
+    def _graph_step(self, inputs, labels, targets_prev, audio, tcap=None, phase=None):
         sig = (bool(audio), tuple(inputs.shape), inputs.dtype, tuple(labels.shape),
                None if targets_prev is None else tuple(targets_prev.shape))
         if tcap is not None:
             sig = sig + (tcap,)
+        if phase is not None:
+            sig = sig + (phase,)
         cap = self._graphs.get(sig)
         if cap is None:
             seen = self._eager_seen.get(sig, 0)
             if seen < self.graph_warmup:
                 self._eager_seen[sig] = seen + 1
-                return self._step_body(inputs, labels, targets_prev, audio, tcap=tcap)
+                return self._step_body(inputs, labels, targets_prev, audio, tcap=tcap, phase=phase)
             if tcap is not None:
                 self._evict_packed(self.pack_graphs - 1)
             try:
-                cap = self._capture(sig, inputs, labels, targets_prev, audio, tcap)
+                cap = self._capture(sig, inputs, labels, targets_prev, audio, tcap, phase)
             except Exception as e:     # noqa: BLE001 — whatever a capture trips over, the eager step is still correct
                 # (nothing executed during the failed capture: the step below is the first to run; the launches the
                 # aborted capture had deferred are dropped — _after_failed_capture and _step_body reset them)
@@ -251,7 +321,7 @@ class Trainer:
                 warnings.warn("hipGraph capture of the training step failed (%s: %s)%s; continuing with eager launches"
                               % (type(e).__name__, _first_line(e), state))
                 self.use_graph = False
-                return self._step_body(inputs, labels, targets_prev, audio, tcap=tcap)
+                return self._step_body(inputs, labels, targets_prev, audio, tcap=tcap, phase=phase)
             if tcap is not None:
                 self._pack_lru.append(sig)
         elif tcap is not None:
@@ -384,7 +454,7 @@ class Trainer:
                 return True
         return False
 
-    def _capture(self, sig, inputs, labels, targets_prev, audio, tcap=None):
+    def _capture(self, sig, inputs, labels, targets_prev, audio, tcap=None, phase=None):
         """Record the step once (nothing executes during capture); `train_step` then replays it, this step included."""
         import gc
         eng = self.engine
@@ -450,7 +520,7 @@ class Trainer:
             with torch.cuda.stream(cs):
                 begin()
                 try:
-                    cap.loss = self._step_body(cap.inputs, cap.labels, cap.prev, audio, cut=cut, tcap=tcap)
+                    cap.loss = self._step_body(cap.inputs, cap.labels, cap.prev, audio, cut=cut, tcap=tcap, phase=phase)
                     g, state["g"] = state["g"], None
                     g.capture_end()
                     cap.tail = g
@@ -495,8 +565,13 @@ class Trainer:
     def save_checkpoint(self, path: str, epoch: int = 0):
         """Write weights + AdamW moments + step in the layout the reference's ModelCheckpoint produces, so
         either side can resume from it (`train.py:61-72`).  `.pt` / `.pth` paths get the bare state dict
-        (`train.py:105-116`)."""
+        (`train.py:105-116`).  Refused while micro-batches of an accumulation cycle are pending: their gradients live
+        only in G, which a checkpoint does not hold."""
         from . import checkpoint as ck
+        if self._micro:
+            raise RuntimeError("save_checkpoint: %d micro-batch(es) of an accumulation cycle are pending (their gradients are "
+                               "not part of a checkpoint); call finish_accumulation() first, or save after the cycle's "
+                               "optimizer step" % self._micro)
         torch.cuda.current_stream().synchronize()
         if str(path).endswith(".ckpt"):
             torch.save(ck.lightning_checkpoint(self.model, self, epoch), path)
@@ -515,7 +590,11 @@ class Trainer:
             step = ck.adamw_state_to_flat(blob["optimizer"], self.flat, order)
             step = max(step, blob["global_step"])
         self.host_step = step
+        self._micro = 0
         self.step_dev.fill_(step)
+        if self.accumulate > 1:          # the micro-batch salt; a checkpoint without it: past every salt it can have used
+            salt = (blob["extra"] or {}).get("dropout_salt")
+            self.salt_dev.fill_(step * self.accumulate if salt is None else int(salt))
         if blob["extra"]:
             self.engine.seed = int(blob["extra"]["dropout_seed"])
             self.engine._stream_ctr = int(blob["extra"]["dropout_stream_ctr"])

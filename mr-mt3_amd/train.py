@@ -18,6 +18,10 @@ The Slakh/ComMU dataset classes themselves are the reference's `dataset/` packag
 scope): put it on PYTHONPATH.  If it cannot be imported the driver STOPS with that message — it
 never silently substitutes synthetic data.
 
+Gradient accumulation: `cfg.trainer.accumulate_grad_batches` (the reference's `${grad_accum}`), else a top-level
+`grad_accum`, else 1 — Lightning's semantics (mrmt3/trainer.py): the optimizer steps after every N-th batch and after an
+epoch's last one; `+max_steps`, `trainer.log_every_n_steps`, the LR schedule and checkpoint steps count optimizer steps.
+
 `cfg.path` has the reference's meaning (`train.py:61-92`): a `.ckpt` resumes weights, AdamW moments and
 the step counter; a `.pth` only loads weights (`strict=False`); anything else is an error.  At the end
 rank 0 writes `<output_dir>/<model_type>_<dataset_type>/version_0/checkpoints/last.ckpt` (Lightning
@@ -103,20 +107,37 @@ class SkippingBatchSampler(torch.utils.data.BatchSampler):
         return itertools.islice(super().__iter__(), skip, None)
 
 
-def resume_position(global_step, steps_per_epoch):
+def accumulate_grad_batches(cfg) -> int:
+    """Micro-batches per optimizer step: `trainer.accumulate_grad_batches`, else a top-level `grad_accum`, else 1."""
+    tr = cfg.get("trainer")
+    n = tr.get("accumulate_grad_batches") if tr is not None else None
+    if n is None:
+        n = cfg.get("grad_accum")
+    return 1 if n is None else int(n)
+
+
+def resume_position(global_step, steps_per_epoch, accumulate=1):
     """(epoch, batches of that epoch already consumed) for a run that has taken `global_step` optimizer steps.  The
     position is derived from the step count alone: a checkpoint's `epoch` field is the epoch in progress OR the one
-    just completed depending on when it was written, the step count is unambiguous."""
+    just completed depending on when it was written, the step count is unambiguous.  `steps_per_epoch` is
+    the loader's length in batches; with `accumulate` = N batches per optimizer step an epoch takes ceil(len / N) steps
+    (the last one possibly partial), so the batches consumed are N per step taken in the epoch."""
     if steps_per_epoch <= 0:
         return 0, 0
-    return global_step // steps_per_epoch, global_step % steps_per_epoch
+    per_epoch = -(-steps_per_epoch // accumulate)
+    return global_step // per_epoch, (global_step % per_epoch) * accumulate
 
 
-def loader_batches(loader, device, epochs, max_steps, start_epoch=0, start_step=0, sampler=None, skip=0):
+def loader_batches(loader, device, epochs, max_steps, start_epoch=0, start_step=0, sampler=None, skip=0, accumulate=1):
     """(epoch, inputs, targets, targets_prev) from the reference's collated batches, moved to the device.  A resumed
     run continues at (start_epoch, start_step) and drops the first `skip` batches of that epoch (the ones the
-    interrupted run consumed): `max_steps` counts global steps, like Lightning's."""
+    interrupted run consumed): `max_steps` counts global optimizer steps, like Lightning's — with `accumulate` = N an
+    optimizer step ends at every N-th batch of an epoch and at its last batch."""
     n = start_step
+    try:
+        per_epoch = len(loader)
+    except TypeError:
+        per_epoch = None
     bs = getattr(loader, "batch_sampler", None)
     index_skip = isinstance(bs, SkippingBatchSampler)
     for ep in range(start_epoch, epochs):
@@ -134,7 +155,9 @@ def loader_batches(loader, device, epochs, max_steps, start_epoch=0, start_step=
             prev = batch[2] if len(batch) > 2 else None
             yield ep, inputs.to(device, non_blocking=True), targets.to(device, non_blocking=True), \
                 (None if prev is None else prev.to(device, non_blocking=True))
-            n += 1
+            pos = bi + (skip if index_skip and ep == start_epoch else 0)      # the batch's index in its epoch
+            if accumulate == 1 or (pos + 1) % accumulate == 0 or (per_epoch is not None and pos + 1 == per_epoch):
+                n += 1
 
 
 def main(argv=None):
@@ -164,8 +187,10 @@ def main(argv=None):
     # packed decoder rows (mrmt3/packing.py): `+pack_targets=true`; absent, MRMT3_PACK_TARGETS decides (default off)
     pack = cfg.get("pack_targets")
     pack = None if pack is None else str(pack).lower() in ("1", "true", "yes", "on")
+    accum = accumulate_grad_batches(cfg)
     trainer = Trainer(task.model, lr=float(cfg.optim.lr), lr_lambda=lam,
-                      weighted_loss=type(task).__name__ == "MT3NetWeightedLoss", pack_targets=pack)
+                      weighted_loss=type(task).__name__ == "MT3NetWeightedLoss", pack_targets=pack,
+                      accumulate_grad_batches=accum)
     task.model.engine.seed = int(cfg.seed)
     with_prev = "WithPrev" in type(task).__name__
     synthetic = bool(cfg.get("synthetic", False))
@@ -181,7 +206,7 @@ def main(argv=None):
         if path.endswith(".ckpt"):
             start = trainer.resume(path)
             if train_loader is not None:
-                start_epoch, skip = resume_position(start, len(train_loader))
+                start_epoch, skip = resume_position(start, len(train_loader), accum)
             if rank == 0:
                 print(f"Resuming from {path} at step {start}, epoch {start_epoch} (+{skip} batches)", flush=True)
         elif path.endswith(".pth"):
@@ -197,8 +222,11 @@ def main(argv=None):
     log_every = max(1, int(cfg.trainer.get("log_every_n_steps", 100)))
     if synthetic:
         steps = 10 if max_steps is None else max_steps
-        for it, (audio, labels, prev) in enumerate(synthetic_batches(cfg, rank, device, steps, with_prev), start):
+        for k, (audio, labels, prev) in enumerate(synthetic_batches(cfg, rank, device, steps * accum, with_prev)):
             loss = trainer.train_step(audio, labels, prev, audio=True)
+            if trainer.pending_micro_batches:
+                continue                 # (mid-cycle: no optimizer step yet)
+            it = start + (k + 1) // accum - 1
             if rank == 0 and (it % log_every == 0 or it == start + steps - 1):
                 print(f"step {it} train_loss {loss.item():.4f}", flush=True)
     else:
@@ -217,17 +245,28 @@ def main(argv=None):
             if rank == 0 and acc[1].item() > 0:
                 print(f"epoch {ep} val_loss {(acc[0] / acc[1]).item():.4f}", flush=True)
 
-        if resumed:
-            validate(start_epoch)        # the reference validates the loaded weights before fit (train.py:61-87)
-        for ep, mel, labels, prev in loader_batches(train_loader, device, int(cfg.num_epochs), max_steps,
-                                                    start_epoch, start, sampler, skip):
-            if ep != last_ep and (last_ep + 1) % val_every == 0:
-                validate(last_ep)
-            last_ep = ep
-            loss = trainer.train_step(mel, labels, prev, audio=False)
+        def stepped(loss):
+            """An optimizer step has run; `loss` is its last micro-batch's."""
+            nonlocal it
             if rank == 0 and it % log_every == 0:
                 print(f"step {it} train_loss {loss.item():.4f}", flush=True)
             it += 1
+
+        if resumed:
+            validate(start_epoch)        # the reference validates the loaded weights before fit (train.py:61-87)
+        for ep, mel, labels, prev in loader_batches(train_loader, device, int(cfg.num_epochs), max_steps,
+                                                    start_epoch, start, sampler, skip, accum):
+            if ep != last_ep:
+                if trainer.finish_accumulation():      # the epoch's partial accumulation cycle steps before validation
+                    stepped(loss)
+                if (last_ep + 1) % val_every == 0:
+                    validate(last_ep)
+            last_ep = ep
+            loss = trainer.train_step(mel, labels, prev, audio=False)
+            if not trainer.pending_micro_batches:
+                stepped(loss)
+        if trainer.finish_accumulation():
+            stepped(loss)
         if rank == 0 and loss is not None and (it - 1) % log_every != 0:
             print(f"step {it - 1} train_loss {loss.item():.4f}", flush=True)
         if (last_ep + 1) % val_every == 0:
