@@ -462,6 +462,39 @@ int mrmt3_decoder_begin(mrmt3_decoder* dec, const mrmt3_decoder_weights* w, cons
  * n_prefix steps of mrmt3_decoder_run only fill the self-attention cache, token steps follow.
  * Needs n_prefix + token steps <= max_len.  mrmt3_decoder_begin clears the prefix. */
 int mrmt3_decoder_set_prefix(mrmt3_decoder* dec, const float* prefix, int n_prefix, void* stream);
+/* Optional, after mrmt3_decoder_begin: greedy decode with banned tokens.  banned_mask is a caller-owned
+ * device [vocab] uint8 (non-zero = banned) or NULL (no ban, the plain argmax).  Banned logits score -inf
+ * before the argmax, NaN included (HF's NoBadWordsLogitsProcessor ahead of greedy search).  Switching
+ * between a mask and none re-captures the step graph.  mrmt3_decoder_begin clears the ban.
+ * Errors in beam mode (the mask is a parameter of mrmt3_decoder_begin_beam there). */
+int mrmt3_decoder_set_ban(mrmt3_decoder* dec, const uint8_t* banned_mask, void* stream);
+/* Beam search (HF 4.18 beam_search + BeamSearchScorer, early_stopping = False, one hypothesis per group;
+ * max_length counts new tokens).  Row r = g * num_beams + j of the batch is beam j of group g; cross_kv
+ * holds groups * num_beams rows (each group's K|V repeated num_beams times).  Caller-owned device buffers:
+ *   tokens_out  int64 [groups*num_beams][max_len+1]  row r's token of step t at [r][t+1] (start at [r][0])
+ *   backptr     int32 [max_len][groups*num_beams][2] {parent row, token} of every row after step t
+ *   beam_scores f32   [groups*num_beams]             running beam scores (sums of log-probabilities)
+ *   hyps        int32 [groups][32]                   per group: [0] hypotheses held, [1] worst kept score
+ *               (f32 bits), [2] done, [3] length of the chosen hypothesis (after finalize), then up to 9
+ *               entries {score (f32 bits), end step e, row}: start token + row's tokens of steps 0..e-1.
+ * banned_mask: device [vocab] uint8 or NULL; banned tokens score -inf after the log-softmax (whose
+ * normaliser still includes them).  Each step appends a select kernel (one workgroup per group: log-softmax,
+ * top 2*num_beams of num_beams*vocab, the scorer walk) and a KV-cache reorder kernel to the step graph; a
+ * done group emits pad_id.  mrmt3_decoder_run / _poll / _logits work as in greedy mode (state [1] = every
+ * group done, [2] = the step it happened).  MRMT3_ERR_INVALID_ARG for num_beams outside 1..8,
+ * groups * num_beams > max_batch, or num_beams * vocab * 4 bytes > 64 KiB.  mrmt3_decoder_set_prefix
+ * is refused in beam mode. */
+int mrmt3_decoder_begin_beam(mrmt3_decoder* dec, const mrmt3_decoder_weights* w, const void* cross_kv,
+                             int groups, int num_beams, int enc_len, int64_t* tokens_out, int start_id,
+                             int eos_id, int pad_id, float length_penalty, const uint8_t* banned_mask,
+                             int32_t* backptr, float* beam_scores, int32_t* hyps, void* stream);
+/* After the beam steps (once per decode): BeamSearchScorer.finalize.  Groups not done add their running
+ * beams; the best hypothesis of each group (the last added of equal best scores) is read back through the
+ * backpointers into out_ids [groups][ld] int64: start token, tokens, eos_id when the hypothesis is
+ * shorter than 1 + max_length, pad_id to ld.  hyps[g][3] receives the hypothesis length (start token
+ * included, EOS excluded): the caller's output width is min(max over groups + 1, 1 + max_length).
+ * Needs ld >= 1 + max_length and max_length = the number of steps run when a group is not done. */
+int mrmt3_decoder_beam_finalize(mrmt3_decoder* dec, int64_t* out_ids, int ld, int max_length, void* stream);
 /* Run n_steps decode steps (graph replays; captured on first use).  No host synchronisation. */
 int mrmt3_decoder_run(mrmt3_decoder* dec, int n_steps, void* stream);
 /* 1 if the current configuration is being replayed from a captured hipGraph (0 = plain launches). */

@@ -16,7 +16,8 @@
 // the re-read of a weight row by the other sequences is an L2 hit), larger batches (<= 256) multiply 16 rows by
 // 16 sequences on the matrix cores with K split over a workgroup; the 45.6 MB (bf16) of per-step weights stay
 // resident in the 256 MB Infinity Cache.  mrmt3_decoder_set_prefix feeds memory rows before the start token
-// (the V1 segment-memory decode).
+// (the V1 segment-memory decode).  mrmt3_decoder_set_ban / mrmt3_decoder_begin_beam swap the step's tail for a masked
+// argmax or for beam search (select + KV-cache reorder); the 65 kernels before it are shared.
 #include "common.h"
 
 #define DMODEL 512
@@ -393,10 +394,14 @@ __device__ __forceinline__ bool argmax_beats(float v, int i, float bv, int bi) {
   return i < bi;
 }
 
+// BAN: banned tokens (ban[c] != 0, a device [V] uint8 mask) score -inf before the argmax, NaN included, as HF's
+// NoBadWordsLogitsProcessor does ahead of the greedy argmax.  The unbanned kernel is this body with BAN = false.
+// (`ban` is the last argument, so the unbanned instantiation keeps every other argument's offset and its code.)
+template <bool BAN>
 __global__ __launch_bounds__(512) void dec_argmax(const float* __restrict__ logits, int V, int B, int64_t* __restrict__ tokens,
                                                   int tok_ld, const float* __restrict__ embed, const float* __restrict__ pos,
                                                   float* __restrict__ x, int* __restrict__ state, int eos, int pad,
-                                                  const float* __restrict__ prefix) {
+                                                  const float* __restrict__ prefix, const uint8_t* __restrict__ ban) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int p = state[ST_T];            // position just processed
   const int npre = state[ST_NPRE];
@@ -429,6 +434,11 @@ __global__ __launch_bounds__(512) void dec_argmax(const float* __restrict__ logi
       float lv[8];
 #pragma unroll
       for (int u = 0; u < 8; ++u) lv[u] = (c0 + 64 * u < V) ? logits[(size_t)b * V + c0 + 64 * u] : -INFINITY;
+      if (BAN) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+          if (c0 + 64 * u < V && ban[c0 + 64 * u]) lv[u] = -INFINITY;
+      }
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         const int c = c0 + 64 * u;
@@ -453,6 +463,275 @@ __global__ __launch_bounds__(512) void dec_argmax(const float* __restrict__ logi
   }
   __syncthreads();
   if (tid == 0) dec_step_close(state, B, p, t, true);
+}
+
+// ---- beam search tail (HF 4.18 beam_search + BeamSearchScorer, early_stopping=False, one hypothesis kept) --------
+// Row r = g * k + j is beam j of group (input segment) g.  Per group the caller owns a record of BEAM_HREC int32:
+//   [0] hypotheses held   [1] worst kept score (f32 bits; 1e9 while fewer than k)   [2] done   [3] length of the
+//   chosen hypothesis (written by the finalize kernel)   then up to k + 1 entries {score (f32 bits), end step, row}.
+// A hypothesis {score, end step e, row r} is the start token plus row r's tokens of steps 0..e-1, read back through
+// the backpointers bp[s][r] = {parent row, token} (int32 [max_len][rows][2]).
+#define BEAM_MAXK 8
+#define BEAM_HREC 32
+#define BEAM_HYP0 4
+
+// BeamHypotheses.add: the list keeps insertion order; past k entries the lowest score leaves (the earliest of equal
+// lowest scores, as sorted((score, index))[0] picks), and the worst score becomes the lowest of the rest.
+__device__ void beam_hyp_add(int* rec, int k, float score, int end_step, int row) {
+  int n = rec[0];
+  float worst = __int_as_float(rec[1]);
+  if (!(n < k || score > worst)) return;
+  int* e = rec + BEAM_HYP0 + 3 * n;
+  e[0] = __float_as_int(score); e[1] = end_step; e[2] = row;
+  ++n;
+  if (n > k) {
+    int lo = 0;
+    for (int i = 1; i < n; ++i)
+      if (__int_as_float(rec[BEAM_HYP0 + 3 * i]) < __int_as_float(rec[BEAM_HYP0 + 3 * lo])) lo = i;
+    for (int i = lo; i + 1 < n; ++i)
+      for (int f = 0; f < 3; ++f) rec[BEAM_HYP0 + 3 * i + f] = rec[BEAM_HYP0 + 3 * (i + 1) + f];
+    --n;
+    worst = __int_as_float(rec[BEAM_HYP0]);
+    for (int i = 1; i < n; ++i) worst = fminf(worst, __int_as_float(rec[BEAM_HYP0 + 3 * i]));
+  } else {
+    worst = (worst < score) ? worst : score;
+  }
+  rec[0] = n;
+  rec[1] = __float_as_int(worst);
+}
+
+// (value, index) pair that ranks first in argmax_beats order; index -1 = none.
+__device__ __forceinline__ void rank_reduce_wave(float& v, int& i) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float ov = __shfl_xor(v, off, 64);
+    const int oi = __shfl_xor(i, off, 64);
+    if (argmax_beats(ov, oi, v, i)) { v = ov; i = oi; }
+  }
+}
+__device__ __forceinline__ float nanmax(float a, float b) { return (b != b || b > a) ? b : a; }
+
+// One workgroup (8 waves) per group.  The k rows' log-softmax (+ ban, + beam score) fill LDS ([k][V] f32), the top 2k
+// of those k*V candidates come out one per round (round r takes the best candidate ranked below round r-1's winner, so
+// nothing is marked; order: score descending, NaN first, then flat index beam * V + token ascending), then lane 0
+// walks them as BeamSearchScorer.process does.  The workgroup writes every row's next token, parent and score, the
+// backpointers of step t, the next input x[row] = embed[token] + pos[t + 1] and, for a group that is done, the
+// finished flags of its rows; the last workgroup folds them into ST_ALL / ST_FIN and advances the step.
+__global__ __launch_bounds__(512) void dec_beam_select(const float* __restrict__ logits, int V, int k, int rows,
+                                                       int64_t* __restrict__ tokens, int tok_ld,
+                                                       const float* __restrict__ embed, const float* __restrict__ pos,
+                                                       float* __restrict__ x, int* __restrict__ state, int eos, int pad,
+                                                       float length_penalty, const uint8_t* __restrict__ ban,
+                                                       float* __restrict__ bscore, int* __restrict__ bp,
+                                                       int* __restrict__ hyp) {
+  extern __shared__ float sc[];                 // [k][V] candidate scores
+  __shared__ float red_v[8][BEAM_MAXK];
+  __shared__ int red_i[8];
+  __shared__ float top_v[2 * BEAM_MAXK];
+  __shared__ int top_i[2 * BEAM_MAXK];
+  __shared__ int n_parent[BEAM_MAXK], n_tok[BEAM_MAXK];
+  __shared__ float n_score[BEAM_MAXK];
+  __shared__ int was_done;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g = blockIdx.x, r0 = g * k;
+  const int t = state[ST_T];                    // token step (beam mode has no prefix)
+  int* rec = hyp + (size_t)g * BEAM_HREC;
+  if (tid == 0) was_done = rec[2];
+  __syncthreads();
+  if (was_done) {
+    // a finished group emits pad and keeps its rows (BeamSearchScorer.process pads a done group)
+    if (tid < k) { n_parent[tid] = r0 + tid; n_tok[tid] = pad; n_score[tid] = 0.f; }
+  } else {
+    const float* lg = logits + (size_t)r0 * V;
+    // row max (NaN-propagating, as log_softmax of a row holding a NaN is NaN everywhere), then sum of exp
+    float m[BEAM_MAXK], se[BEAM_MAXK];
+#pragma unroll
+    for (int j = 0; j < BEAM_MAXK; ++j) {
+      m[j] = -INFINITY;
+      if (j < k)
+        for (int c = tid; c < V; c += 512) m[j] = nanmax(m[j], lg[(size_t)j * V + c]);
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) m[j] = nanmax(m[j], __shfl_xor(m[j], off, 64));
+      if (lane == 0) red_v[wave][j] = m[j];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < BEAM_MAXK; ++j) {
+      float mm = red_v[0][j];
+#pragma unroll
+      for (int w = 1; w < 8; ++w) mm = nanmax(mm, red_v[w][j]);
+      m[j] = mm;
+      se[j] = 0.f;
+      if (j < k)
+        for (int c = tid; c < V; c += 512) se[j] += expf(lg[(size_t)j * V + c] - mm);
+      se[j] = wave_sum(se[j]);
+    }
+    __syncthreads();
+    if (lane == 0) {
+#pragma unroll
+      for (int j = 0; j < BEAM_MAXK; ++j) red_v[wave][j] = se[j];
+    }
+    __syncthreads();
+    for (int j = 0; j < k; ++j) {
+      float s = 0.f;
+#pragma unroll
+      for (int w = 0; w < 8; ++w) s += red_v[w][j];
+      const float lse = logf(s), bs = bscore[r0 + j];
+      for (int c = tid; c < V; c += 512) {
+        const float lp = (lg[(size_t)j * V + c] - m[j]) - lse;          // log_softmax, as torch computes it
+        sc[j * V + c] = (ban != nullptr && ban[c]) ? -INFINITY : lp + bs;
+      }
+    }
+    __syncthreads();
+    // top 2k, one per round
+    const int n = k * V;
+    float pv = 0.f;
+    int pi = -1;
+    for (int rnk = 0; rnk < 2 * k; ++rnk) {
+      float bv = -INFINITY;
+      int bi = -1;
+      for (int c = tid; c < n; c += 512) {
+        const float v = sc[c];
+        if ((pi < 0 || argmax_beats(pv, pi, v, c)) && argmax_beats(v, c, bv, bi)) { bv = v; bi = c; }
+      }
+      rank_reduce_wave(bv, bi);
+      if (lane == 0) { red_v[wave][0] = bv; red_i[wave] = bi; }
+      __syncthreads();
+      bv = red_v[0][0]; bi = red_i[0];
+#pragma unroll
+      for (int w = 1; w < 8; ++w)
+        if (argmax_beats(red_v[w][0], red_i[w], bv, bi)) { bv = red_v[w][0]; bi = red_i[w]; }
+      if (tid == 0) { top_v[rnk] = bv; top_i[rnk] = bi; }
+      pv = bv; pi = bi;
+      __syncthreads();
+    }
+    if (tid == 0) {
+      // BeamSearchScorer.process: cur_len = 1 + t (start token included)
+      const float denom = powf((float)(t + 1), length_penalty);
+      int nb = 0;
+      for (int rnk = 0; rnk < 2 * k && nb < k; ++rnk) {
+        const int c = max(top_i[rnk], 0), j = c / V, tok = c - j * V;
+        if (tok == eos) {
+          if (rnk >= k) continue;                 // an EOS below the top k is not a hypothesis
+          beam_hyp_add(rec, k, top_v[rnk] / denom, t, r0 + j);
+        } else {
+          n_parent[nb] = r0 + j; n_tok[nb] = tok; n_score[nb] = top_v[rnk]; ++nb;
+        }
+      }
+      for (; nb < k; ++nb) { n_parent[nb] = r0 + nb; n_tok[nb] = pad; n_score[nb] = -INFINITY; }   // unreachable: <= k EOS
+      // BeamHypotheses.is_done(best candidate score, cur_len), early_stopping = False
+      if (rec[0] >= k && __int_as_float(rec[1]) >= top_v[0] / denom) rec[2] = 1;
+    }
+  }
+  __syncthreads();
+  const float* pr = pos + (size_t)(t + 1) * DMODEL;
+  for (int j = 0; j < k; ++j) {
+    const int row = r0 + j, tok = n_tok[j];
+    x[(size_t)row * DMODEL + tid] = embed[(size_t)tok * DMODEL + tid] + pr[tid];      // 512 threads = DMODEL
+  }
+  if (tid < k) {
+    const int row = r0 + tid;
+    bscore[row] = n_score[tid];
+    bp[((size_t)t * rows + row) * 2] = n_parent[tid];
+    bp[((size_t)t * rows + row) * 2 + 1] = n_tok[tid];
+    tokens[(size_t)row * tok_ld + t + 1] = n_tok[tid];
+  }
+  __syncthreads();
+  if (tid == 0) {
+    if (rec[2])
+      for (int j = 0; j < k; ++j) __hip_atomic_store(&state[ST_FLAGS + r0 + j], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    dec_step_close(state, rows, t, t, true);
+  }
+}
+
+// KV-cache reorder after dec_beam_select: positions 0..t of every layer's self-attention K and V move from row
+// parent(row) to row, for each row whose parent is another row.  No staging buffer: a parent is always in the row's own
+// group, and one thread owns the same 16-byte slots of every row of a group, so it loads the source of every slot it
+// will write into registers (<= 8 rows x 2 slots), waits for them, then stores: any parent map, swaps and
+// one parent with several children included, is read before it is written.  Work item = (group, layer, K|V, 8 KB
+// chunk of the live prefix); a fixed grid strides over the items that exist at this step (t is read on the device).
+#define REORDER_THREADS 256
+#define REORDER_U4 (2 * REORDER_THREADS)   // 16-byte slots per row per work item
+__global__ __launch_bounds__(REORDER_THREADS) void dec_beam_reorder(char* __restrict__ kc, char* __restrict__ vc,
+                                                                    size_t layer_bytes, size_t row_bytes, int pos_bytes,
+                                                                    int n_layers, int groups, int k,
+                                                                    const int* __restrict__ bp,
+                                                                    const int* __restrict__ state) {
+  const int t1 = state[ST_T];                   // the select kernel has advanced it: live positions 0..t1-1
+  const int rows = groups * k;
+  const size_t n16 = (size_t)t1 * pos_bytes / 16;
+  const int chunks = (int)((n16 + REORDER_U4 - 1) / REORDER_U4);
+  const int items = groups * 2 * n_layers * chunks;
+  const int* par = bp + (size_t)(t1 - 1) * rows * 2;
+  for (int it = blockIdx.x; it < items; it += gridDim.x) {
+    const int ch = it % chunks, lk = (it / chunks) % (2 * n_layers), g = it / (chunks * 2 * n_layers);
+    char* base = ((lk & 1) ? vc : kc) + (size_t)(lk >> 1) * layer_bytes;
+    int pj[BEAM_MAXK];
+    bool any = false;
+#pragma unroll
+    for (int j = 0; j < BEAM_MAXK; ++j) {
+      pj[j] = (j < k) ? par[(size_t)(g * k + j) * 2] : g * k + j;
+      any |= pj[j] != g * k + j;
+    }
+    if (!any) continue;
+    u32x4 buf[BEAM_MAXK][2];
+#pragma unroll
+    for (int j = 0; j < BEAM_MAXK; ++j)
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const size_t e = (size_t)ch * REORDER_U4 + u * REORDER_THREADS + threadIdx.x;
+        if (pj[j] != g * k + j && e < n16) buf[j][u] = ((const u32x4*)(base + (size_t)pj[j] * row_bytes))[e];
+      }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int j = 0; j < BEAM_MAXK; ++j)
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const size_t e = (size_t)ch * REORDER_U4 + u * REORDER_THREADS + threadIdx.x;
+        if (pj[j] != g * k + j && e < n16) ((u32x4*)(base + (size_t)(g * k + j) * row_bytes))[e] = buf[j][u];
+      }
+  }
+}
+
+// Beam scores [0, -1e9, ...] per group, empty hypothesis records.
+__global__ void dec_beam_begin_kernel(int groups, int k, float* bscore, int* hyp) {
+  for (int i = threadIdx.x; i < groups * k; i += blockDim.x) bscore[i] = (i % k == 0) ? 0.f : -1e9f;
+  for (int g = threadIdx.x; g < groups; g += blockDim.x) {
+    int* rec = hyp + (size_t)g * BEAM_HREC;
+    rec[0] = 0; rec[1] = __float_as_int(1e9f); rec[2] = 0; rec[3] = 0;
+  }
+}
+
+// BeamSearchScorer.finalize: the running beams of a group that is not done become hypotheses (length 1 + T, T = steps
+// run), the best one (the last added of equal best scores: stable sort + pop) is read back through the backpointers
+// into out[g] = start, tokens..., EOS when shorter than 1 + max_length, pad to ld.  One thread per group.
+__global__ void dec_beam_finalize_kernel(int groups, int k, int rows, const int* __restrict__ state,
+                                        const float* __restrict__ bscore, const int* __restrict__ bp, int* __restrict__ hyp,
+                                        float length_penalty, int64_t* __restrict__ out, int ld, int max_length,
+                                        int start, int eos, int pad) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= groups) return;
+  int* rec = hyp + (size_t)g * BEAM_HREC;
+  const int T = state[ST_T];
+  if (!rec[2]) {
+    const float denom = powf((float)(T + 1), length_penalty);
+    for (int j = 0; j < k; ++j) beam_hyp_add(rec, k, bscore[g * k + j] / denom, T, g * k + j);
+  }
+  int best = 0;
+  for (int i = 1; i < rec[0]; ++i)
+    if (__int_as_float(rec[BEAM_HYP0 + 3 * i]) >= __int_as_float(rec[BEAM_HYP0 + 3 * best])) best = i;
+  const int e = min(rec[BEAM_HYP0 + 3 * best + 1], max_length);
+  int r = rec[BEAM_HYP0 + 3 * best + 2];
+  int64_t* o = out + (size_t)g * ld;
+  o[0] = start;
+  for (int s = e - 1; s >= 0; --s) {
+    const int* b = bp + ((size_t)s * rows + r) * 2;
+    o[s + 1] = b[1];
+    r = b[0];
+  }
+  const int len = 1 + e;
+  for (int c = len; c < ld; ++c) o[c] = (c == len && len < 1 + max_length) ? eos : pad;
+  rec[3] = len;
 }
 
 // position 0 becomes the first memory row instead of the start token
@@ -490,8 +769,19 @@ struct mrmt3_decoder {
       *w_wi[64], *w_wo[64];
   const void* cross_kv;
   const float* prefix;   // [B][n_prefix][d] f32 memory rows fed before the start token (or null)
-  int B, encLen, eos, pad;
+  int B, encLen, eos, pad, start;
   int64_t* tokens;
+  // what the step's tail bakes into the graph: k = 0 greedy (ban = null: the plain argmax), k > 0 beam search
+  struct Tail {
+    int k, groups;
+    float length_penalty;
+    const uint8_t* ban;
+    float* bscore;
+    int* bp;
+    int* hyp;
+  } tail;
+  Tail cap_tail;    // tail of the captured graph
+  int n_prefix;     // set by mrmt3_decoder_set_prefix since the last begin
   hipGraph_t graph;
   hipGraphExec_t exec;
   int captured;     // 1 = exec valid for the current (B, encLen, pointers)
@@ -556,16 +846,62 @@ extern "C" int mrmt3_decoder_begin(mrmt3_decoder* D, const mrmt3_decoder_weights
     D->ln_ff[l] = w->ln_ff[l]; D->w_wi[l] = w->w_wi[l]; D->w_wo[l] = w->w_wo[l];
   }
   D->cross_kv = cross_kv; D->B = batch; D->encLen = enc_len; D->tokens = tokens_out; D->eos = eos_id; D->pad = pad_id;
+  D->start = start_id;
   if (!same) D->captured = 0;
+  memset(&D->tail, 0, sizeof(D->tail));
+  D->n_prefix = 0;
   hipLaunchKernelGGL(dec_begin_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, batch, tokens_out, D->maxLen + 1,
                      (const float*)w->embed, w->pos, D->x, D->state, start_id);
   MR_CHECK_LAUNCH("decoder_begin");
   return MRMT3_OK;
 }
 
+extern "C" int mrmt3_decoder_set_ban(mrmt3_decoder* D, const uint8_t* banned_mask, void* stream) {
+  (void)stream;
+  MR_CHECK_ARG(D && D->tokens, "decoder_set_ban: call decoder_begin first");
+  MR_CHECK_ARG(D->tail.k == 0, "decoder_set_ban: beam mode takes its mask in decoder_begin_beam");
+  D->tail.ban = banned_mask;
+  return MRMT3_OK;
+}
+
+extern "C" int mrmt3_decoder_begin_beam(mrmt3_decoder* D, const mrmt3_decoder_weights* w, const void* cross_kv, int groups,
+                                        int num_beams, int enc_len, int64_t* tokens_out, int start_id, int eos_id,
+                                        int pad_id, float length_penalty, const uint8_t* banned_mask, int32_t* backptr,
+                                        float* beam_scores, int32_t* hyps, void* stream) {
+  MR_CHECK_ARG(D && w && cross_kv && tokens_out && backptr && beam_scores && hyps, "decoder_begin_beam: null pointer");
+  MR_CHECK_ARG(num_beams >= 1 && num_beams <= BEAM_MAXK, "decoder_begin_beam: need 1 <= num_beams <= 8, got %d", num_beams);
+  MR_CHECK_ARG(groups > 0 && (long)groups * num_beams <= D->maxB, "decoder_begin_beam: groups x num_beams (%d x %d) exceeds max_batch %d",
+               groups, num_beams, D->maxB);
+  MR_CHECK_ARG(D->V >= 2 && (size_t)num_beams * D->V * sizeof(float) <= 65536,
+               "decoder_begin_beam: num_beams x vocab scores must fit 64 KiB of LDS");
+  MR_CHECK_ARG(D->n_prefix == 0, "decoder_begin_beam: a prefix is set on the handle");
+  int rc = mrmt3_decoder_begin(D, w, cross_kv, groups * num_beams, enc_len, tokens_out, start_id, eos_id, pad_id, stream);
+  if (rc != MRMT3_OK) return rc;
+  D->tail.k = num_beams; D->tail.groups = groups; D->tail.length_penalty = length_penalty; D->tail.ban = banned_mask;
+  D->tail.bscore = beam_scores; D->tail.bp = backptr; D->tail.hyp = hyps;
+  hipLaunchKernelGGL(dec_beam_begin_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, groups, num_beams, beam_scores, hyps);
+  MR_CHECK_LAUNCH("decoder_begin_beam");
+  return MRMT3_OK;
+}
+
+extern "C" int mrmt3_decoder_beam_finalize(mrmt3_decoder* D, int64_t* out_ids, int ld, int max_length, void* stream) {
+  MR_CHECK_ARG(D && out_ids, "decoder_beam_finalize: null pointer");
+  MR_CHECK_ARG(D->tokens && D->tail.k > 0, "decoder_beam_finalize: call decoder_begin_beam first");
+  MR_CHECK_ARG(max_length >= 0 && max_length <= D->maxLen && ld >= 1 + max_length,
+               "decoder_beam_finalize: need 0 <= max_length <= max_len and ld >= 1 + max_length");
+  const mrmt3_decoder::Tail& T = D->tail;
+  hipLaunchKernelGGL(dec_beam_finalize_kernel, dim3((unsigned)ceil_div(T.groups, 64)), dim3(64), 0, (hipStream_t)stream,
+                     T.groups, T.k, D->B, (const int*)D->state, (const float*)T.bscore, (const int*)T.bp, T.hyp,
+                     T.length_penalty, out_ids, ld, max_length, D->start, D->eos, D->pad);
+  MR_CHECK_LAUNCH("decoder_beam_finalize");
+  return MRMT3_OK;
+}
+
 extern "C" int mrmt3_decoder_set_prefix(mrmt3_decoder* D, const float* prefix, int n_prefix, void* stream) {
   MR_CHECK_ARG(D && D->tokens, "decoder_set_prefix: call decoder_begin first");
   MR_CHECK_ARG(prefix && n_prefix > 0 && n_prefix < D->maxLen, "decoder_set_prefix: need 0 < n_prefix < max_len rows");
+  MR_CHECK_ARG(D->tail.k == 0, "decoder_set_prefix: not available in beam mode");
+  D->n_prefix = n_prefix;
   if (D->prefix != prefix) { D->prefix = prefix; D->captured = 0; }   // pointer is baked into the graph
   hipLaunchKernelGGL(dec_prefix_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, D->B, n_prefix, prefix, D->w.pos,
                      D->x, D->state);
@@ -575,6 +911,31 @@ extern "C" int mrmt3_decoder_set_prefix(mrmt3_decoder* D, const float* prefix, i
 
 template <typename TW>
 static int launch_step(mrmt3_decoder* D, hipStream_t s);
+
+// the step's last kernel(s): greedy argmax (banned or not), or the beam select + KV-cache reorder
+static void launch_tail(mrmt3_decoder* D, hipStream_t s) {
+  const int B = D->B, V = D->V;
+  if (D->tail.k > 0) {
+    const mrmt3_decoder::Tail& T = D->tail;
+    hipLaunchKernelGGL(dec_beam_select, dim3((unsigned)T.groups), dim3(512), (size_t)T.k * V * sizeof(float), s, D->logits,
+                       V, T.k, B, D->tokens, D->maxLen + 1, (const float*)D->w.embed, D->w.pos, D->x, D->state, D->eos,
+                       D->pad, T.length_penalty, T.ban, T.bscore, T.bp, T.hyp);
+    const size_t esz = D->wdt == MRMT3_BF16 ? 2 : 4;
+    const size_t row_bytes = (size_t)D->maxLen * D->inner * esz, layer_bytes = (size_t)D->maxB * row_bytes;
+    const size_t max_items = (size_t)T.groups * 2 * D->L * ceil_div((int)(row_bytes / 16), REORDER_U4);
+    hipLaunchKernelGGL(dec_beam_reorder, dim3((unsigned)std::min<size_t>(max_items, 2048)), dim3(REORDER_THREADS), 0, s,
+                       (char*)D->kc, (char*)D->vc, layer_bytes, row_bytes, (int)(D->inner * esz), D->L, T.groups, T.k,
+                       (const int*)T.bp, (const int*)D->state);
+  } else if (D->tail.ban) {
+    hipLaunchKernelGGL(dec_argmax<true>, dim3((unsigned)ceil_div(B, 8)), dim3(512), 0, s, D->logits, V, B, D->tokens,
+                       D->maxLen + 1, (const float*)D->w.embed, D->w.pos, D->x, D->state, D->eos, D->pad, D->prefix,
+                       D->tail.ban);
+  } else {
+    hipLaunchKernelGGL(dec_argmax<false>, dim3((unsigned)ceil_div(B, 8)), dim3(512), 0, s, D->logits, V, B, D->tokens,
+                       D->maxLen + 1, (const float*)D->w.embed, D->w.pos, D->x, D->state, D->eos, D->pad, D->prefix,
+                       (const uint8_t*)nullptr);
+  }
+}
 
 // batch > 8, bf16 weights: projections on the matrix cores, 16 sequences per wave
 static int launch_step_mfma(mrmt3_decoder* D, hipStream_t s) {
@@ -609,8 +970,7 @@ static int launch_step_mfma(mrmt3_decoder* D, hipStream_t s) {
   }
   hipLaunchKernelGGL((dec_norm_gemm16<0>), rows(V), blk, 0, s, D->x, D->w.final_ln, (const TW*)D->w.lm_head, V, D->eps,
                      D->logits, (TW*)nullptr, (TW*)nullptr, inner, (size_t)0, D->state, B);
-  hipLaunchKernelGGL(dec_argmax, dim3((unsigned)ceil_div(B, 8)), dim3(512), 0, s, D->logits, V, B, D->tokens,
-                     D->maxLen + 1, (const float*)D->w.embed, D->w.pos, D->x, D->state, D->eos, D->pad, D->prefix);
+  launch_tail(D, s);
   MR_CHECK_LAUNCH("decoder step (mfma)");
   return MRMT3_OK;
 }
@@ -649,8 +1009,7 @@ static int launch_step(mrmt3_decoder* D, hipStream_t s) {
   }
   hipLaunchKernelGGL((dec_norm_gemv<TW, 0>), rows(V), blk, 0, s, D->x, D->w.final_ln, (const TW*)D->w.lm_head, V, D->eps,
                      D->logits, (TW*)nullptr, (TW*)nullptr, inner, (size_t)0, D->state);
-  hipLaunchKernelGGL(dec_argmax, dim3((unsigned)ceil_div(B, 8)), dim3(512), 0, s, D->logits, V, B, D->tokens, D->maxLen + 1,
-                     (const float*)D->w.embed, D->w.pos, D->x, D->state, D->eos, D->pad, D->prefix);
+  launch_tail(D, s);
   MR_CHECK_LAUNCH("decoder step");
   return MRMT3_OK;
 }
@@ -664,7 +1023,12 @@ static int step(mrmt3_decoder* D, hipStream_t s) {
 extern "C" int mrmt3_decoder_run(mrmt3_decoder* D, int n_steps, void* stream) {
   MR_CHECK_ARG(D && D->tokens && n_steps >= 0, "decoder_run: call decoder_begin first");
   hipStream_t s = (hipStream_t)stream;
+  const mrmt3_decoder::Tail &a = D->tail, &c = D->cap_tail;
+  if (a.k != c.k || a.groups != c.groups || a.length_penalty != c.length_penalty || a.ban != c.ban ||
+      a.bscore != c.bscore || a.bp != c.bp || a.hyp != c.hyp)
+    D->captured = 0;                            // greedy <-> beam, ban <-> no ban: the tail is baked into the graph
   if (!D->captured && !D->graph_failed) {
+    D->cap_tail = D->tail;
     if (D->exec) { (void)hipGraphExecDestroy(D->exec); D->exec = nullptr; }
     if (D->graph) { (void)hipGraphDestroy(D->graph); D->graph = nullptr; }
     hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);

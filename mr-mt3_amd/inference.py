@@ -10,10 +10,14 @@
     the note state machine are restated without note_seq/seqio (`contrib/{event_codec,vocabularies,
     run_length_encoding,note_sequences,metrics_utils,midi_io}.py`); `inference(..., outpath=...)`
     writes a Standard MIDI File and returns the note sequence.
+  * `valid_programs` / `num_beams`: the reference passes them to HF `generate` (inference.py:186-190), whose custom
+    `generate` then drops them.  Under `decode_options` (knob MRMT3_DECODE_OPTIONS=1) they are honoured:
+    `model.generate_beam(..., num_beams, length_penalty=0.4, bad_token_ids=program_ban_ids(valid_programs))`.
 """
 from __future__ import annotations
 
 import math
+import os
 
 import numpy as np
 import torch
@@ -52,6 +56,16 @@ def split_into_segments(frames, frame_times, max_length=256):
     return np.stack(batchs, axis=0), np.stack(times, axis=0), paddings
 
 
+def program_ban_ids(valid_programs, codec=None):
+    """Token ids of the programs NOT in `valid_programs`, exactly as the reference's `_get_program_ids`
+    (inference.py:138-147) builds its `bad_words_ids`: `p in range(hi - lo)` of the codec's program range (so the
+    last program, 127, is never banned), then `vocab.encode` (+ the 3 special tokens)."""
+    codec = codec or vocabularies.build_codec(vocabularies.VocabularyConfig(num_velocity_bins=1))
+    lo, hi = codec.event_type_range('program')
+    valid = set(valid_programs)
+    return [lo + p + NUM_SPECIAL_TOKENS for p in range(hi - lo) if p not in valid]
+
+
 def postprocess_batch(result: torch.Tensor, eos_token_id=1, num_special_tokens=NUM_SPECIAL_TOKENS):
     """inference.py:206-215 — positions at/after the first EOS -> -1, drop the 3 specials, drop BOS."""
     after_eos = torch.cumsum((result == eos_token_id).float(), dim=-1)
@@ -62,7 +76,7 @@ def postprocess_batch(result: torch.Tensor, eos_token_id=1, num_special_tokens=N
 
 class InferenceHandler:
     def __init__(self, model=None, weight_path=None, device=torch.device('cuda'), mel_norm=True,
-                 contiguous_inference=False, use_tf_spectral_ops=False) -> None:
+                 contiguous_inference=False, use_tf_spectral_ops=False, decode_options=None) -> None:
         if model is None:
             from models.t5 import T5ForConditionalGeneration
             from mrmt3.synthetic import T5_SMALL
@@ -79,6 +93,19 @@ class InferenceHandler:
         self.device = device
         self.model.to(self.device)
         self.mel_norm = mel_norm
+        # honour `valid_programs` / `num_beams` in `inference` (the reference accepts and drops them)
+        self.decode_options = bool(int(os.environ.get("MRMT3_DECODE_OPTIONS", "0"))) if decode_options is None \
+            else bool(decode_options)
+
+    def _get_program_ids(self, valid_programs):
+        """inference.py:138-147: `bad_words_ids` of the programs outside `valid_programs`, one single-token list each."""
+        return [[p] for p in program_ban_ids(valid_programs, self.codec)]
+
+    def _generate(self, batch, max_length, valid_programs, num_beams):
+        """The reference's `model.generate(..., num_beams, length_penalty=0.4, bad_words_ids=...)` (inference.py:186-190)."""
+        ban = None if valid_programs is None else program_ban_ids(valid_programs, self.codec)
+        return self.model.generate_beam(inputs=batch, num_beams=num_beams, max_length=max_length, length_penalty=0.4,
+                                        bad_token_ids=ban)
 
     def _audio_to_frames(self, audio):
         return audio_to_frames(audio, self.spectrogram_config)
@@ -139,27 +166,38 @@ class InferenceHandler:
             ft = [np.concatenate(ft, axis=0)]
         results = []
         for batch in batches:
-            result = self.model.generate(inputs=batch.to(self.device), max_length=max_length)
+            if self.decode_options:
+                result = self._generate(batch.to(self.device), max_length, valid_programs, num_beams)
+            else:
+                result = self.model.generate(inputs=batch.to(self.device), max_length=max_length)
             results.append(self._postprocess_batch(result))
         if return_tokens:
             return results, ft
         ns = self._to_event(results, ft)
         if outpath is not None:
-            import os
             os.makedirs(os.path.dirname(os.path.abspath(outpath)), exist_ok=True)
             midi_io.note_sequence_to_midi_file(ns, outpath)
         return ns
 
     @torch.no_grad()
-    def inference_many(self, audios, outpaths=None, max_length=1024, return_tokens=False):
+    def inference_many(self, audios, outpaths=None, max_length=1024, return_tokens=False, valid_programs=None,
+                       num_beams=1):
         """Several recordings in one go.  Segment-memory models decode them in lockstep (one batch row per
         recording, `model.generate_songs`); the plain T5 simply batches all segments.  Returns one note sequence
-        (or, with `return_tokens`, one `(token arrays, frame times)` pair) per recording, like `inference`."""
+        (or, with `return_tokens`, one `(token arrays, frame times)` pair) per recording, like `inference`.
+        `valid_programs` / `num_beams` are honoured as given (length penalty 0.4, as `inference` under decode_options)."""
         pre = [self._preprocess(a) for a in audios]
+        opts = valid_programs is not None or num_beams != 1
+        ban = None if valid_programs is None else program_ban_ids(valid_programs, self.codec)
         if hasattr(self.model, "generate_songs"):
-            ids = self.model.generate_songs([x.to(self.device) for x, _ in pre], max_length=max_length)
+            kw = dict(num_beams=num_beams, length_penalty=0.4, bad_token_ids=ban) if opts else {}
+            ids = self.model.generate_songs([x.to(self.device) for x, _ in pre], max_length=max_length, **kw)
         else:
-            flat = self.model.generate(inputs=torch.cat([x for x, _ in pre]).to(self.device), max_length=max_length)
+            x_all = torch.cat([x for x, _ in pre]).to(self.device)
+            if opts:
+                flat = self._generate(x_all, max_length, valid_programs, num_beams)
+            else:
+                flat = self.model.generate(inputs=x_all, max_length=max_length)
             ids, at = [], 0
             for x, _ in pre:
                 ids.append(flat[at:at + x.shape[0]])
@@ -172,7 +210,6 @@ class InferenceHandler:
                 continue
             ns = self._to_event(results, times)
             if outpaths is not None and outpaths[k] is not None:
-                import os
                 os.makedirs(os.path.dirname(os.path.abspath(outpaths[k])), exist_ok=True)
                 midi_io.note_sequence_to_midi_file(ns, outpaths[k])
             out.append(ns)

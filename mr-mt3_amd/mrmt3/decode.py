@@ -8,6 +8,11 @@
     the previous segment's tokens through the segment-memory encoder; returns [n_seg, max_length].
 The encoder, the segment-memory encoder and the cross-attention K/V projections run through the
 same engine kernels as training; only the token loop uses the KV-cached step graph.
+
+`generate_beam` adds what the reference's call site asks of HF `generate` (inference.py:186-190) and its custom
+`generate` drops: beam search (HF 4.18 `beam_search` + `BeamSearchScorer`, early_stopping=False, one hypothesis
+kept; `max_length` counts new tokens as above) and single-token bans (`bad_token_ids`, HF `NoBadWordsLogitsProcessor`).
+`num_beams=1` is the greedy decode with the ban, as HF dispatches it.
 """
 from __future__ import annotations
 
@@ -19,6 +24,8 @@ from . import lib
 
 
 MAX_DECODE_BATCH = 256     # DEC_MAXB of csrc/decode.hip: sequences decoded together (one wave per row x sequence)
+MAX_BEAMS = 8              # BEAM_MAXK of csrc/decode.hip
+BEAM_HREC = 32             # int32 per group of the hypothesis record (csrc/decode.hip, include/mrmt3_hip.h)
 
 
 class _Weights(C.Structure):
@@ -97,11 +104,41 @@ class Decoder:
             lib.gemm_nt(enc_cat, eng.W(f"decoder.{i}.ckv"), out=out[i])
         return out
 
-    def run(self, ckv, B, Lc, max_steps, poll_every=64, prefix=None, logits_out=None):
+    def ban_mask(self, bad_token_ids):
+        """Device [V] uint8 mask of `bad_token_ids` in a buffer of stable address (the step graph bakes the pointer in),
+        or None when there is nothing to ban."""
+        ids = sorted({int(i) for i in (bad_token_ids or ())})
+        if not ids:
+            return None
+        V = self.model.cfg["vocab_size"]
+        if ids[0] < 0 or ids[-1] >= V:
+            raise ValueError(f"bad_token_ids must lie in [0, {V})")
+        if getattr(self, "_ban_buf", None) is None:
+            self._ban_buf = torch.zeros(V, dtype=torch.uint8, device=self.model.device)
+        m = torch.zeros(V, dtype=torch.uint8)
+        m[ids] = 1
+        self._ban_buf.copy_(m)
+        return self._ban_buf
+
+    def cross_kv_beam(self, enc_cat, G, k, Lc):
+        """cross_kv of G segments with every segment's rows repeated k times (one per beam): [layers][G*k*Lc][2*inner].
+        The projections run once per segment; the step kernels then see k independent rows per group."""
+        eng = self.model.engine
+        L = self.model.cfg["num_decoder_layers"]
+        one = torch.empty(L, G * Lc, 2 * eng.inner, device=enc_cat.device, dtype=self.dt)
+        for i in range(L):
+            lib.gemm_nt(enc_cat, eng.W(f"decoder.{i}.ckv"), out=one[i])
+        out = self.ckv_buf[:L * G * k * Lc * 2 * eng.inner].view(L, G, k, Lc, 2 * eng.inner)
+        out.copy_(one.view(L, G, 1, Lc, 2 * eng.inner).expand(L, G, k, Lc, 2 * eng.inner))
+        return out.view(L, G * k * Lc, 2 * eng.inner)
+
+    def run(self, ckv, B, Lc, max_steps, poll_every=64, prefix=None, logits_out=None, ban=None):
         """Decode up to max_steps tokens for B rows; returns (tokens [B, max_len+1] view, steps run,
         finish_step or -1).  `prefix` [B, n, d] f32: memory rows fed as decoder positions 0..n-1.
         `logits_out` [>= n + max_steps, B, V] f32 device tensor (tests): row s receives step s's lm_head
-        output, prefix steps included; steps are then replayed one at a time, each followed by a copy."""
+        output, prefix steps included; steps are then replayed one at a time, each followed by a copy.
+        `ban`: device [V] uint8 mask (`ban_mask`) of tokens the argmax never picks, or None."""
+        self._ban = ban
         cfg = self.model.cfg
         l = lib.load()
         w = self._weights()
@@ -122,6 +159,8 @@ class Decoder:
         lib._check(l.mrmt3_decoder_begin(self.h, C.byref(w), lib._p(ckv), B, Lc, lib._p(self.tokens),
                                          cfg["decoder_start_token_id"], cfg["eos_token_id"], cfg["pad_token_id"],
                                          lib._stream()), "decoder_begin")
+        if self._ban is not None:
+            lib._check(l.mrmt3_decoder_set_ban(self.h, lib._p(self._ban), lib._stream()), "decoder_set_ban")
         if prefix is not None:
             n_pre = prefix.shape[1]
             assert prefix.dtype == torch.float32 and prefix.is_contiguous() and prefix.shape[0] == B
@@ -129,6 +168,11 @@ class Decoder:
             self._prefix = prefix        # keep alive while the graph may read it
             lib._check(l.mrmt3_decoder_set_prefix(self.h, lib._p(prefix), n_pre, lib._stream()), "decoder_set_prefix")
             max_steps += n_pre
+        done, fin = self._loop(l, B, max_steps, poll_every, logits_out)
+        return self.tokens, done, fin
+
+    def _loop(self, l, B, max_steps, poll_every, logits_out):
+        """Replay steps until max_steps or every row (greedy) / group (beam) is done; (steps run, finish step or -1)."""
         done, fin = 0, -1
         while done < max_steps:
             n = min(poll_every, max_steps - done)
@@ -145,7 +189,61 @@ class Decoder:
             if int(self.pinned[1]):
                 fin = int(self.pinned[2])
                 break
-        return self.tokens, done, fin
+        return done, fin
+
+    def run_beam(self, ckv, G, k, Lc, max_steps, length_penalty=1.0, ban=None, poll_every=64, logits_out=None):
+        """Beam search over G groups of k rows (`cross_kv_beam`).  Returns (ids [G, W] int64, steps run, finish step or
+        -1): start token, the best hypothesis, EOS when shorter than 1 + max_steps, pad; W = min(longest + 1,
+        1 + max_steps).  `logits_out` [>= max_steps, G*k, V] f32 (tests) as in `run`.  After the call `bp` [max_len,
+        G*k, 2] (parent row, token per step), `beam_scores` [G*k] and `hyps` [G, BEAM_HREC] hold the search state."""
+        cfg = self.model.cfg
+        B = G * k
+        if not (1 <= k <= MAX_BEAMS) or B > self.max_batch or max_steps > self.max_len or max_steps < 1:
+            raise ValueError(f"run_beam: need 1 <= k <= {MAX_BEAMS}, G*k <= {self.max_batch}, 1 <= steps <= {self.max_len}")
+        if logits_out is not None:
+            assert logits_out.dtype == torch.float32 and logits_out.is_contiguous() and logits_out.is_cuda
+            assert logits_out.dim() == 3 and logits_out.shape[0] >= max_steps and \
+                tuple(logits_out.shape[1:]) == (B, cfg["vocab_size"]), tuple(logits_out.shape)
+        self._ban, self._ckv = ban, ckv
+        l = lib.load()
+        cur = torch.cuda.current_stream()
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            self.begin_beam(ckv, G, k, Lc, length_penalty, ban)
+            done, fin = self._loop(l, B, max_steps, poll_every, logits_out)
+            lib._check(l.mrmt3_decoder_beam_finalize(self.h, lib._p(self._beam_out), self.max_len + 1, max_steps,
+                                                     lib._stream()), "decoder_beam_finalize")
+            lens = self.hyps(G)[:, 3].cpu()             # once per decode
+        cur.wait_stream(self.stream)
+        W = min(int(lens.max()) + 1, 1 + max_steps)
+        return self._beam_out[:G, :W], done, fin
+
+    def begin_beam(self, ckv, G, k, Lc, length_penalty=1.0, ban=None):
+        """mrmt3_decoder_begin_beam on the current stream with this decoder's beam buffers (allocated once: the step
+        graph bakes their addresses in).  `run_beam` is the whole decode; this is its first step, for tools."""
+        cfg = self.model.cfg
+        if getattr(self, "_bp", None) is None:
+            dev = self.model.device
+            self._bp = torch.zeros(self.max_len * self.max_batch * 2, dtype=torch.int32, device=dev)
+            self._bscore = torch.zeros(self.max_batch, dtype=torch.float32, device=dev)
+            self._hyp = torch.zeros(self.max_batch * BEAM_HREC, dtype=torch.int32, device=dev)
+            self._beam_out = torch.zeros(self.max_batch, self.max_len + 1, dtype=torch.int64, device=dev)
+        self._ban, self._ckv = ban, ckv
+        w = self._weights()
+        lib._check(lib.load().mrmt3_decoder_begin_beam(
+            self.h, C.byref(w), lib._p(ckv), G, k, Lc, lib._p(self.tokens), cfg["decoder_start_token_id"],
+            cfg["eos_token_id"], cfg["pad_token_id"], float(length_penalty), lib._p(ban), lib._p(self._bp),
+            lib._p(self._bscore), lib._p(self._hyp), lib._stream()), "decoder_begin_beam")
+
+    def backptr(self, rows):
+        """[max_len, rows, 2] int32 (parent row, token) of the last beam decode."""
+        return self._bp[:self.max_len * rows * 2].view(self.max_len, rows, 2)
+
+    def beam_scores(self, rows):
+        return self._bscore[:rows]
+
+    def hyps(self, G):
+        return self._hyp[:G * BEAM_HREC].view(G, BEAM_HREC)
 
     @property
     def graph_captured(self) -> bool:
@@ -163,6 +261,10 @@ def _decoder_for(model, B, max_len, enc_len) -> Decoder:
 
 @torch.no_grad()
 def generate(model, inputs, max_length=1024, poll_every=64):
+    return _generate(model, inputs, max_length, poll_every)
+
+
+def _generate(model, inputs, max_length, poll_every, bad_token_ids=None):
     eng, cfg = model.engine, model.cfg
     if not inputs.is_cuda:
         raise RuntimeError("generate needs device tensors (no CPU fallback)")
@@ -175,7 +277,7 @@ def generate(model, inputs, max_length=1024, poll_every=64):
             nb = min(MAX_DECODE_BATCH, B - b0)
             dec = _decoder_for(model, nb, max_length, Le)
             ckv = dec.cross_kv(enc.view(B, Le, d)[b0:b0 + nb].reshape(nb * Le, d), nb, Le)
-            toks, done, fin = dec.run(ckv, nb, Le, max_length, poll_every)
+            toks, done, fin = dec.run(ckv, nb, Le, max_length, poll_every, ban=dec.ban_mask(bad_token_ids))
             steps = (fin + 1) if fin >= 0 else max_length
             out.append((toks[:nb, :steps + 1].clone(), steps))
         if len(out) == 1:
@@ -203,7 +305,7 @@ def generate(model, inputs, max_length=1024, poll_every=64):
         mem = _memory(eng, seg_ids, 1, max_length, Ls)                     # [1, Ls, d]
         cur = torch.cat([enc.view(B, Le, d)[i:i + 1], mem], 1).contiguous().view(Le + Ls, d)
         ckv = dec.cross_kv(cur, 1, Le + Ls)
-        toks, done, fin = dec.run(ckv, 1, Le + Ls, max_length, poll_every)
+        toks, done, fin = dec.run(ckv, 1, Le + Ls, max_length, poll_every, ban=dec.ban_mask(bad_token_ids))
         steps = (fin + 1) if fin >= 0 else max_length
         row = torch.zeros(1, max_length, dtype=torch.int64, device=inputs.device)
         n = min(steps + 1, max_length)                   # F.pad(..., max_length - len) truncates (:287-291)
@@ -222,12 +324,14 @@ def _memory(eng, seg_ids, B, L, Ls):
 
 
 @torch.no_grad()
-def generate_2(model, inputs, max_length=1024, poll_every=64):
+def generate_2(model, inputs, max_length=1024, poll_every=64, num_beams=1):
     """`T5SegMem.generate_2` (models/t5_segmem.py:172-252): segments one after the other; the previous
     segment's tokens go through the segment-memory encoder and its first `segmem_length` outputs are
     PREPENDED to the decoder's input embeddings.  With the KV cache that is a prefix fill: the memory
     rows are fed as decoder positions 0..Ls-1 (self-attention K/V only), tokens start at position Ls.
-    A stable prefix buffer keeps the captured step graph valid across segments."""
+    A stable prefix buffer keeps the captured step graph valid across segments.  No beam search here."""
+    if num_beams != 1:
+        raise ValueError("generate_2 (memory-prefixed decode) has no beam search")
     eng, cfg = model.engine, model.cfg
     if not inputs.is_cuda:
         raise RuntimeError("generate_2 needs device tensors (no CPU fallback)")
@@ -258,7 +362,7 @@ def generate_2(model, inputs, max_length=1024, poll_every=64):
 
 
 @torch.no_grad()
-def generate_songs(model, songs, max_length=1024, poll_every=64):
+def generate_songs(model, songs, max_length=1024, poll_every=64, num_beams=1, length_penalty=1.0, bad_token_ids=None):
     """Several recordings decoded in lockstep with the segment-memory models (V2 / V2WithPrev).
 
     The reference transcribes one recording at a time because segment i needs segment i-1's tokens
@@ -266,16 +370,19 @@ def generate_songs(model, songs, max_length=1024, poll_every=64):
     decode batch is recording s's CURRENT segment: every recording keeps its own memory chain, and each row
     produces exactly what `generate` produces for that recording alone (same kernels, one wave per row and
     sequence).  `songs`: list of [n_seg_s, Le, 512] device tensors.  Returns a list of [n_seg_s, max_length]
-    int64 tensors."""
+    int64 tensors.  `num_beams` > 1: recording s is group s of a beam search (`generate_beam` per recording, in
+    lockstep); `bad_token_ids` bans tokens in either mode.  The defaults are the greedy decode above."""
+    _check_beams(num_beams)
     eng, cfg = model.engine, model.cfg
     if model.VARIANT not in ("segmem_v2", "segmem_v2_with_prev"):
         raise RuntimeError("generate_songs is for the segment-memory models; plain T5 batches segments directly")
     if not songs:
         return []
-    if len(songs) > MAX_DECODE_BATCH:
+    per = MAX_DECODE_BATCH // num_beams
+    if len(songs) > per:
         out = []
-        for i in range(0, len(songs), MAX_DECODE_BATCH):
-            out += generate_songs(model, songs[i:i + MAX_DECODE_BATCH], max_length, poll_every)
+        for i in range(0, len(songs), per):
+            out += generate_songs(model, songs[i:i + per], max_length, poll_every, num_beams, length_penalty, bad_token_ids)
         return out
     dev = songs[0].device
     if dev.type != "cuda":
@@ -298,13 +405,88 @@ def generate_songs(model, songs, max_length=1024, poll_every=64):
         seg_ids = torch.stack([prev[s] for s in live])                      # [B, max_length]
         mem = _memory(eng, seg_ids, B, max_length, Ls)                     # [B, Ls, d]
         cur = torch.cat([torch.stack([enc[s][i] for s in live]), mem.to(enc[0].dtype)], 1).contiguous()
-        dec = _decoder_for(model, B, max_length, Le + Ls)
-        ckv = dec.cross_kv(cur.view(B * (Le + Ls), d), B, Le + Ls)
-        toks, done, fin = dec.run(ckv, B, Le + Ls, max_length, poll_every)
-        rows = toks[:B, :max_length].clone()                               # finished rows are already pad(0)-filled
-        if done < max_length:                                              # all rows hit EOS early: the rest is stale
-            rows[:, done + 1:] = 0
+        dec = _decoder_for(model, B * num_beams, max_length, Le + Ls)
+        if num_beams > 1:
+            ckv = dec.cross_kv_beam(cur.view(B * (Le + Ls), d), B, num_beams, Le + Ls)
+            ids, _, _ = dec.run_beam(ckv, B, num_beams, Le + Ls, max_length, length_penalty,
+                                     dec.ban_mask(bad_token_ids), poll_every)
+            rows = _memory_rows(ids, max_length)
+        else:
+            ckv = dec.cross_kv(cur.view(B * (Le + Ls), d), B, Le + Ls)
+            toks, done, fin = dec.run(ckv, B, Le + Ls, max_length, poll_every, ban=dec.ban_mask(bad_token_ids))
+            rows = toks[:B, :max_length].clone()                           # finished rows are already pad(0)-filled
+            if done < max_length:                                          # all rows hit EOS early: the rest is stale
+                rows[:, done + 1:] = 0
         for r, s in enumerate(live):
             outs[s].append(rows[r])
             prev[s] = rows[r]
     return [torch.stack(o) for o in outs]
+
+
+def _check_beams(num_beams):
+    if not (isinstance(num_beams, int) and 1 <= num_beams <= MAX_BEAMS):
+        raise ValueError(f"num_beams must be an int in 1..{MAX_BEAMS}, got {num_beams!r}")
+
+
+def _memory_rows(ids, max_length):
+    """Beam output [n, W] -> [n, max_length]: cut or zero-padded, as the greedy chain does (`F.pad` / slice)."""
+    rows = torch.zeros(ids.shape[0], max_length, dtype=torch.int64, device=ids.device)
+    n = min(ids.shape[1], max_length)
+    rows[:, :n] = ids[:, :n]
+    return rows
+
+
+@torch.no_grad()
+def generate_beam(model, inputs, num_beams=1, max_length=1024, length_penalty=1.0, bad_token_ids=None, poll_every=64):
+    """Beam search with optional single-token bans; the output contract of `generate` for the model's variant.
+
+    Plain T5 / T5SegMem: [B, W] int64, W = min(longest best hypothesis + 1, 1 + max_length) over the batch: start
+    token, tokens, EOS after a hypothesis shorter than 1 + max_length, pad (HF `BeamSearchScorer.finalize`).  Segment
+    memory models: [n_seg, max_length], segments one after the other, each one's memory ids = the previous segment's
+    best hypothesis cut or zero-padded to max_length.  `num_beams=1` is the greedy decode (with the ban); without a ban
+    it equals `generate` bit for bit."""
+    _check_beams(num_beams)
+    if not inputs.is_cuda:
+        raise RuntimeError("generate_beam needs device tensors (no CPU fallback)")
+    if num_beams == 1:
+        return _generate(model, inputs, max_length, poll_every, bad_token_ids)
+    eng, cfg = model.engine, model.cfg
+    k = num_beams
+    eng.prepare(False)
+    B, Le, d = inputs.shape
+    enc = eng.encode(inputs.float() if inputs.dtype not in (torch.float32, torch.bfloat16) else inputs)
+    if model.VARIANT in ("t5", "segmem_v1"):
+        per = MAX_DECODE_BATCH // k
+        out = []
+        for b0 in range(0, B, per):
+            G = min(per, B - b0)
+            dec = _decoder_for(model, G * k, max_length, Le)
+            ckv = dec.cross_kv_beam(enc.view(B, Le, d)[b0:b0 + G].reshape(G * Le, d), G, k, Le)
+            ids, _, _ = dec.run_beam(ckv, G, k, Le, max_length, length_penalty, dec.ban_mask(bad_token_ids), poll_every)
+            out.append(ids.clone())
+        if len(out) == 1:
+            return out[0]
+        W = max(o.shape[1] for o in out)
+        res = torch.full((B, W), cfg["pad_token_id"], dtype=torch.int64, device=inputs.device)
+        r = 0
+        for o in out:
+            res[r:r + o.shape[0], :o.shape[1]] = o
+            r += o.shape[0]
+        return res
+    Ls = min(model.segmem_length, max_length)
+    seg_ids = torch.zeros(1, max_length, dtype=torch.int64, device=inputs.device)
+    if model.VARIANT == "segmem_v2_with_prev":
+        seg_ids[0, 0], seg_ids[0, 1] = 1134, 1
+    else:
+        seg_ids[0, 0] = 1
+    dec = _decoder_for(model, k, max_length, Le + Ls)
+    outs = []
+    for i in range(B):
+        mem = _memory(eng, seg_ids, 1, max_length, Ls)
+        cur = torch.cat([enc.view(B, Le, d)[i:i + 1], mem], 1).contiguous().view(Le + Ls, d)
+        ckv = dec.cross_kv_beam(cur, 1, k, Le + Ls)
+        ids, _, _ = dec.run_beam(ckv, 1, k, Le + Ls, max_length, length_penalty, dec.ban_mask(bad_token_ids), poll_every)
+        row = _memory_rows(ids, max_length)
+        outs.append(row)
+        seg_ids = row
+    return torch.cat(outs, 0)

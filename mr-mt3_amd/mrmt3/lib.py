@@ -87,6 +87,9 @@ _SIGS = {
     "mrmt3_decoder_run": (ci, [vp, ci, vp]),
     "mrmt3_decoder_poll": (ci, [vp, vp, vp]),
     "mrmt3_decoder_logits": (ci, [vp, vp, ci, vp]),
+    "mrmt3_decoder_set_ban": (ci, [vp, vp, vp]),
+    "mrmt3_decoder_begin_beam": (ci, [vp, vp, vp, ci, ci, ci, vp, ci, ci, ci, cf, vp, vp, vp, vp, vp]),
+    "mrmt3_decoder_beam_finalize": (ci, [vp, vp, ci, ci, vp]),
     "mrmt3_comm_unique_id": (ci, [vp]),
     "mrmt3_comm_create": (ci, [vp, ci, ci, C.POINTER(vp)]),
     "mrmt3_comm_destroy": (ci, [vp]),

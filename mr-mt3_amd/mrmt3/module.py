@@ -211,3 +211,10 @@ class MT3Module(nn.Module):
     def generate(self, inputs, max_length=1024, **kwargs):
         from .decode import generate
         return generate(self, inputs, max_length=max_length)
+
+    def generate_beam(self, inputs, num_beams=1, max_length=1024, length_penalty=1.0, bad_token_ids=None, poll_every=64):
+        """Beam search and single-token bans (`mrmt3.decode.generate_beam`); `generate` keeps ignoring such keywords,
+        as the reference's custom `generate` does."""
+        from .decode import generate_beam
+        return generate_beam(self, inputs, num_beams=num_beams, max_length=max_length, length_penalty=length_penalty,
+                             bad_token_ids=bad_token_ids, poll_every=poll_every)
