@@ -19,6 +19,7 @@ typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 // ---- error plumbing (never abort / throw across the C ABI) --------------------------------------
 void mrmt3_set_error(const char* fmt, ...);
 void mrmt3_count(int which);   // diagnostics: launches per kernel family (MRMT3_CNT_*), read by mrmt3_dispatch_counts
+int mrmt3_cu_count();          // compute units of the current device, asked once per process; 256 (the MI355X) if unknown
 // ---- dispatch / tuning switches ("knobs") -------------------------------------------------------------------------------
 // A knob is an environment variable (MRMT3_*) that picks between kernels or tile shapes for A/B runs and parity tests.  The
 // product build reads each one ONCE per process — at the first launch that asks — and never touches the environment on a

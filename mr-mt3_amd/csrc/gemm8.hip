@@ -70,17 +70,6 @@ struct G8Params {
 // 1 25.77, 2 25.61, 0 25.63 — the consumer of C is the next kernel and finds it in the Infinity Cache.
 static int g8_store_mode() { return MR_KNOB("MRMT3_GEMM8_NT", 2) & 3; }
 
-static int g8_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
-
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t g8_rsrc(const void* base, size_t bytes) {
   return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
 }
@@ -529,7 +518,7 @@ int mrmt3_gemm_nt8_try(const void* A, int lda, const void* B, int ldb, void* C, 
   {
     if (MR_KNOB("MRMT3_GEMM8_ALL", 0) != 1) {                   // (1: tuning / tests, take every admissible shape)
       if (accumulate) return 0;
-      const int cu = g8_cus() & ~7, tn = ceil_div(N, 256), t256 = ceil_div(M, 256) * tn;
+      const int cu = mrmt3_cu_count() & ~7, tn = ceil_div(N, 256), t256 = ceil_div(M, 256) * tn;
       const int nt = t256 < cu ? ceil_div(M, 128) * tn : t256;
       const int waves = ceil_div(nt, cu);
       if (nt > cu && nt * 5 < waves * cu * 4) return 0;        // a last wave of workgroups less than 80 % full
@@ -543,7 +532,7 @@ int mrmt3_gemm_nt8_try(const void* A, int lda, const void* B, int ldb, void* C, 
   P.dbg = 0; P.skew_ticks = 0;
   P.nt_c = g8_store_mode();
   P.tiles_n = ceil_div(N, 256);
-  const int cus = g8_cus() & ~7;
+  const int cus = mrmt3_cu_count() & ~7;
   const int tiles256 = ceil_div(M, 256) * P.tiles_n;
   const bool small = tiles256 < cus;                         // not enough 256-row tiles to fill the chip: 128-row tiles
   P.n_tiles = small ? ceil_div(M, 128) * P.tiles_n : tiles256;
@@ -586,7 +575,7 @@ static int g8_splitk_plan(int M, int N, int K, int in_dtype) {
   // K = 6144 98.8 -> 48.0 us and K = 2048 35.8 -> 29.6 us, but K = 1024 / 1152 22.8 -> 28.6 / 24.6 -> 27.9 us: only
   // from K = 2048, with >= 512 per split.
   if (in_dtype != MRMT3_BF16 || M < 1024 || N < 256 || N % 128 != 0 || K < 2048 || K % 128 != 0) return 1;
-  const int cus = g8_cus() & ~7;
+  const int cus = mrmt3_cu_count() & ~7;
   const int tiles = ceil_div(M, 128) * ceil_div(N, 256);
   if (tiles * 2 > cus) return 1;                             // the chip is at least half full without a split
   for (int sp = 4; sp >= 2; --sp)                            // at most one wave of workgroups, >= 512 deep per split
@@ -688,7 +677,7 @@ extern "C" int mrmt3_gemm_nt_geglu(const void* x, int ldx, const void* wi, int l
   P.nt_c = g8_store_mode();
   P.drop = make_drop(p_drop, seed, stream_id, step_dev);
   P.tiles_n = dff / 128;
-  const int cus = g8_cus() & ~7;
+  const int cus = mrmt3_cu_count() & ~7;
   const int tiles256 = ceil_div(rows, 256) * P.tiles_n, tiles128 = ceil_div(rows, 128) * P.tiles_n;
   // 128-row tiles when there are too few 256-row tiles for the chip, or when they come in a badly filled last wave and
   // the 128-row tiling does not (12 segments per GPU: 384 tiles = 1.5 waves against 768 = 3 waves)

@@ -541,23 +541,13 @@ extern "C" int mrmt3_gemm_rows_ok(int M, int N, int K, int lda, int ldw) {
   return 1;
 }
 
-static int gr_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
 // Tile height: 128 rows (one workgroup per CU; half the weight bytes staged per row: a CU takes in ~60 GB/s of LDS-DMA,
 // which is what the 64-row K loop ran at) once there are enough of them to fill the chip, else 64 rows (two per CU).
 // A function of the row count alone: the norm-weight partial rows (one per tile) follow it.  MRMT3_ROWS_BM forces one.
 static int gr_bm(int rows) {
   const int f = MR_KNOB("MRMT3_ROWS_BM", 0);
   if (f == 64 || f == 128) return f;
-  return ceil_div(rows, 128) >= gr_cus() ? 128 : 64;
+  return ceil_div(rows, 128) >= mrmt3_cu_count() ? 128 : 64;
 }
 
 extern "C" int mrmt3_gemm_nt_normbwd_partial_rows(int rows) { return ceil_div(rows, gr_bm(rows)); }

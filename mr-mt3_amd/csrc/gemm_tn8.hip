@@ -9,9 +9,9 @@
 //     [64 tokens][128 features] (256-byte rows, 32-byte units XOR-swizzled by token & 7 on the LDS-DMA source address) and
 //     the MFMA fragments are read with ds_read_b64_tr_b16 (hardware transpose), two reads per 16 x 32 fragment — the
 //     layout and addressing of gemm.hip's first TN kernel, which this one replaces for the large shapes;
-//   * one workgroup = one (tile, token range): a K loop of 16 .. 128 steps, then a 256 KiB f32 slab; the slabs of all
-//     the weight gradients of a step are summed later in one launch (mrmt3_tn_reduce_sites), in split order (bitwise
-//     reproducible, no atomics);
+//   * one workgroup = one (tile, token range): a K loop of 16 .. 128 steps, then a 256 KiB f32 slab; the slabs are summed by a
+//     second launch in split order (bitwise reproducible, no atomics) — slab_reduce_kernel right behind a single product
+//     (mrmt3_gemm_tn), tn8_group_reduce_kernel for all the weight gradients of a grouped launch;
 //   * ragged N1 / N2 (384, 768, 1152): the last tile is shifted to end at N and stores only what the tile before it
 //     does not own.
 #include <stdlib.h>
@@ -326,13 +326,7 @@ int mrmt3_tn8_plan(int M, int N1, int N2, int* tiles, int* splits, int* rows_per
   // with % 8 and came back wrong in rows 512..575).
   if (M < 8192 || N1 < 256 || N2 < 256 || N1 % 128 != 0 || N2 % 64 != 0) return 0;
   if ((size_t)M * (size_t)(N1 > N2 ? N1 : N2) * 2 >= 0x7FFF0000ull) return 0;
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
+  const int cus = mrmt3_cu_count();
   const int t = ceil_div(N1, 256) * ceil_div(N2, 256);
   int s = cus / t;                                           // one workgroup per CU (128 KiB of LDS each)
   if (s < 1) s = 1;
@@ -363,14 +357,7 @@ int mrmt3_tn8_launch(const void* A, int lda, const void* B, int ldb, float* slab
 
 // ---- grouped launch: host planner -----------------------------------------------------------------------------------
 static int t8_cus() {
-  static int hw = 0;
-  if (hw == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) hw = prop.multiProcessorCount;
-    if (hw <= 0) hw = 256;
-  }
-  int cus = hw;
+  int cus = mrmt3_cu_count();
   { const int e = MR_KNOB("MRMT3_TN_GROUP_CTAS", 0); if (e >= 8) cus = e; }   // tests / tuning
   return cus & ~7;
 }

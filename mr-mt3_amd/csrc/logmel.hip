@@ -422,12 +422,7 @@ static int logmel_launch(const float* audio, int batch, int n_samples, int hop, 
       int fpw = (LMW_STRIP_FLOATS - FFT_N) / hop + 1;
       if (fpw > 64) fpw = 64;
       {
-        static int cus = 0;
-        if (cus == 0) {
-          int dev = 0;
-          hipDeviceProp_t prop;
-          cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-        }
+        const int cus = mrmt3_cu_count();
         const long long total = (long long)batch * n_frames;
         while (fpw > LMW_WAVES && total / fpw < cus) fpw >>= 1;
       }

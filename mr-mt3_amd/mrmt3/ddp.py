@@ -134,10 +134,6 @@ class GradBuckets:
         self._fired = set()
         # called right before a bucket's all-reduce is enqueued (the engine sums its queued norm-weight gradients here)
         self.before_fire = None
-        # streams other than the current one that also write gradients (weight gradients are produced on a second
-        # stream, see Engine.wgrad).  The collective is enqueued from a launch stream that waits for the current
-        # stream AND these — the backward pass itself never stops to wait for its own side stream at a bucket boundary.
-        self.producer_streams = None
         self._launch = None
         # single-GPU check of the collective path (profiles/tools/nccl_one_rank_check.py): run the all-reduces at world 1
         self.force = os.environ.get("MRMT3_DDP_FORCE_COLLECTIVES") == "1" and dist.is_available() and dist.is_initialized()
@@ -234,23 +230,11 @@ class GradBuckets:
         grad = self.flat.G[b["start"]:b["end"]]
         if self.exchange_dtype is not None and self.exchange_dtype != grad.dtype:
             return self._fire_compressed(b, grad)
-        extra = [s for s in (self.producer_streams() if self.producer_streams is not None else []) if s is not None]
-        if grad.is_cuda and extra:
-            launch = self._launch_stream(grad.device)
-            launch.wait_stream(torch.cuda.current_stream(grad.device))
-            for s in extra:
-                launch.wait_stream(s)
-            self._works.append(self._all_reduce(grad, launch))
-        else:
-            self._works.append(self._all_reduce(grad))
+        self._works.append(self._all_reduce(grad))
 
     def _fire_compressed(self, b, grad):
         """Round the bucket to the exchange dtype, all-reduce that copy, widen it back into the f32 gradient when the
         collective has finished (`wait()`).  The copies run on the current stream, behind the bucket's producers."""
-        if grad.is_cuda:
-            for s in (self.producer_streams() if self.producer_streams is not None else []):
-                if s is not None:
-                    torch.cuda.current_stream(grad.device).wait_stream(s)
         if self._staging is None or self._staging.device != grad.device:
             self._staging = torch.empty(self.flat.numel, dtype=self.exchange_dtype, device=grad.device)
         low = self._staging[b["start"]:b["end"]]

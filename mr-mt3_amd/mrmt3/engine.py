@@ -58,10 +58,7 @@ class Engine:
         # dtype of sublayer outputs / dgrad outputs entering the fp32 residual add: the compute dtype
         # (bf16 halves that stream's HBM traffic; the residual itself and all statistics stay fp32)
         self.y_dtype = compute_dtype
-        # weight-gradient GEMMs are off the critical dgrad chain (their outputs are only needed by the optimizer / the
-        # gradient exchange): the shapes the grouped kernel takes are deferred to join_wgrad() (tn_group below); the
-        # others run one by one on a second HIP stream and overlap the attention / dgrad kernels of the layers below
-        self.overlap_wgrad = os.environ.get("MRMT3_WGRAD_STREAM", "1") != "0"
+        self.overlap_wgrad = False      # nothing in the package reads it: bench.py's roofline repeat still sets and restores it
         # residual-stream GRADIENT of the bf16 path: bf16 between the norm-backward sites of a stack (f32 at both
         # ends) halves the largest streams of the backward row kernels; the forward residual stays f32
         self.res_grad_dtype = (torch.bfloat16 if compute_dtype == torch.bfloat16 and
@@ -70,20 +67,15 @@ class Engine:
         # the master weights; inference / parity only)
         self.head_dtype = "bf16"
         self._wt32 = {}
-        self._side = None
-        self._side_dirty = False
-        self._held = []
         # bf16(O - bf16(O)) of an attention site is kept for the backward's delta where the value rows share a large common
         # component — cross-attention over near-identical encoder frames.  "all": every site; "cross": the
         # self-attention sites skip the extra 50 MB write + read per site
         self.lo_sites = os.environ.get("MRMT3_ATTN_LO", "all")
         self.norm_dw = lib.NormDwBatch() if os.environ.get("MRMT3_NORM_DW_BATCH", "1") != "0" else None
-        # split-K slabs of the weight-gradient GEMMs: kept per site and summed in one launch (lib.TnBatch)
-        self.tn_batch = lib.TnBatch() if os.environ.get("MRMT3_TN_BATCH", "1") != "0" else None
-        if self.tn_batch is not None:
-            self.tn_batch.before_early_flush = self._join_side
-        # ... and, for every shape the grouped kernel takes, the GEMMs themselves are deferred to the next join_wgrad():
-        # one launch for the weight gradients of a whole gradient bucket (lib.TnGroup)
+        # weight-gradient GEMMs are off the critical dgrad chain (their outputs are only needed by the optimizer / the
+        # gradient exchange): every shape the grouped kernel takes is deferred to the next join_wgrad() — one launch for
+        # the weight gradients of a whole gradient bucket (lib.TnGroup); the others run at once, one by one.
+        # MRMT3_TN_GROUP=0 (A/B switch): every gradient through mrmt3_gemm_tn
         self.tn_group = lib.TnGroup() if os.environ.get("MRMT3_TN_GROUP", "1") != "0" else None
         # projection + row kernel in one launch (csrc/gemm_rows.hip; bf16 engine only).  MRMT3_FUSE_ROWS bits: 1 the o / co /
         # wo projection with the residual add + norm behind it, 2 the 512-column data gradients with the norm backward,
@@ -126,33 +118,15 @@ class Engine:
             self._wt32[name] = t
         return t
 
-    def side_stream(self):
-        if self._side is None or self._side.device != torch.cuda.current_stream().device:
-            self._side = torch.cuda.Stream(priority=int(os.environ.get("MRMT3_WGRAD_PRIO", "-1")))
-            self._events = [torch.cuda.Event() for _ in range(64)]
-            self._ev_i = 0
-        return self._side
-
     def wgrad(self, a, b, out):
         """out += a^T @ b, complete after the next join_wgrad() (inputs were produced on the current stream).
-        Grouped path: only recorded here (operands kept alive), launched with every other gradient that is due.
-        One-by-one path (shapes the grouped kernel does not take): on the side stream, kept cheap on the host — events
-        come from a small ring, the kernel is launched on the side stream directly, and the operands are kept alive by
-        reference until the next join instead of `record_stream` bookkeeping."""
+        Shapes the grouped kernel takes are only recorded here (operands kept alive) and launched with every other
+        gradient that is due; everything else runs now, on the current stream."""
         if a.dtype == torch.float32:                      # fp32 training / parity path: exact-f32 product, in place, now
             return lib.gemm_tn_f32(a, b, out, accumulate=True)
         if self.tn_group is not None and self.tn_group.ok(a, b, out):
             return self.tn_group.add(a, b, out, accumulate=True)
-        if not self.overlap_wgrad:
-            return lib.gemm_tn(a, b, out, accumulate=True, defer=self.tn_batch)
-        side = self.side_stream()
-        ev = self._events[self._ev_i]
-        self._ev_i = (self._ev_i + 1) % len(self._events)
-        ev.record()
-        side.wait_event(ev)
-        lib.gemm_tn(a, b, out, accumulate=True, stream=side, defer=self.tn_batch)
-        self._held.append((a, b))
-        self._side_dirty = True
+        return lib.gemm_tn(a, b, out, accumulate=True)
 
     def _norm_bwd(self, *a, **kw):
         """lib.add_rmsnorm_bwd with the norm-weight gradient deferred to one batched reduction (flush_norm_dw).
@@ -205,39 +179,22 @@ class Engine:
         if self.norm_dw is not None:
             self.norm_dw.flush()
 
-    def _join_side(self):
-        """The current stream waits for the side stream's weight-gradient launches issued so far."""
-        if self.overlap_wgrad and self._side is not None and self._side_dirty:
-            # (only when the side stream has work since the last join: under graph capture a wait on a stream that
-            # is not part of the capture would tie the graph to uncaptured work)
-            self._side_dirty = False
-            torch.cuda.current_stream().wait_stream(self._side)
-            # operands may be recycled now: whatever the current stream does next runs after the side work
-            self._held.clear()
-
     def join_wgrad(self):
-        """Make the current stream wait for every weight gradient issued so far (and sum the queued norm-weight
-        gradients: both are what a gradient bucket needs before it is sent)."""
+        """Launch every weight gradient recorded so far (and sum the queued norm-weight gradients: both are what a
+        gradient bucket needs before it is sent)."""
         self.flush_norm_dw()
-        self._join_side()
-        if self.tn_batch is not None:
-            self.tn_batch.flush()        # behind the GEMMs that produced the slabs (same stream, or joined above)
         if self.tn_group is not None:
             self.tn_group.flush()        # the deferred weight gradients: their operands were produced on this stream
 
     def reset_deferred(self):
-        """Forget every deferred launch: the weight gradients recorded for the grouped launch, the queued split-K slab
-        and norm-weight reductions, the operands held for the side stream.  After an aborted hipGraph capture (or an
-        exception in the middle of a backward pass) these still name tensors of work that never ran — a later flush
-        would accumulate uninitialised memory into the gradients."""
+        """Forget every deferred launch: the weight gradients recorded for the grouped launch and the queued norm-weight
+        reductions.  After an aborted hipGraph capture (or an exception in the middle of a backward pass) these still
+        name tensors of work that never ran — a later flush would accumulate uninitialised memory into the gradients
+        (ADVICE r2)."""
         if self.tn_group is not None:
             self.tn_group._sites.clear()
-        if self.tn_batch is not None:
-            self.tn_batch._queue.clear()
         if self.norm_dw is not None:
             self.norm_dw._queue.clear()
-        self._held.clear()
-        self._side_dirty = False
 
     def prepare(self, training: bool):
         if self.dt == torch.bfloat16:

@@ -20,104 +20,56 @@ HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "
 CSRC_DIR = os.path.join(os.path.dirname(_HERE), "csrc")
 _lib = None
 
-vp, ci, cf, cu64, cu32, csz = C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_uint32, C.c_size_t
+vp = C.c_void_p
 
-_SIGS = {
-    "mrmt3_version": (ci, []),
-    "mrmt3_last_error": (C.c_char_p, []),
-    "mrmt3_set_knob": (ci, [C.c_char_p, ci]),
-    "mrmt3_reset_knobs": (ci, []),
-    "mrmt3_logmel_fwd": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci, vp, vp]),
-    "mrmt3_logmel_crops_fwd": (ci, [vp, C.c_longlong, vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci, vp, vp]),
-    "mrmt3_gemm_nt": (ci, [vp, ci, vp, ci, vp, ci, ci, ci, ci, ci, ci, ci, vp]),
-    "mrmt3_gemm_nt_workspace_bytes": (csz, [ci, ci, ci, ci]),
-    "mrmt3_gemm_nt_ws": (ci, [vp, ci, vp, ci, vp, ci, ci, ci, ci, ci, ci, ci, vp, csz, vp]),
-    "mrmt3_gemm_tn_workspace_bytes": (csz, [ci, ci, ci]),
-    "mrmt3_gemm_tn": (ci, [vp, ci, vp, ci, vp, ci, ci, ci, ci, ci, vp, csz, vp]),
-    "mrmt3_gemm_tn_splits": (ci, [ci, ci, ci]),
-    "mrmt3_gemm_tn_partial": (ci, [vp, ci, vp, ci, ci, ci, ci, vp, csz, vp]),
-    "mrmt3_tn_reduce_sites": (ci, [vp, ci, ci, vp]),
-    "mrmt3_add_rmsnorm_fwd": (ci, [vp, vp, ci, vp, cf, vp, vp, ci, vp, ci, ci, cf, cu64, vp, cu32, cu32, ci, vp]),
-    "mrmt3_add_rmsnorm_bwd_workspace_bytes": (csz, [ci, ci]),
-    "mrmt3_add_rmsnorm_bwd_partial_rows": (ci, [ci]),
-    "mrmt3_norm_dw_reduce": (ci, [vp, vp, vp, ci, ci, vp]),
-    "mrmt3_add_rmsnorm_bwd": (ci, [vp, ci, vp, ci, vp, vp, vp, vp, ci, vp, vp, ci, ci, cf, cu64, vp, cu32, cu32, ci, vp, csz, vp]),
-    "mrmt3_attn_fwd": (ci, [vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, ci, ci, ci, ci, ci, ci, cf, cu64, vp, cu32, vp]),
-    "mrmt3_attn_bwd": (ci, [vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, ci, vp, ci, vp, ci,
-                            ci, ci, ci, ci, ci, cf, cu64, vp, cu32, vp]),
-    "mrmt3_geglu_fwd": (ci, [vp, vp, ci, ci, ci, cf, cu64, vp, cu32, vp]),
-    "mrmt3_gemm_nt_geglu": (ci, [vp, ci, vp, ci, vp, ci, vp, ci, ci, ci, ci, cf, cu64, vp, cu32, vp]),
-    "mrmt3_gemm_rows_ok": (ci, [ci, ci, ci, ci, ci]),
-    "mrmt3_gemm_nt_addnorm": (ci, [vp, ci, vp, ci, ci, ci, vp, vp, cf, vp, vp, vp, cf, cu64, vp, cu32, cu32, ci, vp]),
-    "mrmt3_gemm_nt_normbwd_partial_rows": (ci, [ci]),
-    "mrmt3_gemm_nt_normbwd": (ci, [vp, ci, vp, ci, ci, ci, vp, ci, vp, vp, vp, vp, ci, vp, cf, cu64, vp, cu32, vp, csz, vp]),
-    "mrmt3_gemm_nt_geglubwd": (ci, [vp, ci, vp, ci, vp, vp, ci, ci, ci, cf, cu64, vp, cu32, vp]),
-    "mrmt3_tn_group_ok": (ci, [ci, ci, ci, ci, ci, ci]),
-    "mrmt3_tn_group_plan": (ci, [vp, ci, vp, vp, C.c_size_t, vp]),
-    "mrmt3_tn_group_run": (ci, [vp, vp, vp, vp]),
-    "mrmt3_host_alloc": (vp, [C.c_size_t]),
-    "mrmt3_host_free": (None, [vp]),
-    "mrmt3_dispatch_counts": (ci, [vp, ci, ci]),
-    "mrmt3_geglu_bwd": (ci, [vp, vp, vp, ci, ci, ci, cf, cu64, vp, cu32, vp]),
-    "mrmt3_gemm_tn_f32": (ci, [vp, ci, vp, ci, vp, ci, ci, ci, ci, ci, vp]),
-    "mrmt3_attn_bwd_f32": (ci, [vp, ci, vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, vp, ci, vp, ci, vp, ci, ci, ci, ci, ci, ci,
-                                cf, cu64, vp, cu32, vp]),
-    "mrmt3_attn_fwd_bias": (ci, [vp, ci, vp, ci, vp, ci, vp, C.c_longlong, vp, ci, vp, ci, ci, ci, ci, ci, ci, cf, cu64, vp,
-                                 cu32, vp]),
-    "mrmt3_attn_bwd_bias": (ci, [vp, ci, vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, vp, C.c_longlong, vp, ci, vp, ci, vp, ci, vp,
-                                 ci, ci, ci, ci, ci, ci, cf, cu64, vp, cu32, vp]),
-    "mrmt3_embed_fwd": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, cu64, vp, cu32, vp]),
-    "mrmt3_embed_bwd_workspace_bytes": (csz, [ci, ci, ci]),
-    "mrmt3_embed_bwd": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, cu64, vp, cu32, vp, csz, vp]),
-    "mrmt3_addpos_fwd": (ci, [vp, ci, vp, vp, ci, ci, ci, ci, cf, cu64, vp, cu32, vp]),
-    "mrmt3_dropmask_cast": (ci, [vp, vp, ci, csz, cf, cu64, vp, cu32, vp]),
-    "mrmt3_ce_count": (ci, [vp, ci, ci, ci, ci, vp, vp]),
-    "mrmt3_ce_fwd_bwd": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, cf, vp]),
-    "mrmt3_lmhead_ce_fwd_bwd": (ci, [vp, ci, vp, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, vp, csz, ci, vp]),
-    "mrmt3_adamw_step": (ci, [vp, vp, vp, vp, csz, vp, vp, cf, cf, cf, cf, cf, vp, vp]),
-    "mrmt3_counter_add": (ci, [vp, ci, vp]),
-    "mrmt3_transpose": (ci, [vp, ci, vp, ci, ci, ci, vp]),
-    "mrmt3_cast": (ci, [vp, ci, vp, ci, csz, vp]),
-    "mrmt3_transpose_batched": (ci, [vp, vp, vp, vp, ci, ci, vp]),
-    "mrmt3_decoder_create": (ci, [C.POINTER(vp), ci, ci, ci, ci, ci, ci, ci, ci, ci, cf]),
-    "mrmt3_decoder_destroy": (None, [vp]),
-    "mrmt3_decoder_begin": (ci, [vp, vp, vp, ci, ci, vp, ci, ci, ci, vp]),
-    "mrmt3_decoder_set_prefix": (ci, [vp, vp, ci, vp]),
-    "mrmt3_decoder_graph_captured": (ci, [vp]),
-    "mrmt3_decoder_run": (ci, [vp, ci, vp]),
-    "mrmt3_decoder_poll": (ci, [vp, vp, vp]),
-    "mrmt3_decoder_logits": (ci, [vp, vp, ci, vp]),
-    "mrmt3_decoder_set_ban": (ci, [vp, vp, vp]),
-    "mrmt3_decoder_begin_beam": (ci, [vp, vp, vp, ci, ci, ci, vp, ci, ci, ci, cf, vp, vp, vp, vp, vp]),
-    "mrmt3_decoder_beam_finalize": (ci, [vp, vp, ci, ci, vp]),
-    "mrmt3_comm_unique_id": (ci, [vp]),
-    "mrmt3_comm_create": (ci, [vp, ci, ci, C.POINTER(vp)]),
-    "mrmt3_comm_destroy": (ci, [vp]),
-    "mrmt3_allreduce": (ci, [vp, vp, csz, ci, ci, vp]),
-    "mrmt3_flag_signal": (ci, [vp, vp]),
-    "mrmt3_flag_wait": (ci, [vp, vp, vp, ci, vp]),
-    "mrmt3_stream_capture_status": (ci, [vp]),
-    "mrmt3_stream_abandon_capture": (ci, [vp]),
-    "mrmt3_runtime_error_pop": (ci, [C.c_char_p, ci]),
-    "mrmt3_stream_create": (ci, [C.POINTER(vp), ci]),
-    "mrmt3_stream_destroy": (ci, [vp]),
-    "mrmt3_abort_trace_install": (ci, [C.c_char_p]),
-    "mrmt3_pack_tile_entries": (ci, [ci, ci]),
-    "mrmt3_pack_lengths": (ci, [vp, ci, ci, vp, vp]),
-    "mrmt3_pack_plan": (ci, [vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "mrmt3_embed_fwd_packed": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, cf, cu64, vp, cu32, vp]),
-    "mrmt3_attn_fwd_varlen": (ci, [vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, cu64, vp,
-                                   cu32, vp]),
-    "mrmt3_attn_bwd_varlen": (ci, [vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, ci, vp, ci, vp, ci, vp, vp, ci, ci,
-                                   ci, ci, ci, ci, ci, cf, cu64, vp, cu32, vp]),
-}
+
+def _header_text(path: str) -> str:
+    return re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
 
 
 def header_symbols(path: str = HEADER_PATH):
     """Names of every function the C header declares."""
-    txt = open(path).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(mrmt3_[a-z0-9_]+)\s*\(", txt)))
+    return sorted(set(re.findall(r"\b(mrmt3_[a-z0-9_]+)\s*\(", _header_text(path))))
+
+
+_C_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "float": C.c_float, "size_t": C.c_size_t, "uint32_t": C.c_uint32,
+              "uint64_t": C.c_uint64, "long long": C.c_longlong, "unsigned long long": C.c_ulonglong}
+
+
+def _ctype(decl: str, what: str):
+    """ctypes type of one C type as the header spells it: scalars by value, `const char*` as c_char_p, every other
+    pointer as an address, a pointer to a pointer (an out-parameter for a handle) as POINTER(c_void_p)."""
+    stars = decl.count("*")
+    words = decl.replace("*", " ").split()
+    base = " ".join(w for w in words if w != "const")
+    if stars == 0 and base == "void":
+        return None
+    if stars == 0 and base in _C_SCALARS:
+        return _C_SCALARS[base]
+    if stars == 1:
+        return C.c_char_p if words == ["const", "char"] else C.c_void_p
+    if stars == 2:
+        return C.POINTER(C.c_void_p)
+    raise TypeError(f"{what}: no ctypes mapping for the C type '{decl.strip()}'")
+
+
+def header_signatures(path: str = HEADER_PATH) -> dict:
+    """{name: (restype, argtypes)} of every prototype of the C header (plain C, one prototype per entry point)."""
+    sigs = {}
+    for ret, name, params in re.findall(r"([\w \t\*]+?)\b(mrmt3_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", _header_text(path)):
+        args = []
+        for prm in ([] if params.strip() == "void" else params.split(",")):
+            m = re.fullmatch(r"\s*(.*?[\s\*])\w+\s*", prm, flags=re.S)       # type, then the parameter's name
+            if m is None:
+                raise TypeError(f"{name}: cannot parse the parameter '{prm.strip()}'")
+            args.append(_ctype(m.group(1), name))
+        sigs[name] = (_ctype(ret, name), args)
+    if set(sigs) != set(header_symbols(path)):
+        raise TypeError("unparsed prototypes: %s" % sorted(set(sigs) ^ set(header_symbols(path))))
+    return sigs
+
+
+_SIGS = header_signatures()          # applied by load(): the header is the one place a signature is written down
 
 
 def build(verbose: bool = False, diag: bool = True) -> str:
@@ -154,7 +106,7 @@ def load():
     return lib
 
 
-MIN_VERSION = 113
+MIN_VERSION = 114
 COUNTER_NAMES = ("gemm_nt_tile", "gemm_nt8", "gemm_nt_geglu", "tn_group", "tn8", "tn_tile", "attn_fwd", "attn_bwd",
                  "attn_bwd_onepass", "attn_f32", "tn_f32", "gemm_nt_splitk", "gemm_nt_addnorm", "gemm_nt_normbwd",
                  "gemm_nt_geglubwd", "attn_fwd_varlen", "attn_bwd_varlen")
@@ -188,21 +140,20 @@ PROFILE_BYTES = {}      # family -> algorithmic bytes (operands read once + outp
 
 
 class _Timed:
-    def __init__(self, family, work, unit, stream=None, executed=None):
+    def __init__(self, family, work, unit, executed=None):
         self.args = (family, work, unit)
-        self.stream = stream
         self.executed = executed     # optional second price of the same launch (family "<name>@executed")
 
     def __enter__(self):
         if PROFILE is not None:
             self.e0 = torch.cuda.Event(enable_timing=True)
             self.e1 = torch.cuda.Event(enable_timing=True)
-            self.e0.record(self.stream) if self.stream is not None else self.e0.record()
+            self.e0.record()
         return self
 
     def __exit__(self, *exc):
         if PROFILE is not None:
-            self.e1.record(self.stream) if self.stream is not None else self.e1.record()
+            self.e1.record()
             PROFILE.append(self.args + (self.e0, self.e1))
             if self.executed is not None:
                 PROFILE.append((self.args[0] + "@executed", self.executed, self.args[2], self.e0, self.e1))
@@ -308,10 +259,9 @@ _ws_cache = {}
 _ws_retired = []
 
 
-def workspace(nbytes: int, device, stream=None) -> torch.Tensor:
+def workspace(nbytes: int, device) -> torch.Tensor:
     # one scratch buffer per (device, stream): kernels on different streams may run concurrently
-    key = (device.index if hasattr(device, "index") else 0,
-           (torch.cuda.current_stream() if stream is None else stream).cuda_stream)
+    key = (device.index if hasattr(device, "index") else 0, torch.cuda.current_stream().cuda_stream)
     buf = _ws_cache.get(key)
     if buf is None or buf.numel() < nbytes:
         if buf is not None:
@@ -321,62 +271,6 @@ def workspace(nbytes: int, device, stream=None) -> torch.Tensor:
         buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
         _ws_cache[key] = buf
     return buf
-
-
-class TnBatch:
-    """Weight-gradient GEMMs whose split-K slabs are summed in ONE launch instead of one per GEMM.
-
-    `gemm_tn(..., defer=batch)` runs only the MFMA kernel, leaving the site's f32 slabs in a buffer that belongs to
-    (batch, out address, shape), and queues the site; `flush()` runs `mrmt3_tn_reduce_sites` over everything queued,
-    in queue order, on the current stream (which must already be ordered behind the GEMMs' stream).  Same summation
-    order per element as the immediate form: bit-identical gradients.  The descriptor tables live on the device and
-    are rebuilt only when the set of queued sites changes (never under graph capture after the eager warm-up)."""
-
-    def __init__(self):
-        self._slabs = {}       # (out address, M, N1, N2) -> slab tensor
-        self._queue = []       # [(key, out, ldc, accumulate)]
-        self._tables = {}
-        # called before a flush that site() triggers by itself (the same gradient queued twice): the partial GEMMs of
-        # the queued sites may have been launched on another stream (Engine.wgrad's side stream), which the CURRENT
-        # stream — where the flush's reduce runs — has not joined yet (ADVICE r3).  The engine sets it to its join.
-        self.before_early_flush = None
-
-    def site(self, out, M, N1, N2, accumulate):
-        key = (out.data_ptr(), M, N1, N2, out.stride(0), int(accumulate))
-        if key in self._queue:
-            # the same gradient twice before a flush: its slab buffer is still waiting to be summed
-            if self.before_early_flush is not None:
-                self.before_early_flush()
-            self.flush()
-        buf = self._slabs.get(key)
-        if buf is None:
-            buf = torch.empty(load().mrmt3_gemm_tn_workspace_bytes(M, N1, N2), device=out.device, dtype=torch.uint8)
-            self._slabs[key] = buf
-        self._queue.append(key)
-        self._dev = out.device
-        return buf
-
-    def flush(self):
-        if not self._queue:
-            return
-        import numpy as np
-        keys = tuple(self._queue)
-        tab = self._tables.get(keys)
-        if tab is None:
-            L = load()
-            rec = np.zeros(len(keys), dtype=[("slabs", "<u8"), ("C", "<u8"), ("N1", "<i4"), ("N2", "<i4"), ("ldc", "<i4"),
-                                             ("splits", "<i4"), ("acc", "<i4"), ("block0", "<i4"), ("p0", "<i4"), ("p1", "<i4")])
-            blocks = 0
-            for i, k in enumerate(keys):
-                addr, M, N1, N2, ldc, acc = k
-                rec[i] = (self._slabs[k].data_ptr(), addr, N1, N2, ldc, L.mrmt3_gemm_tn_splits(M, N1, N2), acc, blocks, 0, 0)
-                blocks += -(-(N1 * N2) // 1024)
-            tab = (torch.from_numpy(rec.view(np.uint8).copy()).to(self._dev), len(keys), blocks)
-            self._tables[keys] = tab
-        try:
-            _check(load().mrmt3_tn_reduce_sites(_p(tab[0]), tab[1], tab[2], _stream()), "tn_reduce_sites")
-        finally:
-            self._queue.clear()
 
 
 class _TnGSite(C.Structure):          # = mrmt3_tn_gsite
@@ -520,28 +414,17 @@ def gemm_tn_f32(a, b, out, accumulate=False):
     return out
 
 
-def gemm_tn(a, b, out, accumulate=False, stream=None, defer=None):
-    """out[N1,N2] (+)= a[M,N1]^T @ b[M,N2]  (bf16 in, f32 out).  `stream` (torch.cuda.Stream) launches there
-    instead of on the current stream, without the cost of a stream context switch.  `defer=` a TnBatch: only the
-    slabs are produced now, `out` is complete after the batch's flush()."""
+def gemm_tn(a, b, out, accumulate=False):
+    """out[N1,N2] (+)= a[M,N1]^T @ b[M,N2]  (bf16 in, f32 out), on the current stream."""
     _dev(a, b, out)
     M, N1 = a.shape
     N2 = b.shape[1]
     assert b.shape[0] == M and a.stride(1) == 1 and b.stride(1) == 1 and out.stride(1) == 1
     lib = load()
-    if defer is not None:
-        slabs = defer.site(out, M, N1, N2, accumulate)
-        sp = _stream() if stream is None else C.c_void_p(stream.cuda_stream)
-        with _Timed("gemm_tn_bf16", 2.0 * M * N1 * N2, "FLOP", stream):
-            _check(lib.mrmt3_gemm_tn_partial(_p(a), a.stride(0), _p(b), b.stride(0), M, N1, N2, _p(slabs),
-                                             slabs.numel(), sp), "gemm_tn_partial")
-        return out
-    nbytes = lib.mrmt3_gemm_tn_workspace_bytes(M, N1, N2)
-    ws = workspace(nbytes, a.device, stream)
-    sp = _stream() if stream is None else C.c_void_p(stream.cuda_stream)
-    with _Timed("gemm_tn_bf16", 2.0 * M * N1 * N2, "FLOP", stream):
+    ws = workspace(lib.mrmt3_gemm_tn_workspace_bytes(M, N1, N2), a.device)
+    with _Timed("gemm_tn_bf16", 2.0 * M * N1 * N2, "FLOP"):
         _check(lib.mrmt3_gemm_tn(_p(a), a.stride(0), _p(b), b.stride(0), _p(out), out.stride(0), M, N1, N2,
-                                 int(accumulate), _p(ws), ws.numel(), sp), "gemm_tn")
+                                 int(accumulate), _p(ws), ws.numel(), _stream()), "gemm_tn")
     return out
 
 

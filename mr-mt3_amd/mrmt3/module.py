@@ -176,7 +176,6 @@ class MT3Module(nn.Module):
             from .ddp import GradBuckets
             b = GradBuckets(self.flat, self.cfg["num_layers"], self.cfg["num_decoder_layers"], self.segmem_num_layers > 0)
             b.before_fire = self.engine.join_wgrad
-            b.producer_streams = lambda: [self.engine._side]
             self._auto_buckets = b
             # identical replicas to start from (DDP broadcasts rank 0's parameters at construction)
             dist.broadcast(self.flat.P, src=0)

@@ -7,8 +7,8 @@ optimizer semantics (torch.optim.AdamW defaults, cosine-warmup LambdaLR stepped 
 process per GPU.  Nothing on the host waits for the device inside a step: the learning rate, the
 step counter and the loss stay in device memory.
 
-Host out of the step.  After two eager steps of a given input shape the whole step — ≈700 kernel launches on two
-streams with their event fork/joins — is captured into hipGraphs and replayed: the host then enqueues a handful of
+Host out of the step.  After two eager steps of a given input shape the whole step — ≈700 kernel launches on one
+stream — is captured into hipGraphs and replayed: the host then enqueues a handful of
 graph launches per step instead of ≈600 ctypes calls (19.6 of 28 ms per step in round 1).  What makes the replay equal
 to the eager step bit for bit:
   * dropout masks are keyed by (seed, site, DEVICE step counter): the site ids restart at 0 every step and the
@@ -128,8 +128,7 @@ class Trainer:
         layers_per_bucket = max(1, int(os.environ.get("MRMT3_DDP_LAYERS_PER_BUCKET", layers_per_bucket)))
         self.buckets = GradBuckets(self.flat, cfg["num_layers"], cfg["num_decoder_layers"],
                                    model.segmem_num_layers > 0, layers_per_bucket, exchange_dtype=grad_exchange_dtype)
-        self.buckets.before_fire = model.engine.join_wgrad      # norm-weight partials and split-K slabs are summed here
-        self.buckets.producer_streams = lambda: [model.engine._side]
+        self.buckets.before_fire = model.engine.join_wgrad      # the bucket's deferred weight and norm-weight gradients run here
         self.flat.ensure_grads()
         self.flat.ensure_adam()
         if self.world > 1:   # C2: identical replicas
@@ -219,7 +218,7 @@ class Trainer:
                 idx = [j for j in self.buckets.triggered_by(prefix, i) if j not in sent]
                 if idx:
                     sent.update(idx)
-                    eng.join_wgrad()                         # a capture must end with its forked stream joined
+                    eng.join_wgrad()                         # the segment ends with its bucket's gradients complete
                     cut(idx)
             active = self.buckets.active
             eng.backward(tape, dl, on_layer_done=layer_done if active else None)     # ends with join_wgrad()
@@ -359,10 +358,9 @@ class Trainer:
     # ---- a capture that failed: leave nothing behind -----------------------------------------------------------------
     def _capture_streams(self):
         """Every stream a capture of the step can have pulled into capture mode (a capture spreads to each stream that waits
-        on an event of a capturing one: the capture stream itself, the engine's weight-gradient side stream, the collective
-        stream and the candidates the stream pick made), plus the caller's."""
-        out = {"current": torch.cuda.current_stream(), "capture": self._cap_stream, "side": self.engine._side,
-               "collective": self.buckets._launch}
+        on an event of a capturing one: the capture stream itself, the collective stream and the candidates the stream pick
+        made), plus the caller's."""
+        out = {"current": torch.cuda.current_stream(), "capture": self._cap_stream, "collective": self.buckets._launch}
         for i, s in enumerate(getattr(self, "_stream_candidates", [])):
             out["candidate%d" % i] = s
         seen, uniq = set(), {}
@@ -511,12 +509,9 @@ class Trainer:
             cap.segments.append((g, list(fire)))
             begin()
 
-        overlap_was = eng.overlap_wgrad
         gc_was = gc.isenabled()
         gc.disable()
         try:
-            if os.environ.get("MRMT3_GRAPH_LINEAR", "1") == "1":
-                eng.overlap_wgrad = False          # one chain of nodes, no fork/join edges in the graph
             with torch.cuda.stream(cs):
                 begin()
                 try:
@@ -536,7 +531,6 @@ class Trainer:
                                 pass
                     raise
         finally:
-            eng.overlap_wgrad = overlap_was
             if gc_was:
                 gc.enable()
         cur.wait_stream(cs)

@@ -1,3 +1,5 @@
+# CLOSED (round 8): times lib.TnBatch / mrmt3_tn_reduce_sites, which left the library with the per-gradient deferral layer
+# (ABI 114); kept as the record behind profiles/r02_gemm8_probes.txt, it no longer runs.
 """The batched split-K slab reduction (mrmt3_tn_reduce_sites) on the weight-gradient sites of one training step:
 bytes streamed, time, GB/s."""
 import os, sys

@@ -1,7 +1,6 @@
 """A/B of the two weight-gradient (TN) GEMM kernels (gemm.hip: 128x128 tiles, 2 workgroups per CU; gemm_tn8.hip:
 256x256 ping-pong) on every TN shape of the training step, in one process, interleaved rounds, random operands, with a
-check against an f32 torch product.  Times the MFMA kernel alone (deferred form: slabs only) and the immediate form
-(kernel + its own slab reduce).  Usage: python profiles/tools/gemm_tn_ab.py [rounds] [reps]"""
+check against an f32 torch product.  Times mrmt3_gemm_tn (the MFMA kernel + its own slab reduce).  Usage: python profiles/tools/gemm_tn_ab.py [rounds] [reps]"""
 import os
 import sys
 
@@ -54,22 +53,14 @@ for name, M, N1, N2, per_step in TN:
     rel = ((got - full).abs().max() / full.abs().max()).item()
     assert rel < 2e-5, (name, rel)
     best = {"0": 1e9, "1": 1e9}
-    best_i = {"0": 1e9, "1": 1e9}
-    batches = {"0": lib.TnBatch(), "1": lib.TnBatch()}
     for _ in range(rounds):
         for k in ("0", "1"):
             os.environ["MRMT3_TN8"] = k
-            bt = batches[k]
-
-            def part():
-                lib.gemm_tn(a, b, got, accumulate=True, defer=bt)
-                bt._queue.clear()
-            best[k] = min(best[k], timeit(part))
-            best_i[k] = min(best_i[k], timeit(lambda: lib.gemm_tn(a, b, got, accumulate=False)))
+            best[k] = min(best[k], timeit(lambda: lib.gemm_tn(a, b, got, accumulate=False)))
     f = 2.0 * M * N1 * N2
     for k in best:
         tot[k] += best[k] * per_step
     flops += f * per_step
-    print(f"TN {name:7s} M={M:5d} N1={N1:4d} N2={N2:4d}: old {best['0']*1e6:7.1f} us {f/best['0']/1e12:5.0f} TF (+reduce {best_i['0']*1e6:7.1f}) | "
-          f"new {best['1']*1e6:7.1f} us {f/best['1']/1e12:5.0f} TF (+reduce {best_i['1']*1e6:7.1f}) | x{best['0']/best['1']:.2f}")
-print(f"per step (MFMA kernels only): old {tot['0']*1e3:.2f} ms ({flops/tot['0']/1e12:.0f} TF), new {tot['1']*1e3:.2f} ms ({flops/tot['1']/1e12:.0f} TF)")
+    print(f"TN {name:7s} M={M:5d} N1={N1:4d} N2={N2:4d}: old {best['0']*1e6:7.1f} us {f/best['0']/1e12:5.0f} TF | "
+          f"new {best['1']*1e6:7.1f} us {f/best['1']/1e12:5.0f} TF | x{best['0']/best['1']:.2f}")
+print(f"per step (kernel + slab reduce): old {tot['0']*1e3:.2f} ms ({flops/tot['0']/1e12:.0f} TF), new {tot['1']*1e3:.2f} ms ({flops/tot['1']/1e12:.0f} TF)")

@@ -1,5 +1,5 @@
 """RCCL on the one GPU of the box: (1) the collectives the trainer uses work on slices of a flat buffer, (2) the
-trainer's bucketed exchange (launch stream waiting for the backward stream and the wgrad side stream, async all-reduce,
+trainer's bucketed exchange (launch stream waiting for the backward stream, async all-reduce,
 wait before AdamW) runs over RCCL at world size 1 — a sum over one rank is the identity, so three training steps must
 give bit-identical parameters with and without the forced collectives."""
 import os

@@ -1,5 +1,5 @@
 """Stress of the batched norm-weight-gradient reduction (mrmt3_norm_dw_reduce: last-arriving chunk, relaxed agent-scope
-atomics, no fence — ADVICE round 1) and of the deferred split-K slab reduce: N iterations on fixed inputs, every result
+atomics, no fence — ADVICE round 1) and of the split-K slab reduce of mrmt3_gemm_tn: N iterations on fixed inputs, every result
 compared bit for bit with the first, alone and with a second PROCESS keeping the GPU busy (time slicing, which is what
 the two-rank tests on one GPU do).   python3 profiles/tools/norm_dw_stress.py [iterations] [noise: 0/1]"""
 import os
@@ -33,7 +33,6 @@ for rows in (256, 4096, 65536):
     batch = lib.NormDwBatch()
     a = torch.randn(rows, 512, device=dev).bfloat16()
     b = torch.randn(rows, 384, device=dev).bfloat16()
-    tn = lib.TnBatch()
     gw = torch.zeros(512, 384, device=dev)
     first = None
     nbad = nbad_tn = 0
@@ -43,9 +42,8 @@ for rows in (256, 4096, 65536):
         gw.zero_()
         for i in range(n_sites):
             lib.add_rmsnorm_bwd(gs[i], None, xs[i], rstd, w, dws[i], want_dy=False, defer=batch)
-        lib.gemm_tn(a, b, gw, accumulate=True, defer=tn)
+        lib.gemm_tn(a, b, gw, accumulate=True)
         batch.flush()
-        tn.flush()
         cur = torch.stack(dws).clone()
         if first is None:
             first, first_tn = cur, gw.clone()

@@ -8,7 +8,7 @@ first repetition's.
 
     python3 profiles/tools/two_rank_soak.py <mode> <iterations> [graph]
 
-Environment switches of the engine (MRMT3_WGRAD_STREAM=0, MRMT3_TN_BATCH=0, MRMT3_NORM_DW_BATCH=0, MRMT3_TN_GROUP=0) are
+Environment switches of the engine (MRMT3_NORM_DW_BATCH=0, MRMT3_TN_GROUP=0) are
 inherited by the workers: a mismatch is bisected by repeating the run with one of them set."""
 import os
 import socket

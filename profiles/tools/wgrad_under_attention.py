@@ -61,10 +61,11 @@ ops = [(rnd(rows, n1, scale=0.1), rnd(rows, n2, scale=0.1), torch.zeros(n1, n2, 
 flops_b = sum(2.0 * rows * n1 * n2 for n1, n2 in WG) * N_LAYERS
 
 
-def weight_gradients(stream):
+def weight_gradients():
+    """(launched by wall() under `with torch.cuda.stream(sb)`: lib.gemm_tn runs on the current stream)"""
     for _ in range(N_LAYERS):
         for a, b, out in ops:
-            lib.gemm_tn(a, b, out, accumulate=True, stream=stream)
+            lib.gemm_tn(a, b, out, accumulate=True)
 
 
 sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
@@ -93,11 +94,11 @@ for name, knob in (("round-1 128x128 TN tile kernel (MRMT3_TN8=0)", 0), ("ping-p
     lib.set_knob("MRMT3_TN8", knob)
     before = lib.dispatch_counts()
     for _ in range(2):                                    # warm-up (workspaces, code objects)
-        wall(attention_backward, lambda: weight_gradients(sb), 1)
+        wall(attention_backward, weight_gradients, 1)
     after = lib.dispatch_counts()
     ta = wall(attention_backward, None)
-    tb = wall(None, lambda: weight_gradients(sb))
-    tab = wall(attention_backward, lambda: weight_gradients(sb))
+    tb = wall(None, weight_gradients)
+    tab = wall(attention_backward, weight_gradients)
     tba = wall(lambda: None, None)                         # (launch overhead of an empty round)
     kern = {k: after[k] - before[k] for k in ("tn_tile", "tn8", "attn_bwd", "attn_bwd_onepass") if after[k] != before[k]}
     print("  %-62s t(A) %7.3f   t(B) %7.3f (%.0f TFLOP/s)   t(A||B) %7.3f = %.3f x (t(A) + t(B))   [launches in the warm-up: %s]"

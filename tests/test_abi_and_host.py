@@ -24,6 +24,42 @@ def test_library_exports_every_declared_symbol():
     assert lib.load().mrmt3_version() >= 100
 
 
+def test_header_derived_signatures_match_hand_written_ones():
+    """lib._SIGS is parsed from the prototypes of include/mrmt3_hip.h: a few signatures typed out by hand here, so that a
+    parser regression cannot hide behind itself — the widest argument list, a size_t and a `const char*` return, a
+    `void` return, handle out-parameters, `const char*` and 64-bit scalar arguments."""
+    vp, ci, cf, cu64, cu32, csz = (ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint32,
+                                   ctypes.c_size_t)
+    out_handle = ctypes.POINTER(ctypes.c_void_p)
+    want = {
+        "mrmt3_attn_bwd_varlen": (ci, [vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, ci, vp, ci, vp, ci, vp, vp, ci, ci,
+                                       ci, ci, ci, ci, ci, cf, cu64, vp, cu32, vp]),
+        "mrmt3_gemm_tn_workspace_bytes": (csz, [ci, ci, ci]),
+        "mrmt3_gemm_tn": (ci, [vp, ci, vp, ci, vp, ci, ci, ci, ci, ci, vp, csz, vp]),
+        "mrmt3_last_error": (ctypes.c_char_p, []),
+        "mrmt3_version": (ci, []),
+        "mrmt3_host_alloc": (vp, [csz]),
+        "mrmt3_host_free": (None, [vp]),
+        "mrmt3_set_knob": (ci, [ctypes.c_char_p, ci]),
+        "mrmt3_decoder_create": (ci, [out_handle, ci, ci, ci, ci, ci, ci, ci, ci, ci, cf]),
+        "mrmt3_comm_create": (ci, [vp, ci, ci, out_handle]),
+        "mrmt3_stream_create": (ci, [out_handle, ci]),
+        "mrmt3_logmel_crops_fwd": (ci, [vp, ctypes.c_longlong, vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci, vp, vp]),
+        "mrmt3_adamw_step": (ci, [vp, vp, vp, vp, csz, vp, vp, cf, cf, cf, cf, cf, vp, vp]),
+    }
+    assert len(want["mrmt3_attn_bwd_varlen"][1]) == 33
+    for name, sig in want.items():
+        assert lib._SIGS[name] == sig, (name, lib._SIGS[name])
+    fn = lib.load().mrmt3_attn_bwd_varlen                    # ... and load() has applied them
+    assert fn.restype is ci and list(fn.argtypes) == want["mrmt3_attn_bwd_varlen"][1]
+    assert lib.load().mrmt3_gemm_tn_workspace_bytes.restype is csz and lib.load().mrmt3_last_error.restype is ctypes.c_char_p
+    # a type the parser does not know is an error, not a guess
+    with pytest.raises(TypeError):
+        lib._ctype("double", "test")
+    with pytest.raises(TypeError):
+        lib._ctype("mrmt3_tn_gsite", "test")
+
+
 def test_product_library_carries_no_kernel_diagnostics():
     """the round-4 experiments (knock-out bits, start skews, per-workgroup time stamps) are compiled only
     into the -DMRMT3_DIAG twin that profiles/tools load; the product library neither exports the trace entry point nor

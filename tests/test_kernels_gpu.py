@@ -1015,41 +1015,33 @@ def test_attn_bwd_delta_from_hi_lo_output_keeps_the_common_mode_cancellation(dev
     assert err["hi_only"][0] > 2.5 * err["hi_lo"][0] and err["hi_only"][1] > 2.5 * err["hi_lo"][1]
 
 
-def test_gemm_tn_deferred_batch_is_bitwise_the_immediate_form(dev):
-    """lib.TnBatch: the weight-gradient GEMMs of a step leave their split-K slabs per site and ONE launch sums them all
-    (`mrmt3_tn_reduce_sites`).  Same per-element summation order as `mrmt3_gemm_tn`: bit-identical, accumulate
-    included, tables reused across flushes."""
+def test_gemm_tn_into_a_row_strided_view(dev):
+    """lib.gemm_tn with C a row block of a larger buffer (a third of a fused [1152, 512] weight gradient): overwrite and
+    accumulate land in rows 384..767 only, bit for bit what the call on a buffer of its own gives, and agree with an f32
+    torch product within test_gemm_tn's bound (f32 accumulation of exact bf16 products over 1024 rows)."""
     from mrmt3 import lib
     torch.manual_seed(1)
-    shapes = [(4096, 512, 384), (2048 + 64, 1152, 512), (4096, 2048, 512), (1024, 384, 512), (8192, 512, 1024)]
-    ops = [((torch.randn(M, N1, device=dev) * 0.1).bfloat16(), (torch.randn(M, N2, device=dev) * 0.1).bfloat16())
-           for M, N1, N2 in shapes]
-    want = [torch.randn(N1, N2, device=dev) for _, N1, N2 in shapes]
-    got = [w.clone() for w in want]
-    for (a, b), w in zip(ops, want):
-        lib.gemm_tn(a, b, w, accumulate=True)
-    batch = lib.TnBatch()
-    for rep in range(2):
-        for (a, b), g in zip(ops, got):
-            lib.gemm_tn(a, b, g, accumulate=True, defer=batch)
-        batch.flush()
-        batch.flush()                       # empty flush is a no-op
-        if rep == 0:
-            for g, w in zip(got, want):
-                assert torch.equal(g, w)
-            for (a, b), w in zip(ops, want):
-                lib.gemm_tn(a, b, w, accumulate=True)
-    for g, w in zip(got, want):
-        assert torch.equal(g, w)
-    assert len(batch._tables) == 1
-    # strided C (a row block of a fused weight gradient) and accumulate=False
+    M, N1, N2 = 1024, 384, 512
+    a = (torch.randn(M, N1, device=dev) * 0.1).bfloat16()
+    b = (torch.randn(M, N2, device=dev) * 0.1).bfloat16()
+    prod = a.float().t() @ b.float()
     big = torch.zeros(1152, 512, device=dev)
     ref = torch.zeros(384, 512, device=dev)
-    a, b = ops[3]
     lib.gemm_tn(a, b, ref, accumulate=False)
-    lib.gemm_tn(a, b, big[384:768], accumulate=False, defer=batch)
-    batch.flush()
+    lib.gemm_tn(a, b, big[384:768], accumulate=False)
     assert torch.equal(big[384:768], ref) and big[:384].abs().max() == 0 and big[768:].abs().max() == 0
+    assert _rel(big[384:768], prod) < 1e-5
+    init = torch.randn(1152, 512, device=dev)
+    big, ref = init.clone(), init[384:768].clone()
+    lib.gemm_tn(a, b, ref, accumulate=True)
+    lib.gemm_tn(a, b, big[384:768], accumulate=True)
+    assert torch.equal(big[384:768], ref) and torch.equal(big[:384], init[:384]) and torch.equal(big[768:], init[768:])
+    assert _rel(big[384:768], prod + init[384:768]) < 1e-5
+    # a column block: the row stride of C (1024) differs from its width
+    wide = torch.zeros(384, 1024, device=dev)
+    lib.gemm_tn(a, b, wide[:, 512:], accumulate=False)
+    lib.gemm_tn(a, b, ref, accumulate=False)
+    assert torch.equal(wide[:, 512:], ref) and wide[:, :512].abs().max() == 0
 
 
 @pytest.mark.parametrize("M,N,K,out,acc", [
