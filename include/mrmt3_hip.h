@@ -392,6 +392,28 @@ int mrmt3_lmhead_ce_fwd_bwd(const void* dec, int ld_dec, const void* W, int ldw,
 int mrmt3_adamw_step(float* p, const float* g, float* m, float* v, size_t n, const float* lr_dev,
                      int32_t* step_dev, float beta1, float beta2, float eps, float weight_decay,
                      float grad_scale, void* shadow_bf16, void* stream);
+/* ---- K11b: global gradient norm, clip coefficient and non-finite guard on the device, and the AdamW step that obeys
+ * them (Lightning's `gradient_clip_val` / `gradient_clip_algorithm`, torch.nn.utils.clip_grad_norm_ semantics; the
+ * reference passes its `trainer:` block to pl.Trainer, train.py:43-47).
+ * mrmt3_grad_norm: two launches.  Stage 1 is a FIXED grid (the same on every device and for every n) of 256-thread
+ * workgroups that stride over g with 16-byte loads, accumulate g*g in f64 and leave one f64 partial each in `ws`
+ * (8-byte aligned, at least mrmt3_grad_norm_workspace_elems() floats; no atomics).  Stage 2, one workgroup, sums the
+ * partials in a fixed order in f64 and writes
+ *   stat_dev[0] = norm = (float)(sqrt(sum) * grad_scale)      the norm of the gradient AdamW will see, before clipping
+ *   stat_dev[1] = coef = max_norm > 0 ? min(1, max_norm / (norm + 1e-6)) : 1      (f32)
+ *   stat_dev[2] = skip = 1.0 iff skip_nonfinite and norm is inf or NaN; then also coef = 0 and skipped_dev[0] += 1.
+ * The same g gives the same bits wherever it runs.  n % 4 == 0. */
+size_t mrmt3_grad_norm_workspace_elems(void);
+int mrmt3_grad_norm(const float* g, size_t n, float grad_scale, float max_norm, int skip_nonfinite, float* ws,
+                    size_t ws_elems, float* stat_dev, int32_t* skipped_dev, void* stream);
+/* mrmt3_adamw_step with the gradient g * grad_scale * stat_dev[1], then, when clip_value > 0, clamped to
+ * [-clip_value, clip_value] (`gradient_clip_algorithm: value`).  stat_dev[2] != 0: nothing is stored (p, m, v and the
+ * shadow keep their bits).  step_dev is incremented either way: it counts ATTEMPTED optimizer steps.  With
+ * stat_dev[1] == 1 and clip_value == 0 the result is mrmt3_adamw_step's, bit for bit. */
+int mrmt3_adamw_step_clipped(float* p, const float* g, float* m, float* v, size_t n, const float* lr_dev,
+                             int32_t* step_dev, float beta1, float beta2, float eps, float weight_decay,
+                             float grad_scale, const float* stat_dev, float clip_value, void* shadow_bf16,
+                             void* stream);
 /* ctr[0] += delta on the device (int32, one thread, stream-ordered).  The trainer's gradient accumulation keeps its
  * per-micro-batch dropout salt in such a counter: it is passed as the step_dev of the dropout entry points and bumped
  * once per micro-batch, inside the captured step, so replays draw new masks per micro-batch. */

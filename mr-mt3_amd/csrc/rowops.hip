@@ -1098,6 +1098,162 @@ extern "C" int mrmt3_adamw_step(float* p, const float* g, float* m, float* v, si
   return MRMT3_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Global gradient norm + clip coefficient + non-finite guard, and the AdamW step that obeys them
+// (Lightning's gradient_clip_val / gradient_clip_algorithm; torch.nn.utils.clip_grad_norm_)
+// ------------------------------------------------------------------------------------------------
+// Stage 1 runs a FIXED grid whatever the device and n: the order of every addition is a function of n alone, so every
+// rank and every box lands on the same bits.  2048 workgroups x 4 waves = 32 waves per CU on 256 CUs, 4 x 16 B in
+// flight per lane.  g*g is exact in f64 (24 x 24 significand bits), so the only roundings are the f64 additions.
+#define GN_BLOCKS 2048
+#define GN_PER_LANE (GN_BLOCKS / 256)      // partials per lane of stage 2
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// sum over the 256 threads of a workgroup, valid in thread 0: the wave's xor tree, then the 4 waves in index order
+__device__ __forceinline__ double block_sum_f64(double v, double* lds4) {
+  v = wave_sum_f64(v);
+  if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((lds4[0] + lds4[1]) + lds4[2]) + lds4[3];
+}
+
+__device__ __forceinline__ void sumsq4_f64(const float gv[4], double acc[4]) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const double d = (double)gv[e];
+    acc[e] += d * d;
+  }
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, size_t n4,
+                                                         double* __restrict__ partial) {
+  __shared__ double lds4[4];
+  const size_t stride = (size_t)GN_BLOCKS * 256;
+  size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  for (; i + 3 * stride < n4; i += 4 * stride) {             // four independent 16-byte loads in flight per lane
+    float a[4], b[4], c[4], d[4];
+    load4<float>(g + i * 4, a);
+    load4<float>(g + (i + stride) * 4, b);
+    load4<float>(g + (i + 2 * stride) * 4, c);
+    load4<float>(g + (i + 3 * stride) * 4, d);
+    sumsq4_f64(a, acc); sumsq4_f64(b, acc); sumsq4_f64(c, acc); sumsq4_f64(d, acc);
+  }
+  for (; i < n4; i += stride) {
+    float a[4];
+    load4<float>(g + i * 4, a);
+    sumsq4_f64(a, acc);
+  }
+  const double s = block_sum_f64((acc[0] + acc[1]) + (acc[2] + acc[3]), lds4);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// Stage 2, one workgroup: lane t sums partials [t*8, t*8+8) in index order, then the same fixed tree as stage 1.
+__global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __restrict__ partial, float grad_scale,
+                                                               float max_norm, int skip_nonfinite,
+                                                               float* __restrict__ stat, int32_t* __restrict__ skipped) {
+  __shared__ double lds4[4];
+  double s = 0.0;
+#pragma unroll
+  for (int k = 0; k < GN_PER_LANE; ++k) s += partial[threadIdx.x * GN_PER_LANE + k];
+  s = block_sum_f64(s, lds4);
+  if (threadIdx.x != 0) return;
+  const float norm = (float)(sqrt(s) * (double)grad_scale);
+  float coef = 1.f;
+  if (max_norm > 0.f) {
+    const float c = max_norm / (norm + 1e-6f);
+    coef = c > 1.f ? 1.f : c;                               // clamp(max=1): a NaN stays a NaN, like torch's
+  }
+  float skip = 0.f;
+  if (skip_nonfinite && !(fabsf(norm) <= 3.402823466e38f)) {   // inf or NaN
+    skip = 1.f;
+    coef = 0.f;
+    skipped[0] += 1;
+  }
+  stat[0] = norm;
+  stat[1] = coef;
+  stat[2] = skip;
+}
+
+extern "C" size_t mrmt3_grad_norm_workspace_elems(void) { return (size_t)GN_BLOCKS * 2; }   // one f64 per workgroup
+
+extern "C" int mrmt3_grad_norm(const float* g, size_t n, float grad_scale, float max_norm, int skip_nonfinite, float* ws,
+                               size_t ws_elems, float* stat_dev, int32_t* skipped_dev, void* stream) {
+  MR_CHECK_ARG(g && ws && stat_dev && skipped_dev, "grad_norm: null pointer");
+  MR_CHECK_ARG(n > 0 && n % 4 == 0 && ((uintptr_t)g & 15) == 0, "grad_norm: n = %zu must be a positive multiple of 4 and g 16-byte aligned", n);
+  MR_CHECK_ARG(ws_elems >= mrmt3_grad_norm_workspace_elems() && ((uintptr_t)ws & 7) == 0,
+               "grad_norm: the workspace holds %zu floats, %zu are needed (8-byte aligned)", ws_elems,
+               mrmt3_grad_norm_workspace_elems());
+  MR_CHECK_ARG(max_norm >= 0.f, "grad_norm: max_norm = %g is negative (0: no clipping)", (double)max_norm);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(GN_BLOCKS), dim3(256), 0, s, g, n / 4, (double*)ws);
+  MR_CHECK_LAUNCH("grad_norm");
+  hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)ws, grad_scale, max_norm,
+                     skip_nonfinite, stat_dev, skipped_dev);
+  MR_CHECK_LAUNCH("grad_norm finish");
+  return MRMT3_OK;
+}
+
+// adamw_kernel's arithmetic in adamw_kernel's order on gr = g * gscale * coef (coef = stat[1], read from the device: a
+// captured graph freezes by-value arguments), clamped to +-clip_value when that is positive.  stat[2] != 0: the step
+// is skipped, every thread leaves before its first store.
+__global__ void adamw_clipped_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                     float* __restrict__ v, size_t n4, const float* __restrict__ lr_dev,
+                                     const int32_t* __restrict__ step_dev, float b1, float b2, float eps, float wd,
+                                     float gscale, const float* __restrict__ stat, float clip_value,
+                                     bf16_t* __restrict__ shadow) {
+  if (stat[2] != 0.f) return;
+  const float coef = stat[1];
+  const float lr = lr_dev[0];
+  const int step = step_dev[0] + 1;
+  const double bc1 = 1.0 - pow((double)b1, (double)step);
+  const double bc2 = 1.0 - pow((double)b2, (double)step);
+  const float step_size = (float)((double)lr / bc1);
+  const float bc2_sqrt = (float)sqrt(bc2);
+  const float decay = 1.f - lr * wd;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+    float pv[4], gv[4], mv[4], vv[4];
+    load4<float>(p + i * 4, pv);
+    load4<float>(g + i * 4, gv);
+    load4<float>(m + i * 4, mv);
+    load4<float>(v + i * 4, vv);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float gr = gv[e] * gscale * coef;
+      if (clip_value > 0.f) gr = gr > clip_value ? clip_value : (gr < -clip_value ? -clip_value : gr);   // NaN stays NaN
+      pv[e] *= decay;
+      mv[e] = mv[e] + (gr - mv[e]) * (1.f - b1);
+      vv[e] = vv[e] * b2 + (1.f - b2) * gr * gr;
+      const float denom = sqrtf(vv[e]) / bc2_sqrt + eps;
+      pv[e] -= step_size * (mv[e] / denom);
+    }
+    store4<float>(p + i * 4, pv);
+    store4<float>(m + i * 4, mv);
+    store4<float>(v + i * 4, vv);
+    if (shadow) store4<bf16_t>(shadow + i * 4, pv);
+  }
+}
+
+extern "C" int mrmt3_adamw_step_clipped(float* p, const float* g, float* m, float* v, size_t n, const float* lr_dev,
+                                        int32_t* step_dev, float beta1, float beta2, float eps, float weight_decay,
+                                        float grad_scale, const float* stat_dev, float clip_value, void* shadow_bf16,
+                                        void* stream) {
+  MR_CHECK_ARG(p && g && m && v && lr_dev && step_dev && stat_dev && n % 4 == 0, "adamw_step_clipped: bad args");
+  MR_CHECK_ARG(clip_value >= 0.f, "adamw_step_clipped: clip_value = %g is negative (0: no clamp)", (double)clip_value);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(adamw_clipped_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, s, p, g, m, v, n / 4, lr_dev, step_dev,
+                     beta1, beta2, eps, weight_decay, grad_scale, stat_dev, clip_value, (bf16_t*)shadow_bf16);
+  MR_CHECK_LAUNCH("adamw_step_clipped");
+  hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, s, step_dev);
+  MR_CHECK_LAUNCH("adamw_step_clipped inc");
+  return MRMT3_OK;
+}
+
 __global__ void counter_add_kernel(int32_t* ctr, int32_t delta) { ctr[0] += delta; }
 
 extern "C" int mrmt3_counter_add(int32_t* ctr, int32_t delta, void* stream) {

@@ -106,7 +106,7 @@ def load():
     return lib
 
 
-MIN_VERSION = 114
+MIN_VERSION = 115
 COUNTER_NAMES = ("gemm_nt_tile", "gemm_nt8", "gemm_nt_geglu", "tn_group", "tn8", "tn_tile", "attn_fwd", "attn_bwd",
                  "attn_bwd_onepass", "attn_f32", "tn_f32", "gemm_nt_splitk", "gemm_nt_addnorm", "gemm_nt_normbwd",
                  "gemm_nt_geglubwd", "attn_fwd_varlen", "attn_bwd_varlen")
@@ -915,6 +915,33 @@ def adamw_step(p, g, m, v, lr_dev, step_dev, beta1=0.9, beta2=0.999, eps=1e-8, w
     _dev(p, g, m, v, lr_dev, step_dev)
     _check(load().mrmt3_adamw_step(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(lr_dev), _p(step_dev), beta1, beta2,
                                    eps, weight_decay, grad_scale, _p(shadow), _stream()), "adamw_step")
+
+
+def grad_norm_workspace(device) -> torch.Tensor:
+    """The f32 workspace mrmt3_grad_norm leaves its per-workgroup f64 partials in (allocate once, outside any capture)."""
+    return torch.empty(int(load().mrmt3_grad_norm_workspace_elems()), device=device, dtype=torch.float32)
+
+
+def grad_norm(g, grad_scale, max_norm, skip_nonfinite, ws, stat, skipped):
+    """Global L2 norm of the flat f32 gradient `g` times grad_scale, on the device, in a fixed summation order (f64
+    accumulation): stat[0] = norm, stat[1] = clip coefficient min(1, max_norm / (norm + 1e-6)) (1 when max_norm is 0),
+    stat[2] = 1.0 when skip_nonfinite and the norm is inf / NaN (then coef = 0 and skipped[0] += 1).  No host sync."""
+    _dev(g, ws, stat, skipped)
+    assert g.dtype == torch.float32 and g.is_contiguous() and ws.dtype == torch.float32
+    assert stat.dtype == torch.float32 and stat.numel() >= 3 and skipped.dtype == torch.int32 and skipped.numel() >= 1
+    _check(load().mrmt3_grad_norm(_p(g), g.numel(), float(grad_scale), float(max_norm), int(bool(skip_nonfinite)), _p(ws),
+                                  ws.numel(), _p(stat), _p(skipped), _stream()), "grad_norm")
+
+
+def adamw_step_clipped(p, g, m, v, lr_dev, step_dev, stat, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.01,
+                       grad_scale=1.0, clip_value=0.0, shadow=None):
+    """adamw_step on g * grad_scale * stat[1] (clamped to +-clip_value when > 0); stat[2] != 0 skips the update (step_dev
+    still advances).  `stat` is what grad_norm wrote."""
+    _dev(p, g, m, v, lr_dev, step_dev, stat)
+    assert stat.dtype == torch.float32 and stat.numel() >= 3
+    _check(load().mrmt3_adamw_step_clipped(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(lr_dev), _p(step_dev), beta1, beta2,
+                                           eps, weight_decay, grad_scale, _p(stat), float(clip_value), _p(shadow),
+                                           _stream()), "adamw_step_clipped")
 
 
 def counter_add(ctr, delta=1):

@@ -207,11 +207,25 @@ class FlatParams:
 
     def adamw_step(self, lr_dev, step_dev, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, grad_scale=1.0):
         """torch.optim.AdamW semantics over the whole model in one launch; keeps shadows current."""
+        self._optimizer_launch(lambda: lib.adamw_step(self.P, self.G, self.M, self.V, lr_dev, step_dev, betas[0], betas[1],
+                                                      eps, weight_decay, grad_scale, shadow=self.S))
+
+    def adamw_step_clipped(self, lr_dev, step_dev, stat_dev, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, grad_scale=1.0,
+                           clip_value=0.0):
+        """adamw_step under the clip coefficient / skip flag that lib.grad_norm left in `stat_dev` (device), with an
+        optional clamp of the scaled gradient to +-clip_value.  A skipped step rewrites the transposed shadows from the
+        unchanged bf16 shadow: the same bits."""
+        self._optimizer_launch(lambda: lib.adamw_step_clipped(self.P, self.G, self.M, self.V, lr_dev, step_dev, stat_dev,
+                                                              betas[0], betas[1], eps, weight_decay, grad_scale, clip_value,
+                                                              shadow=self.S))
+
+    def _optimizer_launch(self, launch):
+        """What every optimizer step does around its one launch: moments and shadows exist before it, the transposed
+        shadows and the shadow version follow it."""
         self.ensure_adam()
         if self.S is None:
             self.refresh_shadows()
-        lib.adamw_step(self.P, self.G, self.M, self.V, lr_dev, step_dev, betas[0], betas[1], eps, weight_decay,
-                       grad_scale, shadow=self.S)
+        launch()
         self.refresh_transposed()
         self._shadow_version = self.master_version()
 

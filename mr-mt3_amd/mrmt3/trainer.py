@@ -52,6 +52,18 @@ Dropout salt: `step_dev` counts optimizer steps (AdamW's bias correction); with 
 instead, a device counter of micro-batches bumped at the end of every micro-batch inside the step (mrmt3_counter_add), so
 the micro-batches of one cycle and every replay draw their own masks, the same in eager and replayed steps.  With N = 1
 `salt_dev` IS `step_dev`: the masks are those of the plain step.
+
+Gradient clipping, gradient norm, non-finite guard (`gradient_clip_val`, `gradient_clip_algorithm`, `skip_nonfinite`,
+`track_grad_norm`; Lightning's Trainer arguments of the first two names).  When any of the four is set, the optimizer tail
+of a step — plain step, "last" phase, finish_accumulation() — is mrmt3_grad_norm + mrmt3_adamw_step_clipped instead of
+mrmt3_adamw_step: the norm of G * 1/(world*N) (the mean gradient over ranks and micro-batches, after the exchange) is
+reduced on the device in a fixed order, the clip coefficient and the skip flag stay in device memory (`_clip_stat`) and
+AdamW reads them there, so the captured tail graph clips by this step's norm on every replay and the host never waits.
+Every rank holds the same G after the all-reduce and reduces it in the same order: same coefficient, no extra collective.
+A skipped step (non-finite norm under skip_nonfinite) leaves P, M, V and the shadows untouched; `step_dev` still advances —
+it counts ATTEMPTED optimizer steps and stays equal to host_step, so the dropout salt moves on and checkpoints need no new
+field (AdamW's bias correction counts the skipped step: negligible after warm-up).  With all four off nothing changes:
+the same calls, graphs and launches as before.
 """
 from __future__ import annotations
 
@@ -81,6 +93,27 @@ def _first_line(e) -> str:
     return t.splitlines()[0] if t else ""
 
 
+CLIP_ALGORITHMS = ("norm", "value")
+
+
+def clip_options(gradient_clip_val=None, gradient_clip_algorithm="norm", skip_nonfinite=False, track_grad_norm=False):
+    """Validate the clipping arguments (host only) -> (on, max_norm, clip_value, skip): `on` iff any of the four asks for
+    the norm / clip / guard tail; max_norm > 0 clips by global norm, clip_value > 0 clamps by value, 0 = off."""
+    if gradient_clip_algorithm is None:
+        gradient_clip_algorithm = "norm"
+    if gradient_clip_algorithm not in CLIP_ALGORITHMS:
+        raise ValueError("gradient_clip_algorithm must be one of %s, got %r" % (CLIP_ALGORITHMS, gradient_clip_algorithm))
+    if gradient_clip_val is not None:
+        if isinstance(gradient_clip_val, bool) or not isinstance(gradient_clip_val, (int, float)):
+            raise ValueError("gradient_clip_val must be None or a number > 0, got %r" % (gradient_clip_val,))
+        if not gradient_clip_val > 0 or gradient_clip_val == float("inf"):
+            raise ValueError("gradient_clip_val must be None or a finite number > 0, got %r" % (gradient_clip_val,))
+    val = 0.0 if gradient_clip_val is None else float(gradient_clip_val)
+    by_value = gradient_clip_algorithm == "value"
+    on = gradient_clip_val is not None or bool(skip_nonfinite) or bool(track_grad_norm)
+    return on, (0.0 if by_value else val), (val if by_value else 0.0), bool(skip_nonfinite)
+
+
 class _CapturedStep:
     """One input signature's captured step: graph segments (each followed by the gradient buckets to send), the tail
     graph (AdamW) and the static tensors the graphs read and write."""
@@ -94,7 +127,10 @@ class Trainer:
     def __init__(self, model, lr: float = 2e-4, lr_lambda=None, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.01, weighted_loss: bool = False, layers_per_bucket: int = 4,
                  graph: bool = None, grad_exchange_dtype=None, pack_targets: bool = None,
-                 accumulate_grad_batches: int = 1):
+                 accumulate_grad_batches: int = 1, gradient_clip_val=None, gradient_clip_algorithm: str = "norm",
+                 skip_nonfinite: bool = False, track_grad_norm: bool = False):
+        self.clip_on, self._max_norm, self._clip_value, self.skip_nonfinite = clip_options(
+            gradient_clip_val, gradient_clip_algorithm, skip_nonfinite, track_grad_norm)
         n_acc = int(accumulate_grad_batches)
         if n_acc < 1 or n_acc != accumulate_grad_batches:
             raise ValueError("accumulate_grad_batches must be an integer >= 1, got %r" % (accumulate_grad_batches,))
@@ -134,6 +170,13 @@ class Trainer:
         if self.world > 1:   # C2: identical replicas
             dist.broadcast(self.flat.P, src=0)
         self.last_loss = None
+        # norm / clip coefficient / skip flag of the last optimizer step, the skip counter and the norm kernel's partials:
+        # device memory the captured tail reads and writes, allocated here, never inside a capture
+        self._clip_stat = self._skipped_dev = self._clip_ws = None
+        if self.clip_on:
+            self._clip_stat = torch.zeros(4, device=dev, dtype=torch.float32)
+            self._skipped_dev = torch.zeros(1, device=dev, dtype=torch.int32)
+            self._clip_ws = lib.grad_norm_workspace(dev)
         # every dropout mask of a step is salted in-kernel by a device counter (see module docstring): the optimizer step
         # counter itself, or with accumulation a micro-batch counter of its own
         self.salt_dev = self.step_dev if n_acc == 1 else torch.zeros(1, device=dev, dtype=torch.int32)
@@ -224,11 +267,32 @@ class Trainer:
             eng.backward(tape, dl, on_layer_done=layer_done if active else None)     # ends with join_wgrad()
             cut([j for j in range(len(self.buckets.buckets)) if j not in sent] if active else [])
         if phase in (None, "last"):
-            flat.adamw_step(self.lr_dev, self.step_dev, self.betas, self.eps, self.wd,
-                            grad_scale=1.0 / (self.world * self.accumulate))
+            self._optimizer_tail()
         if self.accumulate > 1:
             lib.counter_add(self.salt_dev, 1)               # the next micro-batch draws other masks
         return loss
+
+    def _optimizer_tail(self):
+        """AdamW on the exchanged G; with clipping / norm tracking / the non-finite guard on, the device-side norm first."""
+        scale = 1.0 / (self.world * self.accumulate)
+        if not self.clip_on:
+            self.flat.adamw_step(self.lr_dev, self.step_dev, self.betas, self.eps, self.wd, grad_scale=scale)
+            return
+        lib.grad_norm(self.flat.G, scale, self._max_norm, self.skip_nonfinite, self._clip_ws, self._clip_stat,
+                      self._skipped_dev)
+        self.flat.adamw_step_clipped(self.lr_dev, self.step_dev, self._clip_stat, self.betas, self.eps, self.wd,
+                                     grad_scale=scale, clip_value=self._clip_value)
+
+    @property
+    def last_grad_norm(self):
+        """Device [1] f32 view (un-synchronised, like last_loss): the global L2 norm of the last optimizer step's mean
+        gradient, before clipping.  None when clipping, norm tracking and the non-finite guard are all off."""
+        return None if self._clip_stat is None else self._clip_stat[0:1]
+
+    @property
+    def skipped_steps(self) -> int:
+        """Optimizer steps the non-finite guard skipped (reads the device counter: waits for the device)."""
+        return 0 if self._skipped_dev is None else int(self._skipped_dev.item())
 
     def train_step(self, inputs, labels, targets_prev=None, audio: bool = False):
         """One optimizer step, or with accumulate_grad_batches = N > 1 one micro-batch (the optimizer steps after every N-th).
@@ -278,8 +342,7 @@ class Trainer:
             self.lr_dev.fill_(self.base_lr * self.lr_lambda(self.host_step))
         self.buckets.reset()
         self.buckets.finish()
-        self.flat.adamw_step(self.lr_dev, self.step_dev, self.betas, self.eps, self.wd,
-                             grad_scale=1.0 / (self.world * self.accumulate))
+        self._optimizer_tail()
         self._micro = 0
         self.host_step += 1
         return True

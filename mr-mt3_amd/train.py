@@ -22,6 +22,11 @@ Gradient accumulation: `cfg.trainer.accumulate_grad_batches` (the reference's `$
 `grad_accum`, else 1 — Lightning's semantics (mrmt3/trainer.py): the optimizer steps after every N-th batch and after an
 epoch's last one; `+max_steps`, `trainer.log_every_n_steps`, the LR schedule and checkpoint steps count optimizer steps.
 
+Gradient clipping: `trainer.gradient_clip_val` / `trainer.gradient_clip_algorithm` (norm, the default, or value) as
+Lightning reads them from the same block (`+trainer.gradient_clip_val=1.0`); `+skip_nonfinite=true` drops an optimizer
+step whose gradient norm is inf / NaN instead of poisoning the weights.  With either on, the step lines also carry
+`grad_norm` (the norm before clipping) and the run ends with `skipped_steps K` when K > 0.
+
 `cfg.path` has the reference's meaning (`train.py:61-92`): a `.ckpt` resumes weights, AdamW moments and
 the step counter; a `.pth` only loads weights (`strict=False`); anything else is an error.  At the end
 rank 0 writes `<output_dir>/<model_type>_<dataset_type>/version_0/checkpoints/last.ckpt` (Lightning
@@ -116,6 +121,23 @@ def accumulate_grad_batches(cfg) -> int:
     return 1 if n is None else int(n)
 
 
+_TRUTHY = ("1", "true", "yes", "on")
+
+
+def gradient_clipping(cfg):
+    """(gradient_clip_val or None, algorithm) from `trainer.gradient_clip_val` / `trainer.gradient_clip_algorithm`, as
+    Lightning reads them: no value, null or 0 means no clipping; the algorithm defaults to "norm"."""
+    from mrmt3.trainer import clip_options
+    tr = cfg.get("trainer")
+    val = tr.get("gradient_clip_val") if tr is not None else None
+    algo = tr.get("gradient_clip_algorithm") if tr is not None else None
+    algo = "norm" if algo is None else str(algo)
+    val = None if val is None or str(val).lower() in ("", "none", "null") else float(val)
+    val = None if val == 0 else val
+    clip_options(val, algo)                      # the trainer's own validation: an unknown algorithm is a ValueError naming it
+    return val, algo
+
+
 def resume_position(global_step, steps_per_epoch, accumulate=1):
     """(epoch, batches of that epoch already consumed) for a run that has taken `global_step` optimizer steps.  The
     position is derived from the step count alone: a checkpoint's `epoch` field is the epoch in progress OR the one
@@ -186,11 +208,22 @@ def main(argv=None):
                                                      min_lr=float(cfg.optim.min_lr))
     # packed decoder rows (mrmt3/packing.py): `+pack_targets=true`; absent, MRMT3_PACK_TARGETS decides (default off)
     pack = cfg.get("pack_targets")
-    pack = None if pack is None else str(pack).lower() in ("1", "true", "yes", "on")
+    pack = None if pack is None else str(pack).lower() in _TRUTHY
     accum = accumulate_grad_batches(cfg)
+    clip_val, clip_algo = gradient_clipping(cfg)
+    skip_nonfinite = str(cfg.get("skip_nonfinite", False)).lower() in _TRUTHY
     trainer = Trainer(task.model, lr=float(cfg.optim.lr), lr_lambda=lam,
                       weighted_loss=type(task).__name__ == "MT3NetWeightedLoss", pack_targets=pack,
-                      accumulate_grad_batches=accum)
+                      accumulate_grad_batches=accum, gradient_clip_val=clip_val, gradient_clip_algorithm=clip_algo,
+                      skip_nonfinite=skip_nonfinite)
+
+    def step_line(it, loss):
+        """Rank 0's log line of optimizer step `it` (reads the device: only at the logging cadence)."""
+        line = f"step {it} train_loss {loss.item():.4f}"
+        if trainer.clip_on:
+            line += f" grad_norm {trainer.last_grad_norm.item():.4f}"
+        return line
+
     task.model.engine.seed = int(cfg.seed)
     with_prev = "WithPrev" in type(task).__name__
     synthetic = bool(cfg.get("synthetic", False))
@@ -228,7 +261,7 @@ def main(argv=None):
                 continue                 # (mid-cycle: no optimizer step yet)
             it = start + (k + 1) // accum - 1
             if rank == 0 and (it % log_every == 0 or it == start + steps - 1):
-                print(f"step {it} train_loss {loss.item():.4f}", flush=True)
+                print(step_line(it, loss), flush=True)
     else:
         val_every = max(1, int(cfg.trainer.get("check_val_every_n_epoch", 1)))
         it, last_ep, loss = start, start_epoch, None
@@ -249,7 +282,7 @@ def main(argv=None):
             """An optimizer step has run; `loss` is its last micro-batch's."""
             nonlocal it
             if rank == 0 and it % log_every == 0:
-                print(f"step {it} train_loss {loss.item():.4f}", flush=True)
+                print(step_line(it, loss), flush=True)
             it += 1
 
         if resumed:
@@ -268,9 +301,13 @@ def main(argv=None):
         if trainer.finish_accumulation():
             stepped(loss)
         if rank == 0 and loss is not None and (it - 1) % log_every != 0:
-            print(f"step {it - 1} train_loss {loss.item():.4f}", flush=True)
+            print(step_line(it - 1, loss), flush=True)
         if (last_ep + 1) % val_every == 0:
             validate(last_ep)
+    if rank == 0 and trainer.clip_on:
+        skipped = trainer.skipped_steps          # (every rank skips the same steps: the norm is of the exchanged gradient)
+        if skipped > 0:
+            print(f"skipped_steps {skipped}", flush=True)
     if rank == 0:
         out_dir = os.path.join(str(cfg.get("output_dir", ".")), f"{cfg.model_type}_{cfg.dataset_type}",
                                "version_0", "checkpoints")
