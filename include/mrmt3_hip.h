@@ -385,6 +385,20 @@ int mrmt3_lmhead_ce_fwd_bwd(const void* dec, int ld_dec, const void* W, int ldw,
                             int d, int weighted, int inst_lo, int inst_hi, float grad_scale, void* workspace,
                             size_t workspace_bytes, int chunk_rows, void* stream);
 
+/* Teacher-forced scoring, forward only.  mrmt3_token_logprob: out[r] = log softmax(logits[r])[targets[r]], or
+ * 0.0 where targets[r] == ignore_index (a target outside [0, V) gives NaN); logits [rows][V] f32, V <= 2048 (an error
+ * beyond: the row lives in one wave's registers).  One wave per row: the
+ * NaN-propagating row maximum, exp(l - max) summed in f32 per lane in ascending column (lane + 64 i) then by the xor
+ * tree, (l[target] - max) - log(sum) -- the arithmetic and order of the decoder's greedy tail.
+ * mrmt3_lmhead_logprob: the chunk loop of mrmt3_lmhead_ce_fwd_bwd with that kernel (ignore_index -100): dec [rows][ld_dec]
+ * and W [V][ldw] both of `dtype` (MRMT3_BF16 or MRMT3_F32), logits of a chunk (f32) in `workspace`
+ * (>= min(rows, chunk_rows)*V*4 bytes); the full [rows][V] logits never exist.  out [rows] f32. */
+int mrmt3_token_logprob(const float* logits, const int64_t* targets, float* out, int rows, int V, int ignore_index,
+                        void* stream);
+int mrmt3_lmhead_logprob(const void* dec, int ld_dec, const void* W, int ldw, const int64_t* targets, float* out,
+                         int rows, int V, int d, int dtype, void* workspace, size_t workspace_bytes, int chunk_rows,
+                         void* stream);
+
 /* ---- K11: AdamW over the flat parameter buffer (torch.optim.AdamW defaults; tasks/mt3_net.py:55)
  * p,g,m,v: flat f32 [n].  lr is read from lr_dev[0] (device), step count from step_dev[0] (int32,
  * incremented by the call).  grad_scale multiplies g (e.g. 1/world_size).  shadow_bf16 (nullable)
@@ -478,6 +492,14 @@ int mrmt3_decoder_set_prefix(mrmt3_decoder* dec, const float* prefix, int n_pref
  * between a mask and none re-captures the step graph.  mrmt3_decoder_begin clears the ban.
  * Errors in beam mode (the mask is a parameter of mrmt3_decoder_begin_beam there). */
 int mrmt3_decoder_set_ban(mrmt3_decoder* dec, const uint8_t* banned_mask, void* stream);
+/* Optional, after mrmt3_decoder_begin (and mrmt3_decoder_set_ban) and before mrmt3_decoder_run: greedy decode that also
+ * writes the log-probability of every emitted token, out[b][t + 1] beside tokens_out[b][t + 1] (caller-owned device
+ * f32 [batch][ld], ld >= max_len + 1; the call writes 0.0 to column 0).  The distribution is the softmax of the logits
+ * after the ban (banned entries -inf); a row that had finished writes 0.0 for its pad tokens; prefix steps write
+ * nothing; a row whose logits hold a NaN that is not banned writes NaN.  NULL turns it off.  On / off (and the
+ * pointer) is part of the captured step's key: switching re-captures, as the ban does; with it off the step is the
+ * plain one.  mrmt3_decoder_begin clears it.  Needs vocab <= 2048; errors in beam mode. */
+int mrmt3_decoder_set_logprobs(mrmt3_decoder* dec, float* out, int ld, void* stream);
 /* Beam search (HF 4.18 beam_search + BeamSearchScorer, early_stopping = False, one hypothesis per group;
  * max_length counts new tokens).  Row r = g * num_beams + j of the batch is beam j of group g; cross_kv
  * holds groups * num_beams rows (each group's K|V repeated num_beams times).  Caller-owned device buffers:
@@ -505,6 +527,12 @@ int mrmt3_decoder_begin_beam(mrmt3_decoder* dec, const mrmt3_decoder_weights* w,
  * included, EOS excluded): the caller's output width is min(max over groups + 1, 1 + max_length).
  * Needs ld >= 1 + max_length and max_length = the number of steps run when a group is not done. */
 int mrmt3_decoder_beam_finalize(mrmt3_decoder* dec, int64_t* out_ids, int ld, int max_length, void* stream);
+/* The same, and out_logp [groups][ld] f32 (nullable) receives the log-probability of every token of the chosen
+ * hypothesis at the token's position: log_softmax of the step's logits (normaliser over the whole vocabulary, as the
+ * search scores them), 0.0 for the start token and the padding; the closing eos_id carries its own value when the
+ * hypothesis ended with it.  Their sum is the hypothesis' raw score (before the length penalty). */
+int mrmt3_decoder_beam_finalize_logprobs(mrmt3_decoder* dec, int64_t* out_ids, float* out_logp, int ld,
+                                         int max_length, void* stream);
 /* Run n_steps decode steps (graph replays; captured on first use).  No host synchronisation. */
 int mrmt3_decoder_run(mrmt3_decoder* dec, int n_steps, void* stream);
 /* 1 if the current configuration is being replayed from a captured hipGraph (0 = plain launches). */

@@ -5,7 +5,8 @@
 from __future__ import annotations
 
 import dataclasses
-from typing import Dict, List, Set, Tuple
+import math
+from typing import Dict, List, Optional, Set, Tuple
 
 from contrib import event_codec, vocabularies
 
@@ -23,6 +24,9 @@ class Note:
     program: int = 0
     is_drum: bool = False
     instrument: int = 0
+    # how sure the model was of this note, in (0, 1] (`decode_note_event_scored`); 1.0 when nothing scored it.  Not part
+    # of a note's identity: two notes that differ only here compare equal.
+    confidence: float = dataclasses.field(default=1.0, compare=False)
 
 
 @dataclasses.dataclass
@@ -135,11 +139,65 @@ class NoteEncodingSpecType:
     flush_decoding_state_fn: object
 
 
+# ---- the same state machine with a confidence per note (not in the reference) ---------------------------------------
+@dataclasses.dataclass
+class ScoredNoteDecodingState(NoteDecodingState):
+    """NoteDecodingState plus what a note's confidence is made of.  All values are log-probabilities."""
+    program_logprob: Optional[float] = None       # the most recent program token of the current segment
+    onset_logprob: Dict[Tuple[int, int], float] = dataclasses.field(default_factory=dict)   # per sounding (pitch, program)
+
+
+def begin_tied_pitches_section_scored(state: ScoredNoteDecodingState) -> None:
+    begin_tied_pitches_section(state)
+    state.program_logprob = None                  # a program token speaks for its own segment only
+
+
+def _stamp(state: ScoredNoteDecodingState, first: int, drum_logprob: float = 0.0) -> None:
+    """Confidence of the notes emitted since index `first`: a pitched note carries the value kept at its onset."""
+    for note in state.note_sequence.notes[first:]:
+        lp = drum_logprob if note.is_drum else state.onset_logprob.pop((note.pitch, note.program), 0.0)
+        note.confidence = math.exp(lp)
+
+
+def decode_note_event_scored(state: ScoredNoteDecodingState, time: float, event: event_codec.Event,
+                             codec: event_codec.Codec, logprob: float, shift_logprob: Optional[float] = None) -> None:
+    """`decode_note_event` that also gives every note it emits a confidence = exp(min(...)) over the log-probabilities of
+    the onset's own pitch or drum token (`logprob`), the most recent program token of that segment, if any, and the last
+    shift token of the run that set its time (`shift_logprob`), if any.  The value is fixed at the onset: a note-off, a
+    re-onset, the end of a tie section or the final flush emit the note with it, so a note tied in from an earlier segment
+    keeps the confidence of its onset.  Raises ValueError exactly where `decode_note_event` does."""
+    first = len(state.note_sequence.notes)
+    onset = event.type == "pitch" and not state.is_tie_section and state.current_velocity != 0
+    parts = [logprob] + [v for v in (state.program_logprob, shift_logprob) if v is not None]
+    value = min(parts)
+    decode_note_event(state, time, event, codec)
+    _stamp(state, first, value)                   # before the onset's own entry replaces a re-struck note's
+    if onset:
+        state.onset_logprob[(event.value, state.current_program)] = value
+    elif event.type == "program":
+        state.program_logprob = logprob
+
+
+def flush_note_decoding_state_scored(state: ScoredNoteDecodingState, min_confidence: Optional[float] = None) -> NoteSequence:
+    """`flush_note_decoding_state`; then notes below `min_confidence` are dropped and the instruments assigned among
+    the notes that stay."""
+    first = len(state.note_sequence.notes)
+    ns = flush_note_decoding_state(state)
+    _stamp(state, first)
+    if min_confidence is not None:
+        ns.notes = [n for n in ns.notes if n.confidence >= min_confidence]
+        assign_instruments(ns)
+    return ns
+
+
 # onsets + offsets with a "tie" section at the start of every segment (the spec inference.py:230 uses)
 NoteEncodingWithTiesSpec = NoteEncodingSpecType(NoteDecodingState, begin_tied_pitches_section, decode_note_event,
                                                 flush_note_decoding_state)
 NoteEncodingSpec = NoteEncodingSpecType(NoteDecodingState, lambda state: None, decode_note_event,
                                         flush_note_decoding_state)
+# the scored twins (run_length_encoding.decode_events_scored feeds decode_event_fn the two extra arguments)
+NoteEncodingWithTiesScoredSpec = NoteEncodingSpecType(ScoredNoteDecodingState, begin_tied_pitches_section_scored,
+                                                      decode_note_event_scored, flush_note_decoding_state_scored)
 
 
 # ---- notes -> timed event data (the tokenisation half; reference :48-66,83-256) ---------------------------

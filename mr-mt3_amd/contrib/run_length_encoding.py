@@ -37,6 +37,39 @@ def decode_events(state, tokens, start_time, max_time: Optional[float], codec, d
     return invalid, dropped
 
 
+def decode_events_scored(state, tokens, logprobs, start_time, max_time: Optional[float], codec,
+                         decode_event_fn: Callable) -> Tuple[int, int]:
+    """`decode_events` with the per-token log-probabilities `logprobs` (one per token) beside the tokens: `decode_event_fn`
+    is called as (state, time, event, codec, logprob of the event's token, logprob of the last shift token of the run that
+    set the time, or None before the segment's first shift).  Same walk, same counts."""
+    assert len(logprobs) == len(tokens), (len(logprobs), len(tokens))
+    invalid = dropped = 0
+    steps = 0
+    now = start_time
+    shift_logprob = None
+    n = len(tokens)
+    for i in range(n):
+        try:
+            event = codec.decode_event_index(tokens[i])
+        except ValueError:
+            invalid += 1
+            continue
+        if event.type == "shift":
+            steps += event.value
+            now = start_time + steps / codec.steps_per_second
+            if max_time and now > max_time:
+                dropped = n - i
+                break
+            shift_logprob = float(logprobs[i])
+        else:
+            steps = 0
+            try:
+                decode_event_fn(state, now, event, codec, float(logprobs[i]), shift_logprob)
+            except ValueError:
+                invalid += 1
+    return invalid, dropped
+
+
 def encode_and_index_events(state, event_times, event_values, encode_event_fn, codec, frame_times,
                             encoding_state_to_events_fn=None):
     """Timed events -> token stream with one `shift 1` per 10 ms step, indexed by audio frame

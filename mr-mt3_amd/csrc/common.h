@@ -95,6 +95,13 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+// NaN-propagating maximum (fmaxf drops a NaN): log_softmax of a row that holds a NaN is NaN everywhere
+__device__ __forceinline__ float nanmax(float a, float b) { return (b != b || b > a) ? b : a; }
+__device__ __forceinline__ float wave_nanmax(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = nanmax(v, __shfl_xor(v, o, 64));
+  return v;
+}
 
 // ---- counter-based mask generator for the element-wise dropout sites ------------------------------------------
 // mask(seed, site, element index): forward and backward regenerate the same mask, nothing is stored.  Two 32-bit

@@ -397,11 +397,17 @@ __device__ __forceinline__ bool argmax_beats(float v, int i, float bv, int bi) {
 // BAN: banned tokens (ban[c] != 0, a device [V] uint8 mask) score -inf before the argmax, NaN included, as HF's
 // NoBadWordsLogitsProcessor does ahead of the greedy argmax.  The unbanned kernel is this body with BAN = false.
 // (`ban` is the last argument, so the unbanned instantiation keeps every other argument's offset and its code.)
-template <bool BAN>
+// LOGP: the wave also writes the log-probability of the token it emits, logp[b * logp_ld + t + 1].  It keeps
+// its row in registers (LOGP_REGS values per lane, V <= 64 * LOGP_REGS), so the row is still read once: maximum after the
+// ban (NaN-propagating), sum of exp(l - max) per lane in ascending index then the xor tree, (l[idx] - max) - log(sum).
+// A row that had finished writes 0.0 for its pad; prefix steps write nothing.  (`logp`, `logp_ld` come after `ban`.)
+#define LOGP_REGS 32
+template <bool BAN, bool LOGP>
 __global__ __launch_bounds__(512) void dec_argmax(const float* __restrict__ logits, int V, int B, int64_t* __restrict__ tokens,
                                                   int tok_ld, const float* __restrict__ embed, const float* __restrict__ pos,
                                                   float* __restrict__ x, int* __restrict__ state, int eos, int pad,
-                                                  const float* __restrict__ prefix, const uint8_t* __restrict__ ban) {
+                                                  const float* __restrict__ prefix, const uint8_t* __restrict__ ban,
+                                                  float* __restrict__ logp, int logp_ld) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int p = state[ST_T];            // position just processed
   const int npre = state[ST_NPRE];
@@ -430,19 +436,38 @@ __global__ __launch_bounds__(512) void dec_argmax(const float* __restrict__ logi
     for (int c = 0; c < DMODEL / 64; ++c) pv[c] = pr[c * 64 + lane];
     float best = -INFINITY;
     int idx = -1;                        // -1: this lane has seen no logit yet (lanes >= V when V < 64)
-    for (int c0 = lane; c0 < V; c0 += 512) {
-      float lv[8];
+    float rl[LOGP ? LOGP_REGS : 1];      // LOGP: the lane's logits after the ban, rl[i] = column lane + 64 i (-inf past V)
+    if (LOGP) {
 #pragma unroll
-      for (int u = 0; u < 8; ++u) lv[u] = (c0 + 64 * u < V) ? logits[(size_t)b * V + c0 + 64 * u] : -INFINITY;
+      for (int i = 0; i < LOGP_REGS; ++i) {
+        const int c = lane + 64 * i;
+        rl[i] = (c < V) ? logits[(size_t)b * V + c] : -INFINITY;
+      }
       if (BAN) {
 #pragma unroll
-        for (int u = 0; u < 8; ++u)
-          if (c0 + 64 * u < V && ban[c0 + 64 * u]) lv[u] = -INFINITY;
+        for (int i = 0; i < LOGP_REGS; ++i)
+          if (lane + 64 * i < V && ban[lane + 64 * i]) rl[i] = -INFINITY;
       }
 #pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int c = c0 + 64 * u;
-        if (argmax_beats(lv[u], c < V ? c : -1, best, idx)) { best = lv[u]; idx = c; }   // ascending c per lane
+      for (int i = 0; i < LOGP_REGS; ++i) {
+        const int c = lane + 64 * i;
+        if (argmax_beats(rl[i], c < V ? c : -1, best, idx)) { best = rl[i]; idx = c; }      // ascending c per lane
+      }
+    } else {
+      for (int c0 = lane; c0 < V; c0 += 512) {
+        float lv[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) lv[u] = (c0 + 64 * u < V) ? logits[(size_t)b * V + c0 + 64 * u] : -INFINITY;
+        if (BAN) {
+#pragma unroll
+          for (int u = 0; u < 8; ++u)
+            if (c0 + 64 * u < V && ban[c0 + 64 * u]) lv[u] = -INFINITY;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int c = c0 + 64 * u;
+          if (argmax_beats(lv[u], c < V ? c : -1, best, idx)) { best = lv[u]; idx = c; }   // ascending c per lane
+        }
       }
     }
 #pragma unroll
@@ -450,6 +475,19 @@ __global__ __launch_bounds__(512) void dec_argmax(const float* __restrict__ logi
       const float ov = __shfl_xor(best, off, 64);
       const int oi = __shfl_xor(idx, off, 64);
       if (argmax_beats(ov, oi, best, idx)) { best = ov; idx = oi; }
+    }
+    float lp_tok = 0.f;
+    if (LOGP) {
+      // best = l[idx] in every lane.  Columns past V and banned ones are -inf: exp gives 0.
+      float mx = -INFINITY;
+#pragma unroll
+      for (int i = 0; i < LOGP_REGS; ++i) mx = nanmax(mx, rl[i]);
+      mx = wave_nanmax(mx);
+      float se = 0.f;
+#pragma unroll
+      for (int i = 0; i < LOGP_REGS; ++i) se += expf(rl[i] - mx);
+      se = wave_sum(se);
+      lp_tok = (best - mx) - logf(se);
     }
     // lane 0 always holds index 0 (V > 0), so idx is in [0, V) here whatever the logits hold
     const int nxt = was_done ? pad : idx;
@@ -459,6 +497,7 @@ __global__ __launch_bounds__(512) void dec_argmax(const float* __restrict__ logi
     if (lane == 0) {
       if (!was_done && nxt == eos) __hip_atomic_store(&state[ST_FLAGS + b], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       tokens[(size_t)b * tok_ld + t + 1] = nxt;
+      if (LOGP) logp[(size_t)b * logp_ld + t + 1] = was_done ? 0.f : lp_tok;
     }
   }
   __syncthreads();
@@ -509,7 +548,6 @@ __device__ __forceinline__ void rank_reduce_wave(float& v, int& i) {
     if (argmax_beats(ov, oi, v, i)) { v = ov; i = oi; }
   }
 }
-__device__ __forceinline__ float nanmax(float a, float b) { return (b != b || b > a) ? b : a; }
 
 // One workgroup (8 waves) per group.  The k rows' log-softmax (+ ban, + beam score) fill LDS ([k][V] f32), the top 2k
 // of those k*V candidates come out one per round (round r takes the best candidate ranked below round r-1's winner, so
@@ -523,7 +561,8 @@ __global__ __launch_bounds__(512) void dec_beam_select(const float* __restrict__
                                                        float* __restrict__ x, int* __restrict__ state, int eos, int pad,
                                                        float length_penalty, const uint8_t* __restrict__ ban,
                                                        float* __restrict__ bscore, int* __restrict__ bp,
-                                                       int* __restrict__ hyp) {
+                                                       int* __restrict__ hyp, float* __restrict__ blp,
+                                                       size_t blp_plane) {
   extern __shared__ float sc[];                 // [k][V] candidate scores
   __shared__ float red_v[8][BEAM_MAXK];
   __shared__ int red_i[8];
@@ -531,6 +570,8 @@ __global__ __launch_bounds__(512) void dec_beam_select(const float* __restrict__
   __shared__ int top_i[2 * BEAM_MAXK];
   __shared__ int n_parent[BEAM_MAXK], n_tok[BEAM_MAXK];
   __shared__ float n_score[BEAM_MAXK];
+  __shared__ float n_lp[BEAM_MAXK], eos_lp[BEAM_MAXK];   // log-probability of each row's chosen token / of EOS after each row
+  __shared__ float row_m[BEAM_MAXK], row_lse[BEAM_MAXK];
   __shared__ int was_done;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = blockIdx.x, r0 = g * k;
@@ -540,7 +581,7 @@ __global__ __launch_bounds__(512) void dec_beam_select(const float* __restrict__
   __syncthreads();
   if (was_done) {
     // a finished group emits pad and keeps its rows (BeamSearchScorer.process pads a done group)
-    if (tid < k) { n_parent[tid] = r0 + tid; n_tok[tid] = pad; n_score[tid] = 0.f; }
+    if (tid < k) { n_parent[tid] = r0 + tid; n_tok[tid] = pad; n_score[tid] = 0.f; n_lp[tid] = 0.f; eos_lp[tid] = 0.f; }
   } else {
     const float* lg = logits + (size_t)r0 * V;
     // row max (NaN-propagating, as log_softmax of a row holding a NaN is NaN everywhere), then sum of exp
@@ -577,6 +618,7 @@ __global__ __launch_bounds__(512) void dec_beam_select(const float* __restrict__
 #pragma unroll
       for (int w = 0; w < 8; ++w) s += red_v[w][j];
       const float lse = logf(s), bs = bscore[r0 + j];
+      if (tid == 0) { row_m[j] = m[j]; row_lse[j] = lse; }
       for (int c = tid; c < V; c += 512) {
         const float lp = (lg[(size_t)j * V + c] - m[j]) - lse;          // log_softmax, as torch computes it
         sc[j * V + c] = (ban != nullptr && ban[c]) ? -INFINITY : lp + bs;
@@ -615,10 +657,15 @@ __global__ __launch_bounds__(512) void dec_beam_select(const float* __restrict__
           if (rnk >= k) continue;                 // an EOS below the top k is not a hypothesis
           beam_hyp_add(rec, k, top_v[rnk] / denom, t, r0 + j);
         } else {
-          n_parent[nb] = r0 + j; n_tok[nb] = tok; n_score[nb] = top_v[rnk]; ++nb;
+          n_parent[nb] = r0 + j; n_tok[nb] = tok; n_score[nb] = top_v[rnk];
+          n_lp[nb] = (lg[(size_t)j * V + tok] - row_m[j]) - row_lse[j];      // the lp that went into sc, bit for bit
+          ++nb;
         }
       }
-      for (; nb < k; ++nb) { n_parent[nb] = r0 + nb; n_tok[nb] = pad; n_score[nb] = -INFINITY; }   // unreachable: <= k EOS
+      for (; nb < k; ++nb) { n_parent[nb] = r0 + nb; n_tok[nb] = pad; n_score[nb] = -INFINITY; n_lp[nb] = 0.f; }   // unreachable: <= k EOS
+      for (int j = 0; j < k; ++j)
+        eos_lp[j] = (eos < 0 || eos >= V) ? 0.f
+                    : (ban != nullptr && ban[eos]) ? -INFINITY : (lg[(size_t)j * V + eos] - row_m[j]) - row_lse[j];
       // BeamHypotheses.is_done(best candidate score, cur_len), early_stopping = False
       if (rec[0] >= k && __int_as_float(rec[1]) >= top_v[0] / denom) rec[2] = 1;
     }
@@ -635,6 +682,9 @@ __global__ __launch_bounds__(512) void dec_beam_select(const float* __restrict__
     bp[((size_t)t * rows + row) * 2] = n_parent[tid];
     bp[((size_t)t * rows + row) * 2 + 1] = n_tok[tid];
     tokens[(size_t)row * tok_ld + t + 1] = n_tok[tid];
+    // plane 0: lp of the token row `row` took at step t; plane 1: lp of EOS after the prefix row `row` held BEFORE step t
+    blp[(size_t)t * rows + row] = n_lp[tid];
+    blp[blp_plane + (size_t)t * rows + row] = eos_lp[tid];
   }
   __syncthreads();
   if (tid == 0) {
@@ -708,7 +758,8 @@ __global__ void dec_beam_begin_kernel(int groups, int k, float* bscore, int* hyp
 __global__ void dec_beam_finalize_kernel(int groups, int k, int rows, const int* __restrict__ state,
                                         const float* __restrict__ bscore, const int* __restrict__ bp, int* __restrict__ hyp,
                                         float length_penalty, int64_t* __restrict__ out, int ld, int max_length,
-                                        int start, int eos, int pad) {
+                                        int start, int eos, int pad, const float* __restrict__ blp, size_t blp_plane,
+                                        float* __restrict__ out_logp) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= groups) return;
   int* rec = hyp + (size_t)g * BEAM_HREC;
@@ -720,16 +771,25 @@ __global__ void dec_beam_finalize_kernel(int groups, int k, int rows, const int*
   int best = 0;
   for (int i = 1; i < rec[0]; ++i)
     if (__int_as_float(rec[BEAM_HYP0 + 3 * i]) >= __int_as_float(rec[BEAM_HYP0 + 3 * best])) best = i;
-  const int e = min(rec[BEAM_HYP0 + 3 * best + 1], max_length);
+  const int end = rec[BEAM_HYP0 + 3 * best + 1];
+  const int e = min(end, max_length);
   int r = rec[BEAM_HYP0 + 3 * best + 2];
   int64_t* o = out + (size_t)g * ld;
+  float* ol = out_logp ? out_logp + (size_t)g * ld : nullptr;
+  const int len = 1 + e;
+  if (ol) {
+    // the closing EOS: a hypothesis that ended at a step (end < T) took EOS after row r's prefix at that step; one
+    // that is a running beam (end = T) has none to score
+    ol[0] = 0.f;
+    for (int c = len; c < ld; ++c) ol[c] = (c == len && len < 1 + max_length && end < T) ? blp[blp_plane + (size_t)end * rows + r] : 0.f;
+  }
   o[0] = start;
   for (int s = e - 1; s >= 0; --s) {
     const int* b = bp + ((size_t)s * rows + r) * 2;
     o[s + 1] = b[1];
+    if (ol) ol[s + 1] = blp[(size_t)s * rows + r];
     r = b[0];
   }
-  const int len = 1 + e;
   for (int c = len; c < ld; ++c) o[c] = (c == len && len < 1 + max_length) ? eos : pad;
   rec[3] = len;
 }
@@ -762,6 +822,7 @@ struct mrmt3_decoder {
   float eps;
   void *kc, *vc;  // [L][maxB][maxLen][inner]
   float *x, *q, *o, *g, *logits;
+  float* blp;     // beam search: [2][maxLen][maxB] f32 log-probabilities beside the backpointers (dec_beam_select)
   int* state;
   // per-batch
   mrmt3_decoder_weights w;
@@ -776,6 +837,8 @@ struct mrmt3_decoder {
     int k, groups;
     float length_penalty;
     const uint8_t* ban;
+    float* logp;      // greedy: per-token log-probabilities [B][logp_ld] (null = off: the plain / banned argmax)
+    int logp_ld;
     float* bscore;
     int* bp;
     int* hyp;
@@ -810,6 +873,7 @@ extern "C" int mrmt3_decoder_create(mrmt3_decoder** out, int n_layers, int d_mod
   if (e == hipSuccess) e = hipMalloc((void**)&D->g, sizeof(float) * max_batch * d_ff);
   if (e == hipSuccess) e = hipMalloc((void**)&D->logits, sizeof(float) * max_batch * vocab);
   if (e == hipSuccess) e = hipMalloc((void**)&D->state, sizeof(int) * (ST_CNT + 1));
+  if (e == hipSuccess) e = hipMalloc((void**)&D->blp, sizeof(float) * 2 * max_len * max_batch);
   if (e != hipSuccess) {
     mrmt3_set_error("decoder_create: hipMalloc failed: %s", hipGetErrorString(e));
     mrmt3_decoder_destroy(D);
@@ -823,7 +887,7 @@ extern "C" void mrmt3_decoder_destroy(mrmt3_decoder* D) {
   if (!D) return;
   if (D->exec) (void)hipGraphExecDestroy(D->exec);
   if (D->graph) (void)hipGraphDestroy(D->graph);
-  void* bufs[] = {D->kc, D->vc, D->x, D->q, D->o, D->g, D->logits, D->state};
+  void* bufs[] = {D->kc, D->vc, D->x, D->q, D->o, D->g, D->logits, D->state, D->blp};
   for (void* b : bufs) if (b) (void)hipFree(b);
   delete D;
 }
@@ -864,6 +928,24 @@ extern "C" int mrmt3_decoder_set_ban(mrmt3_decoder* D, const uint8_t* banned_mas
   return MRMT3_OK;
 }
 
+// column 0 (the start token) of the log-probability rows
+__global__ void dec_logp_begin_kernel(int B, float* logp, int ld) {
+  for (int b = threadIdx.x; b < B; b += blockDim.x) logp[(size_t)b * ld] = 0.f;
+}
+
+extern "C" int mrmt3_decoder_set_logprobs(mrmt3_decoder* D, float* out, int ld, void* stream) {
+  MR_CHECK_ARG(D && D->tokens, "decoder_set_logprobs: call decoder_begin first");
+  MR_CHECK_ARG(D->tail.k == 0, "decoder_set_logprobs: beam mode returns them from decoder_beam_finalize_logprobs");
+  if (!out) { D->tail.logp = nullptr; D->tail.logp_ld = 0; return MRMT3_OK; }
+  MR_CHECK_ARG(ld >= D->maxLen + 1, "decoder_set_logprobs: need ld >= max_len + 1 (%d), got %d", D->maxLen + 1, ld);
+  MR_CHECK_ARG(D->V <= 64 * LOGP_REGS, "decoder_set_logprobs: vocab %d exceeds the %d logits a wave keeps in registers",
+               D->V, 64 * LOGP_REGS);
+  D->tail.logp = out; D->tail.logp_ld = ld;
+  hipLaunchKernelGGL(dec_logp_begin_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, D->B, out, ld);
+  MR_CHECK_LAUNCH("decoder_set_logprobs");
+  return MRMT3_OK;
+}
+
 extern "C" int mrmt3_decoder_begin_beam(mrmt3_decoder* D, const mrmt3_decoder_weights* w, const void* cross_kv, int groups,
                                         int num_beams, int enc_len, int64_t* tokens_out, int start_id, int eos_id,
                                         int pad_id, float length_penalty, const uint8_t* banned_mask, int32_t* backptr,
@@ -885,6 +967,11 @@ extern "C" int mrmt3_decoder_begin_beam(mrmt3_decoder* D, const mrmt3_decoder_we
 }
 
 extern "C" int mrmt3_decoder_beam_finalize(mrmt3_decoder* D, int64_t* out_ids, int ld, int max_length, void* stream) {
+  return mrmt3_decoder_beam_finalize_logprobs(D, out_ids, nullptr, ld, max_length, stream);
+}
+
+extern "C" int mrmt3_decoder_beam_finalize_logprobs(mrmt3_decoder* D, int64_t* out_ids, float* out_logp, int ld,
+                                                    int max_length, void* stream) {
   MR_CHECK_ARG(D && out_ids, "decoder_beam_finalize: null pointer");
   MR_CHECK_ARG(D->tokens && D->tail.k > 0, "decoder_beam_finalize: call decoder_begin_beam first");
   MR_CHECK_ARG(max_length >= 0 && max_length <= D->maxLen && ld >= 1 + max_length,
@@ -892,7 +979,8 @@ extern "C" int mrmt3_decoder_beam_finalize(mrmt3_decoder* D, int64_t* out_ids, i
   const mrmt3_decoder::Tail& T = D->tail;
   hipLaunchKernelGGL(dec_beam_finalize_kernel, dim3((unsigned)ceil_div(T.groups, 64)), dim3(64), 0, (hipStream_t)stream,
                      T.groups, T.k, D->B, (const int*)D->state, (const float*)T.bscore, (const int*)T.bp, T.hyp,
-                     T.length_penalty, out_ids, ld, max_length, D->start, D->eos, D->pad);
+                     T.length_penalty, out_ids, ld, max_length, D->start, D->eos, D->pad, (const float*)D->blp,
+                     (size_t)D->maxLen * D->maxB, out_logp);
   MR_CHECK_LAUNCH("decoder_beam_finalize");
   return MRMT3_OK;
 }
@@ -919,21 +1007,22 @@ static void launch_tail(mrmt3_decoder* D, hipStream_t s) {
     const mrmt3_decoder::Tail& T = D->tail;
     hipLaunchKernelGGL(dec_beam_select, dim3((unsigned)T.groups), dim3(512), (size_t)T.k * V * sizeof(float), s, D->logits,
                        V, T.k, B, D->tokens, D->maxLen + 1, (const float*)D->w.embed, D->w.pos, D->x, D->state, D->eos,
-                       D->pad, T.length_penalty, T.ban, T.bscore, T.bp, T.hyp);
+                       D->pad, T.length_penalty, T.ban, T.bscore, T.bp, T.hyp, D->blp, (size_t)D->maxLen * D->maxB);
     const size_t esz = D->wdt == MRMT3_BF16 ? 2 : 4;
     const size_t row_bytes = (size_t)D->maxLen * D->inner * esz, layer_bytes = (size_t)D->maxB * row_bytes;
     const size_t max_items = (size_t)T.groups * 2 * D->L * ceil_div((int)(row_bytes / 16), REORDER_U4);
     hipLaunchKernelGGL(dec_beam_reorder, dim3((unsigned)std::min<size_t>(max_items, 2048)), dim3(REORDER_THREADS), 0, s,
                        (char*)D->kc, (char*)D->vc, layer_bytes, row_bytes, (int)(D->inner * esz), D->L, T.groups, T.k,
                        (const int*)T.bp, (const int*)D->state);
-  } else if (D->tail.ban) {
-    hipLaunchKernelGGL(dec_argmax<true>, dim3((unsigned)ceil_div(B, 8)), dim3(512), 0, s, D->logits, V, B, D->tokens,
-                       D->maxLen + 1, (const float*)D->w.embed, D->w.pos, D->x, D->state, D->eos, D->pad, D->prefix,
-                       D->tail.ban);
   } else {
-    hipLaunchKernelGGL(dec_argmax<false>, dim3((unsigned)ceil_div(B, 8)), dim3(512), 0, s, D->logits, V, B, D->tokens,
-                       D->maxLen + 1, (const float*)D->w.embed, D->w.pos, D->x, D->state, D->eos, D->pad, D->prefix,
-                       (const uint8_t*)nullptr);
+#define DEC_ARGMAX(BAN, LOGP)                                                                                              \
+  hipLaunchKernelGGL((dec_argmax<BAN, LOGP>), dim3((unsigned)ceil_div(B, 8)), dim3(512), 0, s, D->logits, V, B, D->tokens, \
+                     D->maxLen + 1, (const float*)D->w.embed, D->w.pos, D->x, D->state, D->eos, D->pad, D->prefix,        \
+                     D->tail.ban, D->tail.logp, D->tail.logp_ld)
+    if (D->tail.logp) { if (D->tail.ban) DEC_ARGMAX(true, true); else DEC_ARGMAX(false, true); }
+    else if (D->tail.ban) DEC_ARGMAX(true, false);
+    else DEC_ARGMAX(false, false);
+#undef DEC_ARGMAX
   }
 }
 
@@ -1025,8 +1114,8 @@ extern "C" int mrmt3_decoder_run(mrmt3_decoder* D, int n_steps, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const mrmt3_decoder::Tail &a = D->tail, &c = D->cap_tail;
   if (a.k != c.k || a.groups != c.groups || a.length_penalty != c.length_penalty || a.ban != c.ban ||
-      a.bscore != c.bscore || a.bp != c.bp || a.hyp != c.hyp)
-    D->captured = 0;                            // greedy <-> beam, ban <-> no ban: the tail is baked into the graph
+      a.logp != c.logp || a.logp_ld != c.logp_ld || a.bscore != c.bscore || a.bp != c.bp || a.hyp != c.hyp)
+    D->captured = 0;             // greedy <-> beam, ban <-> no ban, log-probabilities on <-> off: the tail is baked into the graph
   if (!D->captured && !D->graph_failed) {
     D->cap_tail = D->tail;
     if (D->exec) { (void)hipGraphExecDestroy(D->exec); D->exec = nullptr; }

@@ -31,3 +31,25 @@ extern "C" int mrmt3_lmhead_ce_fwd_bwd(const void* dec, int ld_dec, const void* 
   }
   return MRMT3_OK;
 }
+
+// Teacher-forced scoring: out[r] = log p(targets[r]) under softmax(dec[r] . W^T), 0 where the target is -100.  The same
+// chunk loop with mrmt3_token_logprob in place of the loss kernel; forward only, operands bf16 or f32 (`dtype`).
+extern "C" int mrmt3_lmhead_logprob(const void* dec, int ld_dec, const void* W, int ldw, const int64_t* targets, float* out,
+                                    int rows, int V, int d, int dtype, void* workspace, size_t workspace_bytes,
+                                    int chunk_rows, void* stream) {
+  MR_CHECK_ARG(dec && W && targets && out && workspace, "lmhead_logprob: null pointer");
+  MR_CHECK_ARG(rows > 0 && V > 0 && d > 0 && chunk_rows > 0, "lmhead_logprob: bad sizes");
+  MR_CHECK_ARG(dtype == MRMT3_BF16 || dtype == MRMT3_F32, "lmhead_logprob: bad dtype");
+  MR_CHECK_ARG(workspace_bytes >= (size_t)(chunk_rows < rows ? chunk_rows : rows) * V * sizeof(float),
+               "lmhead_logprob: workspace smaller than one chunk of logits");
+  const size_t elt = dtype == MRMT3_BF16 ? 2 : 4;
+  for (int r0 = 0; r0 < rows; r0 += chunk_rows) {
+    const int n = rows - r0 < chunk_rows ? rows - r0 : chunk_rows;
+    int rc = mrmt3_gemm_nt((const char*)dec + (size_t)r0 * ld_dec * elt, ld_dec, W, ldw, workspace, V, n, V, d, dtype,
+                           MRMT3_F32, 0, stream);
+    if (rc != MRMT3_OK) return rc;
+    rc = mrmt3_token_logprob((const float*)workspace, targets + r0, out + r0, n, V, -100, stream);
+    if (rc != MRMT3_OK) return rc;
+  }
+  return MRMT3_OK;
+}

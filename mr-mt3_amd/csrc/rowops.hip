@@ -1049,6 +1049,50 @@ extern "C" int mrmt3_ce_fwd_bwd(const float* logits, const int64_t* targets, con
 }
 
 // ------------------------------------------------------------------------------------------------
+// log-probability of one target per row (teacher-forced scoring; forward only).  One wave per row; the row (up to
+// 64 * TLP_REGS logits; longer rows are refused) stays in registers, so it is read once.  Same arithmetic and
+// summation order as the greedy decoder's tail (decode.hip dec_argmax<., true>): NaN-propagating maximum, exp(l - max)
+// summed per lane in ascending column then the xor tree, (l[target] - max) - log(sum).
+// ------------------------------------------------------------------------------------------------
+#define TLP_REGS 32
+__global__ __launch_bounds__(256) void token_logprob_kernel(const float* __restrict__ logits, const int64_t* __restrict__ targets,
+                                                            float* __restrict__ out, int rows, int V, int ignore_index) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int64_t t = targets[row];
+  if (t == ignore_index || t < 0 || t >= V) {
+    if (lane == 0) out[row] = (t == ignore_index) ? 0.f : __int_as_float(0x7fc00000);   // a target outside [0, V): NaN
+    return;
+  }
+  const float* lp = logits + (size_t)row * V;
+  float v[TLP_REGS];
+  float mx = -INFINITY, se = 0.f;
+#pragma unroll
+  for (int i = 0; i < TLP_REGS; ++i) {
+    const int c = lane + 64 * i;
+    v[i] = (c < V) ? lp[c] : -INFINITY;
+  }
+#pragma unroll
+  for (int i = 0; i < TLP_REGS; ++i) mx = nanmax(mx, v[i]);
+  mx = wave_nanmax(mx);
+#pragma unroll
+  for (int i = 0; i < TLP_REGS; ++i) se += expf(v[i] - mx);        // columns past V are -inf: 0
+  se = wave_sum(se);
+  if (lane == 0) out[row] = (lp[t] - mx) - logf(se);
+}
+
+extern "C" int mrmt3_token_logprob(const float* logits, const int64_t* targets, float* out, int rows, int V,
+                                   int ignore_index, void* stream) {
+  MR_CHECK_ARG(logits && targets && out && rows > 0 && V > 0, "token_logprob: bad args");
+  MR_CHECK_ARG(V <= 64 * TLP_REGS, "token_logprob: vocab %d exceeds the %d logits a wave keeps in registers", V, 64 * TLP_REGS);
+  const dim3 grid((unsigned)ceil_div(rows, 4)), block(256);
+  hipLaunchKernelGGL(token_logprob_kernel, grid, block, 0, (hipStream_t)stream, logits, targets, out, rows, V, ignore_index);
+  MR_CHECK_LAUNCH("token_logprob");
+  return MRMT3_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // AdamW over the flat parameter buffer (torch.optim.AdamW single-tensor semantics)
 // ------------------------------------------------------------------------------------------------
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,

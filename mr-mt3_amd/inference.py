@@ -13,6 +13,9 @@
   * `valid_programs` / `num_beams`: the reference passes them to HF `generate` (inference.py:186-190), whose custom
     `generate` then drops them.  Under `decode_options` (knob MRMT3_DECODE_OPTIONS=1) they are honoured:
     `model.generate_beam(..., num_beams, length_penalty=0.4, bad_token_ids=program_ban_ids(valid_programs))`.
+  * `with_confidence` / `min_confidence` (not in the reference): the decoder's per-token log-probabilities travel beside the
+    tokens and every note gets `confidence` = exp(min(log p)) over its onset token, its segment's program token and the shift
+    that set its time; notes below `min_confidence` are dropped.  The MIDI output carries no confidence.
 """
 from __future__ import annotations
 
@@ -74,6 +77,11 @@ def postprocess_batch(result: torch.Tensor, eos_token_id=1, num_special_tokens=N
     return result[:, 1:].cpu().numpy()
 
 
+def postprocess_logprobs(logp: torch.Tensor):
+    """The log-probabilities that go with `postprocess_batch`'s tokens: the same cut (the BOS column dropped)."""
+    return logp[:, 1:].float().cpu().numpy()
+
+
 class InferenceHandler:
     def __init__(self, model=None, weight_path=None, device=torch.device('cuda'), mel_norm=True,
                  contiguous_inference=False, use_tf_spectral_ops=False, decode_options=None) -> None:
@@ -101,9 +109,13 @@ class InferenceHandler:
         """inference.py:138-147: `bad_words_ids` of the programs outside `valid_programs`, one single-token list each."""
         return [[p] for p in program_ban_ids(valid_programs, self.codec)]
 
-    def _generate(self, batch, max_length, valid_programs, num_beams):
-        """The reference's `model.generate(..., num_beams, length_penalty=0.4, bad_words_ids=...)` (inference.py:186-190)."""
+    def _generate(self, batch, max_length, valid_programs, num_beams, scored=False):
+        """The reference's `model.generate(..., num_beams, length_penalty=0.4, bad_words_ids=...)` (inference.py:186-190).
+        `scored`: (ids, per-token log-probabilities)."""
         ban = None if valid_programs is None else program_ban_ids(valid_programs, self.codec)
+        if scored:
+            return self.model.generate_scored(inputs=batch, max_length=max_length, num_beams=num_beams, length_penalty=0.4,
+                                              bad_token_ids=ban)
         return self.model.generate_beam(inputs=batch, num_beams=num_beams, max_length=max_length, length_penalty=0.4,
                                         bad_token_ids=ban)
 
@@ -138,42 +150,59 @@ class InferenceHandler:
     def _postprocess_batch(self, result):
         return postprocess_batch(result, self.model.config.eos_token_id)
 
-    def _to_event(self, predictions_np, frame_times):
+    def _to_event(self, predictions_np, frame_times, logprobs_np=None, min_confidence=None):
         """inference.py:217-234 — per segment: cut at the first decoded EOS (-1), segment start time =
-        first frame time rounded down to the codec step, then decode all segments with ties."""
+        first frame time rounded down to the codec step, then decode all segments with ties.
+        `logprobs_np` (arrays shaped like `predictions_np`): cut where the tokens are cut, and the notes come back with a
+        confidence each, those below `min_confidence` dropped."""
         predictions = []
         for i, batch in enumerate(predictions_np):
             for j, tokens in enumerate(batch):
                 # NB (kept from the reference): argmax of an all-False mask is 0, so a segment that
                 # never emitted EOS contributes NO tokens.
-                tokens = tokens[:np.argmax(tokens == vocabularies.DECODED_EOS_ID)]
+                n = np.argmax(tokens == vocabularies.DECODED_EOS_ID)
+                tokens = tokens[:n]
                 start_time = frame_times[i][j][0]
                 start_time -= start_time % (1 / self.codec.steps_per_second)
                 predictions.append({"est_tokens": tokens, "start_time": start_time, "raw_inputs": []})
+                if logprobs_np is not None:
+                    predictions[-1]["est_logprobs"] = logprobs_np[i][j][:n]
+        if logprobs_np is not None:
+            result = metrics_utils.event_predictions_to_ns_scored(
+                predictions, codec=self.codec, encoding_spec=note_sequences.NoteEncodingWithTiesScoredSpec,
+                min_confidence=min_confidence)
+            return result["est_ns"]
         result = metrics_utils.event_predictions_to_ns(predictions, codec=self.codec,
                                                        encoding_spec=note_sequences.NoteEncodingWithTiesSpec)
         return result["est_ns"]
 
     @torch.no_grad()
     def inference(self, audio, audio_path=None, outpath=None, valid_programs=None, num_beams=1, batch_size=5,
-                  max_length=1024, verbose=False, return_tokens=False):
+                  max_length=1024, verbose=False, return_tokens=False, with_confidence=False, min_confidence=None):
         """audio -> note sequence (and a MIDI file when `outpath` is given, like inference.py:149-204).
-        `return_tokens=True` returns (post-processed token arrays per batch, frame times) instead."""
+        `return_tokens=True` returns (post-processed token arrays per batch, frame times) instead.
+        `with_confidence` (implied by `min_confidence`): every note carries `confidence` in (0, 1], notes below
+        `min_confidence` are dropped; with `return_tokens` a third item holds the log-probability arrays."""
+        scored = with_confidence or min_confidence is not None
         inputs, frame_times = self._preprocess(audio)
         batches, ft = self._batching(inputs, frame_times, batch_size=batch_size)
         if self.contiguous_inference:
             batches = [torch.cat(batches, dim=0)]
             ft = [np.concatenate(ft, axis=0)]
-        results = []
+        results, logps = [], []
         for batch in batches:
-            if self.decode_options:
+            if scored:
+                opts = (valid_programs, num_beams) if self.decode_options else (None, 1)
+                result, logp = self._generate(batch.to(self.device), max_length, *opts, scored=True)
+                logps.append(postprocess_logprobs(logp))
+            elif self.decode_options:
                 result = self._generate(batch.to(self.device), max_length, valid_programs, num_beams)
             else:
                 result = self.model.generate(inputs=batch.to(self.device), max_length=max_length)
             results.append(self._postprocess_batch(result))
         if return_tokens:
-            return results, ft
-        ns = self._to_event(results, ft)
+            return (results, ft, logps) if scored else (results, ft)
+        ns = self._to_event(results, ft, logps if scored else None, min_confidence)
         if outpath is not None:
             os.makedirs(os.path.dirname(os.path.abspath(outpath)), exist_ok=True)
             midi_io.note_sequence_to_midi_file(ns, outpath)
@@ -181,34 +210,47 @@ class InferenceHandler:
 
     @torch.no_grad()
     def inference_many(self, audios, outpaths=None, max_length=1024, return_tokens=False, valid_programs=None,
-                       num_beams=1):
+                       num_beams=1, with_confidence=False, min_confidence=None):
         """Several recordings in one go.  Segment-memory models decode them in lockstep (one batch row per
         recording, `model.generate_songs`); the plain T5 simply batches all segments.  Returns one note sequence
         (or, with `return_tokens`, one `(token arrays, frame times)` pair) per recording, like `inference`.
-        `valid_programs` / `num_beams` are honoured as given (length penalty 0.4, as `inference` under decode_options)."""
+        `valid_programs` / `num_beams` are honoured as given (length penalty 0.4, as `inference` under decode_options).
+        `with_confidence` / `min_confidence` as in `inference`."""
         pre = [self._preprocess(a) for a in audios]
         opts = valid_programs is not None or num_beams != 1
+        scored = with_confidence or min_confidence is not None
         ban = None if valid_programs is None else program_ban_ids(valid_programs, self.codec)
+        lps = None
         if hasattr(self.model, "generate_songs"):
             kw = dict(num_beams=num_beams, length_penalty=0.4, bad_token_ids=ban) if opts else {}
+            if scored:
+                kw["return_logprobs"] = True
             ids = self.model.generate_songs([x.to(self.device) for x, _ in pre], max_length=max_length, **kw)
+            if scored:
+                ids, lps = ids
         else:
             x_all = torch.cat([x for x, _ in pre]).to(self.device)
-            if opts:
+            flat_lp = None
+            if scored:
+                flat, flat_lp = self._generate(x_all, max_length, valid_programs, num_beams, scored=True)
+            elif opts:
                 flat = self._generate(x_all, max_length, valid_programs, num_beams)
             else:
                 flat = self.model.generate(inputs=x_all, max_length=max_length)
-            ids, at = [], 0
+            ids, lps, at = [], ([] if scored else None), 0
             for x, _ in pre:
                 ids.append(flat[at:at + x.shape[0]])
+                if scored:
+                    lps.append(flat_lp[at:at + x.shape[0]])
                 at += x.shape[0]
         out = []
         for k, (seg_ids, (_, ft)) in enumerate(zip(ids, pre)):
             results, times = [self._postprocess_batch(seg_ids)], [ft]
+            logps = [postprocess_logprobs(lps[k])] if scored else None
             if return_tokens:
-                out.append((results, times))
+                out.append((results, times, logps) if scored else (results, times))
                 continue
-            ns = self._to_event(results, times)
+            ns = self._to_event(results, times, logps, min_confidence)
             if outpaths is not None and outpaths[k] is not None:
                 os.makedirs(os.path.dirname(os.path.abspath(outpaths[k])), exist_ok=True)
                 midi_io.note_sequence_to_midi_file(ns, outpaths[k])

@@ -14,6 +14,6 @@ class T5SegMem(MT3Module):
         super().__init__(config, segmem_num_layers=segmem_num_layers, segmem_length=segmem_length,
                          compute_dtype=compute_dtype or torch.bfloat16)
 
-    def generate_2(self, inputs, max_length=1024, output_hidden_states=False, **kwargs):
+    def generate_2(self, inputs, max_length=1024, output_hidden_states=False, return_logprobs=False, **kwargs):
         from mrmt3.decode import generate_2
-        return generate_2(self, inputs, max_length=max_length)
+        return generate_2(self, inputs, max_length=max_length, return_logprobs=return_logprobs)

@@ -13,10 +13,12 @@ class T5SegMemV2(MT3Module):
         super().__init__(config, segmem_num_layers=segmem_num_layers, segmem_length=segmem_length,
                          compute_dtype=compute_dtype or torch.bfloat16)
 
-    def generate_songs(self, songs, max_length=1024, num_beams=1, length_penalty=1.0, bad_token_ids=None, **kwargs):
+    def generate_songs(self, songs, max_length=1024, num_beams=1, length_penalty=1.0, bad_token_ids=None,
+                       return_logprobs=False, **kwargs):
         """Several recordings at once, one decode-batch row per recording (each keeps its own memory chain);
         row results equal `generate` on that recording alone.  Not in the reference, which is sequential.
-        `num_beams` > 1: one beam group per recording, each equal to `generate_beam` on that recording alone."""
+        `num_beams` > 1: one beam group per recording, each equal to `generate_beam` on that recording alone.
+        `return_logprobs`: (ids per recording, per-token log-probabilities per recording)."""
         from mrmt3.decode import generate_songs
         return generate_songs(self, songs, max_length=max_length, num_beams=num_beams, length_penalty=length_penalty,
-                              bad_token_ids=bad_token_ids)
+                              bad_token_ids=bad_token_ids, return_logprobs=return_logprobs)

@@ -13,6 +13,9 @@ same engine kernels as training; only the token loop uses the KV-cached step gra
 `generate` drops: beam search (HF 4.18 `beam_search` + `BeamSearchScorer`, early_stopping=False, one hypothesis
 kept; `max_length` counts new tokens as above) and single-token bans (`bad_token_ids`, HF `NoBadWordsLogitsProcessor`).
 `num_beams=1` is the greedy decode with the ban, as HF dispatches it.
+
+`return_logprobs=True` (every entry point): `(ids, logp)` instead of `ids`, `logp` f32 of the shape of `ids` with
+the log-probability the model gave each emitted token at its position, 0.0 for the start token and for padding.
 """
 from __future__ import annotations
 
@@ -132,13 +135,21 @@ class Decoder:
         out.copy_(one.view(L, G, 1, Lc, 2 * eng.inner).expand(L, G, k, Lc, 2 * eng.inner))
         return out.view(L, G * k * Lc, 2 * eng.inner)
 
-    def run(self, ckv, B, Lc, max_steps, poll_every=64, prefix=None, logits_out=None, ban=None):
+    def logp_buffer(self):
+        """[max_batch, max_len + 1] f32 beside `tokens`, allocated once (the step graph bakes its address in)."""
+        if getattr(self, "logp", None) is None:
+            self.logp = torch.zeros(self.max_batch, self.max_len + 1, dtype=torch.float32, device=self.model.device)
+        return self.logp
+
+    def run(self, ckv, B, Lc, max_steps, poll_every=64, prefix=None, logits_out=None, ban=None, return_logprobs=False):
         """Decode up to max_steps tokens for B rows; returns (tokens [B, max_len+1] view, steps run,
-        finish_step or -1).  `prefix` [B, n, d] f32: memory rows fed as decoder positions 0..n-1.
+        finish_step or -1) and, with `return_logprobs`, a fourth item: the [B, max_len+1] f32 view of each emitted
+        token's log-probability (mrmt3_decoder_set_logprobs; the step graph with that tail is captured on first use).  `prefix` [B, n, d] f32: memory rows fed as decoder positions 0..n-1.
         `logits_out` [>= n + max_steps, B, V] f32 device tensor (tests): row s receives step s's lm_head
         output, prefix steps included; steps are then replayed one at a time, each followed by a copy.
         `ban`: device [V] uint8 mask (`ban_mask`) of tokens the argmax never picks, or None."""
         self._ban = ban
+        self._logp = self.logp_buffer() if return_logprobs else None
         cfg = self.model.cfg
         l = lib.load()
         w = self._weights()
@@ -153,7 +164,7 @@ class Decoder:
         with torch.cuda.stream(self.stream):
             out = self._run_on_stream(l, w, ckv, B, Lc, max_steps, poll_every, cfg, prefix, logits_out)
         cur.wait_stream(self.stream)
-        return out
+        return out + (self._logp,) if return_logprobs else out
 
     def _run_on_stream(self, l, w, ckv, B, Lc, max_steps, poll_every, cfg, prefix=None, logits_out=None):
         lib._check(l.mrmt3_decoder_begin(self.h, C.byref(w), lib._p(ckv), B, Lc, lib._p(self.tokens),
@@ -161,6 +172,9 @@ class Decoder:
                                          lib._stream()), "decoder_begin")
         if self._ban is not None:
             lib._check(l.mrmt3_decoder_set_ban(self.h, lib._p(self._ban), lib._stream()), "decoder_set_ban")
+        if self._logp is not None:
+            lib._check(l.mrmt3_decoder_set_logprobs(self.h, lib._p(self._logp), self._logp.stride(0), lib._stream()),
+                       "decoder_set_logprobs")
         if prefix is not None:
             n_pre = prefix.shape[1]
             assert prefix.dtype == torch.float32 and prefix.is_contiguous() and prefix.shape[0] == B
@@ -191,11 +205,14 @@ class Decoder:
                 break
         return done, fin
 
-    def run_beam(self, ckv, G, k, Lc, max_steps, length_penalty=1.0, ban=None, poll_every=64, logits_out=None):
+    def run_beam(self, ckv, G, k, Lc, max_steps, length_penalty=1.0, ban=None, poll_every=64, logits_out=None,
+                 return_logprobs=False):
         """Beam search over G groups of k rows (`cross_kv_beam`).  Returns (ids [G, W] int64, steps run, finish step or
         -1): start token, the best hypothesis, EOS when shorter than 1 + max_steps, pad; W = min(longest + 1,
         1 + max_steps).  `logits_out` [>= max_steps, G*k, V] f32 (tests) as in `run`.  After the call `bp` [max_len,
-        G*k, 2] (parent row, token per step), `beam_scores` [G*k] and `hyps` [G, BEAM_HREC] hold the search state."""
+        G*k, 2] (parent row, token per step), `beam_scores` [G*k] and `hyps` [G, BEAM_HREC] hold the search state.
+        `return_logprobs`: a fourth item, [G, W] f32, the best hypothesis' per-token log-probabilities (the closing EOS
+        included; their sum is the hypothesis' raw score)."""
         cfg = self.model.cfg
         B = G * k
         if not (1 <= k <= MAX_BEAMS) or B > self.max_batch or max_steps > self.max_len or max_steps < 1:
@@ -211,11 +228,21 @@ class Decoder:
         with torch.cuda.stream(self.stream):
             self.begin_beam(ckv, G, k, Lc, length_penalty, ban)
             done, fin = self._loop(l, B, max_steps, poll_every, logits_out)
-            lib._check(l.mrmt3_decoder_beam_finalize(self.h, lib._p(self._beam_out), self.max_len + 1, max_steps,
-                                                     lib._stream()), "decoder_beam_finalize")
+            if return_logprobs:
+                if getattr(self, "_beam_logp", None) is None:
+                    self._beam_logp = torch.zeros(self.max_batch, self.max_len + 1, dtype=torch.float32,
+                                                  device=self.model.device)
+                lib._check(l.mrmt3_decoder_beam_finalize_logprobs(self.h, lib._p(self._beam_out), lib._p(self._beam_logp),
+                                                                  self.max_len + 1, max_steps, lib._stream()),
+                           "decoder_beam_finalize_logprobs")
+            else:
+                lib._check(l.mrmt3_decoder_beam_finalize(self.h, lib._p(self._beam_out), self.max_len + 1, max_steps,
+                                                         lib._stream()), "decoder_beam_finalize")
             lens = self.hyps(G)[:, 3].cpu()             # once per decode
         cur.wait_stream(self.stream)
         W = min(int(lens.max()) + 1, 1 + max_steps)
+        if return_logprobs:
+            return self._beam_out[:G, :W], done, fin, self._beam_logp[:G, :W]
         return self._beam_out[:G, :W], done, fin
 
     def begin_beam(self, ckv, G, k, Lc, length_penalty=1.0, ban=None):
@@ -260,11 +287,16 @@ def _decoder_for(model, B, max_len, enc_len) -> Decoder:
 
 
 @torch.no_grad()
-def generate(model, inputs, max_length=1024, poll_every=64):
-    return _generate(model, inputs, max_length, poll_every)
+def generate(model, inputs, max_length=1024, poll_every=64, return_logprobs=False):
+    return _generate(model, inputs, max_length, poll_every, return_logprobs=return_logprobs)
 
 
-def _generate(model, inputs, max_length, poll_every, bad_token_ids=None):
+def _pair(ids, logp, return_logprobs):
+    return (ids, logp) if return_logprobs else ids
+
+
+def _generate(model, inputs, max_length, poll_every, bad_token_ids=None, return_logprobs=False):
+    """`return_logprobs`: every tensor of ids has a float twin cut, padded (0.0) and stacked the same way."""
     eng, cfg = model.engine, model.cfg
     if not inputs.is_cuda:
         raise RuntimeError("generate needs device tensors (no CPU fallback)")
@@ -277,19 +309,23 @@ def _generate(model, inputs, max_length, poll_every, bad_token_ids=None):
             nb = min(MAX_DECODE_BATCH, B - b0)
             dec = _decoder_for(model, nb, max_length, Le)
             ckv = dec.cross_kv(enc.view(B, Le, d)[b0:b0 + nb].reshape(nb * Le, d), nb, Le)
-            toks, done, fin = dec.run(ckv, nb, Le, max_length, poll_every, ban=dec.ban_mask(bad_token_ids))
+            toks, done, fin, *lp = dec.run(ckv, nb, Le, max_length, poll_every, ban=dec.ban_mask(bad_token_ids),
+                                           return_logprobs=return_logprobs)
             steps = (fin + 1) if fin >= 0 else max_length
-            out.append((toks[:nb, :steps + 1].clone(), steps))
+            out.append((toks[:nb, :steps + 1].clone(), steps, lp[0][:nb, :steps + 1].clone() if lp else None))
         if len(out) == 1:
-            return out[0][0]
+            return _pair(out[0][0], out[0][2], return_logprobs)
         # the reference stops when ALL rows are finished: pad shorter groups with pad_token_id
-        steps = max(s for _, s in out)
+        steps = max(s for _, s, _ in out)
         res = torch.full((B, steps + 1), cfg["pad_token_id"], dtype=torch.int64, device=inputs.device)
+        res_lp = torch.zeros(B, steps + 1, dtype=torch.float32, device=inputs.device) if return_logprobs else None
         r = 0
-        for t, s in out:
+        for t, s, lp in out:
             res[r:r + t.shape[0], :s + 1] = t
+            if return_logprobs:
+                res_lp[r:r + t.shape[0], :s + 1] = lp
             r += t.shape[0]
-        return res
+        return _pair(res, res_lp, return_logprobs)
     if model.VARIANT == "segmem_v1":
         raise RuntimeError("T5SegMem.generate is the plain batched decode; memory decode is generate_2")
     # segment-memory models: sequential segments, memory = previous segment's tokens
@@ -300,19 +336,22 @@ def _generate(model, inputs, max_length, poll_every, bad_token_ids=None):
     else:
         seg_ids[0, 0] = 1                                # t5_segmem_v2.py:199
     dec = _decoder_for(model, 1, max_length, Le + Ls)
-    outs = []
+    outs, outs_lp = [], []
     for i in range(B):
         mem = _memory(eng, seg_ids, 1, max_length, Ls)                     # [1, Ls, d]
         cur = torch.cat([enc.view(B, Le, d)[i:i + 1], mem], 1).contiguous().view(Le + Ls, d)
         ckv = dec.cross_kv(cur, 1, Le + Ls)
-        toks, done, fin = dec.run(ckv, 1, Le + Ls, max_length, poll_every, ban=dec.ban_mask(bad_token_ids))
+        toks, done, fin, *lp = dec.run(ckv, 1, Le + Ls, max_length, poll_every, ban=dec.ban_mask(bad_token_ids),
+                                       return_logprobs=return_logprobs)
         steps = (fin + 1) if fin >= 0 else max_length
         row = torch.zeros(1, max_length, dtype=torch.int64, device=inputs.device)
         n = min(steps + 1, max_length)                   # F.pad(..., max_length - len) truncates (:287-291)
         row[0, :n] = toks[0, :n]
         outs.append(row)
+        if lp:
+            outs_lp.append(_logp_rows(lp[0][:1, :n], max_length))
         seg_ids = row
-    return torch.cat(outs, 0)
+    return _pair(torch.cat(outs, 0), torch.cat(outs_lp, 0) if outs_lp else None, return_logprobs)
 
 
 def _memory(eng, seg_ids, B, L, Ls):
@@ -324,7 +363,7 @@ def _memory(eng, seg_ids, B, L, Ls):
 
 
 @torch.no_grad()
-def generate_2(model, inputs, max_length=1024, poll_every=64, num_beams=1):
+def generate_2(model, inputs, max_length=1024, poll_every=64, num_beams=1, return_logprobs=False):
     """`T5SegMem.generate_2` (models/t5_segmem.py:172-252): segments one after the other; the previous
     segment's tokens go through the segment-memory encoder and its first `segmem_length` outputs are
     PREPENDED to the decoder's input embeddings.  With the KV cache that is a prefix fill: the memory
@@ -346,23 +385,27 @@ def generate_2(model, inputs, max_length=1024, poll_every=64, num_beams=1):
     pre = getattr(dec, "_prefix_buf", None)
     if pre is None or pre.shape[1] != Ls:
         pre = dec._prefix_buf = torch.empty(1, Ls, d, device=inputs.device, dtype=torch.float32)
-    outs = []
+    outs, outs_lp = [], []
     for i in range(B):
         if Ls:
             pre.copy_(eng.segmem(seg_ids, 1, max_length).float().view(1, Ls, d))
         ckv = dec.cross_kv(enc.view(B, Le, d)[i].contiguous(), 1, Le)
-        toks, done, fin = dec.run(ckv, 1, Le, max_length, poll_every, prefix=pre if Ls else None)
+        toks, done, fin, *lp = dec.run(ckv, 1, Le, max_length, poll_every, prefix=pre if Ls else None,
+                                       return_logprobs=return_logprobs)
         steps = (fin + 1) if fin >= 0 else max_length
         row = torch.zeros(1, max_length, dtype=torch.int64, device=inputs.device)
         n = min(steps + 1, max_length)
         row[0, :n] = toks[0, :n]
         outs.append(row)
+        if lp:
+            outs_lp.append(_logp_rows(lp[0][:1, :n], max_length))
         seg_ids = row
-    return torch.cat(outs, 0)
+    return _pair(torch.cat(outs, 0), torch.cat(outs_lp, 0) if outs_lp else None, return_logprobs)
 
 
 @torch.no_grad()
-def generate_songs(model, songs, max_length=1024, poll_every=64, num_beams=1, length_penalty=1.0, bad_token_ids=None):
+def generate_songs(model, songs, max_length=1024, poll_every=64, num_beams=1, length_penalty=1.0, bad_token_ids=None,
+                   return_logprobs=False):
     """Several recordings decoded in lockstep with the segment-memory models (V2 / V2WithPrev).
 
     The reference transcribes one recording at a time because segment i needs segment i-1's tokens
@@ -371,19 +414,23 @@ def generate_songs(model, songs, max_length=1024, poll_every=64, num_beams=1, le
     produces exactly what `generate` produces for that recording alone (same kernels, one wave per row and
     sequence).  `songs`: list of [n_seg_s, Le, 512] device tensors.  Returns a list of [n_seg_s, max_length]
     int64 tensors.  `num_beams` > 1: recording s is group s of a beam search (`generate_beam` per recording, in
-    lockstep); `bad_token_ids` bans tokens in either mode.  The defaults are the greedy decode above."""
+    lockstep); `bad_token_ids` bans tokens in either mode.  The defaults are the greedy decode above.
+    `return_logprobs`: (list of ids, list of [n_seg_s, max_length] f32 log-probabilities), rows cut or zero-padded as the ids."""
     _check_beams(num_beams)
     eng, cfg = model.engine, model.cfg
     if model.VARIANT not in ("segmem_v2", "segmem_v2_with_prev"):
         raise RuntimeError("generate_songs is for the segment-memory models; plain T5 batches segments directly")
     if not songs:
-        return []
+        return _pair([], [], return_logprobs)
     per = MAX_DECODE_BATCH // num_beams
     if len(songs) > per:
-        out = []
+        out, out_lp = [], []
         for i in range(0, len(songs), per):
-            out += generate_songs(model, songs[i:i + per], max_length, poll_every, num_beams, length_penalty, bad_token_ids)
-        return out
+            part = generate_songs(model, songs[i:i + per], max_length, poll_every, num_beams, length_penalty, bad_token_ids,
+                                  return_logprobs)
+            out += part[0] if return_logprobs else part
+            out_lp += part[1] if return_logprobs else []
+        return _pair(out, out_lp, return_logprobs)
     dev = songs[0].device
     if dev.type != "cuda":
         raise RuntimeError("generate_songs needs device tensors (no CPU fallback)")
@@ -399,6 +446,7 @@ def generate_songs(model, songs, max_length=1024, poll_every=64, num_beams=1, le
         first[0] = 1
     prev = [first.clone() for _ in range(S)]
     outs = [[] for _ in range(S)]
+    outs_lp = [[] for _ in range(S)]
     for i in range(max(x.shape[0] for x in songs)):
         live = [s for s in range(S) if i < songs[s].shape[0]]
         B = len(live)
@@ -408,19 +456,27 @@ def generate_songs(model, songs, max_length=1024, poll_every=64, num_beams=1, le
         dec = _decoder_for(model, B * num_beams, max_length, Le + Ls)
         if num_beams > 1:
             ckv = dec.cross_kv_beam(cur.view(B * (Le + Ls), d), B, num_beams, Le + Ls)
-            ids, _, _ = dec.run_beam(ckv, B, num_beams, Le + Ls, max_length, length_penalty,
-                                     dec.ban_mask(bad_token_ids), poll_every)
+            ids, _, _, *lp = dec.run_beam(ckv, B, num_beams, Le + Ls, max_length, length_penalty,
+                                          dec.ban_mask(bad_token_ids), poll_every, return_logprobs=return_logprobs)
             rows = _memory_rows(ids, max_length)
+            rows_lp = _logp_rows(lp[0], max_length) if lp else None
         else:
             ckv = dec.cross_kv(cur.view(B * (Le + Ls), d), B, Le + Ls)
-            toks, done, fin = dec.run(ckv, B, Le + Ls, max_length, poll_every, ban=dec.ban_mask(bad_token_ids))
+            toks, done, fin, *lp = dec.run(ckv, B, Le + Ls, max_length, poll_every, ban=dec.ban_mask(bad_token_ids),
+                                           return_logprobs=return_logprobs)
             rows = toks[:B, :max_length].clone()                           # finished rows are already pad(0)-filled
+            rows_lp = lp[0][:B, :max_length].clone() if lp else None
             if done < max_length:                                          # all rows hit EOS early: the rest is stale
                 rows[:, done + 1:] = 0
+                if lp:
+                    rows_lp[:, done + 1:] = 0
         for r, s in enumerate(live):
             outs[s].append(rows[r])
+            if return_logprobs:
+                outs_lp[s].append(rows_lp[r])
             prev[s] = rows[r]
-    return [torch.stack(o) for o in outs]
+    ids = [torch.stack(o) for o in outs]
+    return (ids, [torch.stack(o) for o in outs_lp]) if return_logprobs else ids
 
 
 def _check_beams(num_beams):
@@ -436,8 +492,17 @@ def _memory_rows(ids, max_length):
     return rows
 
 
+def _logp_rows(logp, max_length):
+    """`_memory_rows` for the log-probabilities that go with the ids: cut or padded with 0.0."""
+    rows = torch.zeros(logp.shape[0], max_length, dtype=torch.float32, device=logp.device)
+    n = min(logp.shape[1], max_length)
+    rows[:, :n] = logp[:, :n]
+    return rows
+
+
 @torch.no_grad()
-def generate_beam(model, inputs, num_beams=1, max_length=1024, length_penalty=1.0, bad_token_ids=None, poll_every=64):
+def generate_beam(model, inputs, num_beams=1, max_length=1024, length_penalty=1.0, bad_token_ids=None, poll_every=64,
+                  return_logprobs=False):
     """Beam search with optional single-token bans; the output contract of `generate` for the model's variant.
 
     Plain T5 / T5SegMem: [B, W] int64, W = min(longest best hypothesis + 1, 1 + max_length) over the batch: start
@@ -449,7 +514,7 @@ def generate_beam(model, inputs, num_beams=1, max_length=1024, length_penalty=1.
     if not inputs.is_cuda:
         raise RuntimeError("generate_beam needs device tensors (no CPU fallback)")
     if num_beams == 1:
-        return _generate(model, inputs, max_length, poll_every, bad_token_ids)
+        return _generate(model, inputs, max_length, poll_every, bad_token_ids, return_logprobs)
     eng, cfg = model.engine, model.cfg
     k = num_beams
     eng.prepare(False)
@@ -462,17 +527,21 @@ def generate_beam(model, inputs, num_beams=1, max_length=1024, length_penalty=1.
             G = min(per, B - b0)
             dec = _decoder_for(model, G * k, max_length, Le)
             ckv = dec.cross_kv_beam(enc.view(B, Le, d)[b0:b0 + G].reshape(G * Le, d), G, k, Le)
-            ids, _, _ = dec.run_beam(ckv, G, k, Le, max_length, length_penalty, dec.ban_mask(bad_token_ids), poll_every)
-            out.append(ids.clone())
+            ids, _, _, *lp = dec.run_beam(ckv, G, k, Le, max_length, length_penalty, dec.ban_mask(bad_token_ids), poll_every,
+                                          return_logprobs=return_logprobs)
+            out.append((ids.clone(), lp[0].clone() if lp else None))
         if len(out) == 1:
-            return out[0]
-        W = max(o.shape[1] for o in out)
+            return _pair(out[0][0], out[0][1], return_logprobs)
+        W = max(o.shape[1] for o, _ in out)
         res = torch.full((B, W), cfg["pad_token_id"], dtype=torch.int64, device=inputs.device)
+        res_lp = torch.zeros(B, W, dtype=torch.float32, device=inputs.device) if return_logprobs else None
         r = 0
-        for o in out:
+        for o, lp in out:
             res[r:r + o.shape[0], :o.shape[1]] = o
+            if return_logprobs:
+                res_lp[r:r + o.shape[0], :o.shape[1]] = lp
             r += o.shape[0]
-        return res
+        return _pair(res, res_lp, return_logprobs)
     Ls = min(model.segmem_length, max_length)
     seg_ids = torch.zeros(1, max_length, dtype=torch.int64, device=inputs.device)
     if model.VARIANT == "segmem_v2_with_prev":
@@ -480,13 +549,16 @@ def generate_beam(model, inputs, num_beams=1, max_length=1024, length_penalty=1.
     else:
         seg_ids[0, 0] = 1
     dec = _decoder_for(model, k, max_length, Le + Ls)
-    outs = []
+    outs, outs_lp = [], []
     for i in range(B):
         mem = _memory(eng, seg_ids, 1, max_length, Ls)
         cur = torch.cat([enc.view(B, Le, d)[i:i + 1], mem], 1).contiguous().view(Le + Ls, d)
         ckv = dec.cross_kv_beam(cur, 1, k, Le + Ls)
-        ids, _, _ = dec.run_beam(ckv, 1, k, Le + Ls, max_length, length_penalty, dec.ban_mask(bad_token_ids), poll_every)
+        ids, _, _, *lp = dec.run_beam(ckv, 1, k, Le + Ls, max_length, length_penalty, dec.ban_mask(bad_token_ids), poll_every,
+                                      return_logprobs=return_logprobs)
         row = _memory_rows(ids, max_length)
         outs.append(row)
+        if lp:
+            outs_lp.append(_logp_rows(lp[0], max_length))
         seg_ids = row
-    return torch.cat(outs, 0)
+    return _pair(torch.cat(outs, 0), torch.cat(outs_lp, 0) if outs_lp else None, return_logprobs)

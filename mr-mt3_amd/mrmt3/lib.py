@@ -106,7 +106,7 @@ def load():
     return lib
 
 
-MIN_VERSION = 115
+MIN_VERSION = 116
 COUNTER_NAMES = ("gemm_nt_tile", "gemm_nt8", "gemm_nt_geglu", "tn_group", "tn8", "tn_tile", "attn_fwd", "attn_bwd",
                  "attn_bwd_onepass", "attn_f32", "tn_f32", "gemm_nt_splitk", "gemm_nt_addnorm", "gemm_nt_normbwd",
                  "gemm_nt_geglubwd", "attn_fwd_varlen", "attn_bwd_varlen")
@@ -908,6 +908,35 @@ def lmhead_cross_entropy(dec, w, targets, want_grad=True, grad_dtype=torch.bfloa
                                        rows, V, d, int(weighted), inst_lo, inst_hi, grad_scale, _p(ws), ws.numel(),
                                        chunk_rows, _stream()), "lmhead_ce_fwd_bwd")
     return acc[0:1].float(), dl
+
+
+def token_logprob(logits, targets, ignore_index=-100):
+    """out[r] = log_softmax(logits[r])[targets[r]] (f32), 0 where the target is `ignore_index` (mrmt3_token_logprob)."""
+    _dev(logits, targets)
+    rows, V = logits.shape
+    assert logits.dtype == torch.float32 and logits.is_contiguous()
+    assert targets.dtype == torch.int64 and targets.is_contiguous() and targets.numel() == rows
+    out = torch.empty(rows, device=logits.device, dtype=torch.float32)
+    _check(load().mrmt3_token_logprob(_p(logits), _p(targets), _p(out), rows, V, int(ignore_index), _stream()),
+           "token_logprob")
+    return out
+
+
+def lmhead_logprob(dec, w, targets, chunk_rows=None):
+    """lm_head + log-probability of each row's target over row chunks (mrmt3_lmhead_logprob): dec [rows, d], w [V, d] of
+    one dtype (bf16 or f32), targets [rows] int64 -> [rows] f32, 0 at -100.  The f32 logits exist one chunk at a time."""
+    _dev(dec, w, targets)
+    rows, d = dec.shape
+    V = w.shape[0]
+    assert dec.dtype == w.dtype and w.shape[1] == d and dec.stride(1) == 1 and w.stride(1) == 1
+    assert targets.dtype == torch.int64 and targets.is_contiguous() and targets.numel() == rows
+    if chunk_rows is None:
+        chunk_rows = ce_chunk_rows()
+    out = torch.empty(rows, device=dec.device, dtype=torch.float32)
+    ws = workspace(min(rows, chunk_rows) * V * 4, dec.device)
+    _check(load().mrmt3_lmhead_logprob(_p(dec), dec.stride(0), _p(w), w.stride(0), _p(targets), _p(out), rows, V, d,
+                                       _dt(dec), _p(ws), ws.numel(), int(chunk_rows), _stream()), "lmhead_logprob")
+    return out
 
 
 def adamw_step(p, g, m, v, lr_dev, step_dev, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.01, grad_scale=1.0,

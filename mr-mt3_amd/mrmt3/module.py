@@ -209,11 +209,34 @@ class MT3Module(nn.Module):
 
     def generate(self, inputs, max_length=1024, **kwargs):
         from .decode import generate
-        return generate(self, inputs, max_length=max_length)
+        return generate(self, inputs, max_length=max_length)      # unknown keywords ignored, as the reference does
 
-    def generate_beam(self, inputs, num_beams=1, max_length=1024, length_penalty=1.0, bad_token_ids=None, poll_every=64):
+    def generate_beam(self, inputs, num_beams=1, max_length=1024, length_penalty=1.0, bad_token_ids=None, poll_every=64,
+                      return_logprobs=False):
         """Beam search and single-token bans (`mrmt3.decode.generate_beam`); `generate` keeps ignoring such keywords,
-        as the reference's custom `generate` does."""
+        as the reference's custom `generate` does.  `return_logprobs`: (ids, per-token log-probabilities)."""
         from .decode import generate_beam
         return generate_beam(self, inputs, num_beams=num_beams, max_length=max_length, length_penalty=length_penalty,
-                             bad_token_ids=bad_token_ids, poll_every=poll_every)
+                             bad_token_ids=bad_token_ids, poll_every=poll_every, return_logprobs=return_logprobs)
+
+    def generate_scored(self, inputs, max_length=1024, num_beams=1, length_penalty=1.0, bad_token_ids=None):
+        """`generate_beam` that also says how sure the model was: `(ids, logp)`, `logp` f32 of the shape of `ids` with each
+        emitted token's log-probability at its position (0.0 for the start token and the padding)."""
+        return self.generate_beam(inputs, num_beams=num_beams, max_length=max_length, length_penalty=length_penalty,
+                                  bad_token_ids=bad_token_ids, return_logprobs=True)
+
+    @torch.no_grad()
+    def score(self, inputs, labels, targets_prev=None, chunk_rows=None):
+        """Teacher-forced log-probabilities of `labels` [B, L] under the model: [B, L] f32, 0.0 where the label is -100.
+        Eval mode (no dropout), no tape, no [B*L, V] logits: the engine's `want_logits=False` forward, then lm_head and
+        the per-row log-softmax over row chunks (`mrmt3_lmhead_logprob`; `chunk_rows` defaults to MRMT3_CE_CHUNK).
+        `-score.sum() / (labels != -100).sum()` is the cross-entropy `Trainer.eval_loss` reports.  Dense rows only."""
+        from . import lib
+        eng = self.engine
+        if labels.dim() != 2:
+            raise ValueError("score needs labels [B, L]")
+        labels = labels.to(self.device).contiguous()
+        dec, _ = eng.forward(inputs, labels, targets_prev, training=False, need_grad=False, want_logits=False)
+        # the head of `forward`: f32 weights when the engine returned f32 states (head_dtype "f32"), else the engine's own
+        w_head = self.flat.W("lm_head", torch.float32) if dec.dtype != eng.dt else eng.W("lm_head")
+        return lib.lmhead_logprob(dec, w_head, labels.view(-1), chunk_rows).view(labels.shape)
