@@ -500,6 +500,29 @@ int mrmt3_decoder_set_ban(mrmt3_decoder* dec, const uint8_t* banned_mask, void* 
  * pointer) is part of the captured step's key: switching re-captures, as the ban does; with it off the step is the
  * plain one.  mrmt3_decoder_begin clears it.  Needs vocab <= 2048; errors in beam mode. */
 int mrmt3_decoder_set_logprobs(mrmt3_decoder* dec, float* out, int ld, void* stream);
+/* Optional, after mrmt3_decoder_begin (and _set_ban / _set_logprobs / _set_prefix) and before mrmt3_decoder_run: the step
+ * draws its token instead of taking the argmax (HF 4.18 sample()).  Per row of f32 logits: banned tokens
+ * -> -inf; l / temperature (temperature 1 leaves the bits alone); top_k > 0 removes every logit strictly below the
+ * min(top_k, vocab)-th largest value (ties with it stay); top_p < 1 keeps token c iff the softmax mass of the tokens
+ * with a strictly larger logit is <= top_p (a group of equal logits stays or goes whole; the most likely token always
+ * stays); then the lowest column whose cumulative kept probability, in ascending column order, exceeds u * (kept
+ * mass), u = 24 random bits / 2^24, a pure function of (seed, batch row b, token step t).  Probabilities are f64.  A
+ * row that holds an unbanned NaN, or whose maximum is not finite, emits the greedy token.  Prefix steps draw nothing,
+ * finished rows emit pad_id, EOS bookkeeping and the state block are the greedy step's.  With
+ * mrmt3_decoder_set_logprobs the value written is the greedy one for the drawn token: log_softmax of the logits after
+ * the ban, BEFORE temperature and filters.  The four parameters live in a device record the call writes on `stream`:
+ * only "sampling on" is part of the captured step's key, so switching it on or off re-captures and a new seed or new
+ * parameters do not.  temperature == 0 switches back to the greedy tail (the other arguments are ignored);
+ * mrmt3_decoder_begin clears it.  MRMT3_ERR_INVALID_ARG for temperature < 0 or not finite, top_k < 0, top_p outside
+ * (0, 1], vocab > 2048, or in beam mode. */
+int mrmt3_decoder_set_sampling(mrmt3_decoder* dec, float temperature, int top_k, float top_p,
+                               unsigned long long seed, void* stream);
+/* The same rule on caller-owned logits [rows][V] f32 (V <= 2048, an error beyond), by the same device code: row r draws
+ * with the counter (row0 + r, step), so (row0 = b, step = t) reproduces row b of a decode at step t.  banned_mask:
+ * device [V] uint8 or NULL.  tokens_out [rows] int64; logp_out [rows] f32 (nullable) as above.  temperature > 0. */
+int mrmt3_sample_logits(const float* logits, int rows, int V, const uint8_t* banned_mask, float temperature, int top_k,
+                        float top_p, unsigned long long seed, int step, int row0, int64_t* tokens_out,
+                        float* logp_out, void* stream);
 /* Beam search (HF 4.18 beam_search + BeamSearchScorer, early_stopping = False, one hypothesis per group;
  * max_length counts new tokens).  Row r = g * num_beams + j of the batch is beam j of group g; cross_kv
  * holds groups * num_beams rows (each group's K|V repeated num_beams times).  Caller-owned device buffers:
@@ -537,6 +560,9 @@ int mrmt3_decoder_beam_finalize_logprobs(mrmt3_decoder* dec, int64_t* out_ids, f
 int mrmt3_decoder_run(mrmt3_decoder* dec, int n_steps, void* stream);
 /* 1 if the current configuration is being replayed from a captured hipGraph (0 = plain launches). */
 int mrmt3_decoder_graph_captured(const mrmt3_decoder* dec);
+/* How many step graphs the handle has captured since it was created: a call that changes the captured step's key (batch,
+ * pointers, ban / log-probabilities / sampling on or off, greedy or beam) adds one, a replay adds none. */
+int mrmt3_decoder_capture_count(const mrmt3_decoder* dec);
 /* state_out[0] = steps taken so far, [1] = 1 if every row has emitted EOS, [2] = step index at
  * which the last row finished (or -1); [0] counts prefix positions too, [2] counts token steps only.  Copies 3 int32 asynchronously to caller-owned PINNED host
  * memory; the caller synchronises the stream before reading. */

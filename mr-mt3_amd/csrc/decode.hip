@@ -17,7 +17,8 @@
 // 16 sequences on the matrix cores with K split over a workgroup; the 45.6 MB (bf16) of per-step weights stay
 // resident in the 256 MB Infinity Cache.  mrmt3_decoder_set_prefix feeds memory rows before the start token
 // (the V1 segment-memory decode).  mrmt3_decoder_set_ban / mrmt3_decoder_begin_beam swap the step's tail for a masked
-// argmax or for beam search (select + KV-cache reorder); the 65 kernels before it are shared.
+// argmax or for beam search (select + KV-cache reorder), mrmt3_decoder_set_sampling for a draw from the
+// filtered distribution; the 65 kernels before it are shared.
 #include "common.h"
 
 #define DMODEL 512
@@ -504,6 +505,250 @@ __global__ __launch_bounds__(512) void dec_argmax(const float* __restrict__ logi
   if (tid == 0) dec_step_close(state, B, p, t, true);
 }
 
+// ---- sampled tail (HF 4.18 sample(): ban -> temperature -> top-k -> top-p -> multinomial) -------------
+// One wave owns a row and keeps it in registers, as dec_argmax<., true> does.  Nothing is sorted: a float's bit pattern,
+// sign-folded, orders as the float does, so the k-th largest value and the top-p cut value are each found by building
+// that 32-bit key from its top bit down (32 rounds of compare + accumulate + one wave reduction), and the drawn column
+// by building its index the same way.  Every decision is taken on wave-reduced values: no lane diverges, and the kept
+// set does not depend on timing.  Probabilities are f64 (exp and sums): a cut that sits within f32 rounding of top_p
+// would otherwise move a token in or out of the kept set.
+struct SampleCfg {
+  float temperature;   // > 0; 1 leaves the logits' bits alone
+  int top_k;           // 0 = off
+  float top_p;         // 1 = off, else in (0, 1)
+  unsigned key;        // the seed folded to 32 bits (sample_seed_key)
+};
+static inline unsigned sample_seed_key(unsigned long long seed) {
+  return (unsigned)seed ^ ((unsigned)(seed >> 32) * 0x9E3779B1u);
+}
+// 24 random bits, a pure function of (seed key, row of the launch, token step).  The pair (row, step) is the counter:
+// both enter both mixes, so two rows whose first mix collides (drop_mix keeps 24 bits) still draw different streams.
+__device__ __forceinline__ unsigned sample_u24(unsigned key, unsigned row, unsigned step) {
+  const unsigned a = drop_mix(key + row * 0x9E3779B1u + step * 0xC2B2AE35u);
+  return drop_mix(a + step * 0x85EBCA6Bu + row * 0x27D4EB2Fu + 0x7F4A7C15u) >> 8;
+}
+// unsigned key that orders as the float does (-0 = +0); no NaN reaches it
+__device__ __forceinline__ unsigned sample_order_key(float v) {
+  unsigned b = __float_as_uint(v);
+  if (b == 0x80000000u) b = 0u;
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// The draw.  rl: the lane's logits after the ban (column lane + 64 i, -inf past V; consumed), mx their maximum (finite).
+// Returns the drawn column, the same in every lane, always one with a non-zero kept probability.
+__device__ __forceinline__ int sample_draw(float (&rl)[LOGP_REGS], float mx, int V, int lane, const SampleCfg& c,
+                                           unsigned row, unsigned step) {
+  float smx = mx;
+  if (c.temperature != 1.0f) {
+#pragma unroll
+    for (int i = 0; i < LOGP_REGS; ++i) rl[i] = rl[i] / c.temperature;      // correctly rounded: monotone, max -> max
+    smx = mx / c.temperature;
+  }
+  unsigned key[LOGP_REGS];
+#pragma unroll
+  for (int i = 0; i < LOGP_REGS; ++i) key[i] = sample_order_key(rl[i]);
+  // top-k: thr = the k-th largest key = the largest x with |{key >= x}| >= k.  Columns past V hold -inf: they count only
+  // for x <= key(-inf), where nothing is removed anyway.  Ties with the k-th value stay.
+  unsigned thr = 0u;
+  if (c.top_k > 0 && c.top_k < V) {
+    for (unsigned bit = 0x80000000u; bit; bit >>= 1) {
+      const unsigned cand = thr | bit;
+      int n = 0;
+#pragma unroll
+      for (int i = 0; i < LOGP_REGS; ++i) n += key[i] >= cand ? 1 : 0;
+      if (wave_sum_i(n) >= c.top_k) thr = cand;
+    }
+  }
+  double e[LOGP_REGS];                    // unnormalised kept probability, exp(l - max); the maximum's is 1
+#pragma unroll
+  for (int i = 0; i < LOGP_REGS; ++i) e[i] = key[i] >= thr ? exp((double)rl[i] - (double)smx) : 0.0;
+  // top-p: column c stays iff G(key_c) <= top_p * Z1, G(x) = mass of the keys above x (non-increasing in x).  The cut
+  // is the least x with G(x) <= P: one more than the largest x with G(x) > P.  A group of equal logits shares its key,
+  // so it stays or goes whole; G(largest key) = 0, so the most likely token always stays.
+  if (c.top_p < 1.0f) {
+    double z1 = 0.0;
+#pragma unroll
+    for (int i = 0; i < LOGP_REGS; ++i) z1 += e[i];
+    const double P = (double)c.top_p * wave_sum_d(z1);
+    auto above = [&](unsigned x) {
+      double g = 0.0;
+#pragma unroll
+      for (int i = 0; i < LOGP_REGS; ++i) g += key[i] > x ? e[i] : 0.0;
+      return wave_sum_d(g);
+    };
+    unsigned cut = 0u;
+    if (above(0u) > P) {
+      unsigned y = 0u;
+      for (unsigned bit = 0x80000000u; bit; bit >>= 1)
+        if (above(y | bit) > P) y |= bit;
+      cut = y + 1u;                       // above(0xFFFFFFFF) = 0 <= P: y never reaches the top
+    }
+#pragma unroll
+    for (int i = 0; i < LOGP_REGS; ++i) e[i] = key[i] >= cut ? e[i] : 0.0;
+  }
+  // draw: the lowest column whose cumulative kept mass (ascending column) exceeds u * Z.  z = the number of leading
+  // columns whose mass is still <= the target; a target that rounding puts past every column takes the last kept one.
+  double zs = 0.0;
+  int last = -1;
+#pragma unroll
+  for (int i = 0; i < LOGP_REGS; ++i) {
+    zs += e[i];
+    if (e[i] > 0.0) last = lane + 64 * i;
+  }
+  const double target = (double)sample_u24(c.key, row, step) * 0x1p-24 * wave_sum_d(zs);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) last = max(last, __shfl_xor(last, o, 64));
+  int z = 0;
+  for (int bit = 64 * LOGP_REGS; bit; bit >>= 1) {
+    const int cand = z | bit;
+    double f = 0.0;
+#pragma unroll
+    for (int i = 0; i < LOGP_REGS; ++i) f += lane + 64 * i < cand ? e[i] : 0.0;
+    if (wave_sum_d(f) <= target) z = cand;
+  }
+  return max(min(z, last), 0);         // last >= 0: the maximum's column always has mass
+}
+
+// A row's token and (LOGP) its log-probability: what dec_argmax<., LOGP> computes, the greedy winner replaced by the
+// draw when `draw` and the row's maximum is finite.  A row that holds an unbanned NaN, or no finite maximum (every
+// logit banned or -inf, or a +inf), keeps the greedy winner.  The log-probability is the greedy tail's: log_softmax of
+// the logits after the ban, before temperature and filters, same sums in the same order.  lrow: the row in memory.
+template <bool LOGP>
+__device__ __forceinline__ void sample_token(float (&rl)[LOGP_REGS], const float* __restrict__ lrow, int V, int lane,
+                                             bool draw, const SampleCfg& c, unsigned row, unsigned step, int& tok,
+                                             float& lp) {
+  float best = -INFINITY;
+  int idx = -1;
+#pragma unroll
+  for (int i = 0; i < LOGP_REGS; ++i) {
+    const int col = lane + 64 * i;
+    if (argmax_beats(rl[i], col < V ? col : -1, best, idx)) { best = rl[i]; idx = col; }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float ov = __shfl_xor(best, off, 64);
+    const int oi = __shfl_xor(idx, off, 64);
+    if (argmax_beats(ov, oi, best, idx)) { best = ov; idx = oi; }
+  }
+  float mx = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < LOGP_REGS; ++i) mx = nanmax(mx, rl[i]);
+  mx = wave_nanmax(mx);
+  float se = 0.f;
+  if (LOGP) {
+#pragma unroll
+    for (int i = 0; i < LOGP_REGS; ++i) se += expf(rl[i] - mx);
+    se = wave_sum(se);
+  }
+  tok = idx;
+  if (draw && mx == mx && fabsf(mx) != INFINITY) {
+    tok = sample_draw(rl, mx, V, lane, c, row, step);
+    best = lrow[tok];                     // a drawn column is never a banned one
+  }
+  lp = LOGP ? (best - mx) - logf(se) : 0.f;
+}
+
+template <bool BAN>
+__device__ __forceinline__ void sample_load_row(float (&rl)[LOGP_REGS], const float* __restrict__ lrow, int V, int lane,
+                                                const uint8_t* __restrict__ ban) {
+#pragma unroll
+  for (int i = 0; i < LOGP_REGS; ++i) {
+    const int col = lane + 64 * i;
+    rl[i] = (col < V) ? lrow[col] : -INFINITY;
+  }
+  if (BAN) {
+#pragma unroll
+    for (int i = 0; i < LOGP_REGS; ++i)
+      if (lane + 64 * i < V && ban[lane + 64 * i]) rl[i] = -INFINITY;
+  }
+}
+
+// dec_argmax with the draw in place of the winner: prefix steps, finished rows, EOS bookkeeping, the next embedding and
+// the step close are its own.  `samp` is a device record (mrmt3_decoder_set_sampling writes it on the stream): a replayed
+// graph freezes its by-value arguments, the record's contents are read at every step.  Row b draws with counter (b, t).
+template <bool BAN, bool LOGP>
+__global__ __launch_bounds__(512) void dec_sample(const float* __restrict__ logits, int V, int B, int64_t* __restrict__ tokens,
+                                                  int tok_ld, const float* __restrict__ embed, const float* __restrict__ pos,
+                                                  float* __restrict__ x, int* __restrict__ state, int eos, int pad,
+                                                  const float* __restrict__ prefix, const uint8_t* __restrict__ ban,
+                                                  float* __restrict__ logp, int logp_ld, const SampleCfg* __restrict__ samp) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int p = state[ST_T];
+  const int npre = state[ST_NPRE];
+  if (p + 1 <= npre) {
+    // inside the prefix nothing is drawn: the next input is the next memory row or the start token (see dec_argmax)
+    for (int b = blockIdx.x * 8; b < min(B, (int)blockIdx.x * 8 + 8); ++b) {
+      const float* er = (p + 1 < npre) ? prefix + ((size_t)b * npre + p + 1) * DMODEL
+                                       : embed + (size_t)tokens[(size_t)b * tok_ld] * DMODEL;
+      const float* pr = pos + (size_t)(p + 1) * DMODEL;
+      x[b * DMODEL + tid] = er[tid] + pr[tid];
+    }
+    __syncthreads();
+    if (tid == 0) dec_step_close(state, B, p, 0, false);
+    return;
+  }
+  const int t = p - npre;
+  const int b = blockIdx.x * 8 + wave;
+  if (b < B) {
+    const int was_done = state[ST_FLAGS + b];
+    const SampleCfg cfg = *samp;
+    const float* pr = pos + (size_t)(p + 1) * DMODEL;
+    float pv[DMODEL / 64];
+#pragma unroll
+    for (int c = 0; c < DMODEL / 64; ++c) pv[c] = pr[c * 64 + lane];
+    const float* lrow = logits + (size_t)b * V;
+    float rl[LOGP_REGS];
+    sample_load_row<BAN>(rl, lrow, V, lane, ban);
+    int idx;
+    float lp_tok;
+    sample_token<LOGP>(rl, lrow, V, lane, !was_done, cfg, (unsigned)b, (unsigned)t, idx, lp_tok);
+    const int nxt = was_done ? pad : idx;
+    const float* er = embed + (size_t)nxt * DMODEL;
+#pragma unroll
+    for (int c = 0; c < DMODEL / 64; ++c) x[b * DMODEL + c * 64 + lane] = er[c * 64 + lane] + pv[c];
+    if (lane == 0) {
+      if (!was_done && nxt == eos) __hip_atomic_store(&state[ST_FLAGS + b], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      tokens[(size_t)b * tok_ld + t + 1] = nxt;
+      if (LOGP) logp[(size_t)b * logp_ld + t + 1] = was_done ? 0.f : lp_tok;
+    }
+  }
+  __syncthreads();
+  if (tid == 0) dec_step_close(state, B, p, t, true);
+}
+
+// The rule alone on a caller's [rows][V] logits (mrmt3_sample_logits): row r draws with counter (row0 + r, step).
+template <bool BAN, bool LOGP>
+__global__ __launch_bounds__(512) void sample_logits_kernel(const float* __restrict__ logits, int rows, int V,
+                                                            const uint8_t* __restrict__ ban, SampleCfg cfg, unsigned step,
+                                                            unsigned row0, int64_t* __restrict__ tokens_out,
+                                                            float* __restrict__ logp_out) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = blockIdx.x * 8 + wave;
+  if (r >= rows) return;
+  const float* lrow = logits + (size_t)r * V;
+  float rl[LOGP_REGS];
+  sample_load_row<BAN>(rl, lrow, V, lane, ban);
+  int idx;
+  float lp_tok;
+  sample_token<LOGP>(rl, lrow, V, lane, true, cfg, row0 + (unsigned)r, step, idx, lp_tok);
+  if (lane == 0) {
+    tokens_out[r] = idx;
+    if (LOGP) logp_out[r] = lp_tok;
+  }
+}
+
+__global__ void dec_sampling_set_kernel(SampleCfg* rec, SampleCfg v) { *rec = v; }
+
 // ---- beam search tail (HF 4.18 beam_search + BeamSearchScorer, early_stopping=False, one hypothesis kept) --------
 // Row r = g * k + j is beam j of group (input segment) g.  Per group the caller owns a record of BEAM_HREC int32:
 //   [0] hypotheses held   [1] worst kept score (f32 bits; 1e9 while fewer than k)   [2] done   [3] length of the
@@ -823,6 +1068,7 @@ struct mrmt3_decoder {
   void *kc, *vc;  // [L][maxB][maxLen][inner]
   float *x, *q, *o, *g, *logits;
   float* blp;     // beam search: [2][maxLen][maxB] f32 log-probabilities beside the backpointers (dec_beam_select)
+  SampleCfg* samp;   // sampling parameters and seed, read by dec_sample at every step (mrmt3_decoder_set_sampling)
   int* state;
   // per-batch
   mrmt3_decoder_weights w;
@@ -839,6 +1085,7 @@ struct mrmt3_decoder {
     const uint8_t* ban;
     float* logp;      // greedy: per-token log-probabilities [B][logp_ld] (null = off: the plain / banned argmax)
     int logp_ld;
+    int sample;       // 1: dec_sample draws the token (its parameters live in `samp`, not here: they may change per call)
     float* bscore;
     int* bp;
     int* hyp;
@@ -849,6 +1096,7 @@ struct mrmt3_decoder {
   hipGraphExec_t exec;
   int captured;     // 1 = exec valid for the current (B, encLen, pointers)
   int graph_failed;  // 1 = capture failed once; run with plain launches
+  int captures;      // step graphs instantiated so far (mrmt3_decoder_capture_count)
 };
 
 extern "C" int mrmt3_decoder_create(mrmt3_decoder** out, int n_layers, int d_model, int n_heads, int d_ff, int vocab,
@@ -874,6 +1122,7 @@ extern "C" int mrmt3_decoder_create(mrmt3_decoder** out, int n_layers, int d_mod
   if (e == hipSuccess) e = hipMalloc((void**)&D->logits, sizeof(float) * max_batch * vocab);
   if (e == hipSuccess) e = hipMalloc((void**)&D->state, sizeof(int) * (ST_CNT + 1));
   if (e == hipSuccess) e = hipMalloc((void**)&D->blp, sizeof(float) * 2 * max_len * max_batch);
+  if (e == hipSuccess) e = hipMalloc((void**)&D->samp, sizeof(SampleCfg));
   if (e != hipSuccess) {
     mrmt3_set_error("decoder_create: hipMalloc failed: %s", hipGetErrorString(e));
     mrmt3_decoder_destroy(D);
@@ -887,7 +1136,7 @@ extern "C" void mrmt3_decoder_destroy(mrmt3_decoder* D) {
   if (!D) return;
   if (D->exec) (void)hipGraphExecDestroy(D->exec);
   if (D->graph) (void)hipGraphDestroy(D->graph);
-  void* bufs[] = {D->kc, D->vc, D->x, D->q, D->o, D->g, D->logits, D->state, D->blp};
+  void* bufs[] = {D->kc, D->vc, D->x, D->q, D->o, D->g, D->logits, D->state, D->blp, D->samp};
   for (void* b : bufs) if (b) (void)hipFree(b);
   delete D;
 }
@@ -946,6 +1195,47 @@ extern "C" int mrmt3_decoder_set_logprobs(mrmt3_decoder* D, float* out, int ld, 
   return MRMT3_OK;
 }
 
+static int sample_check_args(const char* who, float temperature, int top_k, float top_p, int V) {
+  MR_CHECK_ARG(temperature > 0.f && temperature <= 3.0e38f, "%s: need a finite temperature > 0, got %g", who, (double)temperature);
+  MR_CHECK_ARG(top_k >= 0, "%s: need top_k >= 0 (0 = off), got %d", who, top_k);
+  MR_CHECK_ARG(top_p > 0.f && top_p <= 1.f, "%s: need top_p in (0, 1], got %g", who, (double)top_p);
+  MR_CHECK_ARG(V <= 64 * LOGP_REGS, "%s: vocab %d exceeds the %d logits a wave keeps in registers", who, V, 64 * LOGP_REGS);
+  return MRMT3_OK;
+}
+
+extern "C" int mrmt3_decoder_set_sampling(mrmt3_decoder* D, float temperature, int top_k, float top_p,
+                                          unsigned long long seed, void* stream) {
+  MR_CHECK_ARG(D && D->tokens, "decoder_set_sampling: call decoder_begin first");
+  if (temperature == 0.f) { D->tail.sample = 0; return MRMT3_OK; }      // back to the greedy tail
+  MR_CHECK_ARG(D->tail.k == 0, "decoder_set_sampling: beam search does not sample");
+  int rc = sample_check_args("decoder_set_sampling", temperature, top_k, top_p, D->V);
+  if (rc != MRMT3_OK) return rc;
+  const SampleCfg c = {temperature, top_k, top_p, sample_seed_key(seed)};
+  hipLaunchKernelGGL(dec_sampling_set_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, D->samp, c);
+  MR_CHECK_LAUNCH("decoder_set_sampling");
+  D->tail.sample = 1;
+  return MRMT3_OK;
+}
+
+extern "C" int mrmt3_sample_logits(const float* logits, int rows, int V, const uint8_t* banned_mask, float temperature,
+                                   int top_k, float top_p, unsigned long long seed, int step, int row0,
+                                   int64_t* tokens_out, float* logp_out, void* stream) {
+  MR_CHECK_ARG(logits && tokens_out && rows > 0 && V > 0 && step >= 0 && row0 >= 0, "sample_logits: bad args");
+  int rc = sample_check_args("sample_logits", temperature, top_k, top_p, V);
+  if (rc != MRMT3_OK) return rc;
+  const SampleCfg c = {temperature, top_k, top_p, sample_seed_key(seed)};
+  const dim3 grid((unsigned)ceil_div(rows, 8)), block(512);
+#define SAMPLE_LOGITS(BAN, LOGP)                                                                                      \
+  hipLaunchKernelGGL((sample_logits_kernel<BAN, LOGP>), grid, block, 0, (hipStream_t)stream, logits, rows, V, banned_mask, \
+                     c, (unsigned)step, (unsigned)row0, tokens_out, logp_out)
+  if (logp_out) { if (banned_mask) SAMPLE_LOGITS(true, true); else SAMPLE_LOGITS(false, true); }
+  else if (banned_mask) SAMPLE_LOGITS(true, false);
+  else SAMPLE_LOGITS(false, false);
+#undef SAMPLE_LOGITS
+  MR_CHECK_LAUNCH("sample_logits");
+  return MRMT3_OK;
+}
+
 extern "C" int mrmt3_decoder_begin_beam(mrmt3_decoder* D, const mrmt3_decoder_weights* w, const void* cross_kv, int groups,
                                         int num_beams, int enc_len, int64_t* tokens_out, int start_id, int eos_id,
                                         int pad_id, float length_penalty, const uint8_t* banned_mask, int32_t* backptr,
@@ -1000,7 +1290,7 @@ extern "C" int mrmt3_decoder_set_prefix(mrmt3_decoder* D, const float* prefix, i
 template <typename TW>
 static int launch_step(mrmt3_decoder* D, hipStream_t s);
 
-// the step's last kernel(s): greedy argmax (banned or not), or the beam select + KV-cache reorder
+// the step's last kernel(s): greedy argmax (banned or not), the sampled tail, or the beam select + KV-cache reorder
 static void launch_tail(mrmt3_decoder* D, hipStream_t s) {
   const int B = D->B, V = D->V;
   if (D->tail.k > 0) {
@@ -1015,14 +1305,23 @@ static void launch_tail(mrmt3_decoder* D, hipStream_t s) {
                        (char*)D->kc, (char*)D->vc, layer_bytes, row_bytes, (int)(D->inner * esz), D->L, T.groups, T.k,
                        (const int*)T.bp, (const int*)D->state);
   } else {
+#define DEC_SAMPLE(BAN, LOGP)                                                                                              \
+  hipLaunchKernelGGL((dec_sample<BAN, LOGP>), dim3((unsigned)ceil_div(B, 8)), dim3(512), 0, s, D->logits, V, B, D->tokens, \
+                     D->maxLen + 1, (const float*)D->w.embed, D->w.pos, D->x, D->state, D->eos, D->pad, D->prefix,        \
+                     D->tail.ban, D->tail.logp, D->tail.logp_ld, (const SampleCfg*)D->samp)
 #define DEC_ARGMAX(BAN, LOGP)                                                                                              \
   hipLaunchKernelGGL((dec_argmax<BAN, LOGP>), dim3((unsigned)ceil_div(B, 8)), dim3(512), 0, s, D->logits, V, B, D->tokens, \
                      D->maxLen + 1, (const float*)D->w.embed, D->w.pos, D->x, D->state, D->eos, D->pad, D->prefix,        \
                      D->tail.ban, D->tail.logp, D->tail.logp_ld)
-    if (D->tail.logp) { if (D->tail.ban) DEC_ARGMAX(true, true); else DEC_ARGMAX(false, true); }
+    if (D->tail.sample) {
+      if (D->tail.logp) { if (D->tail.ban) DEC_SAMPLE(true, true); else DEC_SAMPLE(false, true); }
+      else if (D->tail.ban) DEC_SAMPLE(true, false);
+      else DEC_SAMPLE(false, false);
+    } else if (D->tail.logp) { if (D->tail.ban) DEC_ARGMAX(true, true); else DEC_ARGMAX(false, true); }
     else if (D->tail.ban) DEC_ARGMAX(true, false);
     else DEC_ARGMAX(false, false);
 #undef DEC_ARGMAX
+#undef DEC_SAMPLE
   }
 }
 
@@ -1114,8 +1413,8 @@ extern "C" int mrmt3_decoder_run(mrmt3_decoder* D, int n_steps, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const mrmt3_decoder::Tail &a = D->tail, &c = D->cap_tail;
   if (a.k != c.k || a.groups != c.groups || a.length_penalty != c.length_penalty || a.ban != c.ban ||
-      a.logp != c.logp || a.logp_ld != c.logp_ld || a.bscore != c.bscore || a.bp != c.bp || a.hyp != c.hyp)
-    D->captured = 0;             // greedy <-> beam, ban <-> no ban, log-probabilities on <-> off: the tail is baked into the graph
+      a.logp != c.logp || a.logp_ld != c.logp_ld || a.sample != c.sample || a.bscore != c.bscore || a.bp != c.bp || a.hyp != c.hyp)
+    D->captured = 0;             // greedy <-> beam, ban <-> no ban, log-probabilities or sampling on <-> off: the tail is baked into the graph
   if (!D->captured && !D->graph_failed) {
     D->cap_tail = D->tail;
     if (D->exec) { (void)hipGraphExecDestroy(D->exec); D->exec = nullptr; }
@@ -1127,7 +1426,7 @@ extern "C" int mrmt3_decoder_run(mrmt3_decoder* D, int n_steps, void* stream) {
       if (rc == MRMT3_OK && e2 == hipSuccess && D->graph) e = hipGraphInstantiate(&D->exec, D->graph, nullptr, nullptr, 0);
       else e = hipErrorUnknown;
     }
-    if (e == hipSuccess && D->exec) D->captured = 1;
+    if (e == hipSuccess && D->exec) { D->captured = 1; ++D->captures; }
     else { D->graph_failed = 1; (void)hipGetLastError(); }
   }
   for (int i = 0; i < n_steps; ++i) {
@@ -1142,6 +1441,7 @@ extern "C" int mrmt3_decoder_run(mrmt3_decoder* D, int n_steps, void* stream) {
 }
 
 extern "C" int mrmt3_decoder_graph_captured(const mrmt3_decoder* D) { return D ? D->captured : 0; }
+extern "C" int mrmt3_decoder_capture_count(const mrmt3_decoder* D) { return D ? D->captures : 0; }
 
 extern "C" int mrmt3_decoder_logits(mrmt3_decoder* D, float* dst, int rows, void* stream) {
   MR_CHECK_ARG(D && dst, "decoder_logits: null pointer");

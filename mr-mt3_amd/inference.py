@@ -16,6 +16,9 @@
   * `with_confidence` / `min_confidence` (not in the reference): the decoder's per-token log-probabilities travel beside the
     tokens and every note gets `confidence` = exp(min(log p)) over its onset token, its segment's program token and the shift
     that set its time; notes below `min_confidence` are dropped.  The MIDI output carries no confidence.
+  * `do_sample` / `temperature` / `top_k` / `top_p` / `seed` / `best_of` (the reference's call site pins `do_sample=False`):
+    honoured under `decode_options`, like `num_beams`.  Batch i of a recording draws with `seed + i`; `best_of = n` keeps, per
+    segment, the most likely of n samples (`model.generate_best_of`, plain T5 only).
 """
 from __future__ import annotations
 
@@ -109,10 +112,23 @@ class InferenceHandler:
         """inference.py:138-147: `bad_words_ids` of the programs outside `valid_programs`, one single-token list each."""
         return [[p] for p in program_ban_ids(valid_programs, self.codec)]
 
-    def _generate(self, batch, max_length, valid_programs, num_beams, scored=False):
+    def _generate(self, batch, max_length, valid_programs, num_beams, scored=False, sample=None, best_of=1):
         """The reference's `model.generate(..., num_beams, length_penalty=0.4, bad_words_ids=...)` (inference.py:186-190).
-        `scored`: (ids, per-token log-probabilities)."""
+        `scored`: (ids, per-token log-probabilities).  `sample`: dict of `temperature`, `top_k`, `top_p`, `seed` (the
+        tokens are drawn; not with `num_beams` > 1); `best_of` > 1: the most likely of that many samples per segment."""
         ban = None if valid_programs is None else program_ban_ids(valid_programs, self.codec)
+        if sample is not None:
+            if num_beams != 1:
+                raise ValueError("beam search does not sample: do_sample / best_of need num_beams == 1")
+            if best_of > 1:
+                if not hasattr(self.model, "generate_best_of") or getattr(self.model, "VARIANT", "t5") not in ("t5", "segmem_v1"):
+                    raise ValueError("best_of > 1 is for the plain T5 model (MT3Net); the segment-memory models decode "
+                                     "one sample per segment")
+                ids, logp = self.model.generate_best_of(inputs=batch, n=best_of, max_length=max_length, bad_token_ids=ban,
+                                                        **sample)
+                return (ids, logp) if scored else ids
+            return self.model.generate_sample(inputs=batch, max_length=max_length, bad_token_ids=ban,
+                                              return_logprobs=scored, **sample)
         if scored:
             return self.model.generate_scored(inputs=batch, max_length=max_length, num_beams=num_beams, length_penalty=0.4,
                                               bad_token_ids=ban)
@@ -176,27 +192,40 @@ class InferenceHandler:
                                                        encoding_spec=note_sequences.NoteEncodingWithTiesSpec)
         return result["est_ns"]
 
+    def _sample_options(self, do_sample, temperature, top_k, top_p, seed, best_of):
+        """The sampling keywords as `_generate` takes them, or None: honoured only under `decode_options`."""
+        if not (isinstance(best_of, int) and best_of >= 1):
+            raise ValueError(f"best_of must be an int >= 1, got {best_of!r}")
+        if not self.decode_options or not (do_sample or best_of > 1):
+            return None
+        return dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=int(seed))
+
     @torch.no_grad()
     def inference(self, audio, audio_path=None, outpath=None, valid_programs=None, num_beams=1, batch_size=5,
-                  max_length=1024, verbose=False, return_tokens=False, with_confidence=False, min_confidence=None):
+                  max_length=1024, verbose=False, return_tokens=False, with_confidence=False, min_confidence=None,
+                  do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, best_of=1):
         """audio -> note sequence (and a MIDI file when `outpath` is given, like inference.py:149-204).
         `return_tokens=True` returns (post-processed token arrays per batch, frame times) instead.
         `with_confidence` (implied by `min_confidence`): every note carries `confidence` in (0, 1], notes below
-        `min_confidence` are dropped; with `return_tokens` a third item holds the log-probability arrays."""
+        `min_confidence` are dropped; with `return_tokens` a third item holds the log-probability arrays.
+        `do_sample` (under `decode_options`): the tokens are drawn, batch i with `seed + i`; `best_of` > 1 keeps the most
+        likely of that many samples per segment (plain T5 only) and implies sampling."""
         scored = with_confidence or min_confidence is not None
+        sample = self._sample_options(do_sample, temperature, top_k, top_p, seed, best_of)
         inputs, frame_times = self._preprocess(audio)
         batches, ft = self._batching(inputs, frame_times, batch_size=batch_size)
         if self.contiguous_inference:
             batches = [torch.cat(batches, dim=0)]
             ft = [np.concatenate(ft, axis=0)]
         results, logps = [], []
-        for batch in batches:
+        for i, batch in enumerate(batches):
+            kw = {} if sample is None else dict(sample=dict(sample, seed=sample["seed"] + i), best_of=best_of)
             if scored:
                 opts = (valid_programs, num_beams) if self.decode_options else (None, 1)
-                result, logp = self._generate(batch.to(self.device), max_length, *opts, scored=True)
+                result, logp = self._generate(batch.to(self.device), max_length, *opts, scored=True, **kw)
                 logps.append(postprocess_logprobs(logp))
             elif self.decode_options:
-                result = self._generate(batch.to(self.device), max_length, valid_programs, num_beams)
+                result = self._generate(batch.to(self.device), max_length, valid_programs, num_beams, **kw)
             else:
                 result = self.model.generate(inputs=batch.to(self.device), max_length=max_length)
             results.append(self._postprocess_batch(result))
@@ -210,12 +239,19 @@ class InferenceHandler:
 
     @torch.no_grad()
     def inference_many(self, audios, outpaths=None, max_length=1024, return_tokens=False, valid_programs=None,
-                       num_beams=1, with_confidence=False, min_confidence=None):
+                       num_beams=1, with_confidence=False, min_confidence=None, do_sample=False, temperature=1.0, top_k=0,
+                       top_p=1.0, seed=0, best_of=1):
         """Several recordings in one go.  Segment-memory models decode them in lockstep (one batch row per
         recording, `model.generate_songs`); the plain T5 simply batches all segments.  Returns one note sequence
         (or, with `return_tokens`, one `(token arrays, frame times)` pair) per recording, like `inference`.
         `valid_programs` / `num_beams` are honoured as given (length penalty 0.4, as `inference` under decode_options).
-        `with_confidence` / `min_confidence` as in `inference`."""
+        `with_confidence` / `min_confidence` as in `inference`.  The sampling keywords as in `inference` (under
+        `decode_options`): the plain T5 decodes every segment in one batch under `seed`, the segment-memory models draw
+        segment i of every recording under `seed + i`; `best_of` > 1 is for the plain T5."""
+        sample = self._sample_options(do_sample, temperature, top_k, top_p, seed, best_of)
+        if sample is not None and best_of > 1 and hasattr(self.model, "generate_songs"):
+            raise ValueError("best_of > 1 is for the plain T5 model (MT3Net); the segment-memory models decode one sample "
+                             "per segment")
         pre = [self._preprocess(a) for a in audios]
         opts = valid_programs is not None or num_beams != 1
         scored = with_confidence or min_confidence is not None
@@ -225,16 +261,19 @@ class InferenceHandler:
             kw = dict(num_beams=num_beams, length_penalty=0.4, bad_token_ids=ban) if opts else {}
             if scored:
                 kw["return_logprobs"] = True
+            if sample is not None:
+                kw.update(sample, do_sample=True, bad_token_ids=ban)
             ids = self.model.generate_songs([x.to(self.device) for x, _ in pre], max_length=max_length, **kw)
             if scored:
                 ids, lps = ids
         else:
             x_all = torch.cat([x for x, _ in pre]).to(self.device)
             flat_lp = None
+            kw = {} if sample is None else dict(sample=sample, best_of=best_of)
             if scored:
-                flat, flat_lp = self._generate(x_all, max_length, valid_programs, num_beams, scored=True)
-            elif opts:
-                flat = self._generate(x_all, max_length, valid_programs, num_beams)
+                flat, flat_lp = self._generate(x_all, max_length, valid_programs, num_beams, scored=True, **kw)
+            elif opts or sample is not None:
+                flat = self._generate(x_all, max_length, valid_programs, num_beams, **kw)
             else:
                 flat = self.model.generate(inputs=x_all, max_length=max_length)
             ids, lps, at = [], ([] if scored else None), 0

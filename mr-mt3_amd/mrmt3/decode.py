@@ -16,10 +16,16 @@ kept; `max_length` counts new tokens as above) and single-token bans (`bad_token
 
 `return_logprobs=True` (every entry point): `(ids, logp)` instead of `ids`, `logp` f32 of the shape of `ids` with
 the log-probability the model gave each emitted token at its position, 0.0 for the start token and for padding.
+
+`do_sample=True` (every entry point but the beam search): the step draws its token from the distribution HF's
+`sample()` builds (ban, `temperature`, `top_k`, `top_p`) instead of taking the argmax; the draw is a pure function of
+(`seed`, row of the decode batch, token step).  `generate_sample` / `generate_best_of` draw several transcriptions per segment.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
+from dataclasses import dataclass, replace
 
 import torch
 
@@ -29,6 +35,39 @@ from . import lib
 MAX_DECODE_BATCH = 256     # DEC_MAXB of csrc/decode.hip: sequences decoded together (one wave per row x sequence)
 MAX_BEAMS = 8              # BEAM_MAXK of csrc/decode.hip
 BEAM_HREC = 32             # int32 per group of the hypothesis record (csrc/decode.hip, include/mrmt3_hip.h)
+
+
+MAX_SAMPLE_VOCAB = 2048   # 64 * LOGP_REGS of csrc/decode.hip: the sampled tail keeps a vocabulary row in one wave's registers
+
+
+@dataclass(frozen=True)
+class Sampling:
+    """What `mrmt3_decoder_set_sampling` takes: `temperature` > 0, `top_k` (0 = off), `top_p` in (0, 1] (1 = off), `seed`."""
+    temperature: float = 1.0
+    top_k: int = 0
+    top_p: float = 1.0
+    seed: int = 0
+
+    def __post_init__(self):
+        t, p = self.temperature, self.top_p
+        if not (isinstance(t, (int, float)) and math.isfinite(t) and t > 0):
+            raise ValueError(f"temperature must be a finite number > 0, got {t!r}")
+        if not (isinstance(self.top_k, int) and self.top_k >= 0):
+            raise ValueError(f"top_k must be an int >= 0 (0 = off), got {self.top_k!r}")
+        if not (isinstance(p, (int, float)) and 0.0 < p <= 1.0):
+            raise ValueError(f"top_p must lie in (0, 1], got {p!r}")
+        if not (isinstance(self.seed, int) and 0 <= self.seed < 2 ** 64):
+            raise ValueError(f"seed must be an int in [0, 2^64), got {self.seed!r}")
+
+    def shifted(self, i: int) -> "Sampling":
+        """The same parameters with `seed + i`: decodes that reuse row counters (the next batch, the next segment of a
+        memory chain) must not share draws."""
+        return replace(self, seed=(self.seed + i) % 2 ** 64)
+
+
+def _sampling(do_sample, temperature, top_k, top_p, seed):
+    """The sampling keywords of the entry points -> `Sampling`, or None for `do_sample=False` (then nothing is looked at)."""
+    return Sampling(temperature, top_k, top_p, seed) if do_sample else None
 
 
 class _Weights(C.Structure):
@@ -141,13 +180,21 @@ class Decoder:
             self.logp = torch.zeros(self.max_batch, self.max_len + 1, dtype=torch.float32, device=self.model.device)
         return self.logp
 
-    def run(self, ckv, B, Lc, max_steps, poll_every=64, prefix=None, logits_out=None, ban=None, return_logprobs=False):
+    def run(self, ckv, B, Lc, max_steps, poll_every=64, prefix=None, logits_out=None, ban=None, return_logprobs=False,
+            sampling=None):
         """Decode up to max_steps tokens for B rows; returns (tokens [B, max_len+1] view, steps run,
         finish_step or -1) and, with `return_logprobs`, a fourth item: the [B, max_len+1] f32 view of each emitted
         token's log-probability (mrmt3_decoder_set_logprobs; the step graph with that tail is captured on first use).  `prefix` [B, n, d] f32: memory rows fed as decoder positions 0..n-1.
         `logits_out` [>= n + max_steps, B, V] f32 device tensor (tests): row s receives step s's lm_head
         output, prefix steps included; steps are then replayed one at a time, each followed by a copy.
-        `ban`: device [V] uint8 mask (`ban_mask`) of tokens the argmax never picks, or None."""
+        `ban`: device [V] uint8 mask (`ban_mask`) of tokens the argmax never picks, or None.
+        `sampling`: a `Sampling` (or a (temperature, top_k, top_p, seed) tuple): row b draws its token of step t with the
+        counter (b, t) (mrmt3_decoder_set_sampling; the sampled step is captured once, a new seed or parameters replay it)."""
+        if sampling is not None and not isinstance(sampling, Sampling):
+            sampling = Sampling(*sampling)
+        if sampling is not None and self.model.cfg["vocab_size"] > MAX_SAMPLE_VOCAB:
+            raise ValueError(f"sampling needs vocab_size <= {MAX_SAMPLE_VOCAB}")
+        self._sampling = sampling
         self._ban = ban
         self._logp = self.logp_buffer() if return_logprobs else None
         cfg = self.model.cfg
@@ -175,6 +222,10 @@ class Decoder:
         if self._logp is not None:
             lib._check(l.mrmt3_decoder_set_logprobs(self.h, lib._p(self._logp), self._logp.stride(0), lib._stream()),
                        "decoder_set_logprobs")
+        if self._sampling is not None:
+            sp = self._sampling
+            lib._check(l.mrmt3_decoder_set_sampling(self.h, float(sp.temperature), int(sp.top_k), float(sp.top_p),
+                                                    int(sp.seed), lib._stream()), "decoder_set_sampling")
         if prefix is not None:
             n_pre = prefix.shape[1]
             assert prefix.dtype == torch.float32 and prefix.is_contiguous() and prefix.shape[0] == B
@@ -276,6 +327,11 @@ class Decoder:
     def graph_captured(self) -> bool:
         return bool(lib.load().mrmt3_decoder_graph_captured(self.h))
 
+    @property
+    def capture_count(self) -> int:
+        """Step graphs captured by this handle so far (a replay of the captured step adds none)."""
+        return int(lib.load().mrmt3_decoder_capture_count(self.h))
+
 
 def _decoder_for(model, B, max_len, enc_len) -> Decoder:
     dec = getattr(model, "_decoder", None)
@@ -287,17 +343,62 @@ def _decoder_for(model, B, max_len, enc_len) -> Decoder:
 
 
 @torch.no_grad()
-def generate(model, inputs, max_length=1024, poll_every=64, return_logprobs=False):
-    return _generate(model, inputs, max_length, poll_every, return_logprobs=return_logprobs)
+def generate(model, inputs, max_length=1024, poll_every=64, return_logprobs=False, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0):
+    return _generate(model, inputs, max_length, poll_every, return_logprobs=return_logprobs,
+                     sampling=_sampling(do_sample, temperature, top_k, top_p, seed))
+
+
+@torch.no_grad()
+def generate_sample(model, inputs, max_length=1024, temperature=1.0, top_k=0, top_p=1.0, seed=0, num_return_sequences=1,
+                    bad_token_ids=None, return_logprobs=False, poll_every=64):
+    """`generate` that draws.  Plain T5: `num_return_sequences = n` transcriptions per segment, row g * n + j of the
+    [B * n, W] output is sample j of segment g (its cross K|V repeated as the beam search's are; the row's draw counter is
+    its row in the decode batch).  Segment-memory models decode one sample per segment along their memory chain."""
+    return _generate(model, inputs, max_length, poll_every, bad_token_ids, return_logprobs,
+                     sampling=Sampling(temperature, top_k, top_p, seed), n=num_return_sequences)
+
+
+def best_of_select(ids, logp, n, eos_token_id):
+    """Of every n consecutive rows of `ids` / `logp` [G * n, W], the one whose log-probabilities, summed over the emitted
+    tokens up to and including the first EOS (the whole row when there is none), are highest; ties go to the lowest j.
+    -> (ids [G, W], logp [G, W], j [G]).  Torch ops on the tensors' device, no loop over rows."""
+    if ids.shape != logp.shape or ids.shape[0] % n:
+        raise ValueError(f"best_of_select: ids {tuple(ids.shape)} / logp {tuple(logp.shape)} are not G * {n} matching rows")
+    is_eos = (ids[:, 1:] == eos_token_id).long()
+    live = (torch.cumsum(is_eos, -1) - is_eos) == 0                  # up to and including the first EOS
+    score = torch.where(live, logp[:, 1:].double(), torch.zeros((), dtype=torch.float64, device=logp.device)).sum(-1)
+    j = torch.argmax(score.view(-1, n), dim=1)                       # the first of equal maxima
+    rows = torch.arange(j.shape[0], device=ids.device) * n + j
+    return ids[rows], logp[rows], j
+
+
+@torch.no_grad()
+def generate_best_of(model, inputs, n, max_length=1024, temperature=1.0, top_k=0, top_p=1.0, seed=0, bad_token_ids=None,
+                     poll_every=64):
+    """n samples per segment (`generate_sample`), the most likely one kept: (ids [B, W], logp [B, W]).  Plain T5 only."""
+    if not (isinstance(n, int) and n >= 1):
+        raise ValueError(f"n must be an int >= 1, got {n!r}")
+    if model.VARIANT not in ("t5", "segmem_v1"):
+        raise ValueError("generate_best_of is for the plain T5 decode; the segment-memory chain decodes one sample per segment")
+    ids, logp = generate_sample(model, inputs, max_length, temperature, top_k, top_p, seed, n, bad_token_ids, True, poll_every)
+    ids, logp, _ = best_of_select(ids, logp, n, model.cfg["eos_token_id"])
+    return ids, logp
 
 
 def _pair(ids, logp, return_logprobs):
     return (ids, logp) if return_logprobs else ids
 
 
-def _generate(model, inputs, max_length, poll_every, bad_token_ids=None, return_logprobs=False):
-    """`return_logprobs`: every tensor of ids has a float twin cut, padded (0.0) and stacked the same way."""
+def _generate(model, inputs, max_length, poll_every, bad_token_ids=None, return_logprobs=False, sampling=None, n=1):
+    """`return_logprobs`: every tensor of ids has a float twin cut, padded (0.0) and stacked the same way.
+    `sampling` (a `Sampling`): the tokens are drawn; decode batch c of a plain T5 and segment i of a memory chain use
+    `seed + c` / `seed + i`.  `n` > 1 (plain T5, with `sampling`): n rows per segment, output [B * n, W]."""
     eng, cfg = model.engine, model.cfg
+    if not (isinstance(n, int) and 1 <= n <= MAX_DECODE_BATCH):
+        raise ValueError(f"num_return_sequences must be an int in 1..{MAX_DECODE_BATCH}, got {n!r}")
+    if n > 1 and (sampling is None or model.VARIANT not in ("t5", "segmem_v1")):
+        raise ValueError("num_return_sequences > 1 needs sampling and the plain T5 decode: the segment-memory chain "
+                         "decodes one sample per segment")
     if not inputs.is_cuda:
         raise RuntimeError("generate needs device tensors (no CPU fallback)")
     eng.prepare(False)
@@ -305,20 +406,24 @@ def _generate(model, inputs, max_length, poll_every, bad_token_ids=None, return_
     enc = eng.encode(inputs.float() if inputs.dtype not in (torch.float32, torch.bfloat16) else inputs)
     if model.VARIANT in ("t5", "segmem_v1"):      # T5SegMem.generate ignores the memory (t5_segmem.py:254-311)
         out = []
-        for b0 in range(0, B, MAX_DECODE_BATCH):
-            nb = min(MAX_DECODE_BATCH, B - b0)
+        per = MAX_DECODE_BATCH // n
+        for c, b0 in enumerate(range(0, B, per)):
+            ns = min(per, B - b0)                          # segments of this decode batch, n rows each
+            nb = ns * n
             dec = _decoder_for(model, nb, max_length, Le)
-            ckv = dec.cross_kv(enc.view(B, Le, d)[b0:b0 + nb].reshape(nb * Le, d), nb, Le)
+            enc_c = enc.view(B, Le, d)[b0:b0 + ns].reshape(ns * Le, d)
+            ckv = dec.cross_kv(enc_c, ns, Le) if n == 1 else dec.cross_kv_beam(enc_c, ns, n, Le)
             toks, done, fin, *lp = dec.run(ckv, nb, Le, max_length, poll_every, ban=dec.ban_mask(bad_token_ids),
-                                           return_logprobs=return_logprobs)
+                                           return_logprobs=return_logprobs,
+                                           sampling=sampling.shifted(c) if sampling else None)
             steps = (fin + 1) if fin >= 0 else max_length
             out.append((toks[:nb, :steps + 1].clone(), steps, lp[0][:nb, :steps + 1].clone() if lp else None))
         if len(out) == 1:
             return _pair(out[0][0], out[0][2], return_logprobs)
         # the reference stops when ALL rows are finished: pad shorter groups with pad_token_id
         steps = max(s for _, s, _ in out)
-        res = torch.full((B, steps + 1), cfg["pad_token_id"], dtype=torch.int64, device=inputs.device)
-        res_lp = torch.zeros(B, steps + 1, dtype=torch.float32, device=inputs.device) if return_logprobs else None
+        res = torch.full((B * n, steps + 1), cfg["pad_token_id"], dtype=torch.int64, device=inputs.device)
+        res_lp = torch.zeros(B * n, steps + 1, dtype=torch.float32, device=inputs.device) if return_logprobs else None
         r = 0
         for t, s, lp in out:
             res[r:r + t.shape[0], :s + 1] = t
@@ -342,7 +447,8 @@ def _generate(model, inputs, max_length, poll_every, bad_token_ids=None, return_
         cur = torch.cat([enc.view(B, Le, d)[i:i + 1], mem], 1).contiguous().view(Le + Ls, d)
         ckv = dec.cross_kv(cur, 1, Le + Ls)
         toks, done, fin, *lp = dec.run(ckv, 1, Le + Ls, max_length, poll_every, ban=dec.ban_mask(bad_token_ids),
-                                       return_logprobs=return_logprobs)
+                                       return_logprobs=return_logprobs,
+                                       sampling=sampling.shifted(i) if sampling else None)
         steps = (fin + 1) if fin >= 0 else max_length
         row = torch.zeros(1, max_length, dtype=torch.int64, device=inputs.device)
         n = min(steps + 1, max_length)                   # F.pad(..., max_length - len) truncates (:287-291)
@@ -363,14 +469,16 @@ def _memory(eng, seg_ids, B, L, Ls):
 
 
 @torch.no_grad()
-def generate_2(model, inputs, max_length=1024, poll_every=64, num_beams=1, return_logprobs=False):
+def generate_2(model, inputs, max_length=1024, poll_every=64, num_beams=1, return_logprobs=False, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0):
     """`T5SegMem.generate_2` (models/t5_segmem.py:172-252): segments one after the other; the previous
     segment's tokens go through the segment-memory encoder and its first `segmem_length` outputs are
     PREPENDED to the decoder's input embeddings.  With the KV cache that is a prefix fill: the memory
     rows are fed as decoder positions 0..Ls-1 (self-attention K/V only), tokens start at position Ls.
-    A stable prefix buffer keeps the captured step graph valid across segments.  No beam search here."""
+    A stable prefix buffer keeps the captured step graph valid across segments.  No beam search here.
+    `do_sample`: the token steps draw (segment i with `seed + i`), the prefix steps draw nothing."""
     if num_beams != 1:
         raise ValueError("generate_2 (memory-prefixed decode) has no beam search")
+    sampling = _sampling(do_sample, temperature, top_k, top_p, seed)
     eng, cfg = model.engine, model.cfg
     if not inputs.is_cuda:
         raise RuntimeError("generate_2 needs device tensors (no CPU fallback)")
@@ -391,7 +499,8 @@ def generate_2(model, inputs, max_length=1024, poll_every=64, num_beams=1, retur
             pre.copy_(eng.segmem(seg_ids, 1, max_length).float().view(1, Ls, d))
         ckv = dec.cross_kv(enc.view(B, Le, d)[i].contiguous(), 1, Le)
         toks, done, fin, *lp = dec.run(ckv, 1, Le, max_length, poll_every, prefix=pre if Ls else None,
-                                       return_logprobs=return_logprobs)
+                                       return_logprobs=return_logprobs,
+                                       sampling=sampling.shifted(i) if sampling else None)
         steps = (fin + 1) if fin >= 0 else max_length
         row = torch.zeros(1, max_length, dtype=torch.int64, device=inputs.device)
         n = min(steps + 1, max_length)
@@ -405,7 +514,7 @@ def generate_2(model, inputs, max_length=1024, poll_every=64, num_beams=1, retur
 
 @torch.no_grad()
 def generate_songs(model, songs, max_length=1024, poll_every=64, num_beams=1, length_penalty=1.0, bad_token_ids=None,
-                   return_logprobs=False):
+                   return_logprobs=False, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0):
     """Several recordings decoded in lockstep with the segment-memory models (V2 / V2WithPrev).
 
     The reference transcribes one recording at a time because segment i needs segment i-1's tokens
@@ -415,8 +524,13 @@ def generate_songs(model, songs, max_length=1024, poll_every=64, num_beams=1, le
     sequence).  `songs`: list of [n_seg_s, Le, 512] device tensors.  Returns a list of [n_seg_s, max_length]
     int64 tensors.  `num_beams` > 1: recording s is group s of a beam search (`generate_beam` per recording, in
     lockstep); `bad_token_ids` bans tokens in either mode.  The defaults are the greedy decode above.
-    `return_logprobs`: (list of ids, list of [n_seg_s, max_length] f32 log-probabilities), rows cut or zero-padded as the ids."""
+    `return_logprobs`: (list of ids, list of [n_seg_s, max_length] f32 log-probabilities), rows cut or zero-padded as the ids.
+    `do_sample` (greedy mode only): row s draws segment i with the counter (s, step) under `seed + i`; each recording's
+    memory chain carries its sampled tokens."""
     _check_beams(num_beams)
+    sampling = _sampling(do_sample, temperature, top_k, top_p, seed)
+    if sampling is not None and num_beams > 1:
+        raise ValueError("beam search does not sample: do_sample needs num_beams == 1")
     eng, cfg = model.engine, model.cfg
     if model.VARIANT not in ("segmem_v2", "segmem_v2_with_prev"):
         raise RuntimeError("generate_songs is for the segment-memory models; plain T5 batches segments directly")
@@ -427,7 +541,7 @@ def generate_songs(model, songs, max_length=1024, poll_every=64, num_beams=1, le
         out, out_lp = [], []
         for i in range(0, len(songs), per):
             part = generate_songs(model, songs[i:i + per], max_length, poll_every, num_beams, length_penalty, bad_token_ids,
-                                  return_logprobs)
+                                  return_logprobs, do_sample, temperature, top_k, top_p, seed)
             out += part[0] if return_logprobs else part
             out_lp += part[1] if return_logprobs else []
         return _pair(out, out_lp, return_logprobs)
@@ -463,7 +577,8 @@ def generate_songs(model, songs, max_length=1024, poll_every=64, num_beams=1, le
         else:
             ckv = dec.cross_kv(cur.view(B * (Le + Ls), d), B, Le + Ls)
             toks, done, fin, *lp = dec.run(ckv, B, Le + Ls, max_length, poll_every, ban=dec.ban_mask(bad_token_ids),
-                                           return_logprobs=return_logprobs)
+                                           return_logprobs=return_logprobs,
+                                           sampling=sampling.shifted(i) if sampling else None)
             rows = toks[:B, :max_length].clone()                           # finished rows are already pad(0)-filled
             rows_lp = lp[0][:B, :max_length].clone() if lp else None
             if done < max_length:                                          # all rows hit EOS early: the rest is stale
@@ -502,19 +617,23 @@ def _logp_rows(logp, max_length):
 
 @torch.no_grad()
 def generate_beam(model, inputs, num_beams=1, max_length=1024, length_penalty=1.0, bad_token_ids=None, poll_every=64,
-                  return_logprobs=False):
+                  return_logprobs=False, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0):
     """Beam search with optional single-token bans; the output contract of `generate` for the model's variant.
 
     Plain T5 / T5SegMem: [B, W] int64, W = min(longest best hypothesis + 1, 1 + max_length) over the batch: start
     token, tokens, EOS after a hypothesis shorter than 1 + max_length, pad (HF `BeamSearchScorer.finalize`).  Segment
     memory models: [n_seg, max_length], segments one after the other, each one's memory ids = the previous segment's
     best hypothesis cut or zero-padded to max_length.  `num_beams=1` is the greedy decode (with the ban); without a ban
-    it equals `generate` bit for bit."""
+    it equals `generate` bit for bit.  `do_sample` with `num_beams=1` draws the tokens (`generate`'s keywords); beam
+    search does not sample."""
     _check_beams(num_beams)
+    sampling = _sampling(do_sample, temperature, top_k, top_p, seed)
+    if sampling is not None and num_beams > 1:
+        raise ValueError("beam search does not sample: do_sample needs num_beams == 1")
     if not inputs.is_cuda:
         raise RuntimeError("generate_beam needs device tensors (no CPU fallback)")
     if num_beams == 1:
-        return _generate(model, inputs, max_length, poll_every, bad_token_ids, return_logprobs)
+        return _generate(model, inputs, max_length, poll_every, bad_token_ids, return_logprobs, sampling=sampling)
     eng, cfg = model.engine, model.cfg
     k = num_beams
     eng.prepare(False)

@@ -106,7 +106,7 @@ def load():
     return lib
 
 
-MIN_VERSION = 116
+MIN_VERSION = 117
 COUNTER_NAMES = ("gemm_nt_tile", "gemm_nt8", "gemm_nt_geglu", "tn_group", "tn8", "tn_tile", "attn_fwd", "attn_bwd",
                  "attn_bwd_onepass", "attn_f32", "tn_f32", "gemm_nt_splitk", "gemm_nt_addnorm", "gemm_nt_normbwd",
                  "gemm_nt_geglubwd", "attn_fwd_varlen", "attn_bwd_varlen")
@@ -920,6 +920,21 @@ def token_logprob(logits, targets, ignore_index=-100):
     _check(load().mrmt3_token_logprob(_p(logits), _p(targets), _p(out), rows, V, int(ignore_index), _stream()),
            "token_logprob")
     return out
+
+
+def sample_logits(logits, temperature=1.0, top_k=0, top_p=1.0, seed=0, step=0, row0=0, ban=None, return_logprobs=False):
+    """One draw per row of [rows, V] f32 logits by the decoder's sampling rule (mrmt3_sample_logits): row r
+    uses the counter (row0 + r, step).  `ban`: device [V] uint8 mask or None.  -> tokens [rows] int64, and with
+    `return_logprobs` the log-probability of each under the softmax of the logits after the ban."""
+    _dev(logits)
+    rows, V = logits.shape
+    assert logits.dtype == torch.float32 and logits.is_contiguous()
+    assert ban is None or (ban.dtype == torch.uint8 and ban.is_contiguous() and ban.numel() == V and ban.is_cuda)
+    tok = torch.empty(rows, device=logits.device, dtype=torch.int64)
+    lp = torch.empty(rows, device=logits.device, dtype=torch.float32) if return_logprobs else None
+    _check(load().mrmt3_sample_logits(_p(logits), rows, V, _p(ban), float(temperature), int(top_k), float(top_p), int(seed),
+                                      int(step), int(row0), _p(tok), _p(lp), _stream()), "sample_logits")
+    return (tok, lp) if return_logprobs else tok
 
 
 def lmhead_logprob(dec, w, targets, chunk_rows=None):
