@@ -385,6 +385,22 @@ int mrmt3_lmhead_ce_fwd_bwd(const void* dec, int ld_dec, const void* W, int ldw,
                             int d, int weighted, int inst_lo, int inst_hi, float grad_scale, void* workspace,
                             size_t workspace_bytes, int chunk_rows, void* stream);
 
+/* Label smoothing and the T5X z-loss in the same kernels.  Per scored row, with lse = logsumexp(l):
+ *   nll_i = lse - l[t],  u_i = lse - mean_j l[j],  r_i = (1 - label_smoothing) * nll_i + label_smoothing * u_i + z_loss * lse^2
+ * loss_dev is TWO doubles (zero both first): loss_dev[0] += sum_i w_i * r_i / denom (the objective), loss_dev[1] +=
+ * sum_i w_i * nll_i / denom (the plain NLL, what mrmt3_ce_fwd_bwd returns);
+ * dlogits = grad_scale * w_i / denom * (softmax_j * (1 + 2 * z_loss * lse) - (1 - label_smoothing) * onehot_j - label_smoothing / V).
+ * 0 <= label_smoothing < 1 and z_loss >= 0, anything else is MRMT3_ERR_INVALID_ARG.  Everything else (targets, weights,
+ * denom_dev, the chunk loop and its workspace) as for the two entry points above, which are unchanged. */
+int mrmt3_ce_fwd_bwd_reg(const float* logits, const int64_t* targets, const float* denom_dev, float label_smoothing,
+                         float z_loss, double* loss_dev, void* dlogits, int dl_dtype, int rows, int V, int weighted,
+                         int inst_lo, int inst_hi, float grad_scale, void* stream);
+int mrmt3_lmhead_ce_fwd_bwd_reg(const void* dec, int ld_dec, const void* W, int ldw, const int64_t* targets,
+                                const float* denom_dev, float label_smoothing, float z_loss, double* loss_dev,
+                                void* dlogits, int dl_dtype, int rows, int V, int d, int weighted, int inst_lo,
+                                int inst_hi, float grad_scale, void* workspace, size_t workspace_bytes, int chunk_rows,
+                                void* stream);
+
 /* Teacher-forced scoring, forward only.  mrmt3_token_logprob: out[r] = log softmax(logits[r])[targets[r]], or
  * 0.0 where targets[r] == ignore_index (a target outside [0, V) gives NaN); logits [rows][V] f32, V <= 2048 (an error
  * beyond: the row lives in one wave's registers).  One wave per row: the

@@ -52,6 +52,12 @@ int mrmt3_diag_env(const char* name);
       return MRMT3_ERR_INVALID_ARG;                  \
     }                                                \
   } while (0)
+// the options of the *_reg cross-entropy entry points: 0 <= label_smoothing < 1, z_loss >= 0 and finite (a NaN fails both)
+#define MR_CHECK_CE_OPTIONS(who, eps, z)                                                                          \
+  do {                                                                                                            \
+    MR_CHECK_ARG((eps) >= 0.f && (eps) < 1.f, "%s: label_smoothing must be in [0, 1), got %g", who, (double)(eps)); \
+    MR_CHECK_ARG((z) >= 0.f && (z) <= 3.4e38f, "%s: z_loss must be finite and >= 0, got %g", who, (double)(z));   \
+  } while (0)
 #define MR_CHECK_LAUNCH(name)                                                       \
   do {                                                                              \
     hipError_t e_ = hipGetLastError();                                              \

@@ -32,6 +32,32 @@ extern "C" int mrmt3_lmhead_ce_fwd_bwd(const void* dec, int ld_dec, const void* 
   return MRMT3_OK;
 }
 
+// The same chunk loop with mrmt3_ce_fwd_bwd_reg (label smoothing + z-loss): loss_dev[0] accumulates the objective,
+// loss_dev[1] the plain NLL.
+extern "C" int mrmt3_lmhead_ce_fwd_bwd_reg(const void* dec, int ld_dec, const void* W, int ldw, const int64_t* targets,
+                                           const float* denom_dev, float label_smoothing, float z_loss, double* loss_dev,
+                                           void* dlogits, int dl_dtype, int rows, int V, int d, int weighted, int inst_lo,
+                                           int inst_hi, float grad_scale, void* workspace, size_t workspace_bytes,
+                                           int chunk_rows, void* stream) {
+  MR_CHECK_CE_OPTIONS("lmhead_ce_reg", label_smoothing, z_loss);
+  MR_CHECK_ARG(dec && W && targets && denom_dev && loss_dev && workspace, "lmhead_ce_reg: null pointer");
+  MR_CHECK_ARG(rows > 0 && V > 0 && d > 0 && chunk_rows > 0, "lmhead_ce_reg: bad sizes");
+  MR_CHECK_ARG(workspace_bytes >= (size_t)(chunk_rows < rows ? chunk_rows : rows) * V * sizeof(float),
+               "lmhead_ce_reg: workspace smaller than one chunk of logits");
+  const size_t dl_elt = dl_dtype == MRMT3_BF16 ? 2 : 4;
+  for (int r0 = 0; r0 < rows; r0 += chunk_rows) {
+    const int n = rows - r0 < chunk_rows ? rows - r0 : chunk_rows;
+    int rc = mrmt3_gemm_nt((const char*)dec + (size_t)r0 * ld_dec * 2, ld_dec, W, ldw, workspace, V, n, V, d, MRMT3_BF16,
+                           MRMT3_F32, 0, stream);
+    if (rc != MRMT3_OK) return rc;
+    rc = mrmt3_ce_fwd_bwd_reg((const float*)workspace, targets + r0, denom_dev, label_smoothing, z_loss, loss_dev,
+                              dlogits ? (char*)dlogits + (size_t)r0 * V * dl_elt : nullptr, dl_dtype, n, V, weighted,
+                              inst_lo, inst_hi, grad_scale, stream);
+    if (rc != MRMT3_OK) return rc;
+  }
+  return MRMT3_OK;
+}
+
 // Teacher-forced scoring: out[r] = log p(targets[r]) under softmax(dec[r] . W^T), 0 where the target is -100.  The same
 // chunk loop with mrmt3_token_logprob in place of the loss kernel; forward only, operands bf16 or f32 (`dtype`).
 extern "C" int mrmt3_lmhead_logprob(const void* dec, int ld_dec, const void* W, int ldw, const int64_t* targets, float* out,

@@ -881,12 +881,16 @@ extern "C" int mrmt3_ce_count(const int64_t* targets, int rows, int weighted, in
   return MRMT3_OK;
 }
 
-template <typename TD>
+// REG (label smoothing eps + z-loss z): per scored row r = (1-eps)*nll + eps*(lse - mean_j l[j]) + z*lse^2;
+// loss[0] receives the objective sum_i w_i r_i / denom, loss[1] the plain NLL, and the gradient is
+// gs * (p_j*(1 + 2 z lse) - (1-eps)[j==t] - eps/V).  REG = false is the kernel of before, statement for statement: eps
+// and z are then never read and loss[1] never written.
+template <typename TD, bool REG>
 __global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ logits, const int64_t* __restrict__ targets,
                                                  const float* __restrict__ denom, double* __restrict__ loss,
                                                  TD* __restrict__ dlogits, int rows, int V, int weighted, int lo,
-                                                 int hi, float grad_scale) {
-  __shared__ float red[8];
+                                                 int hi, float grad_scale, float eps, float z) {
+  __shared__ float red[REG ? 12 : 8];
   const int row = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float* lp = logits + (size_t)row * V;
@@ -895,11 +899,12 @@ __global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ logit
   ce_weights(t, weighted, lo, hi, &w, &n);
   TD* dp = dlogits ? dlogits + (size_t)row * V : nullptr;
   if (w == 0.f) {
-    if (dp) for (int c = tid * 4; c < V; c += 1024) { float z[4] = {0.f, 0.f, 0.f, 0.f}; store4<TD>(dp + c, z); }
+    if (dp) for (int c = tid * 4; c < V; c += 1024) { float z4[4] = {0.f, 0.f, 0.f, 0.f}; store4<TD>(dp + c, z4); }
     return;
   }
-  // one pass over the row: running (max, sum of exp) per thread, merged across the workgroup
-  float mx = -INFINITY, se = 0.f;
+  // one pass over the row: running (max, sum of exp) per thread, merged across the workgroup (REG: and the running sum
+  // of the raw logits next to them)
+  float mx = -INFINITY, se = 0.f, sm = 0.f;
   for (int c = tid * 4; c < V; c += 1024) {
     float v[4];
     load4<float>(lp + c, v);
@@ -907,10 +912,16 @@ __global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ logit
     const float mn = fmaxf(mx, m4);
     se = se * expf(mx - mn) + ((expf(v[0] - mn) + expf(v[1] - mn)) + (expf(v[2] - mn) + expf(v[3] - mn)));
     mx = mn;
+    if constexpr (REG) sm += (v[0] + v[1]) + (v[2] + v[3]);
   }
   const float wmx = wave_max(mx);
   se = wave_sum(mx == -INFINITY ? 0.f : se * expf(mx - wmx));
-  if (lane == 0) { red[wave] = wmx; red[4 + wave] = se; }
+  if constexpr (REG) sm = wave_sum(sm);
+  if (lane == 0) {
+    red[wave] = wmx;
+    red[4 + wave] = se;
+    if constexpr (REG) red[8 + wave] = sm;
+  }
   __syncthreads();
   mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
   se = 0.f;
@@ -918,16 +929,33 @@ __global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ logit
   for (int w4 = 0; w4 < 4; ++w4) se += red[4 + w4] * expf(red[w4] - mx);
   const float lse = mx + logf(se);
   const float inv_den = 1.f / denom[0];
-  if (tid == 0) atomicAdd(loss, (double)(w * (lse - lp[t]) * inv_den));
+  if constexpr (REG) {
+    if (tid == 0) {
+      const float nll = lse - lp[t];
+      const float u = lse - ((red[8] + red[9]) + (red[10] + red[11])) * (1.f / (float)V);
+      const float r = (1.f - eps) * nll + eps * u + z * lse * lse;
+      atomicAdd(loss, (double)(w * r * inv_den));
+      atomicAdd(loss + 1, (double)(w * nll * inv_den));
+    }
+  } else {
+    if (tid == 0) atomicAdd(loss, (double)(w * (lse - lp[t]) * inv_den));
+  }
   if (dp) {
     const float gs = w * inv_den * grad_scale;
+    const float pz = REG ? 1.f + 2.f * z * lse : 1.f;           // d(lse + z lse^2)/d lse
+    const float hot = REG ? 1.f - eps : 1.f, uni = REG ? eps / (float)V : 0.f;
     for (int c = tid * 4; c < V; c += 1024) {
       float v[4];
       load4<float>(lp + c, v);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float p = expf(v[e] - lse);
-        if (c + e == t) p -= 1.f;
+        if constexpr (REG) {
+          p = p * pz - uni;
+          if (c + e == t) p -= hot;
+        } else {
+          if (c + e == t) p -= 1.f;
+        }
         v[e] = p * gs;
       }
       store4<TD>(dp + c, v);
@@ -946,17 +974,19 @@ static inline int ce_rows_per_wave(int rows) {
   int r = rows / (4 * 2048);
   return r < 1 ? 1 : (r > 16 ? 16 : r);
 }
-template <typename TD, int NV>
+// REG as in ce_kernel: the row sum of the raw logits is one more per-lane partial of the load pass and one more wave_sum;
+// the workgroup adds two scalars (objective, NLL) instead of one.
+template <typename TD, int NV, bool REG>
 __global__ __launch_bounds__(256) void ce_wave_kernel(const float* __restrict__ logits, const int64_t* __restrict__ targets,
                                                       const float* __restrict__ denom, double* __restrict__ loss,
                                                       TD* __restrict__ dlogits, int rows, int weighted, int lo, int hi,
-                                                      float grad_scale, int rpw) {
+                                                      float grad_scale, int rpw, float eps, float z) {
   constexpr int V = NV * 256;
-  __shared__ float part[4];
+  __shared__ float part[REG ? 8 : 4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int row0 = (blockIdx.x * 4 + wave) * rpw;
   const float inv_den = 1.f / denom[0];
-  float acc = 0.f;
+  float acc = 0.f, acc_nll = 0.f;
   for (int row = row0; row < min(row0 + rpw, rows); ++row) {
     const float* lp = logits + (size_t)row * V;
     const int64_t t = targets[row];
@@ -965,21 +995,23 @@ __global__ __launch_bounds__(256) void ce_wave_kernel(const float* __restrict__ 
     TD* dp = dlogits ? dlogits + (size_t)row * V : nullptr;
     if (w == 0.f) {
       if (dp) {
-        const float z[4] = {0.f, 0.f, 0.f, 0.f};
+        const float z4[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int i = 0; i < NV; ++i) store4<TD>(dp + (i * 64 + lane) * 4, z);
+        for (int i = 0; i < NV; ++i) store4<TD>(dp + (i * 64 + lane) * 4, z4);
       }
       continue;
     }
     float v[NV][4];
-    float mx = -INFINITY;
+    float mx = -INFINITY, sm = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       load4<float>(lp + (i * 64 + lane) * 4, v[i]);
       mx = fmaxf(mx, fmaxf(fmaxf(v[i][0], v[i][1]), fmaxf(v[i][2], v[i][3])));
+      if constexpr (REG) sm += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
     }
     const float zt = lp[t];
     mx = wave_max(mx);
+    if constexpr (REG) sm = wave_sum(sm);
     float se = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i)
@@ -990,40 +1022,67 @@ __global__ __launch_bounds__(256) void ce_wave_kernel(const float* __restrict__ 
       }
     se = wave_sum(se);
     const float lse = mx + logf(se);
-    acc += w * (lse - zt) * inv_den;
+    if constexpr (REG) {
+      const float nll = lse - zt;
+      const float u = lse - sm * (1.f / (float)V);
+      acc += w * ((1.f - eps) * nll + eps * u + z * lse * lse) * inv_den;
+      acc_nll += w * nll * inv_den;
+    } else {
+      acc += w * (lse - zt) * inv_den;
+    }
     if (dp) {
-      const float gs = w * inv_den * grad_scale / se;
+      if constexpr (REG) {
+        const float g0 = w * inv_den * grad_scale;
+        const float gs = g0 * (1.f + 2.f * z * lse) / se;        // v * gs = g0 * p_j * (1 + 2 z lse)
+        const float hot = g0 * (1.f - eps), uni = g0 * (eps / (float)V);
 #pragma unroll
-      for (int i = 0; i < NV; ++i) {
-        const int c = (i * 64 + lane) * 4;
-        float g[4];
+        for (int i = 0; i < NV; ++i) {
+          const int c = (i * 64 + lane) * 4;
+          float g[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) g[e] = v[i][e] * gs - ((c + e == t) ? w * inv_den * grad_scale : 0.f);
-        store4<TD>(dp + c, g);
+          for (int e = 0; e < 4; ++e) g[e] = (v[i][e] * gs - uni) - ((c + e == t) ? hot : 0.f);
+          store4<TD>(dp + c, g);
+        }
+      } else {
+        const float gs = w * inv_den * grad_scale / se;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+          const int c = (i * 64 + lane) * 4;
+          float g[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) g[e] = v[i][e] * gs - ((c + e == t) ? w * inv_den * grad_scale : 0.f);
+          store4<TD>(dp + c, g);
+        }
       }
     }
   }
-  if (lane == 0) part[wave] = acc;
+  if (lane == 0) {
+    part[wave] = acc;
+    if constexpr (REG) part[4 + wave] = acc_nll;
+  }
   __syncthreads();
   if (threadIdx.x == 0) {
     // the loss scalar is a DOUBLE: the order in which the workgroups' sums arrive perturbs it at 1e-16, far below the
     // f32 value that is logged — two runs log the same float (a float accumulator wandered by a few ulp per run)
     const double tot = ((double)part[0] + (double)part[1]) + ((double)part[2] + (double)part[3]);
     if (tot != 0.0) atomicAdd(loss, tot);
+    if constexpr (REG) {
+      const double nll = ((double)part[4] + (double)part[5]) + ((double)part[6] + (double)part[7]);
+      if (nll != 0.0) atomicAdd(loss + 1, nll);
+    }
   }
 }
 
-extern "C" int mrmt3_ce_fwd_bwd(const float* logits, const int64_t* targets, const float* denom_dev, double* loss_dev,
-                                void* dlogits, int dl_dtype, int rows, int V, int weighted, int inst_lo,
-                                int inst_hi, float grad_scale, void* stream) {
-  MR_CHECK_ARG(logits && targets && denom_dev && loss_dev && rows > 0 && V % 4 == 0, "ce_fwd_bwd: bad args");
-  hipStream_t s = (hipStream_t)stream;
+template <bool REG>
+static int ce_launch(const float* logits, const int64_t* targets, const float* denom_dev, double* loss_dev, void* dlogits,
+                     int dl_dtype, int rows, int V, int weighted, int inst_lo, int inst_hi, float grad_scale, float eps,
+                     float z, hipStream_t s, const char* name) {
   if (V == 1536 || V == 1024 || V == 2048 || V == 512) {
     const int rpw = ce_rows_per_wave(rows);
     dim3 grid((unsigned)ceil_div(rows, 4 * rpw)), block(256);
-#define CEW(TD, NV)                                                                                              \
-  hipLaunchKernelGGL((ce_wave_kernel<TD, NV>), grid, block, 0, s, logits, targets, denom_dev, loss_dev, (TD*)dlogits, \
-                     rows, weighted, inst_lo, inst_hi, grad_scale, rpw)
+#define CEW(TD, NV)                                                                                                    \
+  hipLaunchKernelGGL((ce_wave_kernel<TD, NV, REG>), grid, block, 0, s, logits, targets, denom_dev, loss_dev, (TD*)dlogits, \
+                     rows, weighted, inst_lo, inst_hi, grad_scale, rpw, eps, z)
 #define CEV(TD)                                  \
   do {                                           \
     if (V == 1536) CEW(TD, 6);                   \
@@ -1035,17 +1094,34 @@ extern "C" int mrmt3_ce_fwd_bwd(const float* logits, const int64_t* targets, con
     else CEV(float);
 #undef CEV
 #undef CEW
-    MR_CHECK_LAUNCH("ce_fwd_bwd");
+    MR_CHECK_LAUNCH(name);
     return MRMT3_OK;
   }
   if (dl_dtype == MRMT3_BF16)
-    hipLaunchKernelGGL(ce_kernel<bf16_t>, dim3(rows), dim3(256), 0, s, logits, targets, denom_dev, loss_dev,
-                       (bf16_t*)dlogits, rows, V, weighted, inst_lo, inst_hi, grad_scale);
+    hipLaunchKernelGGL((ce_kernel<bf16_t, REG>), dim3(rows), dim3(256), 0, s, logits, targets, denom_dev, loss_dev,
+                       (bf16_t*)dlogits, rows, V, weighted, inst_lo, inst_hi, grad_scale, eps, z);
   else
-    hipLaunchKernelGGL(ce_kernel<float>, dim3(rows), dim3(256), 0, s, logits, targets, denom_dev, loss_dev,
-                       (float*)dlogits, rows, V, weighted, inst_lo, inst_hi, grad_scale);
-  MR_CHECK_LAUNCH("ce_fwd_bwd");
+    hipLaunchKernelGGL((ce_kernel<float, REG>), dim3(rows), dim3(256), 0, s, logits, targets, denom_dev, loss_dev,
+                       (float*)dlogits, rows, V, weighted, inst_lo, inst_hi, grad_scale, eps, z);
+  MR_CHECK_LAUNCH(name);
   return MRMT3_OK;
+}
+
+extern "C" int mrmt3_ce_fwd_bwd(const float* logits, const int64_t* targets, const float* denom_dev, double* loss_dev,
+                                void* dlogits, int dl_dtype, int rows, int V, int weighted, int inst_lo,
+                                int inst_hi, float grad_scale, void* stream) {
+  MR_CHECK_ARG(logits && targets && denom_dev && loss_dev && rows > 0 && V % 4 == 0, "ce_fwd_bwd: bad args");
+  return ce_launch<false>(logits, targets, denom_dev, loss_dev, dlogits, dl_dtype, rows, V, weighted, inst_lo, inst_hi,
+                          grad_scale, 0.f, 0.f, (hipStream_t)stream, "ce_fwd_bwd");
+}
+
+extern "C" int mrmt3_ce_fwd_bwd_reg(const float* logits, const int64_t* targets, const float* denom_dev, float label_smoothing,
+                                    float z_loss, double* loss_dev, void* dlogits, int dl_dtype, int rows, int V,
+                                    int weighted, int inst_lo, int inst_hi, float grad_scale, void* stream) {
+  MR_CHECK_CE_OPTIONS("ce_fwd_bwd_reg", label_smoothing, z_loss);
+  MR_CHECK_ARG(logits && targets && denom_dev && loss_dev && rows > 0 && V > 0 && V % 4 == 0, "ce_fwd_bwd_reg: bad args");
+  return ce_launch<true>(logits, targets, denom_dev, loss_dev, dlogits, dl_dtype, rows, V, weighted, inst_lo, inst_hi,
+                         grad_scale, label_smoothing, z_loss, (hipStream_t)stream, "ce_fwd_bwd_reg");
 }
 
 // ------------------------------------------------------------------------------------------------

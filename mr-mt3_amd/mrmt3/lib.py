@@ -106,7 +106,7 @@ def load():
     return lib
 
 
-MIN_VERSION = 117
+MIN_VERSION = 118
 COUNTER_NAMES = ("gemm_nt_tile", "gemm_nt8", "gemm_nt_geglu", "tn_group", "tn8", "tn_tile", "attn_fwd", "attn_bwd",
                  "attn_bwd_onepass", "attn_f32", "tn_f32", "gemm_nt_splitk", "gemm_nt_addnorm", "gemm_nt_normbwd",
                  "gemm_nt_geglubwd", "attn_fwd_varlen", "attn_bwd_varlen")
@@ -857,20 +857,47 @@ def dropmask_cast(dx, p=0.0, seed=0, stream_id=0, step=None, out_dtype=torch.bfl
     return out
 
 
+def ce_options(label_smoothing=0.0, z_loss=0.0):
+    """Validate the loss options (host only) -> (on, label_smoothing, z_loss) as floats: 0 <= label_smoothing < 1 (the
+    keyword of torch.nn.CrossEntropyLoss), z_loss >= 0 and finite (T5X's z_loss); `on` iff either is non-zero."""
+    out = []
+    for name, val in (("label_smoothing", label_smoothing), ("z_loss", z_loss)):
+        if isinstance(val, bool) or not isinstance(val, (int, float)):
+            raise ValueError("%s must be a number, got %r" % (name, val))
+        out.append(float(val))
+    eps, z = out
+    if not 0.0 <= eps < 1.0:
+        raise ValueError("label_smoothing must be in [0, 1), got %r" % (label_smoothing,))
+    if not 0.0 <= z < float("inf"):
+        raise ValueError("z_loss must be finite and >= 0, got %r" % (z_loss,))
+    return (eps != 0.0 or z != 0.0), eps, z
+
+
 def cross_entropy(logits, targets, want_grad=True, grad_dtype=torch.bfloat16, weighted=False, inst_lo=1135,
-                  inst_hi=1262, grad_scale=1.0):
-    """Returns (loss_dev[1] f32 tensor, dlogits or None).  No host sync."""
+                  inst_hi=1262, grad_scale=1.0, label_smoothing=0.0, z_loss=0.0, return_nll=False):
+    """Returns (loss_dev[1] f32 tensor, dlogits or None).  No host sync.  With label_smoothing / z_loss the
+    first element is the regularised objective, whose gradient dlogits is; `return_nll=True` appends the plain NLL (with
+    both options off the loss itself, from the unchanged mrmt3_ce_fwd_bwd)."""
+    reg, eps, z = ce_options(label_smoothing, z_loss)
     _dev(logits, targets)
     rows, V = logits.shape
-    acc = torch.zeros(2, device=logits.device, dtype=torch.float64)  # [loss (double accumulator), denom (f32 in its first 4 bytes)]
-    den = C.c_void_p(acc.data_ptr() + 8)
+    # [loss (double accumulator), denom (f32 in its first 4 bytes)]; with the options on [objective, nll, denom]
+    acc = torch.zeros(3 if reg else 2, device=logits.device, dtype=torch.float64)
+    den = C.c_void_p(acc.data_ptr() + (16 if reg else 8))
     lib = load()
     _check(lib.mrmt3_ce_count(_p(targets), rows, int(weighted), inst_lo, inst_hi, den, _stream()), "ce_count")
     dl = torch.empty(rows, V, device=logits.device, dtype=grad_dtype) if want_grad else None
+    if reg:
+        _check(lib.mrmt3_ce_fwd_bwd_reg(_p(logits), _p(targets), den, eps, z, _p(acc), _p(dl),
+                                        _dt(dl) if dl is not None else F32, rows, V, int(weighted), inst_lo, inst_hi,
+                                        grad_scale, _stream()), "ce_fwd_bwd_reg")
+        both = acc[0:2].float()
+        return (both[0:1], dl, both[1:2]) if return_nll else (both[0:1], dl)
     _check(lib.mrmt3_ce_fwd_bwd(_p(logits), _p(targets), den, _p(acc), _p(dl),
                                 _dt(dl) if dl is not None else F32, rows, V, int(weighted), inst_lo, inst_hi,
                                 grad_scale, _stream()), "ce_fwd_bwd")
-    return acc[0:1].float(), dl
+    loss = acc[0:1].float()
+    return (loss, dl, loss) if return_nll else (loss, dl)
 
 
 def ce_chunk_rows() -> int:
@@ -886,9 +913,11 @@ def ce_chunk_rows() -> int:
 
 
 def lmhead_cross_entropy(dec, w, targets, want_grad=True, grad_dtype=torch.bfloat16, weighted=False, inst_lo=1135,
-                         inst_hi=1262, grad_scale=1.0, chunk_rows=None):
+                         inst_hi=1262, grad_scale=1.0, chunk_rows=None, label_smoothing=0.0, z_loss=0.0, return_nll=False):
     """lm_head + CE fused over row chunks (mrmt3_lmhead_ce_fwd_bwd): dec [rows, d] bf16, w [V, d] bf16 ->
-    (loss_dev[1] f32, dlogits [rows, V] or None).  The f32 logits only ever exist one chunk at a time, in a workspace."""
+    (loss_dev[1] f32, dlogits [rows, V] or None).  The f32 logits only ever exist one chunk at a time, in a workspace.
+    label_smoothing / z_loss / return_nll as for cross_entropy (mrmt3_lmhead_ce_fwd_bwd_reg when either option is on)."""
+    reg, eps, z = ce_options(label_smoothing, z_loss)
     _dev(dec, w, targets)
     rows, d = dec.shape
     V = w.shape[0]
@@ -897,17 +926,26 @@ def lmhead_cross_entropy(dec, w, targets, want_grad=True, grad_dtype=torch.bfloa
         # 65 536 rows = 403 MB of f32 logits in the workspace: the 64-segment step in ONE chunk (25.41 -> 25.32 ms against
         # four chunks of 16 384, same box); larger batches still go chunk by chunk (MRMT3_CE_CHUNK)
         chunk_rows = ce_chunk_rows()
-    acc = torch.zeros(2, device=dec.device, dtype=torch.float64)  # [loss (double accumulator), denom (f32 in its first 4 bytes)]
-    den = C.c_void_p(acc.data_ptr() + 8)
+    # [loss (double accumulator), denom (f32 in its first 4 bytes)]; with the options on [objective, nll, denom]
+    acc = torch.zeros(3 if reg else 2, device=dec.device, dtype=torch.float64)
+    den = C.c_void_p(acc.data_ptr() + (16 if reg else 8))
     lib = load()
     _check(lib.mrmt3_ce_count(_p(targets), rows, int(weighted), inst_lo, inst_hi, den, _stream()), "ce_count")
     dl = torch.empty(rows, V, device=dec.device, dtype=grad_dtype) if want_grad else None
     ws = workspace(min(rows, chunk_rows) * V * 4, dec.device)
+    if reg:
+        _check(lib.mrmt3_lmhead_ce_fwd_bwd_reg(_p(dec), dec.stride(0), _p(w), w.stride(0), _p(targets), den, eps, z,
+                                               _p(acc), _p(dl), _dt(dl) if dl is not None else F32,
+                                               rows, V, d, int(weighted), inst_lo, inst_hi, grad_scale, _p(ws), ws.numel(),
+                                               chunk_rows, _stream()), "lmhead_ce_fwd_bwd_reg")
+        both = acc[0:2].float()
+        return (both[0:1], dl, both[1:2]) if return_nll else (both[0:1], dl)
     _check(lib.mrmt3_lmhead_ce_fwd_bwd(_p(dec), dec.stride(0), _p(w), w.stride(0), _p(targets),
                                        den, _p(acc), _p(dl), _dt(dl) if dl is not None else F32,
                                        rows, V, d, int(weighted), inst_lo, inst_hi, grad_scale, _p(ws), ws.numel(),
                                        chunk_rows, _stream()), "lmhead_ce_fwd_bwd")
-    return acc[0:1].float(), dl
+    loss = acc[0:1].float()
+    return (loss, dl, loss) if return_nll else (loss, dl)
 
 
 def token_logprob(logits, targets, ignore_index=-100):

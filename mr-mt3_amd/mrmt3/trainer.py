@@ -64,6 +64,13 @@ A skipped step (non-finite norm under skip_nonfinite) leaves P, M, V and the sha
 it counts ATTEMPTED optimizer steps and stays equal to host_step, so the dropout salt moves on and checkpoints need no new
 field (AdamW's bias correction counts the skipped step: negligible after warm-up).  With all four off nothing changes:
 the same calls, graphs and launches as before.
+
+Label smoothing and z-loss (`label_smoothing`, `z_loss`).  With either non-zero the CE of the training step is
+mrmt3_ce_fwd_bwd_reg / mrmt3_lmhead_ce_fwd_bwd_reg: the objective (1-eps)*nll + eps*(lse - mean logit) + z*lse^2 per scored
+row, its gradient, and the plain NLL beside it.  Both are by-value launch arguments fixed at construction: they are part of
+the captured step and of no signature.  `train_step` returns the objective (`last_loss`), `last_nll` is the plain NLL; both
+are handled alike (device scalars, one per micro-batch, reduced over ranks).  `eval_loss` stays the plain NLL.  With both
+zero the old entry points run — the same launches as before — and `last_nll` is `last_loss`.
 """
 from __future__ import annotations
 
@@ -120,7 +127,7 @@ class _CapturedStep:
 
     def __init__(self):
         self.segments, self.tail = [], None
-        self.inputs = self.labels = self.prev = self.loss = None
+        self.inputs = self.labels = self.prev = self.loss = self.nll = None
 
 
 class Trainer:
@@ -128,7 +135,9 @@ class Trainer:
                  weight_decay: float = 0.01, weighted_loss: bool = False, layers_per_bucket: int = 4,
                  graph: bool = None, grad_exchange_dtype=None, pack_targets: bool = None,
                  accumulate_grad_batches: int = 1, gradient_clip_val=None, gradient_clip_algorithm: str = "norm",
-                 skip_nonfinite: bool = False, track_grad_norm: bool = False):
+                 skip_nonfinite: bool = False, track_grad_norm: bool = False, label_smoothing: float = 0.0,
+                 z_loss: float = 0.0):
+        self.loss_reg, self.label_smoothing, self.z_loss = lib.ce_options(label_smoothing, z_loss)
         self.clip_on, self._max_norm, self._clip_value, self.skip_nonfinite = clip_options(
             gradient_clip_val, gradient_clip_algorithm, skip_nonfinite, track_grad_norm)
         n_acc = int(accumulate_grad_batches)
@@ -170,6 +179,7 @@ class Trainer:
         if self.world > 1:   # C2: identical replicas
             dist.broadcast(self.flat.P, src=0)
         self.last_loss = None
+        self.last_nll = None             # the plain NLL of the last (micro-)batch; `last_loss` itself when no loss option is on
         # norm / clip coefficient / skip flag of the last optimizer step, the skip counter and the norm kernel's partials:
         # device memory the captured tail reads and writes, allocated here, never inside a capture
         self._clip_stat = self._skipped_dev = self._clip_ws = None
@@ -230,7 +240,8 @@ class Trainer:
     def _step_body(self, inputs, labels, targets_prev, audio, cut=None, tcap=None, phase=None):
         """Enqueues one optimizer step, or with accumulation one micro-batch of it (`phase`, see _phase).  `cut(bucket_indices)`
         is called where a gradient bucket is complete (only when collectives will run, only in a step that ends with AdamW):
-        under capture it closes the current graph segment.  tcap: packed decoder rows."""
+        under capture it closes the current graph segment.  tcap: packed decoder rows.  Returns (objective, plain NLL): one
+        tensor twice when no loss option is on."""
         eng, flat = self.engine, self.flat
         eng.reset_deferred()                                 # nothing of an aborted capture / failed step leaks into this one
         eng._stream_ctr = 0                                  # dropout site ids are per-step (step_dev salts them)
@@ -240,12 +251,15 @@ class Trainer:
         if eng.dt == torch.bfloat16:
             dec, tape = eng.forward(mel, labels, targets_prev, training=True, need_grad=True, want_logits=False, pack=plan)
             # lm_head + CE over row chunks: the f32 logits exist one chunk at a time in a cache-sized workspace
-            loss, dl = lib.lmhead_cross_entropy(dec, eng.W("lm_head"), targets, want_grad=True,
-                                                grad_dtype=torch.bfloat16, weighted=self.weighted)
+            loss, dl, nll = lib.lmhead_cross_entropy(dec, eng.W("lm_head"), targets, want_grad=True,
+                                                     grad_dtype=torch.bfloat16, weighted=self.weighted,
+                                                     label_smoothing=self.label_smoothing, z_loss=self.z_loss,
+                                                     return_nll=True)
         else:                                                # fp32 engine (`precision: 32`): exact-f32 lm_head, then CE
             logits, tape = eng.forward(mel, labels, targets_prev, training=True, need_grad=True, pack=plan)
-            loss, dl = lib.cross_entropy(logits.reshape(-1, logits.shape[-1]), targets, want_grad=True,
-                                         grad_dtype=torch.float32, weighted=self.weighted)
+            loss, dl, nll = lib.cross_entropy(logits.reshape(-1, logits.shape[-1]), targets, want_grad=True,
+                                              grad_dtype=torch.float32, weighted=self.weighted,
+                                              label_smoothing=self.label_smoothing, z_loss=self.z_loss, return_nll=True)
         if phase in (None, "first"):
             flat.G.zero_()
         self.buckets.reset()
@@ -270,7 +284,7 @@ class Trainer:
             self._optimizer_tail()
         if self.accumulate > 1:
             lib.counter_add(self.salt_dev, 1)               # the next micro-batch draws other masks
-        return loss
+        return loss, nll
 
     def _optimizer_tail(self):
         """AdamW on the exchanged G; with clipping / norm tracking / the non-finite guard on, the device-side norm first."""
@@ -297,7 +311,8 @@ class Trainer:
     def train_step(self, inputs, labels, targets_prev=None, audio: bool = False):
         """One optimizer step, or with accumulate_grad_batches = N > 1 one micro-batch (the optimizer steps after every N-th).
         `inputs` is mel [B,Le,512] or, with audio=True, raw audio [B,n].  Returns the (device, un-synchronised) mean loss of
-        this rank over this (micro-)batch, undivided by N."""
+        this rank over this (micro-)batch, undivided by N: the objective whose gradient was taken.  With label_smoothing /
+        z_loss on, `last_nll` holds the plain NLL of the same (micro-)batch."""
         m, eng = self.model, self.engine
         m.train()
         if self.buckets.active and not self._collective_stream_checked:
@@ -318,9 +333,9 @@ class Trainer:
             labels = labels.to(self.flat.G.device)          # CPU labels: lengths taken above, copied once
         phase = self._phase()
         if self.use_graph:
-            loss = self._graph_step(inputs, labels, targets_prev, audio, tcap, phase)
+            loss, nll = self._graph_step(inputs, labels, targets_prev, audio, tcap, phase)
         else:
-            loss = self._step_body(inputs, labels, targets_prev, audio, tcap=tcap, phase=phase)
+            loss, nll = self._step_body(inputs, labels, targets_prev, audio, tcap=tcap, phase=phase)
         self._micro += 1
         if self._micro == self.accumulate:
             self._micro = 0
@@ -329,7 +344,12 @@ class Trainer:
             loss = loss.clone()
             dist.all_reduce(loss, op=dist.ReduceOp.SUM, async_op=True).wait()   # stream-level wait only
             loss /= self.world
+            if self.loss_reg:
+                nll = nll.clone()
+                dist.all_reduce(nll, op=dist.ReduceOp.SUM, async_op=True).wait()
+                nll /= self.world
         self.last_loss = loss
+        self.last_nll = nll if self.loss_reg else loss
         return loss
 
     def finish_accumulation(self) -> bool:
@@ -401,7 +421,8 @@ class Trainer:
                 self.buckets.fire(idx)
         self.buckets.wait()
         cap.tail.replay()
-        return cap.loss.clone()            # the graph's own loss scalar is overwritten by the next replay
+        loss = cap.loss.clone()            # the graph's own loss scalars are overwritten by the next replay
+        return loss, (cap.nll.clone() if self.loss_reg else loss)
 
     def _evict_packed(self, keep: int):
         """Drop the least recently used captured packed steps until at most `keep` remain.  Called outside any capture: the
@@ -578,7 +599,8 @@ class Trainer:
             with torch.cuda.stream(cs):
                 begin()
                 try:
-                    cap.loss = self._step_body(cap.inputs, cap.labels, cap.prev, audio, cut=cut, tcap=tcap, phase=phase)
+                    cap.loss, cap.nll = self._step_body(cap.inputs, cap.labels, cap.prev, audio, cut=cut, tcap=tcap,
+                                                        phase=phase)
                     g, state["g"] = state["g"], None
                     g.capture_end()
                     cap.tail = g

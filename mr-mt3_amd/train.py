@@ -27,6 +27,10 @@ Lightning reads them from the same block (`+trainer.gradient_clip_val=1.0`); `+s
 step whose gradient norm is inf / NaN instead of poisoning the weights.  With either on, the step lines also carry
 `grad_norm` (the norm before clipping) and the run ends with `skipped_steps K` when K > 0.
 
+Loss options: top-level `label_smoothing` (torch.nn.CrossEntropyLoss's keyword) and `z_loss` (T5X's, MT3's recipe uses
+1e-4): `+label_smoothing=0.1 +z_loss=1e-4`.  With either on, `train_loss` is the regularised objective and the step lines
+carry the plain NLL next to it (`step N train_loss X nll Y`), the number that compares to `val_loss` and to other runs.
+
 `cfg.path` has the reference's meaning (`train.py:61-92`): a `.ckpt` resumes weights, AdamW moments and
 the step counter; a `.pth` only loads weights (`strict=False`); anything else is an error.  At the end
 rank 0 writes `<output_dir>/<model_type>_<dataset_type>/version_0/checkpoints/last.ckpt` (Lightning
@@ -138,6 +142,35 @@ def gradient_clipping(cfg):
     return val, algo
 
 
+def loss_options(cfg):
+    """(label_smoothing, z_loss) from the top-level keys of those names (absent or null: 0), validated like the trainer's
+    arguments: 0 <= label_smoothing < 1, z_loss >= 0, else a ValueError naming the key."""
+    from mrmt3.lib import ce_options
+    vals = []
+    for key in ("label_smoothing", "z_loss"):
+        raw = cfg.get(key)
+        if raw is None or str(raw).lower() in ("", "none", "null"):
+            vals.append(0.0)
+            continue
+        try:
+            vals.append(float(raw))
+        except (TypeError, ValueError):
+            raise ValueError("%s must be a number, got %r" % (key, raw)) from None
+    _, eps, z = ce_options(*vals)
+    return eps, z
+
+
+def format_step_line(it, loss, nll=None, grad_norm=None):
+    """Rank 0's log line of optimizer step `it`: `step N train_loss X`, then `nll Y` when a loss option is on and
+    `grad_norm G` when the clipping tail is (floats; None leaves the field out)."""
+    line = f"step {it} train_loss {loss:.4f}"
+    if nll is not None:
+        line += f" nll {nll:.4f}"
+    if grad_norm is not None:
+        line += f" grad_norm {grad_norm:.4f}"
+    return line
+
+
 def resume_position(global_step, steps_per_epoch, accumulate=1):
     """(epoch, batches of that epoch already consumed) for a run that has taken `global_step` optimizer steps.  The
     position is derived from the step count alone: a checkpoint's `epoch` field is the epoch in progress OR the one
@@ -212,17 +245,16 @@ def main(argv=None):
     accum = accumulate_grad_batches(cfg)
     clip_val, clip_algo = gradient_clipping(cfg)
     skip_nonfinite = str(cfg.get("skip_nonfinite", False)).lower() in _TRUTHY
+    label_smoothing, z_loss = loss_options(cfg)
     trainer = Trainer(task.model, lr=float(cfg.optim.lr), lr_lambda=lam,
                       weighted_loss=type(task).__name__ == "MT3NetWeightedLoss", pack_targets=pack,
                       accumulate_grad_batches=accum, gradient_clip_val=clip_val, gradient_clip_algorithm=clip_algo,
-                      skip_nonfinite=skip_nonfinite)
+                      skip_nonfinite=skip_nonfinite, label_smoothing=label_smoothing, z_loss=z_loss)
 
     def step_line(it, loss):
         """Rank 0's log line of optimizer step `it` (reads the device: only at the logging cadence)."""
-        line = f"step {it} train_loss {loss.item():.4f}"
-        if trainer.clip_on:
-            line += f" grad_norm {trainer.last_grad_norm.item():.4f}"
-        return line
+        return format_step_line(it, loss.item(), trainer.last_nll.item() if trainer.loss_reg else None,
+                                trainer.last_grad_norm.item() if trainer.clip_on else None)
 
     task.model.engine.seed = int(cfg.seed)
     with_prev = "WithPrev" in type(task).__name__
