@@ -444,6 +444,38 @@ int mrmt3_adamw_step_clipped(float* p, const float* g, float* m, float* v, size_
                              int32_t* step_dev, float beta1, float beta2, float eps, float weight_decay,
                              float grad_scale, const float* stat_dev, float clip_value, void* shadow_bf16,
                              void* stream);
+/* ---- K11c: optimizer parameter groups: AdamW and the gradient norm over a table of trainable element ranges
+ * of the flat buffer -- frozen weights (outside every range: never read, never written), per-range weight decay and
+ * learning-rate factor, EMA weights in the same pass.
+ * mrmt3_opt_ranges_plan (host code, no launch): checks `ranges` (sorted, disjoint, bounds multiples of 4 inside [0, n],
+ * finite weight_decay / lr_scale >= 0, at least one range) and writes the table the kernels read into `table_host`
+ * (mrmt3_opt_ranges_table_bytes(n_ranges) bytes: per range its first 16-byte group, the prefix sum of the groups before it
+ * and its two factors, then a sentinel with the total); the caller copies it to the device (8-byte aligned).
+ * *n_trainable (nullable) receives the number of elements inside the ranges.
+ * mrmt3_adamw_step_groups: ONE launch over the trainable elements only (a workgroup owns 1024 consecutive 16-byte groups
+ * of the ranges laid end to end and finds its range by binary search).  Inside a range the arithmetic is
+ * mrmt3_adamw_step's with weight_decay of the range and lr = lr_dev[0] * lr_scale, bit for bit; with stat_dev non-null it
+ * is mrmt3_adamw_step_clipped's (coefficient stat_dev[1], clamp to +-clip_value, stat_dev[2] != 0 skips every store).  With
+ * `ema` non-null (then 0 < ema_decay < 1; ema null needs ema_decay == 0): ema += (1 - ema_decay) * (p_new - ema) in f32
+ * in the same pass; a skipped step leaves ema untouched.  n_trainable is what the planner returned (it sizes the grid;
+ * the kernel's bound is the table's own total).  step_dev is incremented either way.
+ * mrmt3_grad_norm_ranges: mrmt3_grad_norm over the elements of the ranges only (a frozen gradient slot is never read):
+ * the same fixed grid and summation order over the ranges laid end to end -- a function of the table alone; one range
+ * covering the buffer gives mrmt3_grad_norm's bits. */
+typedef struct {
+  long long begin, end;      /* elements, multiples of 4 */
+  float weight_decay, lr_scale;
+} mrmt3_opt_range;
+size_t mrmt3_opt_ranges_table_bytes(int n_ranges);
+int mrmt3_opt_ranges_plan(const mrmt3_opt_range* ranges, int n_ranges, size_t n, void* table_host, size_t table_bytes,
+                          size_t* n_trainable);
+int mrmt3_adamw_step_groups(float* p, const float* g, float* m, float* v, float* ema, size_t n, const void* ranges_dev,
+                            int n_ranges, size_t n_trainable, const float* lr_dev, int32_t* step_dev, float beta1,
+                            float beta2, float eps, float grad_scale, float ema_decay, const float* stat_dev,
+                            float clip_value, void* shadow_bf16, void* stream);
+int mrmt3_grad_norm_ranges(const float* g, size_t n, const void* ranges_dev, int n_ranges, float grad_scale, float max_norm,
+                           int skip_nonfinite, float* ws, size_t ws_elems, float* stat_dev, int32_t* skipped_dev,
+                           void* stream);
 /* ctr[0] += delta on the device (int32, one thread, stream-ordered).  The trainer's gradient accumulation keeps its
  * per-micro-batch dropout salt in such a counter: it is passed as the step_dev of the dropout entry points and bumped
  * once per micro-batch, inside the captured step, so replays draw new masks per micro-batch. */

@@ -6,6 +6,7 @@
 // row statistics in fp32 and reduce with 64-lane wave shuffles.  Reference lines are cited at each
 // entry point.
 #include "common.h"
+#include "opt_ranges.h"
 
 // no implicit FMA formation in this file: gemm_rows.hip restates these kernels' arithmetic and must land on the same bits
 #pragma clang fp contract(off)
@@ -1371,6 +1372,206 @@ extern "C" int mrmt3_adamw_step_clipped(float* p, const float* g, float* m, floa
   MR_CHECK_LAUNCH("adamw_step_clipped");
   hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, s, step_dev);
   MR_CHECK_LAUNCH("adamw_step_clipped inc");
+  return MRMT3_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Parameter groups: AdamW and the gradient norm over a table of trainable ranges (frozen weights, per-range weight decay
+// and learning-rate factor, EMA weights in the same pass).  Table layout and planner: opt_ranges.h
+// ------------------------------------------------------------------------------------------------
+// largest r in [lo, nr) with tab[r].start <= i   (i < tab[nr].start, tab[lo].start <= i)
+__device__ __forceinline__ int opt_locate(const MrOptRec* __restrict__ tab, int lo, int nr, long long i) {
+  int hi = nr;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (tab[mid].start <= i) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// A workgroup owns OG_CHUNK consecutive 16-byte groups of the virtual (trainable-only) array: one binary search for the
+// range of its first group (uniform over the workgroup), then every lane walks forward from there.  Elements outside
+// the ranges are never addressed.  Inside a range: adamw_kernel's / adamw_clipped_kernel's arithmetic in their order with
+// wd and lr * lr_scale of the range, then ema += (1 - ema_decay) * (p_new - ema).
+#define OG_PER_LANE 4
+#define OG_CHUNK (256 * OG_PER_LANE)
+template <bool CLIP, bool EMA>
+__global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                           float* __restrict__ m, float* __restrict__ v,
+                                                           float* __restrict__ ema, const MrOptRec* __restrict__ tab, int nr,
+                                                           const float* __restrict__ lr_dev,
+                                                           const int32_t* __restrict__ step_dev, float b1, float b2, float eps,
+                                                           float gscale, float ema_om, const float* __restrict__ stat,
+                                                           float clip_value, bf16_t* __restrict__ shadow) {
+  float coef = 1.f;
+  if (CLIP) {
+    if (stat[2] != 0.f) return;
+    coef = stat[1];
+  }
+  const long long total = tab[nr].start;
+  const long long base = (long long)blockIdx.x * OG_CHUNK;
+  if (base >= total) return;
+  const float lr0 = lr_dev[0];
+  const int step = step_dev[0] + 1;
+  const double bc1 = 1.0 - pow((double)b1, (double)step);
+  const double bc2 = 1.0 - pow((double)b2, (double)step);
+  const float bc2_sqrt = (float)sqrt(bc2);
+  int r = opt_locate(tab, 0, nr, base);
+  float step_size = 0.f, decay = 1.f;
+  long long r_start = 0, r_next = 0, r_begin4 = 0;           // r_next = 0: the first group always loads its range
+#pragma unroll 1
+  for (int k = 0; k < OG_PER_LANE; ++k) {
+    const long long i = base + (long long)k * 256 + threadIdx.x;
+    if (i >= total) break;
+    if (i >= r_next) {
+      r = opt_locate(tab, r, nr, i);
+      r_start = tab[r].start;
+      r_next = tab[r + 1].start;
+      r_begin4 = tab[r].begin4;
+      const float lr = lr0 * tab[r].lr_scale;
+      step_size = (float)((double)lr / bc1);
+      decay = 1.f - lr * tab[r].wd;
+    }
+    const size_t o = (size_t)(r_begin4 + (i - r_start)) * 4;
+    float pv[4], gv[4], mv[4], vv[4];
+    load4<float>(p + o, pv);
+    load4<float>(g + o, gv);
+    load4<float>(m + o, mv);
+    load4<float>(v + o, vv);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float gr;
+      if (CLIP) {
+        gr = gv[e] * gscale * coef;
+        if (clip_value > 0.f) gr = gr > clip_value ? clip_value : (gr < -clip_value ? -clip_value : gr);   // NaN stays NaN
+      } else {
+        gr = gv[e] * gscale;
+      }
+      pv[e] *= decay;
+      mv[e] = mv[e] + (gr - mv[e]) * (1.f - b1);
+      vv[e] = vv[e] * b2 + (1.f - b2) * gr * gr;
+      const float denom = sqrtf(vv[e]) / bc2_sqrt + eps;
+      pv[e] -= step_size * (mv[e] / denom);
+    }
+    store4<float>(p + o, pv);
+    store4<float>(m + o, mv);
+    store4<float>(v + o, vv);
+    if (shadow) store4<bf16_t>(shadow + o, pv);
+    if (EMA) {
+      float ev[4];
+      load4<float>(ema + o, ev);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) ev[e] = ev[e] + ema_om * (pv[e] - ev[e]);
+      store4<float>(ema + o, ev);
+    }
+  }
+}
+
+extern "C" size_t mrmt3_opt_ranges_table_bytes(int n_ranges) {
+  return n_ranges < 0 ? 0 : ((size_t)n_ranges + 1) * sizeof(MrOptRec);
+}
+
+extern "C" int mrmt3_opt_ranges_plan(const mrmt3_opt_range* ranges, int n_ranges, size_t n, void* table_host,
+                                     size_t table_bytes, size_t* n_trainable) {
+  MR_CHECK_ARG(ranges && table_host, "opt_ranges_plan: null pointer");
+  MR_CHECK_ARG(n_ranges >= 1 && n_ranges <= MR_OPT_MAX_RANGES, "opt_ranges_plan: %d ranges (1 .. %d: freezing everything leaves nothing to step)",
+               n_ranges, MR_OPT_MAX_RANGES);
+  MR_CHECK_ARG(n > 0 && n % 4 == 0, "opt_ranges_plan: n = %zu must be a positive multiple of 4", n);
+  MR_CHECK_ARG(table_bytes >= mrmt3_opt_ranges_table_bytes(n_ranges), "opt_ranges_plan: the table holds %zu bytes, %zu are needed",
+               table_bytes, mrmt3_opt_ranges_table_bytes(n_ranges));
+  int bad = 0;
+  const char* why = mr_opt_ranges_problem(ranges, n_ranges, n, &bad);
+  MR_CHECK_ARG(why[0] == 0, "opt_ranges_plan: range %d [%lld, %lld): %s", bad, ranges[bad].begin, ranges[bad].end, why);
+  const size_t tr = mr_opt_ranges_fill(ranges, n_ranges, (MrOptRec*)table_host);
+  if (n_trainable) *n_trainable = tr;
+  return MRMT3_OK;
+}
+
+extern "C" int mrmt3_adamw_step_groups(float* p, const float* g, float* m, float* v, float* ema, size_t n,
+                                       const void* ranges_dev, int n_ranges, size_t n_trainable, const float* lr_dev,
+                                       int32_t* step_dev, float beta1, float beta2, float eps, float grad_scale,
+                                       float ema_decay, const float* stat_dev, float clip_value, void* shadow_bf16,
+                                       void* stream) {
+  MR_CHECK_ARG(p && g && m && v && lr_dev && step_dev && ranges_dev && n % 4 == 0, "adamw_step_groups: bad args");
+  MR_CHECK_ARG(n_ranges >= 1 && n_ranges <= MR_OPT_MAX_RANGES, "adamw_step_groups: %d ranges (1 .. %d)", n_ranges, MR_OPT_MAX_RANGES);
+  MR_CHECK_ARG(n_trainable > 0 && n_trainable % 4 == 0 && n_trainable <= n,
+               "adamw_step_groups: n_trainable = %zu must be a positive multiple of 4, at most n = %zu", n_trainable, n);
+  MR_CHECK_ARG(((uintptr_t)ranges_dev & 7) == 0, "adamw_step_groups: the range table must be 8-byte aligned");
+  MR_CHECK_ARG(clip_value >= 0.f, "adamw_step_groups: clip_value = %g is negative (0: no clamp)", (double)clip_value);
+  MR_CHECK_ARG(stat_dev || clip_value == 0.f, "adamw_step_groups: clip_value needs stat_dev (the clipped form)");
+  // ema_decay == 0 means "no EMA" and needs ema == null; otherwise 0 < ema_decay < 1 and a buffer
+  MR_CHECK_ARG(ema_decay == 0.f || (ema_decay > 0.f && ema_decay < 1.f), "adamw_step_groups: ema_decay = %g is outside (0, 1)",
+               (double)ema_decay);
+  MR_CHECK_ARG((ema != nullptr) == (ema_decay != 0.f), "adamw_step_groups: ema_decay = %g %s", (double)ema_decay,
+               ema ? "but an ema buffer was given (0 < ema_decay < 1 is needed)" : "needs an ema buffer (null was given)");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t groups = n_trainable / 4;
+  const dim3 grid((unsigned)((groups + OG_CHUNK - 1) / OG_CHUNK)), block(256);
+  const MrOptRec* tab = (const MrOptRec*)ranges_dev;
+  const float om = 1.f - ema_decay;
+#define OG_LAUNCH(C_, E_)                                                                                              \
+  hipLaunchKernelGGL((adamw_groups_kernel<C_, E_>), grid, block, 0, s, p, g, m, v, ema, tab, n_ranges, lr_dev, step_dev, \
+                     beta1, beta2, eps, grad_scale, om, stat_dev, clip_value, (bf16_t*)shadow_bf16)
+  if (stat_dev) { if (ema) OG_LAUNCH(true, true); else OG_LAUNCH(true, false); }
+  else          { if (ema) OG_LAUNCH(false, true); else OG_LAUNCH(false, false); }
+#undef OG_LAUNCH
+  MR_CHECK_LAUNCH("adamw_step_groups");
+  hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, s, step_dev);
+  MR_CHECK_LAUNCH("adamw_step_groups inc");
+  return MRMT3_OK;
+}
+
+// grad_sumsq_kernel over the virtual array of the ranges: the same fixed grid, the same four-strides-at-a-time order, so
+// the result is a function of (ranges) alone — and with ONE range covering the buffer it is mrmt3_grad_norm's, bit for bit.
+__device__ __forceinline__ void opt_load4(const float* __restrict__ g, const MrOptRec* __restrict__ tab, int nr, int& r,
+                                          long long i, float out[4]) {
+  r = opt_locate(tab, r, nr, i);
+  load4<float>(g + (size_t)(tab[r].begin4 + (i - tab[r].start)) * 4, out);
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_ranges_kernel(const float* __restrict__ g, const MrOptRec* __restrict__ tab,
+                                                                int nr, double* __restrict__ partial) {
+  __shared__ double lds4[4];
+  const long long n4 = tab[nr].start;
+  const long long stride = (long long)GN_BLOCKS * 256;
+  long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  int r = 0;                                                  // the indices of a lane only grow: each search starts at the last hit
+  for (; i + 3 * stride < n4; i += 4 * stride) {
+    float a[4], b[4], c[4], d[4];
+    opt_load4(g, tab, nr, r, i, a);
+    opt_load4(g, tab, nr, r, i + stride, b);
+    opt_load4(g, tab, nr, r, i + 2 * stride, c);
+    opt_load4(g, tab, nr, r, i + 3 * stride, d);
+    sumsq4_f64(a, acc); sumsq4_f64(b, acc); sumsq4_f64(c, acc); sumsq4_f64(d, acc);
+  }
+  for (; i < n4; i += stride) {
+    float a[4];
+    opt_load4(g, tab, nr, r, i, a);
+    sumsq4_f64(a, acc);
+  }
+  const double s = block_sum_f64((acc[0] + acc[1]) + (acc[2] + acc[3]), lds4);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+extern "C" int mrmt3_grad_norm_ranges(const float* g, size_t n, const void* ranges_dev, int n_ranges, float grad_scale,
+                                      float max_norm, int skip_nonfinite, float* ws, size_t ws_elems, float* stat_dev,
+                                      int32_t* skipped_dev, void* stream) {
+  MR_CHECK_ARG(g && ws && stat_dev && skipped_dev && ranges_dev, "grad_norm_ranges: null pointer");
+  MR_CHECK_ARG(n > 0 && n % 4 == 0 && ((uintptr_t)g & 15) == 0, "grad_norm_ranges: n = %zu must be a positive multiple of 4 and g 16-byte aligned", n);
+  MR_CHECK_ARG(n_ranges >= 1 && n_ranges <= MR_OPT_MAX_RANGES, "grad_norm_ranges: %d ranges (1 .. %d)", n_ranges, MR_OPT_MAX_RANGES);
+  MR_CHECK_ARG(((uintptr_t)ranges_dev & 7) == 0, "grad_norm_ranges: the range table must be 8-byte aligned");
+  MR_CHECK_ARG(ws_elems >= mrmt3_grad_norm_workspace_elems() && ((uintptr_t)ws & 7) == 0,
+               "grad_norm_ranges: the workspace holds %zu floats, %zu are needed (8-byte aligned)", ws_elems,
+               mrmt3_grad_norm_workspace_elems());
+  MR_CHECK_ARG(max_norm >= 0.f, "grad_norm_ranges: max_norm = %g is negative (0: no clipping)", (double)max_norm);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(grad_sumsq_ranges_kernel, dim3(GN_BLOCKS), dim3(256), 0, s, g, (const MrOptRec*)ranges_dev, n_ranges,
+                     (double*)ws);
+  MR_CHECK_LAUNCH("grad_norm_ranges");
+  hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)ws, grad_scale, max_norm,
+                     skip_nonfinite, stat_dev, skipped_dev);
+  MR_CHECK_LAUNCH("grad_norm_ranges finish");
   return MRMT3_OK;
 }
 

@@ -82,31 +82,58 @@ def load_weights(model, path: str, strict: bool = False):
 
 
 # ---- AdamW state <-> flat moments ----------------------------------------------------------------------
+def optimizer_groups(order, groups, weight_decay: float) -> list:
+    """[(weight_decay, lr_scale, [keys])] as torch.optim.AdamW would hold them for `groups` (a params.ParamGroups, or
+    None): one param group per distinct (weight_decay, lr scale) in order of first appearance, the keys of each in
+    `model.parameters()` order, frozen tensors in none (`requires_grad=False` parameters are not handed to an optimizer)."""
+    if groups is None or groups.trivial:
+        return [(float(weight_decay), 1.0, list(order))]
+    out, index = [], {}
+    for key in order:
+        if key in groups.frozen:
+            continue
+        h = groups.hyper(key, weight_decay)
+        if h not in index:
+            index[h] = len(out)
+            out.append((h[0], h[1], []))
+        out[index[h]][2].append(key)
+    return out
+
+
 def adamw_state_from_flat(flat, order, step: int, lr: float, betas, eps: float, weight_decay: float,
-                          initial_lr: float | None = None) -> dict:
-    """torch.optim.AdamW.state_dict() layout whose exp_avg / exp_avg_sq are views of the flat moments."""
-    state = {}
-    for i, key in enumerate(order):
-        state[i] = {"step": torch.tensor(float(step)), "exp_avg": flat.view(flat.M, key),
-                    "exp_avg_sq": flat.view(flat.V, key)}
-    group = {"lr": lr, "betas": tuple(betas), "eps": eps, "weight_decay": weight_decay, "amsgrad": False,
-             "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
-             "params": list(range(len(order)))}
-    if initial_lr is not None:
-        group["initial_lr"] = initial_lr
-    return {"state": state, "param_groups": [group]}
+                          initial_lr: float | None = None, groups=None) -> dict:
+    """torch.optim.AdamW.state_dict() layout whose exp_avg / exp_avg_sq are views of the flat moments.  With `groups`
+    (params.ParamGroups): one param group per distinct (weight_decay, lr scale), parameter ids numbered through the groups
+    as torch numbers them, frozen tensors absent."""
+    state, pgroups, pos = {}, [], 0
+    for wd, scale, keys in optimizer_groups(order, groups, weight_decay):
+        for i, key in enumerate(keys):
+            state[pos + i] = {"step": torch.tensor(float(step)), "exp_avg": flat.view(flat.M, key),
+                              "exp_avg_sq": flat.view(flat.V, key)}
+        group = {"lr": lr * scale, "betas": tuple(betas), "eps": eps, "weight_decay": wd, "amsgrad": False,
+                 "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
+                 "params": list(range(pos, pos + len(keys)))}
+        if initial_lr is not None:
+            group["initial_lr"] = initial_lr * scale
+        pgroups.append(group)
+        pos += len(keys)
+    return {"state": state, "param_groups": pgroups}
 
 
-def adamw_state_to_flat(opt_state: dict, flat, order) -> int:
-    """Copy a torch AdamW state dict into the flat moments; returns the step count it was saved at."""
+def adamw_state_to_flat(opt_state: dict, flat, order, groups=None, weight_decay: float = 0.01) -> int:
+    """Copy a torch AdamW state dict into the flat moments; returns the step count it was saved at.  `groups`: the
+    parameter groups the state was exported under (adamw_state_from_flat): its ids follow optimizer_groups' order, and
+    the moments of tensors it does not hold (frozen ones) are left as they are."""
     flat.ensure_adam()
     st = opt_state["state"]
-    params = opt_state["param_groups"][0]["params"]
-    if len(params) != len(order):
-        raise ValueError(f"optimizer state has {len(params)} parameters, the model has {len(order)}")
+    keys = [k for _, _, ks in optimizer_groups(order, groups, weight_decay) for k in ks]
+    params = [i for g in opt_state["param_groups"] for i in g["params"]]
+    if len(params) != len(keys):
+        raise ValueError(f"optimizer state has {len(params)} parameters, the model has {len(keys)}"
+                         + (" trainable under the checkpoint's parameter groups" if len(keys) != len(order) else ""))
     step = 0
     with torch.no_grad():
-        for pos, key in enumerate(order):
+        for pos, key in enumerate(keys):
             s = st.get(params[pos])
             if s is None:               # parameter never stepped
                 flat.view(flat.M, key).zero_()
@@ -133,7 +160,7 @@ def lightning_checkpoint(model, trainer=None, epoch: int = 0) -> dict:
         lr_now = (trainer.base_lr * trainer.lr_lambda(trainer.host_step) if trainer.lr_lambda is not None
                   else float(trainer.lr_dev.item()))
         opt = adamw_state_from_flat(model.flat, order, trainer.host_step, lr_now, trainer.betas, trainer.eps,
-                                    trainer.wd, initial_lr=trainer.base_lr)
+                                    trainer.wd, initial_lr=trainer.base_lr, groups=getattr(trainer, "groups", None))
         for s in opt["state"].values():
             s["exp_avg"] = s["exp_avg"].detach().cpu().clone()
             s["exp_avg_sq"] = s["exp_avg_sq"].detach().cpu().clone()
@@ -143,6 +170,13 @@ def lightning_checkpoint(model, trainer=None, epoch: int = 0) -> dict:
         out["mrmt3"] = {"dropout_seed": model.engine.seed, "dropout_stream_ctr": model.engine._stream_ctr}
         if getattr(trainer, "accumulate", 1) > 1:      # gradient accumulation's micro-batch dropout salt
             out["mrmt3"]["dropout_salt"] = int(trainer.salt_dev.item())
+        g = getattr(trainer, "groups", None)
+        if g is not None and (not g.trivial or trainer.ema_decay is not None):
+            # the frozen set, the group hyper-parameters and the EMA weights (canonical keys): what resume() needs to go on
+            out["mrmt3"]["groups"] = dict(g.patterns, ema_decay=trainer.ema_decay)
+            if trainer.ema_decay is not None:
+                out["mrmt3"]["ema"] = OrderedDict((k, model.flat.view(model.flat.E, k).detach().cpu().clone())
+                                                  for k in model.flat.shapes)
         if trainer.lr_lambda is not None:       # LambdaLR.state_dict() (the lambda itself is not pickled)
             out["lr_schedulers"] = [{"base_lrs": [trainer.base_lr], "last_epoch": trainer.host_step,
                                      "verbose": False, "_step_count": trainer.host_step + 1,

@@ -130,6 +130,7 @@ class GradBuckets:
             assert a == pos, "buckets must tile the flat buffer"
             pos = b
         assert pos == flat.numel
+        self._all_buckets = self.buckets
         self._works = []
         self._fired = set()
         # called right before a bucket's all-reduce is enqueued (the engine sums its queued norm-weight gradients here)
@@ -144,6 +145,22 @@ class GradBuckets:
 
     def reset(self):
         self._works, self._fired = [], set()
+
+    def set_trainable(self, spans=None):
+        """Restrict the exchange to the trainable element spans (sorted, disjoint [begin, end) of the flat buffer): each
+        bucket sends only its trainable slices — a frozen tensor's gradient slot is never produced — and a bucket left
+        with none is dropped.  None: every bucket whole, as built."""
+        if spans is None:
+            self.buckets = self._all_buckets
+            for b in self.buckets:
+                b.pop("slices", None)
+            return
+        kept = []
+        for b in self._all_buckets:
+            sl = [(max(a, b["start"]), min(e, b["end"])) for a, e in spans if a < b["end"] and e > b["start"]]
+            if sl:
+                kept.append(dict(b, slices=sl))
+        self.buckets = kept
 
     @property
     def active(self) -> bool:
@@ -227,10 +244,12 @@ class GradBuckets:
         b = self.buckets[idx]
         if self.before_fire is not None:
             self.before_fire()
-        grad = self.flat.G[b["start"]:b["end"]]
-        if self.exchange_dtype is not None and self.exchange_dtype != grad.dtype:
-            return self._fire_compressed(b, grad)
-        self._works.append(self._all_reduce(grad))
+        for start, end in b.get("slices") or ((b["start"], b["end"]),):
+            grad = self.flat.G[start:end]
+            if self.exchange_dtype is not None and self.exchange_dtype != grad.dtype:
+                self._fire_compressed(dict(start=start, end=end), grad)
+            else:
+                self._works.append(self._all_reduce(grad))
 
     def _fire_compressed(self, b, grad):
         """Round the bucket to the exchange dtype, all-reduce that copy, widen it back into the f32 gradient when the

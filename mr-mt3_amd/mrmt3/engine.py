@@ -122,11 +122,32 @@ class Engine:
         """out += a^T @ b, complete after the next join_wgrad() (inputs were produced on the current stream).
         Shapes the grouped kernel takes are only recorded here (operands kept alive) and launched with every other
         gradient that is due; everything else runs now, on the current stream."""
+        if self.flat.is_frozen(out):                      # a frozen weight has no gradient: nothing is queued or launched
+            return None
         if a.dtype == torch.float32:                      # fp32 training / parity path: exact-f32 product, in place, now
             return lib.gemm_tn_f32(a, b, out, accumulate=True)
         if self.tn_group is not None and self.tn_group.ok(a, b, out):
             return self.tn_group.add(a, b, out, accumulate=True)
         return lib.gemm_tn(a, b, out, accumulate=True)
+
+    def ndw(self, key):
+        """The gradient slot of a norm weight, or None when it is frozen (no partial rows, no deferred reduction)."""
+        return None if key in self.flat.frozen else self.flat.grad(key)
+
+    def _embed_bwd(self, *a, **kw):
+        """lib.embed_bwd into the decoder's embedding table, unless the table is frozen."""
+        if "decoder_embed_tokens.weight" not in self.flat.frozen:
+            lib.embed_bwd(*a, **kw)
+
+    def encoder_frozen(self) -> bool:
+        """Every parameter of the encoder stack and its input projection is frozen: backward stops above it."""
+        return self.flat.all_frozen("encoder.") and "proj.weight" in self.flat.frozen
+
+    def segmem_frozen(self) -> bool:
+        """The memory encoder, its projection and the table its input gradient would land in are all frozen."""
+        f = self.flat
+        return (f.all_frozen("segmem_encoder.") and "segmem_proj.weight" in f.frozen and
+                "decoder_embed_tokens.weight" in f.frozen)
 
     def _norm_bwd(self, *a, **kw):
         """lib.add_rmsnorm_bwd with the norm-weight gradient deferred to one batched reduction (flush_norm_dw).
@@ -291,7 +312,7 @@ class Engine:
         has_y = n_layers > 0
         rg = self.res_grad_dtype if has_y else torch.float32
         dx, dy = self._norm_bwd(d_out, None, fin["x1"], fin["rstd"], self.ln(f"{prefix}.final_layer_norm.weight"),
-                                     f.grad(f"{prefix}.final_layer_norm.weight"), want_dy=has_y, p=p, seed=seed, step=self.step_dev,
+                                     self.ndw(f"{prefix}.final_layer_norm.weight"), want_dy=has_y, p=p, seed=seed, step=self.step_dev,
                                      stream_y=fin["s_in"], stream_out=fin["s_out"], out_drop=True, dx1_dtype=rg)
         # gradient of the cross-attention K | V of every layer, side by side like the forward's kv_all: the gradient of
         # the encoder output is then ONE product with K = n_layers * 768 after the loop instead of n_layers f32 accumulations
@@ -307,7 +328,7 @@ class Engine:
                                       stream_id=t["s_g"])
             self.wgrad(dh, t["xn"], f.GW(f"{prefix}.{i}.wi"))
             dx, dy = self._proj_norm_bwd(dh, self.WT(f"{prefix}.{i}.wi"), dx, t["x1"], t["rstd"],
-                                         self.ln(f"{b}.{ff}.layer_norm.weight"), f.grad(f"{b}.{ff}.layer_norm.weight"),
+                                         self.ln(f"{b}.{ff}.layer_norm.weight"), self.ndw(f"{b}.{ff}.layer_norm.weight"),
                                          p=p, seed=seed, step=self.step_dev, stream_y=t["s_in"], dx1=dx)
             if ff == 2:
                 t = tape.pop()
@@ -328,7 +349,7 @@ class Engine:
                 self.wgrad(dq, t["xn"], f.GW(f"{prefix}.{i}.cq"))
                 self.wgrad(dkv, enc, f.GW(f"{prefix}.{i}.ckv"))
                 dx, dy = self._proj_norm_bwd(dq, self.WT(f"{prefix}.{i}.cq"), dx, t["x1"], t["rstd"],
-                                             self.ln(f"{b}.1.layer_norm.weight"), f.grad(f"{b}.1.layer_norm.weight"),
+                                             self.ln(f"{b}.1.layer_norm.weight"), self.ndw(f"{b}.1.layer_norm.weight"),
                                              p=p, seed=seed, step=self.step_dev, stream_y=t["s_in"], dx1=dx)
             t = tape.pop()
             assert t["kind"] == "self" and t["i"] == i
@@ -347,12 +368,12 @@ class Engine:
             self.wgrad(dqkv, t["xn"], f.GW(f"{prefix}.{i}.qkv"))
             last = i == 0                                     # the stack's input gradient leaves in f32
             dx, dy = self._proj_norm_bwd(dqkv, self.WT(f"{prefix}.{i}.qkv"), dx, t["x1"], t["rstd"],
-                                         self.ln(f"{b}.0.layer_norm.weight"), f.grad(f"{b}.0.layer_norm.weight"),
+                                         self.ln(f"{b}.0.layer_norm.weight"), self.ndw(f"{b}.0.layer_norm.weight"),
                                          want_dy=(i > 0), p=p, seed=seed, step=self.step_dev, stream_y=t["s_in"],
                                          dx1=None if (last and dx.dtype != torch.float32) else dx)
             if on_layer_done is not None:
                 on_layer_done(prefix, i)
-        if dkv_all is not None:
+        if dkv_all is not None and d_enc is not None:      # (None: everything below the cross k|v projections is frozen)
             lib.gemm_nt(dkv_all, self.WT(f"{prefix}.ckv_all"), out=d_enc)          # d_enc is written here and nowhere else
         return dx
 
@@ -447,14 +468,14 @@ class Engine:
             GW, WT = f.GW(f"{pre}.0.qkv"), self.WT(f"{pre}.0.qkv")
             d_out = d_mem.contiguous().view(B * Ls, d)
             dx2, dy2 = self._norm_bwd(d_out, None, t["x2"], t["rstd2"], self.ln(f"{pre}.final_layer_norm.weight"),
-                                           f.grad(f"{pre}.final_layer_norm.weight"))
+                                           self.ndw(f"{pre}.final_layer_norm.weight"))
             self.wgrad(dy2, t["g"], f.GW(f"{pre}.0.wo"))
             dg = lib.gemm_nt(dy2, self.WT(f"{pre}.0.wo"))
             dh = lib.geglu_bwd(t["h"], dg)
             self.wgrad(dh, t["xn1"], f.GW(f"{pre}.0.wi"))
             dxn1 = lib.gemm_nt(dh, self.WT(f"{pre}.0.wi"), out_dtype=self.y_dtype)
             dx1, dy = self._norm_bwd(dxn1, dx2, t["x1"], t["rstd1"], self.ln(f"{b}.1.layer_norm.weight"),
-                                          f.grad(f"{b}.1.layer_norm.weight"), dx1=dx2)
+                                          self.ndw(f"{b}.1.layer_norm.weight"), dx1=dx2)
             self.wgrad(dy, t["o"], f.GW(f"{pre}.0.o"))
             do = lib.gemm_nt(dy, self.WT(f"{pre}.0.o"))
             kv = t["kv"]
@@ -469,14 +490,16 @@ class Engine:
             dres = torch.zeros(B, L, d, device=dx1.device, dtype=torch.float32)
             dres[:, :Ls] = dx1.view(B, Ls, d)
             dx, _ = self._norm_bwd(dxn_full, dres.view(B * L, d), t["x"], t["rstd_full"],
-                                        self.ln(f"{b}.0.layer_norm.weight"), f.grad(f"{b}.0.layer_norm.weight"),
+                                        self.ln(f"{b}.0.layer_norm.weight"), self.ndw(f"{b}.0.layer_norm.weight"),
                                         want_dy=False)
         assert t["kind"] == "seg_in"
         dsrc = lib.dropmask_cast(dx, out_dtype=self.dt)
         self.wgrad(dsrc, t["emb"], f.GW("segmem_proj"))
+        if "decoder_embed_tokens.weight" in f.frozen:
+            return
         demb = lib.gemm_nt(dsrc, self.WT("segmem_proj"), out_dtype=torch.float32)
-        lib.embed_bwd(t["ids"], demb, f.grad("decoder_embed_tokens.weight"), t["L"], shift=False,
-                      pad_id=self.cfg["pad_token_id"])
+        self._embed_bwd(t["ids"], demb, f.grad("decoder_embed_tokens.weight"), t["L"], shift=False,
+                        pad_id=self.cfg["pad_token_id"])
 
     @staticmethod
     def prev_row_ids(labels, start_id, pad_id):
@@ -598,7 +621,14 @@ class Engine:
             full = torch.zeros(B, Lx, d, device=d_dec.device, dtype=torch.float32)
             full[:, Ls:] = d_dec.view(B, Ld, d)
             d_dec = full.view(B * Lx, d)
-        d_enc_cat = torch.empty(B * Lc, d, device=d_dec.device, dtype=torch.float32)      # written by stack_bwd's one d_enc product
+        # Backward cut-off: with the whole encoder (and the memory encoder, if there is one) frozen nothing below the
+        # cross-attention k|v projections needs a gradient — d_enc is not formed and those backward passes do not run
+        skip_enc = self.encoder_frozen()
+        skip_mem = variant == "t5" or self.segmem_frozen()
+        # (segmem_v1's memory gradient comes out of the decoder INPUT; the other variants' memory rows are part of d_enc)
+        need_d_enc = not skip_enc if variant in ("t5", "segmem_v1") else not (skip_enc and skip_mem)
+        d_enc_cat = (torch.empty(B * Lc, d, device=d_dec.device, dtype=torch.float32)      # written by stack_bwd's one d_enc product
+                     if need_d_enc else None)
         dx = self.stack_bwd(tape, d_dec, d_enc=d_enc_cat, on_layer_done=on_layer_done)
         t = tape.pop()
         assert t["kind"] == "dec_in"
@@ -609,26 +639,33 @@ class Engine:
             dxm = lib.dropmask_cast(dx, p=t["p"], seed=self.seed, step=self.step_dev, stream_id=t["s_emb"],
                                     out_dtype=self.dt).float().view(B, Lx, d)
             d_mem = dxm[:, :Ls]
-            lib.embed_bwd(t["labels"].view(-1), dxm[:, Ls:].contiguous().view(-1, d), table_g, Ld, shift=True,
-                          start_id=start, pad_id=pad)
+            self._embed_bwd(t["labels"].view(-1), dxm[:, Ls:].contiguous().view(-1, d), table_g, Ld, shift=True,
+                            start_id=start, pad_id=pad)
             d_enc = d_enc_cat
         else:
             if t["pack"] is not None:          # the packed inputs are already shifted: a plain scatter-add over the Tcap rows
-                lib.embed_bwd(t["pack"].dec_ids, dx, table_g, t["pack"].Tcap, shift=False, pad_id=pad, p=t["p"],
-                              seed=self.seed, step=self.step_dev, stream_id=t["s_emb"])
+                self._embed_bwd(t["pack"].dec_ids, dx, table_g, t["pack"].Tcap, shift=False, pad_id=pad, p=t["p"],
+                                seed=self.seed, step=self.step_dev, stream_id=t["s_emb"])
             else:
-                lib.embed_bwd(t["labels"].view(-1), dx, table_g, Ld, shift=True, start_id=start, pad_id=pad, p=t["p"],
-                              seed=self.seed, step=self.step_dev, stream_id=t["s_emb"])
-            if variant != "t5":
+                self._embed_bwd(t["labels"].view(-1), dx, table_g, Ld, shift=True, start_id=start, pad_id=pad, p=t["p"],
+                                seed=self.seed, step=self.step_dev, stream_id=t["s_emb"])
+            if variant != "t5" and d_enc_cat is not None:
                 dcat = d_enc_cat.view(B, Lc, d)
-                d_enc = dcat[:, :Le].contiguous().view(-1, d)
-                d_mem = dcat[:, Le:]
+                d_enc = None if skip_enc else dcat[:, :Le].contiguous().view(-1, d)
+                d_mem = None if skip_mem else dcat[:, Le:]
             else:
                 d_enc = d_enc_cat
-        if d_mem is not None:
-            self.segmem_bwd(tape, d_mem)
+        if variant != "t5":
+            if skip_mem:                                       # frozen memory encoder: its records leave the tape unread
+                while tape.ops.pop()["kind"] != "seg_in":
+                    pass
+            else:
+                self.segmem_bwd(tape, d_mem)
             if on_layer_done is not None:
                 on_layer_done("segmem", 0)                     # the memory encoder's gradients are final (their bucket may leave)
-        self.encode_bwd(tape, d_enc, on_layer_done=on_layer_done)
+        if skip_enc:
+            del tape.ops[:]                                    # frozen encoder: no d_enc was formed, nothing is launched
+        else:
+            self.encode_bwd(tape, d_enc, on_layer_done=on_layer_done)
         self.join_wgrad()
         assert not tape.ops, [o["kind"] for o in tape.ops]

@@ -106,7 +106,7 @@ def load():
     return lib
 
 
-MIN_VERSION = 118
+MIN_VERSION = 119
 COUNTER_NAMES = ("gemm_nt_tile", "gemm_nt8", "gemm_nt_geglu", "tn_group", "tn8", "tn_tile", "attn_fwd", "attn_bwd",
                  "attn_bwd_onepass", "attn_f32", "tn_f32", "gemm_nt_splitk", "gemm_nt_addnorm", "gemm_nt_normbwd",
                  "gemm_nt_geglubwd", "attn_fwd_varlen", "attn_bwd_varlen")
@@ -1024,6 +1024,64 @@ def adamw_step_clipped(p, g, m, v, lr_dev, step_dev, stat, beta1=0.9, beta2=0.99
     _check(load().mrmt3_adamw_step_clipped(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(lr_dev), _p(step_dev), beta1, beta2,
                                            eps, weight_decay, grad_scale, _p(stat), float(clip_value), _p(shadow),
                                            _stream()), "adamw_step_clipped")
+
+
+class _OptRange(C.Structure):          # = mrmt3_opt_range
+    _fields_ = [("begin", C.c_longlong), ("end", C.c_longlong), ("weight_decay", C.c_float), ("lr_scale", C.c_float)]
+
+
+class OptRanges:
+    """The table mrmt3_adamw_step_groups / mrmt3_grad_norm_ranges read: `ranges` = [(begin, end, weight_decay, lr_scale)]
+    over a flat buffer of `n` elements, checked and laid out by the library's host-side planner (mrmt3_opt_ranges_plan; no
+    GPU needed for that: a ValueError names what is wrong).  `to(device)` copies the table there once; the kernels read it
+    by pointer, so a captured step keeps following the same table object."""
+
+    def __init__(self, ranges, n: int):
+        self.ranges = [(int(a), int(b), float(wd), float(sc)) for a, b, wd, sc in ranges]
+        self.n = int(n)
+        L = load()
+        arr = (_OptRange * max(1, len(self.ranges)))()
+        for i, r in enumerate(self.ranges):
+            arr[i] = _OptRange(*r)
+        nbytes = int(L.mrmt3_opt_ranges_table_bytes(len(self.ranges)))
+        self.host = torch.zeros(max(nbytes, 8), dtype=torch.uint8)
+        tr = C.c_size_t(0)
+        rc = L.mrmt3_opt_ranges_plan(arr, len(self.ranges), self.n, C.c_void_p(self.host.data_ptr()), nbytes, C.byref(tr))
+        if rc != 0:
+            raise ValueError(L.mrmt3_last_error().decode())
+        self.n_trainable = int(tr.value)
+        self.table = None
+
+    def __len__(self):
+        return len(self.ranges)
+
+    def to(self, device):
+        if self.table is None or self.table.device != torch.device(device):
+            self.table = self.host.to(device)
+        return self
+
+
+def adamw_step_groups(p, g, m, v, ranges: OptRanges, lr_dev, step_dev, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0,
+                      ema=None, ema_decay=0.0, stat=None, clip_value=0.0, shadow=None):
+    """AdamW over the elements of `ranges` only, each range with its own weight decay and lr factor (everything else
+    keeps its bits); `ema`/`ema_decay`: the EMA weights follow in the same pass; `stat` (what grad_norm_ranges wrote):
+    the clipped / skipping form."""
+    _dev(p, g, m, v, ranges.table, ema, stat)
+    assert p.dtype == torch.float32 and p.is_contiguous() and p.numel() == ranges.n
+    _check(load().mrmt3_adamw_step_groups(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), _p(ranges.table), len(ranges),
+                                          ranges.n_trainable, _p(lr_dev), _p(step_dev), beta1, beta2, eps, grad_scale,
+                                          float(ema_decay), _p(stat), float(clip_value), _p(shadow), _stream()),
+           "adamw_step_groups")
+
+
+def grad_norm_ranges(g, ranges: OptRanges, grad_scale, max_norm, skip_nonfinite, ws, stat, skipped):
+    """lib.grad_norm over the elements of `ranges` only (frozen gradient slots hold stale values and are not read)."""
+    _dev(g, ranges.table, ws, stat, skipped)
+    assert g.dtype == torch.float32 and stat.dtype == torch.float32 and stat.numel() >= 3 and skipped.dtype == torch.int32
+    assert g.numel() == ranges.n
+    _check(load().mrmt3_grad_norm_ranges(_p(g), g.numel(), _p(ranges.table), len(ranges), float(grad_scale), float(max_norm),
+                                         int(bool(skip_nonfinite)), _p(ws), ws.numel(), _p(stat), _p(skipped), _stream()),
+           "grad_norm_ranges")
 
 
 def counter_add(ctr, delta=1):

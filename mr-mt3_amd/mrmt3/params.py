@@ -12,12 +12,93 @@ buffer, so the reference's state-dict schema is preserved byte for
 """
 from __future__ import annotations
 
+import fnmatch
 from collections import OrderedDict
 
 import torch
 
 from . import lib
 from .synthetic import state_dict_shapes
+
+
+# state-dict aliases of the model classes (module.py): a pattern that matches the alias names the tensor itself
+ALIASES = {"encoder.embed_tokens.weight": "proj.weight", "decoder.embed_tokens.weight": "decoder_embed_tokens.weight",
+           "segmem_encoder.embed_tokens.weight": "segmem_proj.weight"}
+
+
+def match_keys(keys, patterns, what: str) -> set:
+    """Canonical keys of `keys` that one of the fnmatch `patterns` matches (an alias of ALIASES counts for its tensor).
+    A pattern that matches nothing is a ValueError naming it."""
+    if patterns is None:
+        return set()
+    if isinstance(patterns, str):
+        raise ValueError("%s must be a list of patterns, got the string %r" % (what, patterns))
+    keys = list(keys)
+    names = [(k, k) for k in keys] + [(a, k) for a, k in ALIASES.items() if k in set(keys)]
+    out = set()
+    for pat in patterns:
+        if not isinstance(pat, str):
+            raise ValueError("%s: a pattern is a string, got %r" % (what, pat))
+        hit = {k for name, k in names if fnmatch.fnmatchcase(name, pat)}
+        if not hit:
+            raise ValueError("%s: the pattern %r matches no parameter" % (what, pat))
+        out |= hit
+    return out
+
+
+def ema_decay_option(ema_decay):
+    """None (off) or a float in (0, 1); anything else is a ValueError."""
+    if ema_decay is None:
+        return None
+    if isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float)) or not 0.0 < float(ema_decay) < 1.0:
+        raise ValueError("ema_decay must be None or a number in (0, 1), got %r" % (ema_decay,))
+    return float(ema_decay)
+
+
+class ParamGroups:
+    """Which tensors train and with which hyper-parameters: `frozen` / `no_decay` lists of fnmatch patterns over the
+    state-dict keys, `lr_scale` {pattern: factor} (a later pattern overrides an earlier one).  Host only."""
+
+    def __init__(self, keys, frozen=None, no_decay=None, lr_scale=None):
+        keys = list(keys)
+        self.patterns = dict(frozen=list(frozen or []), no_decay=list(no_decay or []),
+                             lr_scale=dict(lr_scale or {}))
+        self.frozen = match_keys(keys, frozen, "frozen")
+        self.no_decay = match_keys(keys, no_decay, "no_decay")
+        self.scale = {}
+        if lr_scale is not None and not isinstance(lr_scale, dict):
+            raise ValueError("lr_scale must map a pattern to a factor, got %r" % (lr_scale,))
+        for pat, f in (lr_scale or {}).items():
+            if isinstance(f, bool) or not isinstance(f, (int, float)) or not 0.0 <= float(f) < float("inf"):
+                raise ValueError("lr_scale[%r] must be a finite number >= 0, got %r" % (pat, f))
+            for k in match_keys(keys, [pat], "lr_scale"):
+                self.scale[k] = float(f)
+        if len(self.frozen) == len(keys):
+            raise ValueError("frozen: every parameter is frozen, nothing is left to train")
+
+    @property
+    def trivial(self) -> bool:
+        """No option given: the one-group step of before."""
+        return not (self.frozen or self.no_decay or self.scale)
+
+    def hyper(self, key, weight_decay):
+        """(weight_decay, lr_scale) of a trainable tensor."""
+        return (0.0 if key in self.no_decay else float(weight_decay)), self.scale.get(key, 1.0)
+
+    def ranges(self, flat, weight_decay):
+        """[(begin, end, weight_decay, lr_scale)] over the flat buffer in its own order: one entry per run of adjacent
+        trainable tensors with equal hyper-parameters."""
+        out = []
+        for key, off in flat.offsets.items():
+            if key in self.frozen:
+                continue
+            n = flat.numel_of(key)
+            wd, sc = self.hyper(key, weight_decay)
+            if out and out[-1][1] == off and out[-1][2] == wd and out[-1][3] == sc:
+                out[-1] = (out[-1][0], off + n, wd, sc)
+            else:
+                out.append((off, off + n, wd, sc))
+        return out
 
 
 class FlatParams:
@@ -55,11 +136,15 @@ class FlatParams:
         self.V = None          # AdamW exp_avg_sq
         self.S = None          # bf16 shadow of P
         self.ST = None         # pre-transposed bf16 weights for dgrad
+        self.E = None          # EMA of P (f32), when the trainer keeps one
+        self.opt_ranges = None  # lib.OptRanges of the trainable tensors (None: one group, everything trains)
+        self.frozen = frozenset()   # canonical keys without a gradient (Engine.wgrad and friends skip them)
         self._shadow_version = -1
         # tensors other than P whose in-place updates also change the master (the nn.Parameter views of
         # MT3Module: after `.to(device)` each owns a version counter of its own, so torch.optim / load_state_dict
         # writes do not bump P._version)
         self.version_sources = ()
+        self._frozen_spans = None
         self._build_groups(segmem_num_layers)
 
     # ---- fused weight groups ------------------------------------------------------------------------
@@ -115,8 +200,79 @@ class FlatParams:
         o = self.offsets[key]
         return buf[o:o + n].view(shp)
 
+    def numel_of(self, key):
+        n = 1
+        for s in self.shapes[key]:
+            n *= s
+        return n
+
     def master(self, key):
         return self.view(self.P, key)
+
+    # ---- parameter groups ----------------------------------------------------------------------------
+    def set_groups(self, groups, weight_decay):
+        """Install (or, with None / a trivial spec, remove) the range table of `groups` (a ParamGroups)."""
+        if groups is None or groups.trivial:
+            self.opt_ranges, self.frozen = None, frozenset()
+            return None
+        tab = lib.OptRanges(groups.ranges(self, weight_decay), self.numel)
+        if self.P.is_cuda:
+            tab.to(self.P.device)
+        self.opt_ranges, self.frozen = tab, frozenset(groups.frozen)
+        return tab
+
+    def all_range(self, weight_decay):
+        """The table of the one-group step (EMA without any other option)."""
+        tab = lib.OptRanges([(0, self.numel, float(weight_decay), 1.0)], self.numel)
+        if self.P.is_cuda:
+            tab.to(self.P.device)
+        self.opt_ranges, self.frozen = tab, frozenset()
+        return tab
+
+    def is_frozen(self, t) -> bool:
+        """Does the gradient tensor `t` (a contiguous view of G) lie wholly inside frozen tensors?  (A fused q|k|v view
+        with only some members frozen does not: its gradient is computed, the frozen part is never read.)"""
+        if not self.frozen or self.G is None:
+            return False
+        if self._frozen_spans is None or self._frozen_spans[0] is not self.frozen:
+            spans = []
+            for a, b in sorted((self.offsets[k], self.offsets[k] + self.numel_of(k)) for k in self.frozen):
+                if spans and spans[-1][1] == a:
+                    spans[-1][1] = b
+                else:
+                    spans.append([a, b])
+            self._frozen_spans = (self.frozen, spans, [a for a, _ in spans])
+        import bisect
+        off = (t.data_ptr() - self.G.data_ptr()) // 4
+        _, spans, starts = self._frozen_spans
+        i = bisect.bisect_right(starts, off) - 1
+        return i >= 0 and spans[i][0] <= off and off + t.numel() <= spans[i][1]
+
+    def trainable_spans(self):
+        """Merged [begin, end) element spans of the tensors that train (whatever their hyper-parameters)."""
+        out = []
+        for key, off in self.offsets.items():
+            if key in self.frozen:
+                continue
+            n = self.numel_of(key)
+            if out and out[-1][1] == off:
+                out[-1] = (out[-1][0], off + n)
+            else:
+                out.append((off, off + n))
+        return out
+
+    def all_frozen(self, prefix: str) -> bool:
+        """Is every tensor whose key starts with `prefix` frozen?"""
+        if not self.frozen:
+            return False
+        ks = [k for k in self.shapes if k.startswith(prefix)]
+        return bool(ks) and all(k in self.frozen for k in ks)
+
+    def ensure_ema(self):
+        """The EMA buffer, a copy of P when first switched on."""
+        if self.E is None or self.E.device != self.P.device:
+            self.E = self.P.detach().clone()
+        return self.E
 
     def grad(self, key):
         return self.view(self.G, key)
@@ -140,13 +296,15 @@ class FlatParams:
     # ---- device / shadows --------------------------------------------------------------------------
     def to(self, fn):
         self.P = fn(self.P)
-        for n in ("G", "M", "V"):
+        for n in ("G", "M", "V", "E"):
             b = getattr(self, n)
             if b is not None:
                 setattr(self, n, fn(b))
         self.S = None
         self.ST = None
         self._shadow_version = -1
+        if self.opt_ranges is not None and self.P.is_cuda:
+            self.opt_ranges.to(self.P.device)
         if self.P.dtype != torch.float32:
             raise TypeError("MR-MT3 master weights stay fp32; pick the compute dtype on the model")
 
@@ -218,6 +376,18 @@ class FlatParams:
         self._optimizer_launch(lambda: lib.adamw_step_clipped(self.P, self.G, self.M, self.V, lr_dev, step_dev, stat_dev,
                                                               betas[0], betas[1], eps, weight_decay, grad_scale, clip_value,
                                                               shadow=self.S))
+
+    def adamw_step_groups(self, lr_dev, step_dev, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, ema_decay=None,
+                          stat_dev=None, clip_value=0.0):
+        """adamw_step / adamw_step_clipped (with `stat_dev`) over the installed range table only — weight decay and lr
+        factor come from the table — and, with `ema_decay`, the EMA of P in the same launch."""
+        if self.opt_ranges is None:
+            raise RuntimeError("adamw_step_groups: no range table is installed (FlatParams.set_groups)")
+        ema = self.ensure_ema() if ema_decay is not None else None
+        self._optimizer_launch(lambda: lib.adamw_step_groups(self.P, self.G, self.M, self.V, self.opt_ranges.to(self.P.device),
+                                                             lr_dev, step_dev, betas[0], betas[1], eps, grad_scale,
+                                                             ema=ema, ema_decay=ema_decay or 0.0, stat=stat_dev,
+                                                             clip_value=clip_value, shadow=self.S))
 
     def _optimizer_launch(self, launch):
         """What every optimizer step does around its one launch: moments and shadows exist before it, the transposed

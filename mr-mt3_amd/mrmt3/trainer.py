@@ -71,9 +71,20 @@ row, its gradient, and the plain NLL beside it.  Both are by-value launch argume
 the captured step and of no signature.  `train_step` returns the objective (`last_loss`), `last_nll` is the plain NLL; both
 are handled alike (device scalars, one per micro-batch, reduced over ranks).  `eval_loss` stays the plain NLL.  With both
 zero the old entry points run — the same launches as before — and `last_nll` is `last_loss`.
+
+Parameter groups and EMA weights (`frozen`, `no_decay`, `lr_scale`, `ema_decay`).  The patterns are fnmatch patterns
+over the state-dict keys.  With any of them given the optimizer tail is mrmt3_adamw_step_groups (and mrmt3_grad_norm_ranges
+when the clipping tail is on) over a device table of the trainable ranges: a frozen tensor is never read or written, gets no
+weight gradient (Engine.wgrad drops it, so the grouped launch plans fewer items), no place in a gradient bucket, and when the
+whole encoder is frozen the backward stops at the cross-attention k|v projections.  The table is device memory read by
+pointer: the captured step follows it.  `set_frozen()` changes the set between steps and drops the captured graphs (two
+eager warm-up steps, then a new capture); moments are never zeroed, a re-thawed tensor resumes with the ones it had.  With
+`ema_decay` the same launch keeps `flat.E`, the EMA of the weights (`ema_state_dict()`, `with trainer.ema_weights():`).  With
+none of the four given nothing changes: the same calls, graphs and launches as before.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import torch
@@ -81,6 +92,7 @@ import torch.distributed as dist
 
 from . import lib
 from .ddp import GradBuckets
+from .params import ALIASES, ParamGroups, ema_decay_option
 
 
 _RETIRED = []
@@ -136,7 +148,9 @@ class Trainer:
                  graph: bool = None, grad_exchange_dtype=None, pack_targets: bool = None,
                  accumulate_grad_batches: int = 1, gradient_clip_val=None, gradient_clip_algorithm: str = "norm",
                  skip_nonfinite: bool = False, track_grad_norm: bool = False, label_smoothing: float = 0.0,
-                 z_loss: float = 0.0):
+                 z_loss: float = 0.0, frozen=None, no_decay=None, lr_scale=None, ema_decay=None):
+        self.ema_decay = ema_decay_option(ema_decay)
+        self._ema_swapped = False
         self.loss_reg, self.label_smoothing, self.z_loss = lib.ce_options(label_smoothing, z_loss)
         self.clip_on, self._max_norm, self._clip_value, self.skip_nonfinite = clip_options(
             gradient_clip_val, gradient_clip_algorithm, skip_nonfinite, track_grad_norm)
@@ -152,6 +166,7 @@ class Trainer:
             raise ValueError("pack_targets is not supported for segmem_v1: its memory slots are prepended to the decoder input, "
                              "so the decoder rows cannot be cut to the scored prefix")
         self.model, self.flat, self.engine = model, model.flat, model.engine
+        self.groups = ParamGroups(model.flat.shapes, frozen, no_decay, lr_scale)      # (host only: raises before anything is built)
         assert model.device.type == "cuda", "the trainer drives the HIP kernels: move the model to the GPU first"
         self.base_lr, self.lr_lambda = lr, lr_lambda
         self.betas, self.eps, self.wd = betas, eps, weight_decay
@@ -178,6 +193,10 @@ class Trainer:
         self.flat.ensure_adam()
         if self.world > 1:   # C2: identical replicas
             dist.broadcast(self.flat.P, src=0)
+        self._install_groups()
+        if self.ema_decay is not None:
+            self.flat.E = None
+            self.flat.ensure_ema()                           # a copy of P (after the broadcast: the same on every rank)
         self.last_loss = None
         self.last_nll = None             # the plain NLL of the last (micro-)batch; `last_loss` itself when no loss option is on
         # norm / clip coefficient / skip flag of the last optimizer step, the skip counter and the norm kernel's partials:
@@ -286,9 +305,108 @@ class Trainer:
             lib.counter_add(self.salt_dev, 1)               # the next micro-batch draws other masks
         return loss, nll
 
+    # ---- parameter groups / EMA -----------------------------------------------------------------------------------------
+    @property
+    def groups_on(self) -> bool:
+        """Does the optimizer tail run over a range table (any group option, or EMA)?"""
+        return self.flat.opt_ranges is not None
+
+    def _install_groups(self):
+        """The range table of `self.groups` in device memory (EMA alone: one range over everything), the trainable slices
+        of the gradient buckets; with no option at all: nothing, the one-group step."""
+        if self.groups.trivial:
+            self.flat.set_groups(None, self.wd)
+            if self.ema_decay is not None:
+                self.flat.all_range(self.wd)
+            self.buckets.set_trainable(None)
+        else:
+            self.flat.set_groups(self.groups, self.wd)
+            self.buckets.set_trainable(self.flat.trainable_spans() if self.groups.frozen else None)
+
+    def _drop_graphs(self):
+        """Forget every captured step, outside any capture (see close()); the next steps warm up eagerly and recapture."""
+        import gc
+        torch.cuda.synchronize()
+        self._graphs.clear()
+        self._eager_seen.clear()
+        self._pack_lru.clear()
+        gc.collect()
+        torch.cuda.synchronize()
+
+    def set_frozen(self, patterns):
+        """Change the frozen set between optimizer steps (None / []: thaw everything).  Nothing is zeroed — a thawed
+        tensor continues with the moments it had; the captured graphs are dropped, so the next steps of each input shape
+        run eagerly (`graph_warmup`) and are then captured again with the new pruning."""
+        if self._micro:
+            raise RuntimeError("set_frozen: %d micro-batch(es) of an accumulation cycle are pending" % self._micro)
+        if self._ema_swapped:
+            raise RuntimeError("set_frozen inside `with trainer.ema_weights()`")
+        groups = ParamGroups(self.flat.shapes, patterns, self.groups.patterns["no_decay"], self.groups.patterns["lr_scale"])
+        self._drop_graphs()
+        self.engine.reset_deferred()
+        self.groups = groups
+        self._install_groups()
+
+    def ema_state_dict(self):
+        """The EMA weights in the model's (= the reference's) state-dict schema, on the CPU."""
+        if self.ema_decay is None:
+            raise RuntimeError("ema_state_dict: the trainer was built without ema_decay")
+        torch.cuda.current_stream().synchronize()
+        out = type(self.model.state_dict())()
+        for k, v in self.model.state_dict().items():
+            key = ALIASES.get(k, k)
+            src = self.flat.view(self.flat.E, key) if key in self.flat.shapes else v
+            out[k] = src.detach().cpu().clone()
+        return out
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Evaluate / decode / score with the EMA weights: inside the block the master buffer holds the EMA (the buffers
+        keep their addresses — parameters, decoder handles and captured graphs all point into them — their contents are
+        exchanged), the bf16 shadow and the transposed copies are rebuilt from it; on exit the training weights and their
+        shadow come back bit for bit.  Training inside the block is a RuntimeError."""
+        if self.ema_decay is None:
+            raise RuntimeError("ema_weights: the trainer was built without ema_decay")
+        if self._ema_swapped:
+            raise RuntimeError("ema_weights: already inside the context")
+        flat = self.flat
+        with torch.no_grad():
+            keep_p = flat.P.clone()
+            keep_s = None if flat.S is None else flat.S.clone()
+            flat.P.copy_(flat.E)
+            if flat.S is not None:
+                flat.refresh_shadows(force=True, need_transposed=flat.ST is not None)
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            with torch.no_grad():
+                flat.P.copy_(keep_p)
+                if keep_s is not None:
+                    flat.S.copy_(keep_s)
+                    if flat.ST is not None:
+                        flat.refresh_transposed()
+                    flat._shadow_version = flat.master_version()
+                else:
+                    flat._shadow_version = -1                # a shadow first made inside the block holds the EMA: recast
+            self._ema_swapped = False
+
+    def _no_training_in_ema(self, what):
+        if self._ema_swapped:
+            raise RuntimeError("%s inside `with trainer.ema_weights()`: the master buffer holds the EMA weights" % what)
+
     def _optimizer_tail(self):
         """AdamW on the exchanged G; with clipping / norm tracking / the non-finite guard on, the device-side norm first."""
         scale = 1.0 / (self.world * self.accumulate)
+        if self.groups_on:
+            tab = self.flat.opt_ranges
+            if self.clip_on:
+                lib.grad_norm_ranges(self.flat.G, tab, scale, self._max_norm, self.skip_nonfinite, self._clip_ws,
+                                     self._clip_stat, self._skipped_dev)
+            self.flat.adamw_step_groups(self.lr_dev, self.step_dev, self.betas, self.eps, grad_scale=scale,
+                                        ema_decay=self.ema_decay, stat_dev=self._clip_stat if self.clip_on else None,
+                                        clip_value=self._clip_value if self.clip_on else 0.0)
+            return
         if not self.clip_on:
             self.flat.adamw_step(self.lr_dev, self.step_dev, self.betas, self.eps, self.wd, grad_scale=scale)
             return
@@ -314,6 +432,7 @@ class Trainer:
         this rank over this (micro-)batch, undivided by N: the objective whose gradient was taken.  With label_smoothing /
         z_loss on, `last_nll` holds the plain NLL of the same (micro-)batch."""
         m, eng = self.model, self.engine
+        self._no_training_in_ema("train_step")
         m.train()
         if self.buckets.active and not self._collective_stream_checked:
             # once, before the first exchange: the collectives only overlap the rest of backward if their stream sits on
@@ -358,6 +477,7 @@ class Trainer:
         1/(world*N) as a full cycle.  Nothing happens when no micro-batch is pending.  Returns whether a step ran."""
         if self._micro == 0:
             return False
+        self._no_training_in_ema("finish_accumulation")
         if self.lr_lambda is not None:
             self.lr_dev.fill_(self.base_lr * self.lr_lambda(self.host_step))
         self.buckets.reset()
@@ -626,13 +746,7 @@ class Trainer:
         """Release what the trainer holds on the device in an order that is safe: drain, drop the captured graphs (their
         executables are destroyed now, not by the garbage collector at some later HIP-illegal moment), then the library's
         communicator if the buckets made one.  The trainer is unusable for graph replay afterwards; eager steps still work."""
-        import gc
-        torch.cuda.synchronize()
-        self._graphs.clear()
-        self._eager_seen.clear()
-        self._pack_lru.clear()
-        gc.collect()
-        torch.cuda.synchronize()
+        self._drop_graphs()
         self._drop_capture_stream()
         self.buckets.close()
 
@@ -662,11 +776,27 @@ class Trainer:
         step training continues from."""
         from . import checkpoint as ck
         blob = ck.read_checkpoint(path)
+        self._no_training_in_ema("resume")
         self.model.load_state_dict(blob["state_dict"], strict=strict)
         step = 0
+        saved = (blob["extra"] or {}).get("groups")
+        if saved is not None:            # the run's frozen set and group hyper-parameters (a checkpoint without: as built)
+            groups = ParamGroups(self.flat.shapes, saved["frozen"], saved["no_decay"], saved["lr_scale"])
+            self._drop_graphs()
+            self.groups = groups
+            if saved.get("ema_decay") is not None:
+                self.ema_decay = ema_decay_option(saved["ema_decay"])
+            self._install_groups()
+        if self.ema_decay is not None:
+            ema = (blob["extra"] or {}).get("ema")
+            self.flat.E = None
+            self.flat.ensure_ema()       # a checkpoint without an EMA: it restarts from the loaded weights
+            if ema is not None:
+                for k, v in ema.items():
+                    self.flat.view(self.flat.E, k).copy_(v)
         if blob["optimizer"] is not None:
             order = ck.reference_parameter_order(self.model.cfg, self.model.segmem_num_layers)
-            step = ck.adamw_state_to_flat(blob["optimizer"], self.flat, order)
+            step = ck.adamw_state_to_flat(blob["optimizer"], self.flat, order, groups=self.groups, weight_decay=self.wd)
             step = max(step, blob["global_step"])
         self.host_step = step
         self._micro = 0
@@ -681,6 +811,8 @@ class Trainer:
             dist.broadcast(self.flat.P, src=0)
             dist.broadcast(self.flat.M, src=0)
             dist.broadcast(self.flat.V, src=0)
+            if self.flat.E is not None:
+                dist.broadcast(self.flat.E, src=0)
         return step
 
     @torch.no_grad()

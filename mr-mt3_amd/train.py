@@ -31,6 +31,12 @@ Loss options: top-level `label_smoothing` (torch.nn.CrossEntropyLoss's keyword) 
 1e-4): `+label_smoothing=0.1 +z_loss=1e-4`.  With either on, `train_loss` is the regularised objective and the step lines
 carry the plain NLL next to it (`step N train_loss X nll Y`), the number that compares to `val_loss` and to other runs.
 
+Parameter groups and EMA weights: top-level `freeze` and `no_decay`, lists of fnmatch patterns over the
+state-dict keys (`+freeze='["encoder.*"]' +no_decay='["*layer_norm.weight"]'`), and `ema_decay` (`+ema_decay=0.999`).
+Frozen tensors get no gradient and no update; `no_decay` tensors step with weight decay 0.  With `ema_decay`, validation
+prints `val_loss` (training weights) and `val_loss_ema`, and `last_ema.pt` (the EMA weights as a bare state dict) is written
+next to `last.pt`; `+export_weights=ema` makes `last.pt` itself the EMA weights.
+
 `cfg.path` has the reference's meaning (`train.py:61-92`): a `.ckpt` resumes weights, AdamW moments and
 the step counter; a `.pth` only loads weights (`strict=False`); anything else is an error.  At the end
 rank 0 writes `<output_dir>/<model_type>_<dataset_type>/version_0/checkpoints/last.ckpt` (Lightning
@@ -160,6 +166,48 @@ def loss_options(cfg):
     return eps, z
 
 
+def _pattern_list(cfg, key):
+    """A top-level list of fnmatch patterns (absent or null: None).  Anything but a list of strings is a ValueError
+    naming the key; whether a pattern matches a parameter is the trainer's check."""
+    raw = cfg.get(key)
+    if raw is None or (isinstance(raw, str) and raw.lower() in ("", "none", "null")):
+        return None
+    if isinstance(raw, str) or not hasattr(raw, "__iter__"):
+        raise ValueError("%s must be a list of patterns, e.g. +%s='[\"encoder.*\"]', got %r" % (key, key, raw))
+    out = list(raw)
+    for pat in out:
+        if not isinstance(pat, str) or not pat:
+            raise ValueError("%s must be a list of non-empty strings, got the entry %r" % (key, pat))
+    return out or None
+
+
+EXPORT_CHOICES = ("train", "ema")
+
+
+def group_options(cfg):
+    """(frozen, no_decay, ema_decay, export) from the top-level keys `freeze`, `no_decay`, `ema_decay` and
+    `export_weights`, validated like the loss options: a ValueError names the key."""
+    from mrmt3.params import ema_decay_option
+    frozen, no_decay = _pattern_list(cfg, "freeze"), _pattern_list(cfg, "no_decay")
+    raw = cfg.get("ema_decay")
+    if raw is None or str(raw).lower() in ("", "none", "null"):
+        ema = None
+    else:
+        try:
+            ema = float(raw)
+        except (TypeError, ValueError):
+            raise ValueError("ema_decay must be a number in (0, 1), got %r" % (raw,)) from None
+        if isinstance(raw, bool):
+            raise ValueError("ema_decay must be a number in (0, 1), got %r" % (raw,))
+        ema = ema_decay_option(ema)
+    export = str(cfg.get("export_weights", "train")).lower()
+    if export not in EXPORT_CHOICES:
+        raise ValueError("export_weights must be one of %s, got %r" % (EXPORT_CHOICES, export))
+    if export == "ema" and ema is None:
+        raise ValueError("export_weights=ema needs ema_decay")
+    return frozen, no_decay, ema, export
+
+
 def format_step_line(it, loss, nll=None, grad_norm=None):
     """Rank 0's log line of optimizer step `it`: `step N train_loss X`, then `nll Y` when a loss option is on and
     `grad_norm G` when the clipping tail is (floats; None leaves the field out)."""
@@ -246,10 +294,12 @@ def main(argv=None):
     clip_val, clip_algo = gradient_clipping(cfg)
     skip_nonfinite = str(cfg.get("skip_nonfinite", False)).lower() in _TRUTHY
     label_smoothing, z_loss = loss_options(cfg)
+    frozen, no_decay, ema_decay, export = group_options(cfg)
     trainer = Trainer(task.model, lr=float(cfg.optim.lr), lr_lambda=lam,
                       weighted_loss=type(task).__name__ == "MT3NetWeightedLoss", pack_targets=pack,
                       accumulate_grad_batches=accum, gradient_clip_val=clip_val, gradient_clip_algorithm=clip_algo,
-                      skip_nonfinite=skip_nonfinite, label_smoothing=label_smoothing, z_loss=z_loss)
+                      skip_nonfinite=skip_nonfinite, label_smoothing=label_smoothing, z_loss=z_loss, frozen=frozen,
+                      no_decay=no_decay, ema_decay=ema_decay)
 
     def step_line(it, loss):
         """Rank 0's log line of optimizer step `it` (reads the device: only at the logging cadence)."""
@@ -309,6 +359,18 @@ def main(argv=None):
                 dist.all_reduce(acc, op=dist.ReduceOp.SUM)
             if rank == 0 and acc[1].item() > 0:
                 print(f"epoch {ep} val_loss {(acc[0] / acc[1]).item():.4f}", flush=True)
+            if ema_decay is None:
+                return
+            acc.zero_()
+            with trainer.ema_weights():
+                for b in val_loader:
+                    prev = b[2].to(device) if len(b) > 2 else None
+                    acc[0] += trainer.eval_loss(b[0].to(device), b[1].to(device), prev).double().sum()
+                    acc[1] += 1
+            if world > 1:
+                dist.all_reduce(acc, op=dist.ReduceOp.SUM)
+            if rank == 0 and acc[1].item() > 0:
+                print(f"epoch {ep} val_loss_ema {(acc[0] / acc[1]).item():.4f}", flush=True)
 
         def stepped(loss):
             """An optimizer step has run; `loss` is its last micro-batch's."""
@@ -345,7 +407,12 @@ def main(argv=None):
                                "version_0", "checkpoints")
         os.makedirs(out_dir, exist_ok=True)
         trainer.save_checkpoint(os.path.join(out_dir, "last.ckpt"), epoch=0 if synthetic else last_ep)
-        trainer.save_checkpoint(os.path.join(out_dir, "last.pt"))
+        if ema_decay is not None:
+            torch.save(trainer.ema_state_dict(), os.path.join(out_dir, "last_ema.pt"))
+        if export == "ema":
+            torch.save(trainer.ema_state_dict(), os.path.join(out_dir, "last.pt"))
+        else:
+            trainer.save_checkpoint(os.path.join(out_dir, "last.pt"))
         print(f"Saved model in {os.path.join(out_dir, 'last.pt')}.", flush=True)
     trainer.close()                      # captured graphs, then the library's own RCCL communicator (MRMT3_DDP_NATIVE), before torch's
     if world > 1:
