@@ -945,11 +945,15 @@ def test_transpose_cast(dev):
 
 
 def test_transpose_batched_even_and_odd_shapes(dev):
-    """One launch, several matrices in flat buffers: pair-vectorised path (even dims / offsets) and the scalar
-    fallback (odd dims or offsets), tiles that overhang the matrix."""
+    """One launch, several matrices laid out back to back in flat buffers.  Which path each takes (csrc/rowops.hip
+    transpose_batched_kernel): (384, 512) at offset 0 moves 16 bytes per lane; (70, 130) has even dimensions and an even
+    offset and moves pairs, with overhanging tiles; (33, 7) has odd dimensions and moves single elements.  Its 231 elements
+    leave EVERY later matrix at an odd offset, so (64, 64), (5, 1000), (136, 72), (2048, 512) and (72, 200) move single
+    elements too, whatever their dimensions.  The 16-byte path next to overhanging tiles of the same matrix, and the pair
+    path at offsets = 2 (mod 8), are run by tests/test_exact_rows_gpu.py."""
     import numpy as np
     from mrmt3 import lib
-    shapes = [(384, 512), (70, 130), (33, 7), (64, 64), (5, 1000), (136, 72), (2048, 512), (72, 200)]   # (multiples of 8: the 16-byte path inside, the scalar path on overhanging tiles)
+    shapes = [(384, 512), (70, 130), (33, 7), (64, 64), (5, 1000), (136, 72), (2048, 512), (72, 200)]
     src_parts, recs, starts, tot, so, do = [], [], [], 0, 0, 0
     for r, c in shapes:
         src_parts.append(torch.randn(r * c, device=dev).bfloat16())
