@@ -395,14 +395,106 @@ __device__ __forceinline__ bool argmax_beats(float v, int i, float bv, int bi) {
   return i < bi;
 }
 
-// BAN: banned tokens (ban[c] != 0, a device [V] uint8 mask) score -inf before the argmax, NaN included, as HF's
-// NoBadWordsLogitsProcessor does ahead of the greedy argmax.  The unbanned kernel is this body with BAN = false.
-// (`ban` is the last argument, so the unbanned instantiation keeps every other argument's offset and its code.)
-// LOGP: the wave also writes the log-probability of the token it emits, logp[b * logp_ld + t + 1].  It keeps
-// its row in registers (LOGP_REGS values per lane, V <= 64 * LOGP_REGS), so the row is still read once: maximum after the
-// ban (NaN-propagating), sum of exp(l - max) per lane in ascending index then the xor tree, (l[idx] - max) - log(sum).
-// A row that had finished writes 0.0 for its pad; prefix steps write nothing.  (`logp`, `logp_ld` come after `ban`.)
+// ---- a vocabulary row in one wave's registers (LOGP_REGS values per lane, V <= 64 * LOGP_REGS): rl[i] = column lane + 64 i
 #define LOGP_REGS 32
+// the row after the ban: banned columns and columns past V hold -inf
+template <bool BAN>
+__device__ __forceinline__ void load_row(float (&rl)[LOGP_REGS], const float* __restrict__ lrow, int V, int lane,
+                                         const uint8_t* __restrict__ ban) {
+#pragma unroll
+  for (int i = 0; i < LOGP_REGS; ++i) {
+    const int col = lane + 64 * i;
+    rl[i] = (col < V) ? lrow[col] : -INFINITY;
+  }
+  if (BAN) {
+#pragma unroll
+    for (int i = 0; i < LOGP_REGS; ++i)
+      if (lane + 64 * i < V && ban[lane + 64 * i]) rl[i] = -INFINITY;
+  }
+}
+// its argmax (ascending column per lane, then the xor tree): best = l[idx] in every lane
+__device__ __forceinline__ void argmax_row(const float (&rl)[LOGP_REGS], int V, int lane, float& best, int& idx) {
+  float bv = -INFINITY;                  // accumulated in locals, not through the references: one chain of selects
+  int bi = -1;                           // -1: this lane has seen no logit yet (lanes >= V when V < 64)
+#pragma unroll
+  for (int i = 0; i < LOGP_REGS; ++i) {
+    const int col = lane + 64 * i;
+    if (argmax_beats(rl[i], col < V ? col : -1, bv, bi)) { bv = rl[i]; bi = col; }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float ov = __shfl_xor(bv, off, 64);
+    const int oi = __shfl_xor(bi, off, 64);
+    if (argmax_beats(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+  }
+  best = bv;
+  idx = bi;
+}
+// its log-softmax sums: mx the NaN-propagating maximum, se (SUM) the sum of exp(l - mx), per lane in ascending
+// index then the xor tree; log p(c) = (l[c] - mx) - log(se).  -inf columns add exp(-inf) = 0.
+template <bool SUM>
+__device__ __forceinline__ void row_logsumexp(const float (&rl)[LOGP_REGS], float& mx, float& se) {
+  mx = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < LOGP_REGS; ++i) mx = nanmax(mx, rl[i]);
+  mx = wave_nanmax(mx);
+  se = 0.f;
+  if (SUM) {
+#pragma unroll
+    for (int i = 0; i < LOGP_REGS; ++i) se += expf(rl[i] - mx);
+    se = wave_sum(se);
+  }
+}
+
+// ---- what the greedy and the sampled tail share -------------------------------------------------------------------
+// A step inside the prefix (p + 1 <= npre): the next input is the next memory row, or the start token right after the last
+// one (models/t5_segmem.py:203-213); this step's logits are discarded and nothing is drawn.  512 threads = DMODEL.
+__device__ __forceinline__ void dec_prefix_step(int B, const int64_t* __restrict__ tokens, int tok_ld,
+                                                const float* __restrict__ embed, const float* __restrict__ pos,
+                                                float* __restrict__ x, int* __restrict__ state,
+                                                const float* __restrict__ prefix, int p, int npre) {
+  const int tid = threadIdx.x;
+  for (int b = blockIdx.x * 8; b < min(B, (int)blockIdx.x * 8 + 8); ++b) {
+    const float* er = (p + 1 < npre) ? prefix + ((size_t)b * npre + p + 1) * DMODEL
+                                     : embed + (size_t)tokens[(size_t)b * tok_ld] * DMODEL;
+    const float* pr = pos + (size_t)(p + 1) * DMODEL;
+    x[b * DMODEL + tid] = er[tid] + pr[tid];
+  }
+  __syncthreads();
+  if (tid == 0) dec_step_close(state, B, p, 0, false);
+}
+// The lane's share of the next position's positional row: it does not depend on the token, so a token step requests it
+// (and the finished flag) before its argmax or draw.
+__device__ __forceinline__ void dec_load_pos(float (&pv)[DMODEL / 64], const float* __restrict__ pos, int p, int lane) {
+  const float* pr = pos + (size_t)(p + 1) * DMODEL;
+#pragma unroll
+  for (int c = 0; c < DMODEL / 64; ++c) pv[c] = pr[c * 64 + lane];
+}
+// Row b's epilogue of token step t, by its wave: the chosen `idx` (in [0, V): lane 0 always holds index 0) or pad for a
+// row that had finished, the next input x = embedding + positional row, the EOS flag, the token and (LOGP) its
+// log-probability, 0.0 for a pad.
+template <bool LOGP>
+__device__ __forceinline__ void dec_emit_row(int b, int t, int lane, int idx, float lp_tok, int was_done, int eos, int pad,
+                                             const float (&pv)[DMODEL / 64], const float* __restrict__ embed,
+                                             float* __restrict__ x, int* __restrict__ state, int64_t* __restrict__ tokens,
+                                             int tok_ld, float* __restrict__ logp, int logp_ld) {
+  const int nxt = was_done ? pad : idx;
+  const float* er = embed + (size_t)nxt * DMODEL;
+#pragma unroll
+  for (int c = 0; c < DMODEL / 64; ++c) x[b * DMODEL + c * 64 + lane] = er[c * 64 + lane] + pv[c];
+  if (lane == 0) {
+    if (!was_done && nxt == eos) __hip_atomic_store(&state[ST_FLAGS + b], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    tokens[(size_t)b * tok_ld + t + 1] = nxt;
+    if (LOGP) logp[(size_t)b * logp_ld + t + 1] = was_done ? 0.f : lp_tok;
+  }
+}
+
+// The greedy tail.  BAN: banned tokens (ban[c] != 0, a device [V] uint8 mask) score -inf before the argmax, NaN included, as
+// HF's NoBadWordsLogitsProcessor does ahead of the greedy argmax.  The unbanned kernel is this body with BAN = false.
+// (`ban` is the last argument, so the unbanned instantiation keeps every other argument's offset and its code.)
+// LOGP: the wave also writes the log-probability of the token it emits, logp[b * logp_ld + t + 1], and keeps
+// its row in registers, so the row is still read once; without LOGP it streams the row eight values at a time.
+// Prefix steps write nothing.  (`logp`, `logp_ld` come after `ban`.)
 template <bool BAN, bool LOGP>
 __global__ __launch_bounds__(512) void dec_argmax(const float* __restrict__ logits, int V, int B, int64_t* __restrict__ tokens,
                                                   int tok_ld, const float* __restrict__ embed, const float* __restrict__ pos,
@@ -413,47 +505,23 @@ __global__ __launch_bounds__(512) void dec_argmax(const float* __restrict__ logi
   const int p = state[ST_T];            // position just processed
   const int npre = state[ST_NPRE];
   if (p + 1 <= npre) {
-    // still inside the prefix: the next input is the next memory row, or the start token right after
-    // the last one (models/t5_segmem.py:203-213); this step's logits are discarded
-    for (int b = blockIdx.x * 8; b < min(B, (int)blockIdx.x * 8 + 8); ++b) {
-      const float* er = (p + 1 < npre) ? prefix + ((size_t)b * npre + p + 1) * DMODEL
-                                       : embed + (size_t)tokens[(size_t)b * tok_ld] * DMODEL;
-      const float* pr = pos + (size_t)(p + 1) * DMODEL;
-      x[b * DMODEL + tid] = er[tid] + pr[tid];          // 512 threads = DMODEL
-    }
-    __syncthreads();
-    if (tid == 0) dec_step_close(state, B, p, 0, false);
+    dec_prefix_step(B, tokens, tok_ld, embed, pos, x, state, prefix, p, npre);
     return;
   }
   const int t = p - npre;               // token step
-  // first-maximum argmax, EOS bookkeeping, next embedding.  Everything that does not depend on the winner
-  // (finished flag, positional row) is requested up front.
   const int b = blockIdx.x * 8 + wave;
   if (b < B) {
     const int was_done = state[ST_FLAGS + b];
-    const float* pr = pos + (size_t)(p + 1) * DMODEL;
     float pv[DMODEL / 64];
-#pragma unroll
-    for (int c = 0; c < DMODEL / 64; ++c) pv[c] = pr[c * 64 + lane];
-    float best = -INFINITY;
-    int idx = -1;                        // -1: this lane has seen no logit yet (lanes >= V when V < 64)
-    float rl[LOGP ? LOGP_REGS : 1];      // LOGP: the lane's logits after the ban, rl[i] = column lane + 64 i (-inf past V)
+    dec_load_pos(pv, pos, p, lane);
+    float best = -INFINITY, lp_tok = 0.f;
+    int idx = -1;
     if (LOGP) {
-#pragma unroll
-      for (int i = 0; i < LOGP_REGS; ++i) {
-        const int c = lane + 64 * i;
-        rl[i] = (c < V) ? logits[(size_t)b * V + c] : -INFINITY;
-      }
-      if (BAN) {
-#pragma unroll
-        for (int i = 0; i < LOGP_REGS; ++i)
-          if (lane + 64 * i < V && ban[lane + 64 * i]) rl[i] = -INFINITY;
-      }
-#pragma unroll
-      for (int i = 0; i < LOGP_REGS; ++i) {
-        const int c = lane + 64 * i;
-        if (argmax_beats(rl[i], c < V ? c : -1, best, idx)) { best = rl[i]; idx = c; }      // ascending c per lane
-      }
+      float rl[LOGP_REGS], mx, se;
+      load_row<BAN>(rl, logits + (size_t)b * V, V, lane, ban);
+      argmax_row(rl, V, lane, best, idx);
+      row_logsumexp<true>(rl, mx, se);
+      lp_tok = (best - mx) - logf(se);
     } else {
       for (int c0 = lane; c0 < V; c0 += 512) {
         float lv[8];
@@ -470,36 +538,14 @@ __global__ __launch_bounds__(512) void dec_argmax(const float* __restrict__ logi
           if (argmax_beats(lv[u], c < V ? c : -1, best, idx)) { best = lv[u]; idx = c; }   // ascending c per lane
         }
       }
-    }
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float ov = __shfl_xor(best, off, 64);
-      const int oi = __shfl_xor(idx, off, 64);
-      if (argmax_beats(ov, oi, best, idx)) { best = ov; idx = oi; }
+      for (int off = 32; off > 0; off >>= 1) {
+        const float ov = __shfl_xor(best, off, 64);
+        const int oi = __shfl_xor(idx, off, 64);
+        if (argmax_beats(ov, oi, best, idx)) { best = ov; idx = oi; }
+      }
     }
-    float lp_tok = 0.f;
-    if (LOGP) {
-      // best = l[idx] in every lane.  Columns past V and banned ones are -inf: exp gives 0.
-      float mx = -INFINITY;
-#pragma unroll
-      for (int i = 0; i < LOGP_REGS; ++i) mx = nanmax(mx, rl[i]);
-      mx = wave_nanmax(mx);
-      float se = 0.f;
-#pragma unroll
-      for (int i = 0; i < LOGP_REGS; ++i) se += expf(rl[i] - mx);
-      se = wave_sum(se);
-      lp_tok = (best - mx) - logf(se);
-    }
-    // lane 0 always holds index 0 (V > 0), so idx is in [0, V) here whatever the logits hold
-    const int nxt = was_done ? pad : idx;
-    const float* er = embed + (size_t)nxt * DMODEL;
-#pragma unroll
-    for (int c = 0; c < DMODEL / 64; ++c) x[b * DMODEL + c * 64 + lane] = er[c * 64 + lane] + pv[c];
-    if (lane == 0) {
-      if (!was_done && nxt == eos) __hip_atomic_store(&state[ST_FLAGS + b], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      tokens[(size_t)b * tok_ld + t + 1] = nxt;
-      if (LOGP) logp[(size_t)b * logp_ld + t + 1] = was_done ? 0.f : lp_tok;
-    }
+    dec_emit_row<LOGP>(b, t, lane, idx, lp_tok, was_done, eos, pad, pv, embed, x, state, tokens, tok_ld, logp, logp_ld);
   }
   __syncthreads();
   if (tid == 0) dec_step_close(state, B, p, t, true);
@@ -627,30 +673,9 @@ template <bool LOGP>
 __device__ __forceinline__ void sample_token(float (&rl)[LOGP_REGS], const float* __restrict__ lrow, int V, int lane,
                                              bool draw, const SampleCfg& c, unsigned row, unsigned step, int& tok,
                                              float& lp) {
-  float best = -INFINITY;
-  int idx = -1;
-#pragma unroll
-  for (int i = 0; i < LOGP_REGS; ++i) {
-    const int col = lane + 64 * i;
-    if (argmax_beats(rl[i], col < V ? col : -1, best, idx)) { best = rl[i]; idx = col; }
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float ov = __shfl_xor(best, off, 64);
-    const int oi = __shfl_xor(idx, off, 64);
-    if (argmax_beats(ov, oi, best, idx)) { best = ov; idx = oi; }
-  }
-  float mx = -INFINITY;
-#pragma unroll
-  for (int i = 0; i < LOGP_REGS; ++i) mx = nanmax(mx, rl[i]);
-  mx = wave_nanmax(mx);
-  float se = 0.f;
-  if (LOGP) {
-#pragma unroll
-    for (int i = 0; i < LOGP_REGS; ++i) se += expf(rl[i] - mx);
-    se = wave_sum(se);
-  }
-  tok = idx;
+  float best, mx, se;
+  argmax_row(rl, V, lane, best, tok);
+  row_logsumexp<LOGP>(rl, mx, se);
   if (draw && mx == mx && fabsf(mx) != INFINITY) {
     tok = sample_draw(rl, mx, V, lane, c, row, step);
     best = lrow[tok];                     // a drawn column is never a banned one
@@ -658,24 +683,9 @@ __device__ __forceinline__ void sample_token(float (&rl)[LOGP_REGS], const float
   lp = LOGP ? (best - mx) - logf(se) : 0.f;
 }
 
-template <bool BAN>
-__device__ __forceinline__ void sample_load_row(float (&rl)[LOGP_REGS], const float* __restrict__ lrow, int V, int lane,
-                                                const uint8_t* __restrict__ ban) {
-#pragma unroll
-  for (int i = 0; i < LOGP_REGS; ++i) {
-    const int col = lane + 64 * i;
-    rl[i] = (col < V) ? lrow[col] : -INFINITY;
-  }
-  if (BAN) {
-#pragma unroll
-    for (int i = 0; i < LOGP_REGS; ++i)
-      if (lane + 64 * i < V && ban[lane + 64 * i]) rl[i] = -INFINITY;
-  }
-}
-
-// dec_argmax with the draw in place of the winner: prefix steps, finished rows, EOS bookkeeping, the next embedding and
-// the step close are its own.  `samp` is a device record (mrmt3_decoder_set_sampling writes it on the stream): a replayed
-// graph freezes its by-value arguments, the record's contents are read at every step.  Row b draws with counter (b, t).
+// dec_argmax with the draw in place of the winner.  `samp` is a device record (mrmt3_decoder_set_sampling writes it on the
+// stream): a replayed graph freezes its by-value arguments, the record's contents are read at every step.  Row b draws
+// with counter (b, t).
 template <bool BAN, bool LOGP>
 __global__ __launch_bounds__(512) void dec_sample(const float* __restrict__ logits, int V, int B, int64_t* __restrict__ tokens,
                                                   int tok_ld, const float* __restrict__ embed, const float* __restrict__ pos,
@@ -686,15 +696,7 @@ __global__ __launch_bounds__(512) void dec_sample(const float* __restrict__ logi
   const int p = state[ST_T];
   const int npre = state[ST_NPRE];
   if (p + 1 <= npre) {
-    // inside the prefix nothing is drawn: the next input is the next memory row or the start token (see dec_argmax)
-    for (int b = blockIdx.x * 8; b < min(B, (int)blockIdx.x * 8 + 8); ++b) {
-      const float* er = (p + 1 < npre) ? prefix + ((size_t)b * npre + p + 1) * DMODEL
-                                       : embed + (size_t)tokens[(size_t)b * tok_ld] * DMODEL;
-      const float* pr = pos + (size_t)(p + 1) * DMODEL;
-      x[b * DMODEL + tid] = er[tid] + pr[tid];
-    }
-    __syncthreads();
-    if (tid == 0) dec_step_close(state, B, p, 0, false);
+    dec_prefix_step(B, tokens, tok_ld, embed, pos, x, state, prefix, p, npre);
     return;
   }
   const int t = p - npre;
@@ -702,25 +704,15 @@ __global__ __launch_bounds__(512) void dec_sample(const float* __restrict__ logi
   if (b < B) {
     const int was_done = state[ST_FLAGS + b];
     const SampleCfg cfg = *samp;
-    const float* pr = pos + (size_t)(p + 1) * DMODEL;
     float pv[DMODEL / 64];
-#pragma unroll
-    for (int c = 0; c < DMODEL / 64; ++c) pv[c] = pr[c * 64 + lane];
+    dec_load_pos(pv, pos, p, lane);
     const float* lrow = logits + (size_t)b * V;
     float rl[LOGP_REGS];
-    sample_load_row<BAN>(rl, lrow, V, lane, ban);
+    load_row<BAN>(rl, lrow, V, lane, ban);
     int idx;
     float lp_tok;
     sample_token<LOGP>(rl, lrow, V, lane, !was_done, cfg, (unsigned)b, (unsigned)t, idx, lp_tok);
-    const int nxt = was_done ? pad : idx;
-    const float* er = embed + (size_t)nxt * DMODEL;
-#pragma unroll
-    for (int c = 0; c < DMODEL / 64; ++c) x[b * DMODEL + c * 64 + lane] = er[c * 64 + lane] + pv[c];
-    if (lane == 0) {
-      if (!was_done && nxt == eos) __hip_atomic_store(&state[ST_FLAGS + b], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      tokens[(size_t)b * tok_ld + t + 1] = nxt;
-      if (LOGP) logp[(size_t)b * logp_ld + t + 1] = was_done ? 0.f : lp_tok;
-    }
+    dec_emit_row<LOGP>(b, t, lane, idx, lp_tok, was_done, eos, pad, pv, embed, x, state, tokens, tok_ld, logp, logp_ld);
   }
   __syncthreads();
   if (tid == 0) dec_step_close(state, B, p, t, true);
@@ -737,7 +729,7 @@ __global__ __launch_bounds__(512) void sample_logits_kernel(const float* __restr
   if (r >= rows) return;
   const float* lrow = logits + (size_t)r * V;
   float rl[LOGP_REGS];
-  sample_load_row<BAN>(rl, lrow, V, lane, ban);
+  load_row<BAN>(rl, lrow, V, lane, ban);
   int idx;
   float lp_tok;
   sample_token<LOGP>(rl, lrow, V, lane, true, cfg, row0 + (unsigned)r, step, idx, lp_tok);
@@ -1305,23 +1297,18 @@ static void launch_tail(mrmt3_decoder* D, hipStream_t s) {
                        (char*)D->kc, (char*)D->vc, layer_bytes, row_bytes, (int)(D->inner * esz), D->L, T.groups, T.k,
                        (const int*)T.bp, (const int*)D->state);
   } else {
-#define DEC_SAMPLE(BAN, LOGP)                                                                                              \
-  hipLaunchKernelGGL((dec_sample<BAN, LOGP>), dim3((unsigned)ceil_div(B, 8)), dim3(512), 0, s, D->logits, V, B, D->tokens, \
-                     D->maxLen + 1, (const float*)D->w.embed, D->w.pos, D->x, D->state, D->eos, D->pad, D->prefix,        \
-                     D->tail.ban, D->tail.logp, D->tail.logp_ld, (const SampleCfg*)D->samp)
-#define DEC_ARGMAX(BAN, LOGP)                                                                                              \
-  hipLaunchKernelGGL((dec_argmax<BAN, LOGP>), dim3((unsigned)ceil_div(B, 8)), dim3(512), 0, s, D->logits, V, B, D->tokens, \
-                     D->maxLen + 1, (const float*)D->w.embed, D->w.pos, D->x, D->state, D->eos, D->pad, D->prefix,        \
-                     D->tail.ban, D->tail.logp, D->tail.logp_ld)
-    if (D->tail.sample) {
-      if (D->tail.logp) { if (D->tail.ban) DEC_SAMPLE(true, true); else DEC_SAMPLE(false, true); }
-      else if (D->tail.ban) DEC_SAMPLE(true, false);
-      else DEC_SAMPLE(false, false);
-    } else if (D->tail.logp) { if (D->tail.ban) DEC_ARGMAX(true, true); else DEC_ARGMAX(false, true); }
-    else if (D->tail.ban) DEC_ARGMAX(true, false);
-    else DEC_ARGMAX(false, false);
-#undef DEC_ARGMAX
-#undef DEC_SAMPLE
+    // the argument list dec_argmax and dec_sample share; `more`: what dec_sample takes beyond it
+    auto launch = [&](auto kernel, auto... more) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)ceil_div(B, 8)), dim3(512), 0, s, D->logits, V, B, D->tokens, D->maxLen + 1,
+                         (const float*)D->w.embed, D->w.pos, D->x, D->state, D->eos, D->pad, D->prefix, D->tail.ban,
+                         D->tail.logp, D->tail.logp_ld, more...);
+    };
+    auto tail = [&](auto ban, auto lp) {
+      if (D->tail.sample) launch(dec_sample<ban.value, lp.value>, (const SampleCfg*)D->samp);
+      else launch(dec_argmax<ban.value, lp.value>);
+    };
+    auto with_lp = [&](auto ban) { D->tail.logp ? tail(ban, std::true_type{}) : tail(ban, std::false_type{}); };
+    D->tail.ban ? with_lp(std::true_type{}) : with_lp(std::false_type{});
   }
 }
 

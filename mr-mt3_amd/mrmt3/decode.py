@@ -20,6 +20,12 @@ the log-probability the model gave each emitted token at its position, 0.0 for t
 `do_sample=True` (every entry point but the beam search): the step draws its token from the distribution HF's
 `sample()` builds (ban, `temperature`, `top_k`, `top_p`) instead of taking the argmax; the draw is a pure function of
 (`seed`, row of the decode batch, token step).  `generate_sample` / `generate_best_of` draw several transcriptions per segment.
+
+Structure: every entry point folds its keywords into one `_Options` record.  `Decoder.decode` decodes one batch in any mode
+(greedy, sampled, n samples per segment, beam) and returns owned `(ids, logp)`.  Three loops call it: `_decode_batched`
+(plain T5 and `segmem_v1`: chunks of `MAX_DECODE_BATCH` rows, padded and stacked), `_decode_chains` (the segment-memory
+chain of S recordings in lockstep; `generate` / `generate_beam` are S = 1, `generate_songs` groups of S) and `generate_2`'s
+prefix chain (the memory is a decoder prefix there, not extra cross-attention rows).
 """
 from __future__ import annotations
 
@@ -70,6 +76,24 @@ def _sampling(do_sample, temperature, top_k, top_p, seed):
     return Sampling(temperature, top_k, top_p, seed) if do_sample else None
 
 
+@dataclass(frozen=True)
+class _Options:
+    """What an entry point's keywords say about the decode, built once per call and handed down the loops."""
+    num_beams: int = 1
+    length_penalty: float = 1.0
+    bad_token_ids: object = None
+    sampling: "Sampling | None" = None
+    return_logprobs: bool = False
+    poll_every: int = 64
+    n: int = 1                     # rows per segment of a sampled decode (`num_return_sequences`)
+    through_poll: bool = False     # greedy / sampled ids run to the last step replayed, not to the finish step (`generate_songs`)
+
+    @property
+    def rows(self) -> int:
+        """Decode-batch rows per segment."""
+        return self.num_beams * self.n
+
+
 class _Weights(C.Structure):
     _fields_ = [("embed", C.c_void_p), ("pos", C.c_void_p), ("lm_head", C.c_void_p), ("final_ln", C.c_void_p)] + \
                [(n, C.POINTER(C.c_void_p)) for n in ("ln_self", "w_qkv", "w_o_self", "ln_cross", "w_q_cross",
@@ -98,6 +122,9 @@ class Decoder:
         # persistent cross-attention K|V buffer: a stable address lets the captured graph be reused
         self.ckv_buf = torch.empty(cfg["num_decoder_layers"] * max_batch * max_enc_len * 2 * eng.inner,
                                    device=model.device, dtype=self.dt)
+        # made on first use, then never reallocated: a captured step graph bakes their addresses in
+        self._ban_buf = self.logp = self._beam_logp = self._prefix_buf = None
+        self._bp = self._bscore = self._hyp = self._beam_out = None
 
     def __del__(self):
         try:
@@ -155,7 +182,7 @@ class Decoder:
         V = self.model.cfg["vocab_size"]
         if ids[0] < 0 or ids[-1] >= V:
             raise ValueError(f"bad_token_ids must lie in [0, {V})")
-        if getattr(self, "_ban_buf", None) is None:
+        if self._ban_buf is None:
             self._ban_buf = torch.zeros(V, dtype=torch.uint8, device=self.model.device)
         m = torch.zeros(V, dtype=torch.uint8)
         m[ids] = 1
@@ -176,9 +203,55 @@ class Decoder:
 
     def logp_buffer(self):
         """[max_batch, max_len + 1] f32 beside `tokens`, allocated once (the step graph bakes its address in)."""
-        if getattr(self, "logp", None) is None:
-            self.logp = torch.zeros(self.max_batch, self.max_len + 1, dtype=torch.float32, device=self.model.device)
+        if self.logp is None:
+            self.logp = self._f32_rows()
         return self.logp
+
+    def _f32_rows(self):
+        return torch.zeros(self.max_batch, self.max_len + 1, dtype=torch.float32, device=self.model.device)
+
+    def prefix_buffer(self, n_pre):
+        """[1, n_pre, d] f32 for `generate_2`'s memory rows: one address across segments keeps the captured graph valid."""
+        if self._prefix_buf is None or self._prefix_buf.shape[1] != n_pre:
+            self._prefix_buf = torch.empty(1, n_pre, self.model.cfg["d_model"], device=self.model.device, dtype=torch.float32)
+        return self._prefix_buf
+
+    def _on_stream(self, fn):
+        """`fn()` on the decoder's stream, ordered after the caller's work and before what the caller does next."""
+        cur = torch.cuda.current_stream()
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            out = fn()
+        cur.wait_stream(self.stream)
+        return out
+
+    def _check_logits_out(self, logits_out, steps, B):
+        if logits_out is None:
+            return
+        assert logits_out.dtype == torch.float32 and logits_out.is_contiguous() and logits_out.is_cuda
+        assert logits_out.dim() == 3 and logits_out.shape[0] >= steps and \
+            tuple(logits_out.shape[1:]) == (B, self.model.cfg["vocab_size"]), tuple(logits_out.shape)
+
+    def decode(self, enc_rows, G, Lc, max_steps, o: _Options, shift=0, prefix=None):
+        """One decode batch in the mode `o` names: G segments' encoder rows [G * Lc, d], `o.rows` decode rows per segment
+        (beam j / sample j of segment g is row g * o.rows + j), sampled with `seed + shift`.  -> (ids [rows, W] int64, logp
+        [rows, W] f32 or None), owned: the start token first, nothing stale.  Greedy / sampled: rows = G * o.n and W = 1 +
+        the step the last row finished at (`max_steps` when one never did; with `o.through_poll` 1 + the token steps
+        replayed, finished rows padded to there).  Beam: rows = G and W is `run_beam`'s."""
+        if o.num_beams > 1:
+            ckv = self.cross_kv_beam(enc_rows, G, o.num_beams, Lc)
+            ids, _, _, *lp = self.run_beam(ckv, G, o.num_beams, Lc, max_steps, o.length_penalty, self.ban_mask(o.bad_token_ids),
+                                           o.poll_every, return_logprobs=o.return_logprobs)
+            return ids.clone(), lp[0].clone() if lp else None
+        ckv = self.cross_kv(enc_rows, G, Lc) if o.n == 1 else self.cross_kv_beam(enc_rows, G, o.n, Lc)
+        toks, done, fin, *lp = self.run(ckv, G * o.n, Lc, max_steps, o.poll_every, prefix=prefix,
+                                        ban=self.ban_mask(o.bad_token_ids), return_logprobs=o.return_logprobs,
+                                        sampling=o.sampling.shifted(shift) if o.sampling else None)
+        if o.through_poll:
+            W = 1 + done - (0 if prefix is None else prefix.shape[1])
+        else:
+            W = 1 + (fin + 1 if fin >= 0 else max_steps)
+        return toks[:G * o.n, :W].clone(), lp[0][:G * o.n, :W].clone() if lp else None
 
     def run(self, ckv, B, Lc, max_steps, poll_every=64, prefix=None, logits_out=None, ban=None, return_logprobs=False,
             sampling=None):
@@ -201,16 +274,8 @@ class Decoder:
         l = lib.load()
         w = self._weights()
         self._ckv = ckv
-        if logits_out is not None:
-            n_pre = 0 if prefix is None else prefix.shape[1]
-            assert logits_out.dtype == torch.float32 and logits_out.is_contiguous() and logits_out.is_cuda
-            assert logits_out.dim() == 3 and logits_out.shape[0] >= n_pre + max_steps and \
-                tuple(logits_out.shape[1:]) == (B, cfg["vocab_size"]), tuple(logits_out.shape)
-        cur = torch.cuda.current_stream()
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            out = self._run_on_stream(l, w, ckv, B, Lc, max_steps, poll_every, cfg, prefix, logits_out)
-        cur.wait_stream(self.stream)
+        self._check_logits_out(logits_out, (0 if prefix is None else prefix.shape[1]) + max_steps, B)
+        out = self._on_stream(lambda: self._run_on_stream(l, w, ckv, B, Lc, max_steps, poll_every, cfg, prefix, logits_out))
         return out + (self._logp,) if return_logprobs else out
 
     def _run_on_stream(self, l, w, ckv, B, Lc, max_steps, poll_every, cfg, prefix=None, logits_out=None):
@@ -264,33 +329,28 @@ class Decoder:
         G*k, 2] (parent row, token per step), `beam_scores` [G*k] and `hyps` [G, BEAM_HREC] hold the search state.
         `return_logprobs`: a fourth item, [G, W] f32, the best hypothesis' per-token log-probabilities (the closing EOS
         included; their sum is the hypothesis' raw score)."""
-        cfg = self.model.cfg
         B = G * k
         if not (1 <= k <= MAX_BEAMS) or B > self.max_batch or max_steps > self.max_len or max_steps < 1:
             raise ValueError(f"run_beam: need 1 <= k <= {MAX_BEAMS}, G*k <= {self.max_batch}, 1 <= steps <= {self.max_len}")
-        if logits_out is not None:
-            assert logits_out.dtype == torch.float32 and logits_out.is_contiguous() and logits_out.is_cuda
-            assert logits_out.dim() == 3 and logits_out.shape[0] >= max_steps and \
-                tuple(logits_out.shape[1:]) == (B, cfg["vocab_size"]), tuple(logits_out.shape)
+        self._check_logits_out(logits_out, max_steps, B)
         self._ban, self._ckv = ban, ckv
         l = lib.load()
-        cur = torch.cuda.current_stream()
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
+
+        def search():
             self.begin_beam(ckv, G, k, Lc, length_penalty, ban)
             done, fin = self._loop(l, B, max_steps, poll_every, logits_out)
             if return_logprobs:
-                if getattr(self, "_beam_logp", None) is None:
-                    self._beam_logp = torch.zeros(self.max_batch, self.max_len + 1, dtype=torch.float32,
-                                                  device=self.model.device)
+                if self._beam_logp is None:
+                    self._beam_logp = self._f32_rows()
                 lib._check(l.mrmt3_decoder_beam_finalize_logprobs(self.h, lib._p(self._beam_out), lib._p(self._beam_logp),
                                                                   self.max_len + 1, max_steps, lib._stream()),
                            "decoder_beam_finalize_logprobs")
             else:
                 lib._check(l.mrmt3_decoder_beam_finalize(self.h, lib._p(self._beam_out), self.max_len + 1, max_steps,
                                                          lib._stream()), "decoder_beam_finalize")
-            lens = self.hyps(G)[:, 3].cpu()             # once per decode
-        cur.wait_stream(self.stream)
+            return done, fin, self.hyps(G)[:, 3].cpu()             # once per decode
+
+        done, fin, lens = self._on_stream(search)
         W = min(int(lens.max()) + 1, 1 + max_steps)
         if return_logprobs:
             return self._beam_out[:G, :W], done, fin, self._beam_logp[:G, :W]
@@ -300,7 +360,7 @@ class Decoder:
         """mrmt3_decoder_begin_beam on the current stream with this decoder's beam buffers (allocated once: the step
         graph bakes their addresses in).  `run_beam` is the whole decode; this is its first step, for tools."""
         cfg = self.model.cfg
-        if getattr(self, "_bp", None) is None:
+        if self._bp is None:
             dev = self.model.device
             self._bp = torch.zeros(self.max_len * self.max_batch * 2, dtype=torch.int32, device=dev)
             self._bscore = torch.zeros(self.max_batch, dtype=torch.float32, device=dev)
@@ -344,8 +404,8 @@ def _decoder_for(model, B, max_len, enc_len) -> Decoder:
 
 @torch.no_grad()
 def generate(model, inputs, max_length=1024, poll_every=64, return_logprobs=False, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0):
-    return _generate(model, inputs, max_length, poll_every, return_logprobs=return_logprobs,
-                     sampling=_sampling(do_sample, temperature, top_k, top_p, seed))
+    return _generate(model, inputs, max_length, _Options(sampling=_sampling(do_sample, temperature, top_k, top_p, seed),
+                                                         return_logprobs=return_logprobs, poll_every=poll_every))
 
 
 @torch.no_grad()
@@ -354,8 +414,10 @@ def generate_sample(model, inputs, max_length=1024, temperature=1.0, top_k=0, to
     """`generate` that draws.  Plain T5: `num_return_sequences = n` transcriptions per segment, row g * n + j of the
     [B * n, W] output is sample j of segment g (its cross K|V repeated as the beam search's are; the row's draw counter is
     its row in the decode batch).  Segment-memory models decode one sample per segment along their memory chain."""
-    return _generate(model, inputs, max_length, poll_every, bad_token_ids, return_logprobs,
-                     sampling=Sampling(temperature, top_k, top_p, seed), n=num_return_sequences)
+    return _generate(model, inputs, max_length, _Options(bad_token_ids=bad_token_ids,
+                                                         sampling=Sampling(temperature, top_k, top_p, seed),
+                                                         return_logprobs=return_logprobs, poll_every=poll_every,
+                                                         n=num_return_sequences))
 
 
 def best_of_select(ids, logp, n, eos_token_id):
@@ -389,75 +451,27 @@ def _pair(ids, logp, return_logprobs):
     return (ids, logp) if return_logprobs else ids
 
 
-def _generate(model, inputs, max_length, poll_every, bad_token_ids=None, return_logprobs=False, sampling=None, n=1):
-    """`return_logprobs`: every tensor of ids has a float twin cut, padded (0.0) and stacked the same way.
-    `sampling` (a `Sampling`): the tokens are drawn; decode batch c of a plain T5 and segment i of a memory chain use
-    `seed + c` / `seed + i`.  `n` > 1 (plain T5, with `sampling`): n rows per segment, output [B * n, W]."""
-    eng, cfg = model.engine, model.cfg
-    if not (isinstance(n, int) and 1 <= n <= MAX_DECODE_BATCH):
-        raise ValueError(f"num_return_sequences must be an int in 1..{MAX_DECODE_BATCH}, got {n!r}")
-    if n > 1 and (sampling is None or model.VARIANT not in ("t5", "segmem_v1")):
-        raise ValueError("num_return_sequences > 1 needs sampling and the plain T5 decode: the segment-memory chain "
-                         "decodes one sample per segment")
-    if not inputs.is_cuda:
-        raise RuntimeError("generate needs device tensors (no CPU fallback)")
-    eng.prepare(False)
-    B, Le, d = inputs.shape
-    enc = eng.encode(inputs.float() if inputs.dtype not in (torch.float32, torch.bfloat16) else inputs)
-    if model.VARIANT in ("t5", "segmem_v1"):      # T5SegMem.generate ignores the memory (t5_segmem.py:254-311)
-        out = []
-        per = MAX_DECODE_BATCH // n
-        for c, b0 in enumerate(range(0, B, per)):
-            ns = min(per, B - b0)                          # segments of this decode batch, n rows each
-            nb = ns * n
-            dec = _decoder_for(model, nb, max_length, Le)
-            enc_c = enc.view(B, Le, d)[b0:b0 + ns].reshape(ns * Le, d)
-            ckv = dec.cross_kv(enc_c, ns, Le) if n == 1 else dec.cross_kv_beam(enc_c, ns, n, Le)
-            toks, done, fin, *lp = dec.run(ckv, nb, Le, max_length, poll_every, ban=dec.ban_mask(bad_token_ids),
-                                           return_logprobs=return_logprobs,
-                                           sampling=sampling.shifted(c) if sampling else None)
-            steps = (fin + 1) if fin >= 0 else max_length
-            out.append((toks[:nb, :steps + 1].clone(), steps, lp[0][:nb, :steps + 1].clone() if lp else None))
-        if len(out) == 1:
-            return _pair(out[0][0], out[0][2], return_logprobs)
-        # the reference stops when ALL rows are finished: pad shorter groups with pad_token_id
-        steps = max(s for _, s, _ in out)
-        res = torch.full((B * n, steps + 1), cfg["pad_token_id"], dtype=torch.int64, device=inputs.device)
-        res_lp = torch.zeros(B * n, steps + 1, dtype=torch.float32, device=inputs.device) if return_logprobs else None
-        r = 0
-        for t, s, lp in out:
-            res[r:r + t.shape[0], :s + 1] = t
-            if return_logprobs:
-                res_lp[r:r + t.shape[0], :s + 1] = lp
-            r += t.shape[0]
-        return _pair(res, res_lp, return_logprobs)
-    if model.VARIANT == "segmem_v1":
-        raise RuntimeError("T5SegMem.generate is the plain batched decode; memory decode is generate_2")
-    # segment-memory models: sequential segments, memory = previous segment's tokens
-    Ls = min(model.segmem_length, max_length)            # `[:, :segmem_length]` of a max_length-long sequence
-    seg_ids = torch.zeros(1, max_length, dtype=torch.int64, device=inputs.device)
-    if model.VARIANT == "segmem_v2_with_prev":
-        seg_ids[0, 0], seg_ids[0, 1] = 1134, 1          # tie token + EOS (t5_segmem_v2_with_prev.py:257-258)
+def _check_beams(num_beams):
+    if not (isinstance(num_beams, int) and 1 <= num_beams <= MAX_BEAMS):
+        raise ValueError(f"num_beams must be an int in 1..{MAX_BEAMS}, got {num_beams!r}")
+
+
+def _memory_rows(x, max_length):
+    """Ids or log-probabilities [n, W] -> [n, max_length]: cut or zero-padded, as the reference's chain does (`F.pad` / slice)."""
+    rows = torch.zeros(x.shape[0], max_length, dtype=x.dtype, device=x.device)
+    n = min(x.shape[1], max_length)
+    rows[:, :n] = x[:, :n]
+    return rows
+
+
+def _first_memory_ids(max_length, device, with_prev=False):
+    """[max_length] memory ids of a recording's first segment; `with_prev`: the V2WithPrev model's."""
+    ids = torch.zeros(max_length, dtype=torch.int64, device=device)
+    if with_prev:
+        ids[0], ids[1] = 1134, 1                         # tie token + EOS (t5_segmem_v2_with_prev.py:257-258)
     else:
-        seg_ids[0, 0] = 1                                # t5_segmem_v2.py:199
-    dec = _decoder_for(model, 1, max_length, Le + Ls)
-    outs, outs_lp = [], []
-    for i in range(B):
-        mem = _memory(eng, seg_ids, 1, max_length, Ls)                     # [1, Ls, d]
-        cur = torch.cat([enc.view(B, Le, d)[i:i + 1], mem], 1).contiguous().view(Le + Ls, d)
-        ckv = dec.cross_kv(cur, 1, Le + Ls)
-        toks, done, fin, *lp = dec.run(ckv, 1, Le + Ls, max_length, poll_every, ban=dec.ban_mask(bad_token_ids),
-                                       return_logprobs=return_logprobs,
-                                       sampling=sampling.shifted(i) if sampling else None)
-        steps = (fin + 1) if fin >= 0 else max_length
-        row = torch.zeros(1, max_length, dtype=torch.int64, device=inputs.device)
-        n = min(steps + 1, max_length)                   # F.pad(..., max_length - len) truncates (:287-291)
-        row[0, :n] = toks[0, :n]
-        outs.append(row)
-        if lp:
-            outs_lp.append(_logp_rows(lp[0][:1, :n], max_length))
-        seg_ids = row
-    return _pair(torch.cat(outs, 0), torch.cat(outs_lp, 0) if outs_lp else None, return_logprobs)
+        ids[0] = 1                                       # t5_segmem_v2.py:199, t5_segmem.py:190-196
+    return ids
 
 
 def _memory(eng, seg_ids, B, L, Ls):
@@ -466,6 +480,79 @@ def _memory(eng, seg_ids, B, L, Ls):
     if Ls == 0:
         return torch.empty(B, 0, eng.d, device=seg_ids.device, dtype=eng.dt)
     return eng.segmem(seg_ids, B, L)
+
+
+def _stack(parts, pad_token_id):
+    """Decode batches' (ids, logp) -> one: the reference stops when ALL rows are finished, so the narrower batches are
+    padded to the widest, ids with `pad_token_id` and log-probabilities with 0.0."""
+    if len(parts) == 1:
+        return parts[0]
+    W = max(ids.shape[1] for ids, _ in parts)
+    wide = lambda x, fill: torch.cat([x, x.new_full((x.shape[0], W - x.shape[1]), fill)], 1)
+    return (torch.cat([wide(ids, pad_token_id) for ids, _ in parts]),
+            torch.cat([wide(lp, 0.0) for _, lp in parts]) if parts[0][1] is not None else None)
+
+
+def _decode_batched(model, enc, B, Le, max_length, o):
+    """Plain T5 (and T5SegMem.generate, which ignores the memory: t5_segmem.py:254-311): the B segments in decode batches
+    of MAX_DECODE_BATCH rows, batch c sampled with `seed + c`.  -> (ids [B * o.rows / num_beams, W], logp or None)."""
+    per = MAX_DECODE_BATCH // o.rows
+    parts = []
+    for c, b0 in enumerate(range(0, B, per)):
+        G = min(per, B - b0)
+        dec = _decoder_for(model, G * o.rows, max_length, Le)
+        parts.append(dec.decode(enc.view(B, Le, -1)[b0:b0 + G].reshape(G * Le, -1), G, Le, max_length, o, shift=c))
+    return _stack(parts, model.cfg["pad_token_id"])
+
+
+def _decode_chains(model, songs, max_length, o):
+    """The segment-memory chain (V2 / V2WithPrev) of S recordings in lockstep: row s of decode batch i is recording s's
+    segment i, its encoder states followed by the memory encoder's view of that recording's segment i - 1 as decoded, cut
+    or zero-padded to max_length; segment i is sampled with `seed + i`.  A recording shorter than the longest drops out.
+    `songs`: list of [n_seg_s, Le, d].  -> (list of ids [n_seg_s, max_length], list of their logp or [])."""
+    eng = model.engine
+    S, dev = len(songs), songs[0].device
+    Le, d = songs[0].shape[1], songs[0].shape[2]
+    Ls = min(model.segmem_length, max_length)            # `[:, :segmem_length]` of a max_length-long sequence
+    enc = [eng.encode(x).view(x.shape[0], Le, d) for x in songs]           # per recording, all its segments
+    prev = [_first_memory_ids(max_length, dev, model.VARIANT == "segmem_v2_with_prev")] * S
+    outs = [[] for _ in range(S)]
+    outs_lp = [[] for _ in range(S)]
+    for i in range(max(x.shape[0] for x in songs)):
+        live = [s for s in range(S) if i < songs[s].shape[0]]
+        B = len(live)
+        mem = _memory(eng, torch.stack([prev[s] for s in live]), B, max_length, Ls)       # [B, Ls, d]
+        cur = torch.cat([torch.stack([enc[s][i] for s in live]), mem.to(enc[0].dtype)], 1).contiguous()
+        dec = _decoder_for(model, B * o.rows, max_length, Le + Ls)
+        ids, lp = dec.decode(cur.view(B * (Le + Ls), d), B, Le + Ls, max_length, o, shift=i)
+        rows = _memory_rows(ids, max_length)
+        rows_lp = _memory_rows(lp, max_length) if lp is not None else None
+        for r, s in enumerate(live):
+            outs[s].append(rows[r])
+            if lp is not None:
+                outs_lp[s].append(rows_lp[r])
+            prev[s] = rows[r]
+    return [torch.stack(x) for x in outs], [torch.stack(x) for x in outs_lp if x]
+
+
+def _generate(model, inputs, max_length, o):
+    """`generate`, `generate_sample` and `generate_beam` behind their keyword checks: [B, Le, d] segments of one recording
+    -> ids, or (ids, logp) with `o.return_logprobs`."""
+    if not (isinstance(o.n, int) and 1 <= o.n <= MAX_DECODE_BATCH):
+        raise ValueError(f"num_return_sequences must be an int in 1..{MAX_DECODE_BATCH}, got {o.n!r}")
+    if o.n > 1 and (o.sampling is None or model.VARIANT not in ("t5", "segmem_v1")):
+        raise ValueError("num_return_sequences > 1 needs sampling and the plain T5 decode: the segment-memory chain "
+                         "decodes one sample per segment")
+    if not inputs.is_cuda:
+        raise RuntimeError("generate needs device tensors (no CPU fallback)")
+    model.engine.prepare(False)
+    if inputs.dtype not in (torch.float32, torch.bfloat16):
+        inputs = inputs.float()
+    if model.VARIANT in ("t5", "segmem_v1"):
+        B, Le, _ = inputs.shape
+        return _pair(*_decode_batched(model, model.engine.encode(inputs), B, Le, max_length, o), o.return_logprobs)
+    ids, lp = _decode_chains(model, [inputs], max_length, o)
+    return _pair(ids[0], lp[0] if lp else None, o.return_logprobs)
 
 
 @torch.no_grad()
@@ -478,8 +565,9 @@ def generate_2(model, inputs, max_length=1024, poll_every=64, num_beams=1, retur
     `do_sample`: the token steps draw (segment i with `seed + i`), the prefix steps draw nothing."""
     if num_beams != 1:
         raise ValueError("generate_2 (memory-prefixed decode) has no beam search")
-    sampling = _sampling(do_sample, temperature, top_k, top_p, seed)
-    eng, cfg = model.engine, model.cfg
+    o = _Options(sampling=_sampling(do_sample, temperature, top_k, top_p, seed), return_logprobs=return_logprobs,
+                 poll_every=poll_every)
+    eng = model.engine
     if not inputs.is_cuda:
         raise RuntimeError("generate_2 needs device tensors (no CPU fallback)")
     Ls = model.segmem_length
@@ -487,28 +575,18 @@ def generate_2(model, inputs, max_length=1024, poll_every=64, num_beams=1, retur
     eng.prepare(False)
     B, Le, d = inputs.shape
     enc = eng.encode(inputs)
-    seg_ids = torch.zeros(1, max_length, dtype=torch.int64, device=inputs.device)
-    seg_ids[0, 0] = 1                                          # t5_segmem.py:190-196
+    seg_ids = _first_memory_ids(max_length, inputs.device)[None]
     dec = _decoder_for(model, 1, max_length + Ls, Le)
-    pre = getattr(dec, "_prefix_buf", None)
-    if pre is None or pre.shape[1] != Ls:
-        pre = dec._prefix_buf = torch.empty(1, Ls, d, device=inputs.device, dtype=torch.float32)
+    pre = dec.prefix_buffer(Ls)
     outs, outs_lp = [], []
     for i in range(B):
         if Ls:
             pre.copy_(eng.segmem(seg_ids, 1, max_length).float().view(1, Ls, d))
-        ckv = dec.cross_kv(enc.view(B, Le, d)[i].contiguous(), 1, Le)
-        toks, done, fin, *lp = dec.run(ckv, 1, Le, max_length, poll_every, prefix=pre if Ls else None,
-                                       return_logprobs=return_logprobs,
-                                       sampling=sampling.shifted(i) if sampling else None)
-        steps = (fin + 1) if fin >= 0 else max_length
-        row = torch.zeros(1, max_length, dtype=torch.int64, device=inputs.device)
-        n = min(steps + 1, max_length)
-        row[0, :n] = toks[0, :n]
-        outs.append(row)
-        if lp:
-            outs_lp.append(_logp_rows(lp[0][:1, :n], max_length))
-        seg_ids = row
+        ids, lp = dec.decode(enc.view(B, Le, d)[i].contiguous(), 1, Le, max_length, o, shift=i, prefix=pre if Ls else None)
+        seg_ids = _memory_rows(ids, max_length)
+        outs.append(seg_ids)
+        if lp is not None:
+            outs_lp.append(_memory_rows(lp, max_length))
     return _pair(torch.cat(outs, 0), torch.cat(outs_lp, 0) if outs_lp else None, return_logprobs)
 
 
@@ -531,88 +609,19 @@ def generate_songs(model, songs, max_length=1024, poll_every=64, num_beams=1, le
     sampling = _sampling(do_sample, temperature, top_k, top_p, seed)
     if sampling is not None and num_beams > 1:
         raise ValueError("beam search does not sample: do_sample needs num_beams == 1")
-    eng, cfg = model.engine, model.cfg
     if model.VARIANT not in ("segmem_v2", "segmem_v2_with_prev"):
         raise RuntimeError("generate_songs is for the segment-memory models; plain T5 batches segments directly")
-    if not songs:
-        return _pair([], [], return_logprobs)
+    o = _Options(num_beams, length_penalty, bad_token_ids, sampling, return_logprobs, poll_every, through_poll=True)
     per = MAX_DECODE_BATCH // num_beams
-    if len(songs) > per:
-        out, out_lp = [], []
-        for i in range(0, len(songs), per):
-            part = generate_songs(model, songs[i:i + per], max_length, poll_every, num_beams, length_penalty, bad_token_ids,
-                                  return_logprobs, do_sample, temperature, top_k, top_p, seed)
-            out += part[0] if return_logprobs else part
-            out_lp += part[1] if return_logprobs else []
-        return _pair(out, out_lp, return_logprobs)
-    dev = songs[0].device
-    if dev.type != "cuda":
-        raise RuntimeError("generate_songs needs device tensors (no CPU fallback)")
-    eng.prepare(False)
-    S = len(songs)
-    Le, d = songs[0].shape[1], songs[0].shape[2]
-    Ls = min(model.segmem_length, max_length)
-    enc = [eng.encode(x).view(x.shape[0], Le, d) for x in songs]           # per recording, all its segments
-    first = torch.zeros(max_length, dtype=torch.int64, device=dev)
-    if model.VARIANT == "segmem_v2_with_prev":
-        first[0], first[1] = 1134, 1
-    else:
-        first[0] = 1
-    prev = [first.clone() for _ in range(S)]
-    outs = [[] for _ in range(S)]
-    outs_lp = [[] for _ in range(S)]
-    for i in range(max(x.shape[0] for x in songs)):
-        live = [s for s in range(S) if i < songs[s].shape[0]]
-        B = len(live)
-        seg_ids = torch.stack([prev[s] for s in live])                      # [B, max_length]
-        mem = _memory(eng, seg_ids, B, max_length, Ls)                     # [B, Ls, d]
-        cur = torch.cat([torch.stack([enc[s][i] for s in live]), mem.to(enc[0].dtype)], 1).contiguous()
-        dec = _decoder_for(model, B * num_beams, max_length, Le + Ls)
-        if num_beams > 1:
-            ckv = dec.cross_kv_beam(cur.view(B * (Le + Ls), d), B, num_beams, Le + Ls)
-            ids, _, _, *lp = dec.run_beam(ckv, B, num_beams, Le + Ls, max_length, length_penalty,
-                                          dec.ban_mask(bad_token_ids), poll_every, return_logprobs=return_logprobs)
-            rows = _memory_rows(ids, max_length)
-            rows_lp = _logp_rows(lp[0], max_length) if lp else None
-        else:
-            ckv = dec.cross_kv(cur.view(B * (Le + Ls), d), B, Le + Ls)
-            toks, done, fin, *lp = dec.run(ckv, B, Le + Ls, max_length, poll_every, ban=dec.ban_mask(bad_token_ids),
-                                           return_logprobs=return_logprobs,
-                                           sampling=sampling.shifted(i) if sampling else None)
-            rows = toks[:B, :max_length].clone()                           # finished rows are already pad(0)-filled
-            rows_lp = lp[0][:B, :max_length].clone() if lp else None
-            if done < max_length:                                          # all rows hit EOS early: the rest is stale
-                rows[:, done + 1:] = 0
-                if lp:
-                    rows_lp[:, done + 1:] = 0
-        for r, s in enumerate(live):
-            outs[s].append(rows[r])
-            if return_logprobs:
-                outs_lp[s].append(rows_lp[r])
-            prev[s] = rows[r]
-    ids = [torch.stack(o) for o in outs]
-    return (ids, [torch.stack(o) for o in outs_lp]) if return_logprobs else ids
-
-
-def _check_beams(num_beams):
-    if not (isinstance(num_beams, int) and 1 <= num_beams <= MAX_BEAMS):
-        raise ValueError(f"num_beams must be an int in 1..{MAX_BEAMS}, got {num_beams!r}")
-
-
-def _memory_rows(ids, max_length):
-    """Beam output [n, W] -> [n, max_length]: cut or zero-padded, as the greedy chain does (`F.pad` / slice)."""
-    rows = torch.zeros(ids.shape[0], max_length, dtype=torch.int64, device=ids.device)
-    n = min(ids.shape[1], max_length)
-    rows[:, :n] = ids[:, :n]
-    return rows
-
-
-def _logp_rows(logp, max_length):
-    """`_memory_rows` for the log-probabilities that go with the ids: cut or padded with 0.0."""
-    rows = torch.zeros(logp.shape[0], max_length, dtype=torch.float32, device=logp.device)
-    n = min(logp.shape[1], max_length)
-    rows[:, :n] = logp[:, :n]
-    return rows
+    ids, lp = [], []
+    for i in range(0, len(songs), per):
+        if songs[i].device.type != "cuda":
+            raise RuntimeError("generate_songs needs device tensors (no CPU fallback)")
+        model.engine.prepare(False)
+        part = _decode_chains(model, songs[i:i + per], max_length, o)
+        ids += part[0]
+        lp += part[1]
+    return _pair(ids, lp, return_logprobs)
 
 
 @torch.no_grad()
@@ -632,52 +641,5 @@ def generate_beam(model, inputs, num_beams=1, max_length=1024, length_penalty=1.
         raise ValueError("beam search does not sample: do_sample needs num_beams == 1")
     if not inputs.is_cuda:
         raise RuntimeError("generate_beam needs device tensors (no CPU fallback)")
-    if num_beams == 1:
-        return _generate(model, inputs, max_length, poll_every, bad_token_ids, return_logprobs, sampling=sampling)
-    eng, cfg = model.engine, model.cfg
-    k = num_beams
-    eng.prepare(False)
-    B, Le, d = inputs.shape
-    enc = eng.encode(inputs.float() if inputs.dtype not in (torch.float32, torch.bfloat16) else inputs)
-    if model.VARIANT in ("t5", "segmem_v1"):
-        per = MAX_DECODE_BATCH // k
-        out = []
-        for b0 in range(0, B, per):
-            G = min(per, B - b0)
-            dec = _decoder_for(model, G * k, max_length, Le)
-            ckv = dec.cross_kv_beam(enc.view(B, Le, d)[b0:b0 + G].reshape(G * Le, d), G, k, Le)
-            ids, _, _, *lp = dec.run_beam(ckv, G, k, Le, max_length, length_penalty, dec.ban_mask(bad_token_ids), poll_every,
-                                          return_logprobs=return_logprobs)
-            out.append((ids.clone(), lp[0].clone() if lp else None))
-        if len(out) == 1:
-            return _pair(out[0][0], out[0][1], return_logprobs)
-        W = max(o.shape[1] for o, _ in out)
-        res = torch.full((B, W), cfg["pad_token_id"], dtype=torch.int64, device=inputs.device)
-        res_lp = torch.zeros(B, W, dtype=torch.float32, device=inputs.device) if return_logprobs else None
-        r = 0
-        for o, lp in out:
-            res[r:r + o.shape[0], :o.shape[1]] = o
-            if return_logprobs:
-                res_lp[r:r + o.shape[0], :o.shape[1]] = lp
-            r += o.shape[0]
-        return _pair(res, res_lp, return_logprobs)
-    Ls = min(model.segmem_length, max_length)
-    seg_ids = torch.zeros(1, max_length, dtype=torch.int64, device=inputs.device)
-    if model.VARIANT == "segmem_v2_with_prev":
-        seg_ids[0, 0], seg_ids[0, 1] = 1134, 1
-    else:
-        seg_ids[0, 0] = 1
-    dec = _decoder_for(model, k, max_length, Le + Ls)
-    outs, outs_lp = [], []
-    for i in range(B):
-        mem = _memory(eng, seg_ids, 1, max_length, Ls)
-        cur = torch.cat([enc.view(B, Le, d)[i:i + 1], mem], 1).contiguous().view(Le + Ls, d)
-        ckv = dec.cross_kv_beam(cur, 1, k, Le + Ls)
-        ids, _, _, *lp = dec.run_beam(ckv, 1, k, Le + Ls, max_length, length_penalty, dec.ban_mask(bad_token_ids), poll_every,
-                                      return_logprobs=return_logprobs)
-        row = _memory_rows(ids, max_length)
-        outs.append(row)
-        if lp:
-            outs_lp.append(_logp_rows(lp[0], max_length))
-        seg_ids = row
-    return _pair(torch.cat(outs, 0), torch.cat(outs_lp, 0) if outs_lp else None, return_logprobs)
+    return _generate(model, inputs, max_length, _Options(num_beams, length_penalty, bad_token_ids, sampling, return_logprobs,
+                                                         poll_every))

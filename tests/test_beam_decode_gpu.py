@@ -375,3 +375,37 @@ def test_generate_beam_matches_an_fp64_cpu_beam_search(dev):
         want, ref = beam_search(logits_fn, 2, 3, cfg["vocab_size"], 24, length_penalty=0.4)
     print(f"[f] smallest rank gap {min(ref.margins):.3e}")
     assert got.shape == want.shape and (got.numpy() == want).all(), (got, want)
+
+
+def test_beam_decode_batches_of_different_widths_are_padded_and_stacked(dev):
+    """5 segments, k = 4, room for 8 rows: `generate_beam` decodes 2 + 2 + 1 segments.  Its output is the three batches decoded
+    by calls of their own, stacked to the widest: ids padded with pad_token_id, log-probabilities with 0.0, bit for bit.  EOS
+    is made the twin of a token the last segment emits early, so its batch is narrower than the others (two layers, fp32)."""
+    import mrmt3.decode as dec_mod
+    from mrmt3.decode import generate_beam
+    from mrmt3.synthetic import T5_SMALL
+    from models.t5 import T5ForConditionalGeneration
+    m = T5ForConditionalGeneration(dict(T5_SMALL, num_layers=2, num_decoder_layers=2), compute_dtype=torch.float32)
+    m = m.load_golden().to(dev).eval()
+    _edit(m, _no_eos)
+    mel, _ = _enc(m, 5, seed=7, frames=16)
+    kw = dict(num_beams=4, max_length=24, length_penalty=0.4, return_logprobs=True)
+    old = dec_mod.MAX_DECODE_BATCH
+    try:
+        dec_mod.MAX_DECODE_BATCH = 8
+        m._decoder = None
+        tok = int(generate_beam(m, mel, num_beams=4, max_length=24)[4, 3])
+        _edit(m, lambda w: w[1].copy_(w[tok] * 1.001))               # where `tok` would win, EOS now does, by a margin
+        ids, lp = generate_beam(m, mel, **kw)
+        parts = [generate_beam(m, mel[a:b], **kw) for a, b in ((0, 2), (2, 4), (4, 5))]
+    finally:
+        dec_mod.MAX_DECODE_BATCH = old
+        m._decoder = None
+    widths = [p[0].shape[1] for p in parts]
+    print(f"[beam across batches] EOS = twin of {tok}; widths {widths}")
+    assert len(set(widths)) > 1, widths                              # or nothing is padded and the test says nothing
+    W, pad = max(widths), m.cfg["pad_token_id"]
+    want = torch.cat([torch.nn.functional.pad(i, (0, W - i.shape[1]), value=pad) for i, _ in parts])
+    want_lp = torch.cat([torch.nn.functional.pad(l, (0, W - l.shape[1]), value=0.0) for _, l in parts])
+    assert ids.shape == (5, W) and torch.equal(ids, want)
+    assert lp.dtype == torch.float32 and torch.equal(lp.view(torch.int32), want_lp.view(torch.int32))

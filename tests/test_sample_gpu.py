@@ -441,3 +441,41 @@ def test_inference_handler_samples_only_under_decode_options(dev):
     assert len(best) == (n_seg + 1) // 2 and all(t.shape == l.shape for t, l in zip(best, lps))
     many = on.inference_many([audio, audio[:32768]], return_tokens=True, **kw)
     assert len(many) == 2 and many[0][0][0].shape[0] == n_seg
+
+
+def test_several_samples_per_segment_across_decode_batches(dev):
+    """`num_return_sequences` = 4 with room for 8 rows: 3 segments decode as 2 + 1, batch c under `seed + c`, the batches padded
+    to the widest and stacked.  Against `Decoder.run` driven by hand, bit for bit; row g * 4 + j is sample j of segment g."""
+    import mrmt3.decode as dec_mod
+    from mrmt3.decode import Decoder, Sampling, generate_sample
+    from mrmt3.synthetic import T5_SMALL
+    from models.t5 import T5ForConditionalGeneration
+    G, n, Le, ML, seed = 3, 4, 16, STEPS, 5
+    m = T5ForConditionalGeneration(dict(T5_SMALL, num_layers=2, num_decoder_layers=2), compute_dtype=torch.float32)
+    m = m.load_golden().to(dev).eval()
+    _edit(m, lambda w: w[1].mul_(3.5))                               # EOS is drawn now and then: the batches end at different steps
+    pad, d = m.cfg["pad_token_id"], m.cfg["d_model"]
+    mel, enc = _enc(m, G, seed=7, frames=Le)
+    kw = dict(temperature=1.0, top_k=50, top_p=0.95)
+    old = dec_mod.MAX_DECODE_BATCH
+    try:
+        dec_mod.MAX_DECODE_BATCH = 8
+        m._decoder = None
+        ids, lp = generate_sample(m, mel, max_length=ML, num_return_sequences=n, seed=seed, return_logprobs=True, **kw)
+    finally:
+        dec_mod.MAX_DECODE_BATCH = old
+        m._decoder = None
+    parts = []
+    for c, (g0, ns) in enumerate(((0, 2), (2, 1))):
+        dec = Decoder(m, ns * n, ML, Le)
+        with torch.no_grad():
+            ckv = dec.cross_kv_beam(enc[g0:g0 + ns].reshape(ns * Le, d).contiguous(), ns, n, Le)
+            toks, _, fin, logp = dec.run(ckv, ns * n, Le, ML, sampling=Sampling(seed=seed + c, **kw), return_logprobs=True)
+        w = 1 + (fin + 1 if fin >= 0 else ML)
+        parts.append((toks[:ns * n, :w].clone(), logp[:ns * n, :w].clone()))
+    W = max(t.shape[1] for t, _ in parts)
+    print(f"[n=4 across batches] widths {[t.shape[1] for t, _ in parts]}")
+    want = torch.cat([torch.nn.functional.pad(t, (0, W - t.shape[1]), value=pad) for t, _ in parts])
+    want_lp = torch.cat([torch.nn.functional.pad(l, (0, W - l.shape[1]), value=0.0) for _, l in parts])
+    assert ids.shape == (G * n, W) and torch.equal(ids, want)
+    assert lp.dtype == torch.float32 and torch.equal(lp.view(torch.int32), want_lp.view(torch.int32))
