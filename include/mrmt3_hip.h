@@ -621,6 +621,57 @@ int mrmt3_decoder_poll(mrmt3_decoder* dec, int32_t* state_out_pinned, void* stre
  * stream capture.  For tests: call after mrmt3_decoder_run(dec, 1, stream). */
 int mrmt3_decoder_logits(mrmt3_decoder* dec, float* dst, int rows, void* stream);
 
+/* ---- grammar-constrained decoding: only token sequences the MT3 event decoder accepts ----------------
+ * The event grammar is a small state machine per decode row, held on the device and advanced inside the captured step by
+ * one kernel after the tail (dec_grammar_step); it writes each row's [vocab] uint8 mask (1 = banned) for the next step, which
+ * the greedy, sampled and beam tails read where they read the static ban (row stride `vocab` instead of 0).
+ * All ids are MODEL ids (the 3 special tokens included); ranges are {first id, count}.  "Off" is the first velocity id. */
+typedef struct {
+  int shift0, n_shift;        /* shift by v steps = shift0 + v, v in [0, n_shift) */
+  int pitch0, n_pitch;        /* n_pitch <= 128 */
+  int velocity0, n_velocity;  /* velocity0 = note-off, every other velocity id = on */
+  int tie;
+  int program0, n_program;    /* n_program <= 128 */
+  int drum0, n_drum;
+  int eos, pad;
+  int max_shift_steps;        /* a shift run may not carry time past this many steps from the segment start */
+  int tie_section;            /* 1: a row starts in the tie section, 0: in the body */
+} mrmt3_grammar;
+#define MRMT3_GRAMMAR_SET_BYTES 2048   /* a 128 x 128 bit set over (program, pitch): bit program * 128 + pitch, LSB first */
+/* Stand-alone state (the decoder owns one of its own): `state` is caller-owned device memory of
+ * mrmt3_grammar_state_bytes(rows) bytes, 16-byte aligned.  mrmt3_grammar_init writes every row's start state (program and
+ * velocity unset, time 0, tie section or body) and its first mask into mask_out [rows][V] uint8.  carry: device
+ * [rows][2048] bit sets of the notes sounding when the segment began, or NULL; banned_mask: device [V] uint8 OR-ed into every
+ * mask, or NULL.  Both pointers are kept in `state` and read again by mrmt3_grammar_advance: they must stay valid.
+ * mrmt3_grammar_advance: row r takes the state of row parents[r] (r itself when parents is NULL), pushes tokens[r] and
+ * writes its next mask: the device function of the decoder's step kernel.  `rows` and `V` as given to _init.  A token equal
+ * to pad leaves the row's state and mask as they are (row r keeps its own state, whatever parents[r] says).
+ * mrmt3_grammar_active copies every row's current `active` set to out [rows][2048]. */
+size_t mrmt3_grammar_state_bytes(int rows);
+int mrmt3_grammar_init(const mrmt3_grammar* g, void* state, const uint8_t* carry, const uint8_t* banned_mask, int rows,
+                       int V, uint8_t* mask_out, void* stream);
+int mrmt3_grammar_advance(const mrmt3_grammar* g, void* state, const int32_t* parents_or_null, const int64_t* tokens,
+                          int rows, int V, uint8_t* mask_out, void* stream);
+int mrmt3_grammar_active(const void* state, int rows, uint8_t* out, void* stream);
+/* The `active` set a row of token ids leaves behind: ids [rows][ld] int64 with the start token in column 0; the tokens of
+ * columns 1 .. n_tokens (fewer when ld is shorter) are pushed from the start state, up to the first eos or pad.  V: the
+ * vocabulary the id ranges must lie in.  carry [rows][2048] or NULL; out [rows][2048].  For rows that were cut after the
+ * decode (the segment-memory chains keep max_length columns). */
+int mrmt3_grammar_replay(const mrmt3_grammar* g, const int64_t* ids, int ld, int rows, int n_tokens, int V,
+                         const uint8_t* carry, uint8_t* out, void* stream);
+/* Optional, after mrmt3_decoder_begin / _begin_beam and after mrmt3_decoder_set_ban (the static mask in force is OR-ed
+ * into the row masks), before mrmt3_decoder_run: decode under the grammar.  Writes the start state and the step-0 masks;
+ * the step graph gains dec_grammar_step and is re-captured when the grammar goes on or off, as for a ban; a new descriptor
+ * or carry replays it.  carry: device [rows][2048] (rows = batch, or groups * num_beams) or NULL, valid until the decode
+ * ends.  Rows that have finished and the prefix steps of mrmt3_decoder_set_prefix leave state and masks untouched.
+ * g = NULL turns it off.  mrmt3_decoder_begin clears it.  Needs n_pitch, n_program <= 128 and every range inside vocab. */
+int mrmt3_decoder_set_grammar(mrmt3_decoder* dec, const mrmt3_grammar* g, const uint8_t* carry, void* stream);
+/* After the decode (beam: after mrmt3_decoder_beam_finalize): out [rows][2048] receives each row's final `active` set, the
+ * notes left sounding by the tokens it emitted (greedy / sampled: rows = batch; beam: rows = groups, the set of the
+ * hypothesis returned).  The emitted tokens are pushed again from the start state, so the result does not depend on
+ * which rows held the hypothesis' prefix along the way. */
+int mrmt3_decoder_grammar_active(mrmt3_decoder* dec, uint8_t* out, void* stream);
+
 /* ---- gradient exchange (data parallel, one process per GPU): RCCL communicators as opaque handles ----------------
  * Replaces what the reference gets from Lightning's `ddp_find_unused_parameters_false` strategy (config/config.yaml:45,
  * train.sh:6): torch DDP's bucketed NCCL all-reduce of the gradients.  The flat f32 gradient buffer is exchanged as a few

@@ -112,11 +112,13 @@ class InferenceHandler:
         """inference.py:138-147: `bad_words_ids` of the programs outside `valid_programs`, one single-token list each."""
         return [[p] for p in program_ban_ids(valid_programs, self.codec)]
 
-    def _generate(self, batch, max_length, valid_programs, num_beams, scored=False, sample=None, best_of=1):
+    def _generate(self, batch, max_length, valid_programs, num_beams, scored=False, sample=None, best_of=1, constrained=False):
         """The reference's `model.generate(..., num_beams, length_penalty=0.4, bad_words_ids=...)` (inference.py:186-190).
         `scored`: (ids, per-token log-probabilities).  `sample`: dict of `temperature`, `top_k`, `top_p`, `seed` (the
-        tokens are drawn; not with `num_beams` > 1); `best_of` > 1: the most likely of that many samples per segment."""
+        tokens are drawn; not with `num_beams` > 1); `best_of` > 1: the most likely of that many samples per segment.
+        `constrained`: decode under the event grammar (`mrmt3.grammar`)."""
         ban = None if valid_programs is None else program_ban_ids(valid_programs, self.codec)
+        ckw = dict(constrained=constrained) if constrained is not False else {}
         if sample is not None:
             if num_beams != 1:
                 raise ValueError("beam search does not sample: do_sample / best_of need num_beams == 1")
@@ -125,15 +127,19 @@ class InferenceHandler:
                     raise ValueError("best_of > 1 is for the plain T5 model (MT3Net); the segment-memory models decode "
                                      "one sample per segment")
                 ids, logp = self.model.generate_best_of(inputs=batch, n=best_of, max_length=max_length, bad_token_ids=ban,
-                                                        **sample)
+                                                        **sample, **ckw)
                 return (ids, logp) if scored else ids
+            if ckw:
+                from mrmt3.decode import generate_sample
+                return generate_sample(self.model, batch, max_length=max_length, bad_token_ids=ban, return_logprobs=scored,
+                                       **sample, **ckw)
             return self.model.generate_sample(inputs=batch, max_length=max_length, bad_token_ids=ban,
                                               return_logprobs=scored, **sample)
         if scored:
             return self.model.generate_scored(inputs=batch, max_length=max_length, num_beams=num_beams, length_penalty=0.4,
-                                              bad_token_ids=ban)
+                                              bad_token_ids=ban, **ckw)
         return self.model.generate_beam(inputs=batch, num_beams=num_beams, max_length=max_length, length_penalty=0.4,
-                                        bad_token_ids=ban)
+                                        bad_token_ids=ban, **ckw)
 
     def _audio_to_frames(self, audio):
         return audio_to_frames(audio, self.spectrogram_config)
@@ -203,13 +209,16 @@ class InferenceHandler:
     @torch.no_grad()
     def inference(self, audio, audio_path=None, outpath=None, valid_programs=None, num_beams=1, batch_size=5,
                   max_length=1024, verbose=False, return_tokens=False, with_confidence=False, min_confidence=None,
-                  do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, best_of=1):
+                  do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, best_of=1, constrained=False):
         """audio -> note sequence (and a MIDI file when `outpath` is given, like inference.py:149-204).
         `return_tokens=True` returns (post-processed token arrays per batch, frame times) instead.
         `with_confidence` (implied by `min_confidence`): every note carries `confidence` in (0, 1], notes below
         `min_confidence` are dropped; with `return_tokens` a third item holds the log-probability arrays.
         `do_sample` (under `decode_options`): the tokens are drawn, batch i with `seed + i`; `best_of` > 1 keeps the most
-        likely of that many samples per segment (plain T5 only) and implies sampling."""
+        likely of that many samples per segment (plain T5 only) and implies sampling.
+        `constrained` (under `decode_options`; True or an `EventGrammar`): the decoder emits only tokens the event decoder
+        accepts.  The plain T5 decodes a batch's segments side by side, each knowing only its own tie section; the
+        segment-memory models hand the sounding notes from segment to segment within a batch."""
         scored = with_confidence or min_confidence is not None
         sample = self._sample_options(do_sample, temperature, top_k, top_p, seed, best_of)
         inputs, frame_times = self._preprocess(audio)
@@ -220,6 +229,8 @@ class InferenceHandler:
         results, logps = [], []
         for i, batch in enumerate(batches):
             kw = {} if sample is None else dict(sample=dict(sample, seed=sample["seed"] + i), best_of=best_of)
+            if self.decode_options and constrained is not False:
+                kw["constrained"] = constrained
             if scored:
                 opts = (valid_programs, num_beams) if self.decode_options else (None, 1)
                 result, logp = self._generate(batch.to(self.device), max_length, *opts, scored=True, **kw)
@@ -240,14 +251,15 @@ class InferenceHandler:
     @torch.no_grad()
     def inference_many(self, audios, outpaths=None, max_length=1024, return_tokens=False, valid_programs=None,
                        num_beams=1, with_confidence=False, min_confidence=None, do_sample=False, temperature=1.0, top_k=0,
-                       top_p=1.0, seed=0, best_of=1):
+                       top_p=1.0, seed=0, best_of=1, constrained=False):
         """Several recordings in one go.  Segment-memory models decode them in lockstep (one batch row per
         recording, `model.generate_songs`); the plain T5 simply batches all segments.  Returns one note sequence
         (or, with `return_tokens`, one `(token arrays, frame times)` pair) per recording, like `inference`.
         `valid_programs` / `num_beams` are honoured as given (length penalty 0.4, as `inference` under decode_options).
         `with_confidence` / `min_confidence` as in `inference`.  The sampling keywords as in `inference` (under
         `decode_options`): the plain T5 decodes every segment in one batch under `seed`, the segment-memory models draw
-        segment i of every recording under `seed + i`; `best_of` > 1 is for the plain T5."""
+        segment i of every recording under `seed + i`; `best_of` > 1 is for the plain T5.  `constrained` as in `inference`,
+        honoured as given."""
         sample = self._sample_options(do_sample, temperature, top_k, top_p, seed, best_of)
         if sample is not None and best_of > 1 and hasattr(self.model, "generate_songs"):
             raise ValueError("best_of > 1 is for the plain T5 model (MT3Net); the segment-memory models decode one sample "
@@ -263,6 +275,8 @@ class InferenceHandler:
                 kw["return_logprobs"] = True
             if sample is not None:
                 kw.update(sample, do_sample=True, bad_token_ids=ban)
+            if constrained is not False:
+                kw["constrained"] = constrained
             ids = self.model.generate_songs([x.to(self.device) for x, _ in pre], max_length=max_length, **kw)
             if scored:
                 ids, lps = ids
@@ -270,9 +284,11 @@ class InferenceHandler:
             x_all = torch.cat([x for x, _ in pre]).to(self.device)
             flat_lp = None
             kw = {} if sample is None else dict(sample=sample, best_of=best_of)
+            if constrained is not False:
+                kw["constrained"] = constrained
             if scored:
                 flat, flat_lp = self._generate(x_all, max_length, valid_programs, num_beams, scored=True, **kw)
-            elif opts or sample is not None:
+            elif opts or sample is not None or constrained is not False:
                 flat = self._generate(x_all, max_length, valid_programs, num_beams, **kw)
             else:
                 flat = self.model.generate(inputs=x_all, max_length=max_length)

@@ -14,7 +14,8 @@ class T5SegMem(MT3Module):
         super().__init__(config, segmem_num_layers=segmem_num_layers, segmem_length=segmem_length,
                          compute_dtype=compute_dtype or torch.bfloat16)
 
-    def generate_2(self, inputs, max_length=1024, output_hidden_states=False, return_logprobs=False, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, **kwargs):
+    def generate_2(self, inputs, max_length=1024, output_hidden_states=False, return_logprobs=False, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0,
+                   constrained=False, **kwargs):
         from mrmt3.decode import generate_2
         return generate_2(self, inputs, max_length=max_length, return_logprobs=return_logprobs,
-                          do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
+                          do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, constrained=constrained)

@@ -21,6 +21,10 @@ the log-probability the model gave each emitted token at its position, 0.0 for t
 `sample()` builds (ban, `temperature`, `top_k`, `top_p`) instead of taking the argmax; the draw is a pure function of
 (`seed`, row of the decode batch, token step).  `generate_sample` / `generate_best_of` draw several transcriptions per segment.
 
+`constrained=True` (every entry point): only token sequences the MT3 event decoder accepts.  The event grammar is a
+state machine per decode row on the device, advanced inside the captured step; its per-row mask acts where `bad_token_ids`
+acts.  Along a memory chain (`_decode_chains`, `generate_2`) segment i + 1 starts from the notes segment i left sounding.
+
 Structure: every entry point folds its keywords into one `_Options` record.  `Decoder.decode` decodes one batch in any mode
 (greedy, sampled, n samples per segment, beam) and returns owned `(ids, logp)`.  Three loops call it: `_decode_batched`
 (plain T5 and `segmem_v1`: chunks of `MAX_DECODE_BATCH` rows, padded and stacked), `_decode_chains` (the segment-memory
@@ -36,6 +40,7 @@ from dataclasses import dataclass, replace
 import torch
 
 from . import lib
+from .grammar import ACTIVE_BYTES, EventGrammar, resolve as _grammar
 
 
 MAX_DECODE_BATCH = 256     # DEC_MAXB of csrc/decode.hip: sequences decoded together (one wave per row x sequence)
@@ -87,6 +92,7 @@ class _Options:
     poll_every: int = 64
     n: int = 1                     # rows per segment of a sampled decode (`num_return_sequences`)
     through_poll: bool = False     # greedy / sampled ids run to the last step replayed, not to the finish step (`generate_songs`)
+    grammar: "EventGrammar | None" = None   # constrained decoding (`constrained=`): the event grammar every row obeys
 
     @property
     def rows(self) -> int:
@@ -232,21 +238,28 @@ class Decoder:
         assert logits_out.dim() == 3 and logits_out.shape[0] >= steps and \
             tuple(logits_out.shape[1:]) == (B, self.model.cfg["vocab_size"]), tuple(logits_out.shape)
 
-    def decode(self, enc_rows, G, Lc, max_steps, o: _Options, shift=0, prefix=None):
+    def decode(self, enc_rows, G, Lc, max_steps, o: _Options, shift=0, prefix=None, carry=None):
         """One decode batch in the mode `o` names: G segments' encoder rows [G * Lc, d], `o.rows` decode rows per segment
         (beam j / sample j of segment g is row g * o.rows + j), sampled with `seed + shift`.  -> (ids [rows, W] int64, logp
         [rows, W] f32 or None), owned: the start token first, nothing stale.  Greedy / sampled: rows = G * o.n and W = 1 +
         the step the last row finished at (`max_steps` when one never did; with `o.through_poll` 1 + the token steps
-        replayed, finished rows padded to there).  Beam: rows = G and W is `run_beam`'s."""
+        replayed, finished rows padded to there).  Beam: rows = G and W is `run_beam`'s.
+        With `o.grammar` the decode is constrained; `carry` [G, 2048] uint8 (or None) holds the notes sounding when each
+        segment began (`grammar_active` afterwards: the notes each returned row leaves sounding)."""
+        if o.grammar is not None:
+            o.grammar.check_ban(o.bad_token_ids)
+            if carry is not None and o.rows > 1:
+                carry = carry.repeat_interleave(o.rows, 0)
         if o.num_beams > 1:
             ckv = self.cross_kv_beam(enc_rows, G, o.num_beams, Lc)
             ids, _, _, *lp = self.run_beam(ckv, G, o.num_beams, Lc, max_steps, o.length_penalty, self.ban_mask(o.bad_token_ids),
-                                           o.poll_every, return_logprobs=o.return_logprobs)
+                                           o.poll_every, return_logprobs=o.return_logprobs, grammar=o.grammar, carry=carry)
             return ids.clone(), lp[0].clone() if lp else None
         ckv = self.cross_kv(enc_rows, G, Lc) if o.n == 1 else self.cross_kv_beam(enc_rows, G, o.n, Lc)
         toks, done, fin, *lp = self.run(ckv, G * o.n, Lc, max_steps, o.poll_every, prefix=prefix,
                                         ban=self.ban_mask(o.bad_token_ids), return_logprobs=o.return_logprobs,
-                                        sampling=o.sampling.shifted(shift) if o.sampling else None)
+                                        sampling=o.sampling.shifted(shift) if o.sampling else None, grammar=o.grammar,
+                                        carry=carry)
         if o.through_poll:
             W = 1 + done - (0 if prefix is None else prefix.shape[1])
         else:
@@ -254,7 +267,7 @@ class Decoder:
         return toks[:G * o.n, :W].clone(), lp[0][:G * o.n, :W].clone() if lp else None
 
     def run(self, ckv, B, Lc, max_steps, poll_every=64, prefix=None, logits_out=None, ban=None, return_logprobs=False,
-            sampling=None):
+            sampling=None, grammar=None, carry=None):
         """Decode up to max_steps tokens for B rows; returns (tokens [B, max_len+1] view, steps run,
         finish_step or -1) and, with `return_logprobs`, a fourth item: the [B, max_len+1] f32 view of each emitted
         token's log-probability (mrmt3_decoder_set_logprobs; the step graph with that tail is captured on first use).  `prefix` [B, n, d] f32: memory rows fed as decoder positions 0..n-1.
@@ -262,13 +275,16 @@ class Decoder:
         output, prefix steps included; steps are then replayed one at a time, each followed by a copy.
         `ban`: device [V] uint8 mask (`ban_mask`) of tokens the argmax never picks, or None.
         `sampling`: a `Sampling` (or a (temperature, top_k, top_p, seed) tuple): row b draws its token of step t with the
-        counter (b, t) (mrmt3_decoder_set_sampling; the sampled step is captured once, a new seed or parameters replay it)."""
+        counter (b, t) (mrmt3_decoder_set_sampling; the sampled step is captured once, a new seed or parameters replay it).
+        `grammar`: an `EventGrammar`: every row obeys it (mrmt3_decoder_set_grammar), `ban` OR-ed into its masks; `carry`
+        [B, 2048] uint8 device bit sets of the notes sounding when each row's segment began, or None."""
         if sampling is not None and not isinstance(sampling, Sampling):
             sampling = Sampling(*sampling)
         if sampling is not None and self.model.cfg["vocab_size"] > MAX_SAMPLE_VOCAB:
             raise ValueError(f"sampling needs vocab_size <= {MAX_SAMPLE_VOCAB}")
         self._sampling = sampling
         self._ban = ban
+        self._set_grammar_args(grammar, carry, B)
         self._logp = self.logp_buffer() if return_logprobs else None
         cfg = self.model.cfg
         l = lib.load()
@@ -291,6 +307,7 @@ class Decoder:
             sp = self._sampling
             lib._check(l.mrmt3_decoder_set_sampling(self.h, float(sp.temperature), int(sp.top_k), float(sp.top_p),
                                                     int(sp.seed), lib._stream()), "decoder_set_sampling")
+        self._set_grammar(l)
         if prefix is not None:
             n_pre = prefix.shape[1]
             assert prefix.dtype == torch.float32 and prefix.is_contiguous() and prefix.shape[0] == B
@@ -300,6 +317,26 @@ class Decoder:
             max_steps += n_pre
         done, fin = self._loop(l, B, max_steps, poll_every, logits_out)
         return self.tokens, done, fin
+
+    def _set_grammar_args(self, grammar, carry, rows):
+        if carry is not None:
+            assert grammar is not None and carry.dtype == torch.uint8 and carry.is_cuda and carry.is_contiguous() and \
+                tuple(carry.shape) == (rows, ACTIVE_BYTES), "carry: [rows, 2048] uint8 on the device"
+        self._gram = (grammar.c_struct(), carry) if grammar is not None else None     # kept alive through the decode
+
+    def _set_grammar(self, l):
+        """After begin / begin_beam and the ban: the start states and the step-0 masks, on the current stream."""
+        if self._gram is not None:
+            g, carry = self._gram
+            lib._check(l.mrmt3_decoder_set_grammar(self.h, C.byref(g), lib._p(carry), lib._stream()), "decoder_set_grammar")
+
+    def grammar_active(self, rows):
+        """[rows, 2048] uint8, owned: the `active` set each row of the last constrained decode ends with (beam: each group's
+        returned hypothesis), mrmt3_decoder_grammar_active."""
+        out = torch.empty(rows, ACTIVE_BYTES, dtype=torch.uint8, device=self.model.device)
+        self._on_stream(lambda: lib._check(lib.load().mrmt3_decoder_grammar_active(self.h, lib._p(out), lib._stream()),
+                                           "decoder_grammar_active"))
+        return out
 
     def _loop(self, l, B, max_steps, poll_every, logits_out):
         """Replay steps until max_steps or every row (greedy) / group (beam) is done; (steps run, finish step or -1)."""
@@ -322,22 +359,24 @@ class Decoder:
         return done, fin
 
     def run_beam(self, ckv, G, k, Lc, max_steps, length_penalty=1.0, ban=None, poll_every=64, logits_out=None,
-                 return_logprobs=False):
+                 return_logprobs=False, grammar=None, carry=None):
         """Beam search over G groups of k rows (`cross_kv_beam`).  Returns (ids [G, W] int64, steps run, finish step or
         -1): start token, the best hypothesis, EOS when shorter than 1 + max_steps, pad; W = min(longest + 1,
         1 + max_steps).  `logits_out` [>= max_steps, G*k, V] f32 (tests) as in `run`.  After the call `bp` [max_len,
         G*k, 2] (parent row, token per step), `beam_scores` [G*k] and `hyps` [G, BEAM_HREC] hold the search state.
         `return_logprobs`: a fourth item, [G, W] f32, the best hypothesis' per-token log-probabilities (the closing EOS
-        included; their sum is the hypothesis' raw score)."""
+        included; their sum is the hypothesis' raw score).  `grammar`, `carry` [G * k, 2048] as in `run`."""
         B = G * k
         if not (1 <= k <= MAX_BEAMS) or B > self.max_batch or max_steps > self.max_len or max_steps < 1:
             raise ValueError(f"run_beam: need 1 <= k <= {MAX_BEAMS}, G*k <= {self.max_batch}, 1 <= steps <= {self.max_len}")
         self._check_logits_out(logits_out, max_steps, B)
         self._ban, self._ckv = ban, ckv
+        self._set_grammar_args(grammar, carry, B)
         l = lib.load()
 
         def search():
             self.begin_beam(ckv, G, k, Lc, length_penalty, ban)
+            self._set_grammar(l)
             done, fin = self._loop(l, B, max_steps, poll_every, logits_out)
             if return_logprobs:
                 if self._beam_logp is None:
@@ -403,21 +442,23 @@ def _decoder_for(model, B, max_len, enc_len) -> Decoder:
 
 
 @torch.no_grad()
-def generate(model, inputs, max_length=1024, poll_every=64, return_logprobs=False, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0):
+def generate(model, inputs, max_length=1024, poll_every=64, return_logprobs=False, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0,
+             constrained=False):
     return _generate(model, inputs, max_length, _Options(sampling=_sampling(do_sample, temperature, top_k, top_p, seed),
-                                                         return_logprobs=return_logprobs, poll_every=poll_every))
+                                                         return_logprobs=return_logprobs, poll_every=poll_every,
+                                                         grammar=_grammar(constrained, model)))
 
 
 @torch.no_grad()
 def generate_sample(model, inputs, max_length=1024, temperature=1.0, top_k=0, top_p=1.0, seed=0, num_return_sequences=1,
-                    bad_token_ids=None, return_logprobs=False, poll_every=64):
+                    bad_token_ids=None, return_logprobs=False, poll_every=64, constrained=False):
     """`generate` that draws.  Plain T5: `num_return_sequences = n` transcriptions per segment, row g * n + j of the
     [B * n, W] output is sample j of segment g (its cross K|V repeated as the beam search's are; the row's draw counter is
     its row in the decode batch).  Segment-memory models decode one sample per segment along their memory chain."""
     return _generate(model, inputs, max_length, _Options(bad_token_ids=bad_token_ids,
                                                          sampling=Sampling(temperature, top_k, top_p, seed),
                                                          return_logprobs=return_logprobs, poll_every=poll_every,
-                                                         n=num_return_sequences))
+                                                         n=num_return_sequences, grammar=_grammar(constrained, model)))
 
 
 def best_of_select(ids, logp, n, eos_token_id):
@@ -436,13 +477,14 @@ def best_of_select(ids, logp, n, eos_token_id):
 
 @torch.no_grad()
 def generate_best_of(model, inputs, n, max_length=1024, temperature=1.0, top_k=0, top_p=1.0, seed=0, bad_token_ids=None,
-                     poll_every=64):
+                     poll_every=64, constrained=False):
     """n samples per segment (`generate_sample`), the most likely one kept: (ids [B, W], logp [B, W]).  Plain T5 only."""
     if not (isinstance(n, int) and n >= 1):
         raise ValueError(f"n must be an int >= 1, got {n!r}")
     if model.VARIANT not in ("t5", "segmem_v1"):
         raise ValueError("generate_best_of is for the plain T5 decode; the segment-memory chain decodes one sample per segment")
-    ids, logp = generate_sample(model, inputs, max_length, temperature, top_k, top_p, seed, n, bad_token_ids, True, poll_every)
+    ids, logp = generate_sample(model, inputs, max_length, temperature, top_k, top_p, seed, n, bad_token_ids, True, poll_every,
+                                constrained)
     ids, logp, _ = best_of_select(ids, logp, n, model.cfg["eos_token_id"])
     return ids, logp
 
@@ -509,7 +551,10 @@ def _decode_chains(model, songs, max_length, o):
     """The segment-memory chain (V2 / V2WithPrev) of S recordings in lockstep: row s of decode batch i is recording s's
     segment i, its encoder states followed by the memory encoder's view of that recording's segment i - 1 as decoded, cut
     or zero-padded to max_length; segment i is sampled with `seed + i`.  A recording shorter than the longest drops out.
-    `songs`: list of [n_seg_s, Le, d].  -> (list of ids [n_seg_s, max_length], list of their logp or [])."""
+    `songs`: list of [n_seg_s, Le, d].  -> (list of ids [n_seg_s, max_length], list of their logp or []).
+    Constrained (`o.grammar`): segment i + 1 of a recording starts with `carry` = the notes segment i left sounding: the
+    `active` set of its row as returned, i.e. cut to max_length (`lib.grammar_replay`, device to device).  A recording's
+    first segment starts from the empty set: nothing sounds before a recording begins, so its tie section can declare nothing."""
     eng = model.engine
     S, dev = len(songs), songs[0].device
     Le, d = songs[0].shape[1], songs[0].shape[2]
@@ -518,20 +563,27 @@ def _decode_chains(model, songs, max_length, o):
     prev = [_first_memory_ids(max_length, dev, model.VARIANT == "segmem_v2_with_prev")] * S
     outs = [[] for _ in range(S)]
     outs_lp = [[] for _ in range(S)]
+    sounding = [None] * S
     for i in range(max(x.shape[0] for x in songs)):
         live = [s for s in range(S) if i < songs[s].shape[0]]
         B = len(live)
         mem = _memory(eng, torch.stack([prev[s] for s in live]), B, max_length, Ls)       # [B, Ls, d]
         cur = torch.cat([torch.stack([enc[s][i] for s in live]), mem.to(enc[0].dtype)], 1).contiguous()
         dec = _decoder_for(model, B * o.rows, max_length, Le + Ls)
-        ids, lp = dec.decode(cur.view(B * (Le + Ls), d), B, Le + Ls, max_length, o, shift=i)
+        carry = None
+        if o.grammar is not None:
+            carry = torch.stack([sounding[s] for s in live]) if i > 0 else torch.zeros(B, ACTIVE_BYTES, dtype=torch.uint8, device=dev)
+        ids, lp = dec.decode(cur.view(B * (Le + Ls), d), B, Le + Ls, max_length, o, shift=i, carry=carry)
         rows = _memory_rows(ids, max_length)
         rows_lp = _memory_rows(lp, max_length) if lp is not None else None
+        left = lib.grammar_replay(o.grammar, rows, model.cfg["vocab_size"], carry) if o.grammar is not None else None
         for r, s in enumerate(live):
             outs[s].append(rows[r])
             if lp is not None:
                 outs_lp[s].append(rows_lp[r])
             prev[s] = rows[r]
+            if left is not None:
+                sounding[s] = left[r]
     return [torch.stack(x) for x in outs], [torch.stack(x) for x in outs_lp if x]
 
 
@@ -556,17 +608,20 @@ def _generate(model, inputs, max_length, o):
 
 
 @torch.no_grad()
-def generate_2(model, inputs, max_length=1024, poll_every=64, num_beams=1, return_logprobs=False, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0):
+def generate_2(model, inputs, max_length=1024, poll_every=64, num_beams=1, return_logprobs=False, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0,
+               constrained=False):
     """`T5SegMem.generate_2` (models/t5_segmem.py:172-252): segments one after the other; the previous
     segment's tokens go through the segment-memory encoder and its first `segmem_length` outputs are
     PREPENDED to the decoder's input embeddings.  With the KV cache that is a prefix fill: the memory
     rows are fed as decoder positions 0..Ls-1 (self-attention K/V only), tokens start at position Ls.
     A stable prefix buffer keeps the captured step graph valid across segments.  No beam search here.
-    `do_sample`: the token steps draw (segment i with `seed + i`), the prefix steps draw nothing."""
+    `do_sample`: the token steps draw (segment i with `seed + i`), the prefix steps draw nothing.
+    `constrained`: the token steps obey the event grammar (the prefix steps leave its state alone); segment i + 1 starts
+    from the notes segment i left sounding, the first from none."""
     if num_beams != 1:
         raise ValueError("generate_2 (memory-prefixed decode) has no beam search")
     o = _Options(sampling=_sampling(do_sample, temperature, top_k, top_p, seed), return_logprobs=return_logprobs,
-                 poll_every=poll_every)
+                 poll_every=poll_every, grammar=_grammar(constrained, model))
     eng = model.engine
     if not inputs.is_cuda:
         raise RuntimeError("generate_2 needs device tensors (no CPU fallback)")
@@ -579,11 +634,15 @@ def generate_2(model, inputs, max_length=1024, poll_every=64, num_beams=1, retur
     dec = _decoder_for(model, 1, max_length + Ls, Le)
     pre = dec.prefix_buffer(Ls)
     outs, outs_lp = [], []
+    sounding = torch.zeros(1, ACTIVE_BYTES, dtype=torch.uint8, device=inputs.device) if o.grammar is not None else None
     for i in range(B):
         if Ls:
             pre.copy_(eng.segmem(seg_ids, 1, max_length).float().view(1, Ls, d))
-        ids, lp = dec.decode(enc.view(B, Le, d)[i].contiguous(), 1, Le, max_length, o, shift=i, prefix=pre if Ls else None)
+        ids, lp = dec.decode(enc.view(B, Le, d)[i].contiguous(), 1, Le, max_length, o, shift=i, prefix=pre if Ls else None,
+                             carry=sounding)
         seg_ids = _memory_rows(ids, max_length)
+        if o.grammar is not None:
+            sounding = lib.grammar_replay(o.grammar, seg_ids, model.cfg["vocab_size"], sounding)
         outs.append(seg_ids)
         if lp is not None:
             outs_lp.append(_memory_rows(lp, max_length))
@@ -592,7 +651,7 @@ def generate_2(model, inputs, max_length=1024, poll_every=64, num_beams=1, retur
 
 @torch.no_grad()
 def generate_songs(model, songs, max_length=1024, poll_every=64, num_beams=1, length_penalty=1.0, bad_token_ids=None,
-                   return_logprobs=False, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0):
+                   return_logprobs=False, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, constrained=False):
     """Several recordings decoded in lockstep with the segment-memory models (V2 / V2WithPrev).
 
     The reference transcribes one recording at a time because segment i needs segment i-1's tokens
@@ -611,7 +670,8 @@ def generate_songs(model, songs, max_length=1024, poll_every=64, num_beams=1, le
         raise ValueError("beam search does not sample: do_sample needs num_beams == 1")
     if model.VARIANT not in ("segmem_v2", "segmem_v2_with_prev"):
         raise RuntimeError("generate_songs is for the segment-memory models; plain T5 batches segments directly")
-    o = _Options(num_beams, length_penalty, bad_token_ids, sampling, return_logprobs, poll_every, through_poll=True)
+    o = _Options(num_beams, length_penalty, bad_token_ids, sampling, return_logprobs, poll_every, through_poll=True,
+                 grammar=_grammar(constrained, model))
     per = MAX_DECODE_BATCH // num_beams
     ids, lp = [], []
     for i in range(0, len(songs), per):
@@ -626,7 +686,7 @@ def generate_songs(model, songs, max_length=1024, poll_every=64, num_beams=1, le
 
 @torch.no_grad()
 def generate_beam(model, inputs, num_beams=1, max_length=1024, length_penalty=1.0, bad_token_ids=None, poll_every=64,
-                  return_logprobs=False, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0):
+                  return_logprobs=False, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, constrained=False):
     """Beam search with optional single-token bans; the output contract of `generate` for the model's variant.
 
     Plain T5 / T5SegMem: [B, W] int64, W = min(longest best hypothesis + 1, 1 + max_length) over the batch: start
@@ -642,4 +702,4 @@ def generate_beam(model, inputs, num_beams=1, max_length=1024, length_penalty=1.
     if not inputs.is_cuda:
         raise RuntimeError("generate_beam needs device tensors (no CPU fallback)")
     return _generate(model, inputs, max_length, _Options(num_beams, length_penalty, bad_token_ids, sampling, return_logprobs,
-                                                         poll_every))
+                                                         poll_every, grammar=_grammar(constrained, model)))

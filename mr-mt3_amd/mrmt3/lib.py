@@ -106,7 +106,7 @@ def load():
     return lib
 
 
-MIN_VERSION = 119
+MIN_VERSION = 120
 COUNTER_NAMES = ("gemm_nt_tile", "gemm_nt8", "gemm_nt_geglu", "tn_group", "tn8", "tn_tile", "attn_fwd", "attn_bwd",
                  "attn_bwd_onepass", "attn_f32", "tn_f32", "gemm_nt_splitk", "gemm_nt_addnorm", "gemm_nt_normbwd",
                  "gemm_nt_geglubwd", "attn_fwd_varlen", "attn_bwd_varlen")
@@ -973,6 +973,54 @@ def sample_logits(logits, temperature=1.0, top_k=0, top_p=1.0, seed=0, step=0, r
     _check(load().mrmt3_sample_logits(_p(logits), rows, V, _p(ban), float(temperature), int(top_k), float(top_p), int(seed),
                                       int(step), int(row0), _p(tok), _p(lp), _stream()), "sample_logits")
     return (tok, lp) if return_logprobs else tok
+
+
+class GrammarState:
+    """A stand-alone grammar state on the device (mrmt3_grammar_init / _advance / _active): `rows` event-grammar
+    state machines and their [rows, V] uint8 masks (1 = the row may not emit that token next).  The decoder keeps one of its
+    own inside the captured step; this is the same device code on its own, for tests and tools."""
+
+    def __init__(self, grammar, rows, V, device, carry=None, ban=None):
+        assert carry is None or (carry.dtype == torch.uint8 and carry.is_contiguous() and carry.is_cuda
+                                 and tuple(carry.shape) == (rows, 2048))
+        assert ban is None or (ban.dtype == torch.uint8 and ban.is_contiguous() and ban.numel() == V and ban.is_cuda)
+        self.grammar, self.rows, self.V = grammar, rows, V
+        self._g = grammar.c_struct()
+        self._keep = (carry, ban)          # the state keeps both pointers
+        self.state = torch.zeros(int(load().mrmt3_grammar_state_bytes(rows)), dtype=torch.uint8, device=device)
+        self.mask = torch.empty(rows, V, dtype=torch.uint8, device=device)
+        _check(load().mrmt3_grammar_init(C.byref(self._g), _p(self.state), _p(carry), _p(ban), rows, V, _p(self.mask),
+                                         _stream()), "grammar_init")
+
+    def advance(self, tokens, parents=None):
+        """Row r takes row parents[r]'s state (its own without `parents`), pushes tokens[r]; -> the new masks (a view)."""
+        assert tokens.dtype == torch.int64 and tokens.is_contiguous() and tokens.numel() == self.rows and tokens.is_cuda
+        assert parents is None or (parents.dtype == torch.int32 and parents.is_contiguous() and parents.numel() == self.rows
+                                   and parents.is_cuda)
+        _check(load().mrmt3_grammar_advance(C.byref(self._g), _p(self.state), _p(parents), _p(tokens), self.rows, self.V,
+                                            _p(self.mask), _stream()), "grammar_advance")
+        return self.mask
+
+    def active(self):
+        """[rows, 2048] uint8: every row's `active` bit set (bit program * 128 + pitch)."""
+        out = torch.empty(self.rows, 2048, dtype=torch.uint8, device=self.state.device)
+        _check(load().mrmt3_grammar_active(_p(self.state), self.rows, _p(out), _stream()), "grammar_active")
+        return out
+
+
+def grammar_replay(grammar, ids, V, carry=None):
+    """[rows, 2048] uint8: the `active` set each row of `ids` [rows, W] int64 (start token first) leaves behind under
+    `grammar`, from `carry` [rows, 2048] or nothing (mrmt3_grammar_replay): the next segment's carry."""
+    _dev(ids)
+    rows, W = ids.shape
+    assert ids.dtype == torch.int64 and ids.is_contiguous()
+    assert carry is None or (carry.dtype == torch.uint8 and carry.is_contiguous() and carry.is_cuda
+                             and tuple(carry.shape) == (rows, 2048))
+    g = grammar.c_struct()
+    out = torch.empty(rows, 2048, dtype=torch.uint8, device=ids.device)
+    _check(load().mrmt3_grammar_replay(C.byref(g), _p(ids), W, rows, W - 1, int(V), _p(carry), _p(out), _stream()),
+           "grammar_replay")
+    return out
 
 
 def lmhead_logprob(dec, w, targets, chunk_rows=None):

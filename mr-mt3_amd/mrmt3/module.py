@@ -212,14 +212,16 @@ class MT3Module(nn.Module):
         return generate(self, inputs, max_length=max_length)      # unknown keywords ignored, as the reference does
 
     def generate_beam(self, inputs, num_beams=1, max_length=1024, length_penalty=1.0, bad_token_ids=None, poll_every=64,
-                      return_logprobs=False, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0):
+                      return_logprobs=False, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, constrained=False):
         """Beam search and single-token bans (`mrmt3.decode.generate_beam`); `generate` keeps ignoring such keywords,
         as the reference's custom `generate` does.  `return_logprobs`: (ids, per-token log-probabilities).
-        `do_sample` (with `num_beams=1`; beam search does not sample): the tokens are drawn, see `generate_sample`."""
+        `do_sample` (with `num_beams=1`; beam search does not sample): the tokens are drawn, see `generate_sample`.
+        `constrained` (True, or an `mrmt3.grammar.EventGrammar`): only sequences the event decoder accepts."""
         from .decode import generate_beam
         return generate_beam(self, inputs, num_beams=num_beams, max_length=max_length, length_penalty=length_penalty,
                              bad_token_ids=bad_token_ids, poll_every=poll_every, return_logprobs=return_logprobs,
-                             do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
+                             do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
+                             constrained=constrained)
 
     def generate_sample(self, inputs, max_length=1024, temperature=1.0, top_k=0, top_p=1.0, seed=0, num_return_sequences=1,
                         bad_token_ids=None, return_logprobs=False):
@@ -227,24 +229,27 @@ class MT3Module(nn.Module):
         ban, `temperature`, `top_k` and `top_p`; the draw is a pure function of (`seed`, decode-batch row, step), so a seed
         names a transcription.  Plain T5: `num_return_sequences = n` gives [B * n, W], row g * n + j = sample j of segment
         g.  Segment-memory models decode one sample per segment along the memory chain (n > 1: ValueError).
-        `return_logprobs`: (ids, the model's own log-probability of every drawn token, as `generate_scored` returns)."""
+        `return_logprobs`: (ids, the model's own log-probability of every drawn token, as `generate_scored` returns).
+        (Constrained sampling: `mrmt3.decode.generate_sample(model, ..., constrained=True)`, or `generate_beam(do_sample=True,
+        constrained=True)` for one sample per segment; this method's signature is kept as it is.)"""
         from .decode import generate_sample
         return generate_sample(self, inputs, max_length=max_length, temperature=temperature, top_k=top_k, top_p=top_p,
                                seed=seed, num_return_sequences=num_return_sequences, bad_token_ids=bad_token_ids,
                                return_logprobs=return_logprobs)
 
-    def generate_best_of(self, inputs, n, max_length=1024, temperature=1.0, top_k=0, top_p=1.0, seed=0, bad_token_ids=None):
+    def generate_best_of(self, inputs, n, max_length=1024, temperature=1.0, top_k=0, top_p=1.0, seed=0, bad_token_ids=None,
+                         constrained=False):
         """n samples per segment, the one the model scores highest kept (sum of log-probabilities up to and including its
         EOS; ties to the lowest sample): `(ids [B, W], logp [B, W])`.  Plain T5 only."""
         from .decode import generate_best_of
         return generate_best_of(self, inputs, n, max_length=max_length, temperature=temperature, top_k=top_k, top_p=top_p,
-                                seed=seed, bad_token_ids=bad_token_ids)
+                                seed=seed, bad_token_ids=bad_token_ids, constrained=constrained)
 
-    def generate_scored(self, inputs, max_length=1024, num_beams=1, length_penalty=1.0, bad_token_ids=None):
+    def generate_scored(self, inputs, max_length=1024, num_beams=1, length_penalty=1.0, bad_token_ids=None, constrained=False):
         """`generate_beam` that also says how sure the model was: `(ids, logp)`, `logp` f32 of the shape of `ids` with each
         emitted token's log-probability at its position (0.0 for the start token and the padding)."""
         return self.generate_beam(inputs, num_beams=num_beams, max_length=max_length, length_penalty=length_penalty,
-                                  bad_token_ids=bad_token_ids, return_logprobs=True)
+                                  bad_token_ids=bad_token_ids, return_logprobs=True, constrained=constrained)
 
     @torch.no_grad()
     def score(self, inputs, labels, targets_prev=None, chunk_rows=None):
