@@ -415,16 +415,27 @@ int mrmt3_lmhead_logprob(const void* dec, int ld_dec, const void* W, int ldw, co
                          int rows, int V, int d, int dtype, void* workspace, size_t workspace_bytes, int chunk_rows,
                          void* stream);
 
-/* ---- K11: AdamW over the flat parameter buffer (torch.optim.AdamW defaults; tasks/mt3_net.py:55)
- * p,g,m,v: flat f32 [n].  lr is read from lr_dev[0] (device), step count from step_dev[0] (int32,
- * incremented by the call).  grad_scale multiplies g (e.g. 1/world_size).  shadow_bf16 (nullable)
- * receives the updated parameters in bf16. */
-int mrmt3_adamw_step(float* p, const float* g, float* m, float* v, size_t n, const float* lr_dev,
-                     int32_t* step_dev, float beta1, float beta2, float eps, float weight_decay,
-                     float grad_scale, void* shadow_bf16, void* stream);
-/* ---- K11b: global gradient norm, clip coefficient and non-finite guard on the device, and the AdamW step that obeys
- * them (Lightning's `gradient_clip_val` / `gradient_clip_algorithm`, torch.nn.utils.clip_grad_norm_ semantics; the
- * reference passes its `trainer:` block to pl.Trainer, train.py:43-47).
+/* ---- K11: the optimizer tail.  AdamW over the flat parameter buffer (torch.optim.AdamW defaults; tasks/mt3_net.py:55),
+ * optionally under the clip coefficient / skip flag of mrmt3_grad_norm (Lightning's `gradient_clip_val` /
+ * `gradient_clip_algorithm`, torch.nn.utils.clip_grad_norm_ semantics; the reference passes its `trainer:` block to
+ * pl.Trainer, train.py:43-47) and optionally over a table of trainable element ranges (frozen weights, per-range
+ * weight decay and learning-rate factor, EMA weights in the same pass).
+ * mrmt3_adamw_step: p,g,m,v: flat f32 [n], n % 4 == 0.  lr is read from lr_dev[0] (device), the step count from
+ * step_dev[0] (int32, incremented by the call whatever happens: it counts ATTEMPTED optimizer steps).  grad_scale
+ * multiplies g (e.g. 1/world_size).  shadow_bf16 (nullable) receives the updated parameters in bf16.
+ *   stat_dev non-null (what mrmt3_grad_norm wrote): the gradient is g * grad_scale * stat_dev[1], then, when
+ *     clip_value > 0, clamped to [-clip_value, clip_value] (`gradient_clip_algorithm: value`); stat_dev[2] != 0: nothing is
+ *     stored (p, m, v, ema and the shadow keep their bits).  With stat_dev[1] == 1 and clip_value == 0 the result is the
+ *     plain step's, bit for bit.  clip_value != 0 needs stat_dev.
+ *   ranges_dev == NULL and n_ranges == 0: the flat form, one grid-stride launch over all n elements with `weight_decay`;
+ *     ema must be NULL and n_trainable is not read.
+ *   ranges_dev non-null (n_ranges >= 1; one given without the other is an error): ONE launch over the trainable elements
+ *     only (a workgroup owns 1024 consecutive 16-byte groups of the ranges laid end to end and finds its range by binary
+ *     search); elements outside every range are never read or written.  Inside a range the arithmetic is the flat form's
+ *     with the range's weight decay and lr = lr_dev[0] * lr_scale, bit for bit; `weight_decay` is NOT read.  n_trainable is
+ *     what the planner returned (it sizes the grid; the kernel's bound is the table's own total).  With `ema` non-null
+ *     (then 0 < ema_decay < 1; ema null needs ema_decay == 0): ema += (1 - ema_decay) * (p_new - ema) in f32 in the same
+ *     pass.
  * mrmt3_grad_norm: two launches.  Stage 1 is a FIXED grid (the same on every device and for every n) of 256-thread
  * workgroups that stride over g with 16-byte loads, accumulate g*g in f64 and leave one f64 partial each in `ws`
  * (8-byte aligned, at least mrmt3_grad_norm_workspace_elems() floats; no atomics).  Stage 2, one workgroup, sums the
@@ -432,36 +443,15 @@ int mrmt3_adamw_step(float* p, const float* g, float* m, float* v, size_t n, con
  *   stat_dev[0] = norm = (float)(sqrt(sum) * grad_scale)      the norm of the gradient AdamW will see, before clipping
  *   stat_dev[1] = coef = max_norm > 0 ? min(1, max_norm / (norm + 1e-6)) : 1      (f32)
  *   stat_dev[2] = skip = 1.0 iff skip_nonfinite and norm is inf or NaN; then also coef = 0 and skipped_dev[0] += 1.
- * The same g gives the same bits wherever it runs.  n % 4 == 0. */
-size_t mrmt3_grad_norm_workspace_elems(void);
-int mrmt3_grad_norm(const float* g, size_t n, float grad_scale, float max_norm, int skip_nonfinite, float* ws,
-                    size_t ws_elems, float* stat_dev, int32_t* skipped_dev, void* stream);
-/* mrmt3_adamw_step with the gradient g * grad_scale * stat_dev[1], then, when clip_value > 0, clamped to
- * [-clip_value, clip_value] (`gradient_clip_algorithm: value`).  stat_dev[2] != 0: nothing is stored (p, m, v and the
- * shadow keep their bits).  step_dev is incremented either way: it counts ATTEMPTED optimizer steps.  With
- * stat_dev[1] == 1 and clip_value == 0 the result is mrmt3_adamw_step's, bit for bit. */
-int mrmt3_adamw_step_clipped(float* p, const float* g, float* m, float* v, size_t n, const float* lr_dev,
-                             int32_t* step_dev, float beta1, float beta2, float eps, float weight_decay,
-                             float grad_scale, const float* stat_dev, float clip_value, void* shadow_bf16,
-                             void* stream);
-/* ---- K11c: optimizer parameter groups: AdamW and the gradient norm over a table of trainable element ranges
- * of the flat buffer -- frozen weights (outside every range: never read, never written), per-range weight decay and
- * learning-rate factor, EMA weights in the same pass.
+ * The same g gives the same bits wherever it runs.  n % 4 == 0.  ranges_dev / n_ranges as above: NULL and 0 sum all of g;
+ * a table sums the elements of its ranges only (a frozen gradient slot is never read), the same fixed grid and summation
+ * order over the ranges laid end to end -- a function of the table alone; one range covering the buffer gives the flat
+ * form's bits.
  * mrmt3_opt_ranges_plan (host code, no launch): checks `ranges` (sorted, disjoint, bounds multiples of 4 inside [0, n],
  * finite weight_decay / lr_scale >= 0, at least one range) and writes the table the kernels read into `table_host`
  * (mrmt3_opt_ranges_table_bytes(n_ranges) bytes: per range its first 16-byte group, the prefix sum of the groups before it
  * and its two factors, then a sentinel with the total); the caller copies it to the device (8-byte aligned).
- * *n_trainable (nullable) receives the number of elements inside the ranges.
- * mrmt3_adamw_step_groups: ONE launch over the trainable elements only (a workgroup owns 1024 consecutive 16-byte groups
- * of the ranges laid end to end and finds its range by binary search).  Inside a range the arithmetic is
- * mrmt3_adamw_step's with weight_decay of the range and lr = lr_dev[0] * lr_scale, bit for bit; with stat_dev non-null it
- * is mrmt3_adamw_step_clipped's (coefficient stat_dev[1], clamp to +-clip_value, stat_dev[2] != 0 skips every store).  With
- * `ema` non-null (then 0 < ema_decay < 1; ema null needs ema_decay == 0): ema += (1 - ema_decay) * (p_new - ema) in f32
- * in the same pass; a skipped step leaves ema untouched.  n_trainable is what the planner returned (it sizes the grid;
- * the kernel's bound is the table's own total).  step_dev is incremented either way.
- * mrmt3_grad_norm_ranges: mrmt3_grad_norm over the elements of the ranges only (a frozen gradient slot is never read):
- * the same fixed grid and summation order over the ranges laid end to end -- a function of the table alone; one range
- * covering the buffer gives mrmt3_grad_norm's bits. */
+ * *n_trainable (nullable) receives the number of elements inside the ranges. */
 typedef struct {
   long long begin, end;      /* elements, multiples of 4 */
   float weight_decay, lr_scale;
@@ -469,13 +459,13 @@ typedef struct {
 size_t mrmt3_opt_ranges_table_bytes(int n_ranges);
 int mrmt3_opt_ranges_plan(const mrmt3_opt_range* ranges, int n_ranges, size_t n, void* table_host, size_t table_bytes,
                           size_t* n_trainable);
-int mrmt3_adamw_step_groups(float* p, const float* g, float* m, float* v, float* ema, size_t n, const void* ranges_dev,
-                            int n_ranges, size_t n_trainable, const float* lr_dev, int32_t* step_dev, float beta1,
-                            float beta2, float eps, float grad_scale, float ema_decay, const float* stat_dev,
-                            float clip_value, void* shadow_bf16, void* stream);
-int mrmt3_grad_norm_ranges(const float* g, size_t n, const void* ranges_dev, int n_ranges, float grad_scale, float max_norm,
-                           int skip_nonfinite, float* ws, size_t ws_elems, float* stat_dev, int32_t* skipped_dev,
-                           void* stream);
+int mrmt3_adamw_step(float* p, const float* g, float* m, float* v, float* ema, size_t n, const void* ranges_dev,
+                     int n_ranges, size_t n_trainable, const float* lr_dev, int32_t* step_dev, float beta1, float beta2,
+                     float eps, float weight_decay, float grad_scale, float ema_decay, const float* stat_dev,
+                     float clip_value, void* shadow_bf16, void* stream);
+size_t mrmt3_grad_norm_workspace_elems(void);
+int mrmt3_grad_norm(const float* g, size_t n, const void* ranges_dev, int n_ranges, float grad_scale, float max_norm,
+                    int skip_nonfinite, float* ws, size_t ws_elems, float* stat_dev, int32_t* skipped_dev, void* stream);
 /* ctr[0] += delta on the device (int32, one thread, stream-ordered).  The trainer's gradient accumulation keeps its
  * per-micro-batch dropout salt in such a counter: it is passed as the step_dev of the dropout entry points and bumped
  * once per micro-batch, inside the captured step, so replays draw new masks per micro-batch. */

@@ -106,7 +106,7 @@ def load():
     return lib
 
 
-MIN_VERSION = 120
+MIN_VERSION = 121
 COUNTER_NAMES = ("gemm_nt_tile", "gemm_nt8", "gemm_nt_geglu", "tn_group", "tn8", "tn_tile", "attn_fwd", "attn_bwd",
                  "attn_bwd_onepass", "attn_f32", "tn_f32", "gemm_nt_splitk", "gemm_nt_addnorm", "gemm_nt_normbwd",
                  "gemm_nt_geglubwd", "attn_fwd_varlen", "attn_bwd_varlen")
@@ -1040,49 +1040,15 @@ def lmhead_logprob(dec, w, targets, chunk_rows=None):
     return out
 
 
-def adamw_step(p, g, m, v, lr_dev, step_dev, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.01, grad_scale=1.0,
-               shadow=None):
-    _dev(p, g, m, v, lr_dev, step_dev)
-    _check(load().mrmt3_adamw_step(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(lr_dev), _p(step_dev), beta1, beta2,
-                                   eps, weight_decay, grad_scale, _p(shadow), _stream()), "adamw_step")
-
-
-def grad_norm_workspace(device) -> torch.Tensor:
-    """The f32 workspace mrmt3_grad_norm leaves its per-workgroup f64 partials in (allocate once, outside any capture)."""
-    return torch.empty(int(load().mrmt3_grad_norm_workspace_elems()), device=device, dtype=torch.float32)
-
-
-def grad_norm(g, grad_scale, max_norm, skip_nonfinite, ws, stat, skipped):
-    """Global L2 norm of the flat f32 gradient `g` times grad_scale, on the device, in a fixed summation order (f64
-    accumulation): stat[0] = norm, stat[1] = clip coefficient min(1, max_norm / (norm + 1e-6)) (1 when max_norm is 0),
-    stat[2] = 1.0 when skip_nonfinite and the norm is inf / NaN (then coef = 0 and skipped[0] += 1).  No host sync."""
-    _dev(g, ws, stat, skipped)
-    assert g.dtype == torch.float32 and g.is_contiguous() and ws.dtype == torch.float32
-    assert stat.dtype == torch.float32 and stat.numel() >= 3 and skipped.dtype == torch.int32 and skipped.numel() >= 1
-    _check(load().mrmt3_grad_norm(_p(g), g.numel(), float(grad_scale), float(max_norm), int(bool(skip_nonfinite)), _p(ws),
-                                  ws.numel(), _p(stat), _p(skipped), _stream()), "grad_norm")
-
-
-def adamw_step_clipped(p, g, m, v, lr_dev, step_dev, stat, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.01,
-                       grad_scale=1.0, clip_value=0.0, shadow=None):
-    """adamw_step on g * grad_scale * stat[1] (clamped to +-clip_value when > 0); stat[2] != 0 skips the update (step_dev
-    still advances).  `stat` is what grad_norm wrote."""
-    _dev(p, g, m, v, lr_dev, step_dev, stat)
-    assert stat.dtype == torch.float32 and stat.numel() >= 3
-    _check(load().mrmt3_adamw_step_clipped(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(lr_dev), _p(step_dev), beta1, beta2,
-                                           eps, weight_decay, grad_scale, _p(stat), float(clip_value), _p(shadow),
-                                           _stream()), "adamw_step_clipped")
-
-
 class _OptRange(C.Structure):          # = mrmt3_opt_range
     _fields_ = [("begin", C.c_longlong), ("end", C.c_longlong), ("weight_decay", C.c_float), ("lr_scale", C.c_float)]
 
 
 class OptRanges:
-    """The table mrmt3_adamw_step_groups / mrmt3_grad_norm_ranges read: `ranges` = [(begin, end, weight_decay, lr_scale)]
-    over a flat buffer of `n` elements, checked and laid out by the library's host-side planner (mrmt3_opt_ranges_plan; no
-    GPU needed for that: a ValueError names what is wrong).  `to(device)` copies the table there once; the kernels read it
-    by pointer, so a captured step keeps following the same table object."""
+    """The table adamw_step / grad_norm read through `ranges=`: `ranges` = [(begin, end, weight_decay, lr_scale)] over a
+    flat buffer of `n` elements, checked and laid out by the library's host-side planner (mrmt3_opt_ranges_plan; no GPU
+    needed for that: a ValueError names what is wrong).  `to(device)` copies the table there once; the kernels read it by
+    pointer, so a captured step keeps following the same table object."""
 
     def __init__(self, ranges, n: int):
         self.ranges = [(int(a), int(b), float(wd), float(sc)) for a, b, wd, sc in ranges]
@@ -1109,27 +1075,43 @@ class OptRanges:
         return self
 
 
-def adamw_step_groups(p, g, m, v, ranges: OptRanges, lr_dev, step_dev, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0,
-                      ema=None, ema_decay=0.0, stat=None, clip_value=0.0, shadow=None):
-    """AdamW over the elements of `ranges` only, each range with its own weight decay and lr factor (everything else
-    keeps its bits); `ema`/`ema_decay`: the EMA weights follow in the same pass; `stat` (what grad_norm_ranges wrote):
-    the clipped / skipping form."""
-    _dev(p, g, m, v, ranges.table, ema, stat)
-    assert p.dtype == torch.float32 and p.is_contiguous() and p.numel() == ranges.n
-    _check(load().mrmt3_adamw_step_groups(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), _p(ranges.table), len(ranges),
-                                          ranges.n_trainable, _p(lr_dev), _p(step_dev), beta1, beta2, eps, grad_scale,
-                                          float(ema_decay), _p(stat), float(clip_value), _p(shadow), _stream()),
-           "adamw_step_groups")
+def adamw_step(p, g, m, v, lr_dev, step_dev, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=None, grad_scale=1.0,
+               shadow=None, stat=None, clip_value=0.0, ranges: OptRanges = None, ema=None, ema_decay=0.0):
+    """One AdamW step over the flat buffers; step_dev advances whatever happens.  `stat` (what grad_norm wrote): the
+    gradient is g * grad_scale * stat[1], clamped to +-clip_value when > 0, and stat[2] != 0 skips the update.  `ranges`:
+    only the elements of the table step, each range with its own weight decay and lr factor (everything else keeps its
+    bits; `weight_decay` must then be left out), and with `ema`/`ema_decay` the EMA weights follow in the same pass.
+    Without `ranges`, `weight_decay` defaults to 0.01."""
+    if ranges is not None and weight_decay is not None:
+        raise ValueError("adamw_step: weight_decay comes from the range table; do not pass it together with `ranges`")
+    _dev(p, g, m, v, lr_dev, step_dev, stat, ema, None if ranges is None else ranges.table)
+    assert stat is None or (stat.dtype == torch.float32 and stat.numel() >= 3)
+    assert ranges is None or (p.dtype == torch.float32 and p.is_contiguous() and p.numel() == ranges.n)
+    tab, nr, ntr = (None, 0, 0) if ranges is None else (ranges.table, len(ranges), ranges.n_trainable)
+    wd = 0.01 if weight_decay is None else weight_decay
+    _check(load().mrmt3_adamw_step(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), _p(tab), nr, ntr, _p(lr_dev),
+                                   _p(step_dev), beta1, beta2, eps, wd, grad_scale, float(ema_decay), _p(stat),
+                                   float(clip_value), _p(shadow), _stream()), "adamw_step")
 
 
-def grad_norm_ranges(g, ranges: OptRanges, grad_scale, max_norm, skip_nonfinite, ws, stat, skipped):
-    """lib.grad_norm over the elements of `ranges` only (frozen gradient slots hold stale values and are not read)."""
-    _dev(g, ranges.table, ws, stat, skipped)
-    assert g.dtype == torch.float32 and stat.dtype == torch.float32 and stat.numel() >= 3 and skipped.dtype == torch.int32
-    assert g.numel() == ranges.n
-    _check(load().mrmt3_grad_norm_ranges(_p(g), g.numel(), _p(ranges.table), len(ranges), float(grad_scale), float(max_norm),
-                                         int(bool(skip_nonfinite)), _p(ws), ws.numel(), _p(stat), _p(skipped), _stream()),
-           "grad_norm_ranges")
+def grad_norm_workspace(device) -> torch.Tensor:
+    """The f32 workspace mrmt3_grad_norm leaves its per-workgroup f64 partials in (allocate once, outside any capture)."""
+    return torch.empty(int(load().mrmt3_grad_norm_workspace_elems()), device=device, dtype=torch.float32)
+
+
+def grad_norm(g, grad_scale, max_norm, skip_nonfinite, ws, stat, skipped, ranges: OptRanges = None):
+    """Global L2 norm of the flat f32 gradient `g` times grad_scale, on the device, in a fixed summation order (f64
+    accumulation): stat[0] = norm, stat[1] = clip coefficient min(1, max_norm / (norm + 1e-6)) (1 when max_norm is 0),
+    stat[2] = 1.0 when skip_nonfinite and the norm is inf / NaN (then coef = 0 and skipped[0] += 1).  No host sync.
+    `ranges`: over the elements of the table only (frozen gradient slots hold stale values and are not read)."""
+    _dev(g, ws, stat, skipped, None if ranges is None else ranges.table)
+    assert g.dtype == torch.float32 and g.is_contiguous() and ws.dtype == torch.float32
+    assert stat.dtype == torch.float32 and stat.numel() >= 3 and skipped.dtype == torch.int32 and skipped.numel() >= 1
+    assert ranges is None or g.numel() == ranges.n
+    tab, nr = (None, 0) if ranges is None else (ranges.table, len(ranges))
+    _check(load().mrmt3_grad_norm(_p(g), g.numel(), _p(tab), nr, float(grad_scale), float(max_norm),
+                                  int(bool(skip_nonfinite)), _p(ws), ws.numel(), _p(stat), _p(skipped), _stream()),
+           "grad_norm")
 
 
 def counter_add(ctr, delta=1):

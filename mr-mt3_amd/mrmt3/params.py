@@ -363,39 +363,23 @@ class FlatParams:
             self._tr_n, self._tr_tiles = len(rec), tot
         lib.transpose_batched(self.S, self.ST, self._tr_tab, self._tr_start, self._tr_n, self._tr_tiles)
 
-    def adamw_step(self, lr_dev, step_dev, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, grad_scale=1.0):
-        """torch.optim.AdamW semantics over the whole model in one launch; keeps shadows current."""
-        self._optimizer_launch(lambda: lib.adamw_step(self.P, self.G, self.M, self.V, lr_dev, step_dev, betas[0], betas[1],
-                                                      eps, weight_decay, grad_scale, shadow=self.S))
-
-    def adamw_step_clipped(self, lr_dev, step_dev, stat_dev, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, grad_scale=1.0,
-                           clip_value=0.0):
-        """adamw_step under the clip coefficient / skip flag that lib.grad_norm left in `stat_dev` (device), with an
-        optional clamp of the scaled gradient to +-clip_value.  A skipped step rewrites the transposed shadows from the
-        unchanged bf16 shadow: the same bits."""
-        self._optimizer_launch(lambda: lib.adamw_step_clipped(self.P, self.G, self.M, self.V, lr_dev, step_dev, stat_dev,
-                                                              betas[0], betas[1], eps, weight_decay, grad_scale, clip_value,
-                                                              shadow=self.S))
-
-    def adamw_step_groups(self, lr_dev, step_dev, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, ema_decay=None,
-                          stat_dev=None, clip_value=0.0):
-        """adamw_step / adamw_step_clipped (with `stat_dev`) over the installed range table only — weight decay and lr
-        factor come from the table — and, with `ema_decay`, the EMA of P in the same launch."""
-        if self.opt_ranges is None:
-            raise RuntimeError("adamw_step_groups: no range table is installed (FlatParams.set_groups)")
-        ema = self.ensure_ema() if ema_decay is not None else None
-        self._optimizer_launch(lambda: lib.adamw_step_groups(self.P, self.G, self.M, self.V, self.opt_ranges.to(self.P.device),
-                                                             lr_dev, step_dev, betas[0], betas[1], eps, grad_scale,
-                                                             ema=ema, ema_decay=ema_decay or 0.0, stat=stat_dev,
-                                                             clip_value=clip_value, shadow=self.S))
-
-    def _optimizer_launch(self, launch):
-        """What every optimizer step does around its one launch: moments and shadows exist before it, the transposed
-        shadows and the shadow version follow it."""
+    def adamw_step(self, lr_dev, step_dev, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, grad_scale=1.0, stat_dev=None,
+                   clip_value=0.0, ema_decay=None):
+        """torch.optim.AdamW semantics over the whole model in one launch; keeps shadows current.  With a range table
+        installed (set_groups / all_range) only its elements step, weight decay and lr factor come from the table
+        (`weight_decay` is not passed on) and, with `ema_decay`, the EMA of P follows in the same launch.  `stat_dev`: under
+        the clip coefficient / skip flag that lib.grad_norm left there, with an optional clamp of the scaled gradient to
+        +-clip_value; a skipped step rewrites the transposed shadows from the unchanged bf16 shadow: the same bits."""
+        tab = self.opt_ranges
+        if ema_decay is not None and tab is None:
+            raise RuntimeError("adamw_step: ema_decay needs a range table (FlatParams.all_range / set_groups)")
         self.ensure_adam()
         if self.S is None:
             self.refresh_shadows()
-        launch()
+        lib.adamw_step(self.P, self.G, self.M, self.V, lr_dev, step_dev, betas[0], betas[1], eps,
+                       weight_decay if tab is None else None, grad_scale, shadow=self.S, stat=stat_dev, clip_value=clip_value,
+                       ranges=None if tab is None else tab.to(self.P.device),
+                       ema=None if ema_decay is None else self.ensure_ema(), ema_decay=ema_decay or 0.0)
         self.refresh_transposed()
         self._shadow_version = self.master_version()
 

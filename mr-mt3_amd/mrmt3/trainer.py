@@ -55,8 +55,8 @@ the micro-batches of one cycle and every replay draw their own masks, the same i
 
 Gradient clipping, gradient norm, non-finite guard (`gradient_clip_val`, `gradient_clip_algorithm`, `skip_nonfinite`,
 `track_grad_norm`; Lightning's Trainer arguments of the first two names).  When any of the four is set, the optimizer tail
-of a step — plain step, "last" phase, finish_accumulation() — is mrmt3_grad_norm + mrmt3_adamw_step_clipped instead of
-mrmt3_adamw_step: the norm of G * 1/(world*N) (the mean gradient over ranks and micro-batches, after the exchange) is
+of a step — plain step, "last" phase, finish_accumulation() — is mrmt3_grad_norm + mrmt3_adamw_step with `stat_dev` instead
+of the plain mrmt3_adamw_step: the norm of G * 1/(world*N) (the mean gradient over ranks and micro-batches, after the exchange) is
 reduced on the device in a fixed order, the clip coefficient and the skip flag stay in device memory (`_clip_stat`) and
 AdamW reads them there, so the captured tail graph clips by this step's norm on every replay and the host never waits.
 Every rank holds the same G after the all-reduce and reduces it in the same order: same coefficient, no extra collective.
@@ -73,8 +73,8 @@ are handled alike (device scalars, one per micro-batch, reduced over ranks).  `e
 zero the old entry points run — the same launches as before — and `last_nll` is `last_loss`.
 
 Parameter groups and EMA weights (`frozen`, `no_decay`, `lr_scale`, `ema_decay`).  The patterns are fnmatch patterns
-over the state-dict keys.  With any of them given the optimizer tail is mrmt3_adamw_step_groups (and mrmt3_grad_norm_ranges
-when the clipping tail is on) over a device table of the trainable ranges: a frozen tensor is never read or written, gets no
+over the state-dict keys.  With any of them given the optimizer tail is mrmt3_adamw_step (and mrmt3_grad_norm when the
+clipping tail is on) over a device table of the trainable ranges: a frozen tensor is never read or written, gets no
 weight gradient (Engine.wgrad drops it, so the grouped launch plans fewer items), no place in a gradient bucket, and when the
 whole encoder is frozen the backward stops at the cross-attention k|v projections.  The table is device memory read by
 pointer: the captured step follows it.  `set_frozen()` changes the set between steps and drops the captured graphs (two
@@ -396,24 +396,15 @@ class Trainer:
             raise RuntimeError("%s inside `with trainer.ema_weights()`: the master buffer holds the EMA weights" % what)
 
     def _optimizer_tail(self):
-        """AdamW on the exchanged G; with clipping / norm tracking / the non-finite guard on, the device-side norm first."""
+        """AdamW on the exchanged G (over the range table when one is installed); with clipping / norm tracking / the
+        non-finite guard on, the device-side norm first."""
         scale = 1.0 / (self.world * self.accumulate)
-        if self.groups_on:
-            tab = self.flat.opt_ranges
-            if self.clip_on:
-                lib.grad_norm_ranges(self.flat.G, tab, scale, self._max_norm, self.skip_nonfinite, self._clip_ws,
-                                     self._clip_stat, self._skipped_dev)
-            self.flat.adamw_step_groups(self.lr_dev, self.step_dev, self.betas, self.eps, grad_scale=scale,
-                                        ema_decay=self.ema_decay, stat_dev=self._clip_stat if self.clip_on else None,
-                                        clip_value=self._clip_value if self.clip_on else 0.0)
-            return
-        if not self.clip_on:
-            self.flat.adamw_step(self.lr_dev, self.step_dev, self.betas, self.eps, self.wd, grad_scale=scale)
-            return
-        lib.grad_norm(self.flat.G, scale, self._max_norm, self.skip_nonfinite, self._clip_ws, self._clip_stat,
-                      self._skipped_dev)
-        self.flat.adamw_step_clipped(self.lr_dev, self.step_dev, self._clip_stat, self.betas, self.eps, self.wd,
-                                     grad_scale=scale, clip_value=self._clip_value)
+        if self.clip_on:
+            lib.grad_norm(self.flat.G, scale, self._max_norm, self.skip_nonfinite, self._clip_ws, self._clip_stat,
+                          self._skipped_dev, ranges=self.flat.opt_ranges)
+        self.flat.adamw_step(self.lr_dev, self.step_dev, self.betas, self.eps, self.wd, grad_scale=scale,
+                             stat_dev=self._clip_stat if self.clip_on else None,
+                             clip_value=self._clip_value if self.clip_on else 0.0, ema_decay=self.ema_decay)
 
     @property
     def last_grad_norm(self):

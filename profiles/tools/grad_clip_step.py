@@ -1,5 +1,5 @@
 """Cost of gradient clipping in the captured training step (Trainer(gradient_clip_val=...), mrmt3_grad_norm +
-mrmt3_adamw_step_clipped): the 64-segment MT3Net step of bench.py (bf16, raw audio in, dropout on, graph replay), timed
+mrmt3_adamw_step with stat_dev): the 64-segment MT3Net step of bench.py (bf16, raw audio in, dropout on, graph replay), timed
 with the feature off and on in ONE process, alternating blocks of steps, wall clock around each block with a device
 synchronise; then the norm kernels alone on the model's G (device events), cache-warm and behind a 1 GiB flush.
     python3 profiles/tools/grad_clip_step.py [mode = ab|off|clip] [rounds = 6] [steps per block = 20]

@@ -45,7 +45,7 @@ def test_header_derived_signatures_match_hand_written_ones():
         "mrmt3_comm_create": (ci, [vp, ci, ci, out_handle]),
         "mrmt3_stream_create": (ci, [out_handle, ci]),
         "mrmt3_logmel_crops_fwd": (ci, [vp, ctypes.c_longlong, vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci, vp, vp]),
-        "mrmt3_adamw_step": (ci, [vp, vp, vp, vp, csz, vp, vp, cf, cf, cf, cf, cf, vp, vp]),
+        "mrmt3_adamw_step": (ci, [vp, vp, vp, vp, vp, csz, vp, ci, csz, vp, vp, cf, cf, cf, cf, cf, cf, vp, cf, vp, vp]),
     }
     assert len(want["mrmt3_attn_bwd_varlen"][1]) == 33
     for name, sig in want.items():

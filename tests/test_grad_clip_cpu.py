@@ -1,5 +1,5 @@
 """Gradient clipping without a GPU: train.py's reading of `trainer.gradient_clip_val` / `trainer.gradient_clip_algorithm`
-on composed configs, the trainer's argument validation, and the two new entry points in the header and the binding."""
+on composed configs, the trainer's argument validation, and the norm / step entry points in the header and the binding."""
 import ctypes
 
 import pytest
@@ -56,27 +56,31 @@ def test_new_entry_points_are_declared_bound_and_exported():
     vp, ci, cf, csz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
     want = {
         "mrmt3_grad_norm_workspace_elems": (csz, []),
-        "mrmt3_grad_norm": (ci, [vp, csz, cf, cf, ci, vp, csz, vp, vp, vp]),
-        "mrmt3_adamw_step_clipped": (ci, [vp, vp, vp, vp, csz, vp, vp, cf, cf, cf, cf, cf, vp, cf, vp, vp]),
+        "mrmt3_grad_norm": (ci, [vp, csz, vp, ci, cf, cf, ci, vp, csz, vp, vp, vp]),
+        "mrmt3_adamw_step": (ci, [vp, vp, vp, vp, vp, csz, vp, ci, csz, vp, vp, cf, cf, cf, cf, cf, cf, vp, cf, vp, vp]),
     }
     names = lib.header_symbols()
     for name, sig in want.items():
         assert name in names and lib._SIGS[name] == sig, (name, lib._SIGS.get(name))
-    # the clipped step = mrmt3_adamw_step's arguments plus (stat_dev, clip_value) in front of (shadow, stream)
-    plain = lib._SIGS["mrmt3_adamw_step"][1]
-    assert want["mrmt3_adamw_step_clipped"][1] == plain[:-2] + [vp, cf] + plain[-2:]
+    # one step and one norm: the header declares no sibling of either
+    assert {n for n in names if "adamw" in n or "grad_norm" in n} == set(want)
     so = lib.load()
-    assert so.mrmt3_version() >= 115 and lib.MIN_VERSION >= 115
+    assert so.mrmt3_version() >= 121 and lib.MIN_VERSION >= 121
     assert so.mrmt3_grad_norm_workspace_elems() >= 2 and so.mrmt3_grad_norm_workspace_elems() % 2 == 0
-    assert callable(lib.grad_norm) and callable(lib.adamw_step_clipped)
+    assert callable(lib.grad_norm) and callable(lib.adamw_step)
     assert "grad_norm" not in lib.COUNTER_NAMES and len(lib.COUNTER_NAMES) == 17
     # argument errors come back as codes with a message, before anything is launched (no device needed)
     buf = (ctypes.c_double * 8)()
     a = (ctypes.addressof(buf) + 15) & ~15
-    assert so.mrmt3_grad_norm(a, 6, 1.0, 0.0, 0, a, 1 << 20, a, a, None) != 0 and b"multiple of 4" in so.mrmt3_last_error()
-    assert so.mrmt3_grad_norm(a, 8, 1.0, 0.0, 0, a, 16, a, a, None) != 0 and b"workspace" in so.mrmt3_last_error()
-    assert so.mrmt3_grad_norm(a, 8, 1.0, -1.0, 0, a, 1 << 20, a, a, None) != 0 and b"max_norm" in so.mrmt3_last_error()
-    assert so.mrmt3_grad_norm(None, 8, 1.0, 0.0, 0, a, 1 << 20, a, a, None) != 0 and b"null" in so.mrmt3_last_error()
-    assert so.mrmt3_adamw_step_clipped(a, a, a, a, 8, a, a, 0.9, 0.999, 1e-8, 0.01, 1.0, None, 0.0, None, None) != 0
-    assert so.mrmt3_adamw_step_clipped(a, a, a, a, 8, a, a, 0.9, 0.999, 1e-8, 0.01, 1.0, a, -1.0, None, None) != 0
-    assert b"clip_value" in so.mrmt3_last_error()
+    assert so.mrmt3_grad_norm(a, 6, None, 0, 1.0, 0.0, 0, a, 1 << 20, a, a, None) != 0 and b"multiple of 4" in so.mrmt3_last_error()
+    assert so.mrmt3_grad_norm(a, 8, None, 0, 1.0, 0.0, 0, a, 16, a, a, None) != 0 and b"workspace" in so.mrmt3_last_error()
+    assert so.mrmt3_grad_norm(a, 8, None, 0, 1.0, -1.0, 0, a, 1 << 20, a, a, None) != 0 and b"max_norm" in so.mrmt3_last_error()
+    assert so.mrmt3_grad_norm(None, 8, None, 0, 1.0, 0.0, 0, a, 1 << 20, a, a, None) != 0 and b"null" in so.mrmt3_last_error()
+
+    def flat_step(stat, clip, n=8, p=a):       # the flat form: no ema, no table
+        return so.mrmt3_adamw_step(p, a, a, a, None, n, None, 0, 0, a, a, 0.9, 0.999, 1e-8, 0.01, 1.0, 0.0, stat, clip, None, None)
+    assert flat_step(None, 0.5) != 0 and b"needs stat_dev" in so.mrmt3_last_error()      # a clamp without the clipped form
+    assert flat_step(a, -1.0) != 0 and b"clip_value" in so.mrmt3_last_error()
+    assert flat_step(None, -1.0) != 0 and b"clip_value" in so.mrmt3_last_error()
+    assert flat_step(a, 0.0, n=6) != 0 and b"bad args" in so.mrmt3_last_error()
+    assert flat_step(a, 0.0, p=None) != 0 and b"bad args" in so.mrmt3_last_error()

@@ -1,6 +1,6 @@
 """Gradient clipping by global norm / by value, the logged gradient norm and the non-finite guard of the trainer
 (`Trainer(gradient_clip_val=, gradient_clip_algorithm=, skip_nonfinite=, track_grad_norm=)`, mrmt3_grad_norm +
-mrmt3_adamw_step_clipped) on the MI355X: the norm kernel against float64, the clipped AdamW step against float64, the
+mrmt3_adamw_step with `stat_dev`) on the MI355X: the norm kernel against float64, the clipped AdamW step against float64, the
 unclipped step's bits, graph replay against eager launches, accumulation, two ranks, skipped steps, train.py's log lines."""
 import os
 import re
@@ -162,7 +162,8 @@ def test_clipped_step_equals_float64_adamw_by_norm_and_by_value(dev):
 # ---- 3. neutrality -------------------------------------------------------------------------------------------------
 def test_coefficient_one_is_the_unclipped_step_bit_for_bit(dev, monkeypatch):
     """bf16, dropout on, three steps: gradient_clip_val = 1e30 (coef exactly 1) leaves P, M, V and the bf16 shadow bit-equal
-    to a trainer built without any of the options — and that trainer never calls the norm / clipped entry points."""
+    to a trainer built without any of the options — and that trainer never calls the norm entry points, builds no range
+    table, and calls lib.adamw_step without `stat`, `ranges` or `ema`."""
     from mrmt3 import lib
     from mrmt3.trainer import Trainer
     data = [_micro(dev, B=2, L=128, seed=20 + i) for i in range(3)]
@@ -172,16 +173,22 @@ def test_coefficient_one_is_the_unclipped_step_bit_for_bit(dev, monkeypatch):
         if clip is None:
             def boom(*a, **k):
                 raise AssertionError("the feature is off: no norm / clipped launch may be issued")
-            monkeypatch.setattr(lib, "grad_norm", boom)
-            monkeypatch.setattr(lib, "adamw_step_clipped", boom)
-            monkeypatch.setattr(lib, "grad_norm_workspace", boom)
+            plain_step, plain_calls = lib.adamw_step, []
+
+            def spy(*a, stat=None, ranges=None, ema=None, **k):
+                assert stat is None and ranges is None and ema is None and len(a) <= 12, "the feature is off: the plain step"
+                plain_calls.append(1)
+                return plain_step(*a, **k)
+            for name in ("grad_norm", "grad_norm_workspace", "OptRanges"):
+                monkeypatch.setattr(lib, name, boom)
+            monkeypatch.setattr(lib, "adamw_step", spy)
         tr = Trainer(m, lr=1e-3, graph=False, gradient_clip_val=clip)
         assert tr.clip_on == (clip is not None)
         for x in data:
             tr.train_step(*x)
         torch.cuda.synchronize()
         if clip is None:
-            assert tr.last_grad_norm is None and tr.skipped_steps == 0
+            assert tr.last_grad_norm is None and tr.skipped_steps == 0 and len(plain_calls) == len(data)
         else:
             assert float(tr._clip_stat[1].item()) == 1.0 and float(tr.last_grad_norm.item()) > 0
         runs[clip] = [t.clone() for t in (m.flat.P, m.flat.M, m.flat.V, m.flat.S)]
@@ -191,7 +198,7 @@ def test_coefficient_one_is_the_unclipped_step_bit_for_bit(dev, monkeypatch):
 
 @pytest.mark.parametrize("scale", [0.25, 1.0 / 3.0])
 def test_abi_clipped_step_with_coefficient_one_equals_adamw_step_bitwise(dev, scale):
-    """Also with an inexact grad_scale (1/3: three micro-batches or ranks): rowops.hip is compiled with fp contract off, so
+    """adamw_step(stat=[., 1, 0]) (adamw_kernel<true>) against adamw_step() (adamw_kernel<false>).  Also with an inexact grad_scale (1/3: three micro-batches or ranks): rowops.hip is compiled with fp contract off, so
     neither kernel fuses g * scale into the next operation and the extra `* 1.0f` changes no bit."""
     from mrmt3 import lib
     n = 4 * 70001
@@ -206,7 +213,7 @@ def test_abi_clipped_step_with_coefficient_one_equals_adamw_step_bitwise(dev, sc
         step = torch.full((1,), 6, device=dev, dtype=torch.int32)
         if clipped:
             stat = torch.tensor([1.0, 1.0, 0.0, 0.0], device=dev)
-            lib.adamw_step_clipped(P, g, M, V, lr, step, stat, grad_scale=scale, clip_value=0.0, shadow=S)
+            lib.adamw_step(P, g, M, V, lr, step, grad_scale=scale, stat=stat, clip_value=0.0, shadow=S)
         else:
             lib.adamw_step(P, g, M, V, lr, step, grad_scale=scale, shadow=S)
         torch.cuda.synchronize()
@@ -355,7 +362,7 @@ def test_abi_nonfinite_gradient_skips_the_step(dev, poison):
     step = torch.full((1,), 3, device=dev, dtype=torch.int32)
     lib.grad_norm(g, 0.5, 1.0, True, ws, stat, skipped)
     P, M, V, S = p.clone(), m.clone(), v.clone(), s.clone()
-    lib.adamw_step_clipped(P, g, M, V, lr, step, stat, grad_scale=0.5, shadow=S)
+    lib.adamw_step(P, g, M, V, lr, step, grad_scale=0.5, stat=stat, shadow=S)
     torch.cuda.synchronize()
     st = stat.cpu().numpy()
     assert not np.isfinite(st[0]) and st[1] == 0.0 and st[2] == 1.0 and int(skipped.item()) == 1
@@ -368,7 +375,7 @@ def test_abi_nonfinite_gradient_skips_the_step(dev, poison):
     torch.cuda.synchronize()
     assert int(skipped.item()) == 2
     lib.grad_norm(g, 0.5, 1.0, True, ws, stat, skipped)
-    lib.adamw_step_clipped(P, g, M, V, lr, step, stat, grad_scale=0.5, shadow=S)
+    lib.adamw_step(P, g, M, V, lr, step, grad_scale=0.5, stat=stat, shadow=S)
     torch.cuda.synchronize()
     st = stat.cpu().numpy()
     assert np.isfinite(st[0]) and 0 < st[1] < 1 and st[2] == 0.0 and int(skipped.item()) == 2 and int(step.item()) == 5

@@ -94,15 +94,19 @@ def test_step_entry_points_check_their_arguments_before_any_launch():
     tab = C.c_void_p(0x2000)
 
     def step(ema=None, ema_decay=0.0, stat=None, clip=0.0, n=1024, nr=1, ntr=1024, table=tab):
-        return L.mrmt3_adamw_step_groups(p, p, p, p, ema, n, table, nr, ntr, p, p, 0.9, 0.999, 1e-8, 1.0, ema_decay, stat, clip,
-                                         None, None)
+        return L.mrmt3_adamw_step(p, p, p, p, ema, n, table, nr, ntr, p, p, 0.9, 0.999, 1e-8, 0.01, 1.0, ema_decay, stat, clip,
+                                  None, None)
 
     for kw, why in ((dict(ema_decay=0.9), b"needs an ema buffer"), (dict(ema=p, ema_decay=0.0), b"ema buffer was given"),
                     (dict(ema=p, ema_decay=1.0), b"outside (0, 1)"), (dict(ema=p, ema_decay=-0.5), b"outside (0, 1)"),
                     (dict(ema=p, ema_decay=float("nan")), b"outside (0, 1)"), (dict(clip=-1.0), b"clip_value"),
                     (dict(clip=0.5), b"needs stat_dev"), (dict(n=1022), b"bad args"), (dict(nr=0), b"ranges"),
-                    (dict(ntr=2048), b"n_trainable"), (dict(ntr=0), b"n_trainable"), (dict(table=None), b"bad args"),
-                    (dict(table=C.c_void_p(0x2004)), b"8-byte aligned")):
+                    (dict(nr=-1), b"ranges"), (dict(nr=1 << 20), b"ranges"),
+                    (dict(ntr=2048), b"n_trainable"), (dict(ntr=0), b"n_trainable"), (dict(table=None, nr=1), b"bad args"),
+                    (dict(table=C.c_void_p(0x2004)), b"8-byte aligned"),
+                    # a null table with 0 ranges is the flat form, which keeps no EMA
+                    (dict(table=None, nr=0, ema=p, ema_decay=0.9), b"keeps no EMA"),
+                    (dict(table=None, nr=0, ema_decay=0.9), b"needs an ema buffer")):
         assert step(**kw) == 1, kw
         assert why in L.mrmt3_last_error(), (kw, L.mrmt3_last_error())
     ws = C.c_void_p(0x3000)
@@ -110,10 +114,23 @@ def test_step_entry_points_check_their_arguments_before_any_launch():
     for args, why in (((p, 1022, tab, 1, 1.0, 0.0, 0, ws, need, p, p, None), b"multiple of 4"),
                       ((p, 1024, None, 1, 1.0, 0.0, 0, ws, need, p, p, None), b"null pointer"),
                       ((p, 1024, tab, 0, 1.0, 0.0, 0, ws, need, p, p, None), b"ranges"),
+                      ((p, 1024, tab, -1, 1.0, 0.0, 0, ws, need, p, p, None), b"ranges"),
+                      ((p, 1024, C.c_void_p(0x2004), 1, 1.0, 0.0, 0, ws, need, p, p, None), b"8-byte aligned"),
                       ((p, 1024, tab, 1, 1.0, -1.0, 0, ws, need, p, p, None), b"max_norm"),
                       ((p, 1024, tab, 1, 1.0, 0.0, 0, ws, 8, p, p, None), b"workspace")):
-        assert L.mrmt3_grad_norm_ranges(*args) == 1, args
+        assert L.mrmt3_grad_norm(*args) == 1, args
         assert why in L.mrmt3_last_error(), (args, L.mrmt3_last_error())
+
+
+def test_binding_takes_weight_decay_from_the_table_only():
+    """lib.adamw_step(ranges=...) with a weight_decay beside it is a ValueError before anything else is looked at."""
+    from mrmt3 import lib
+    t = lib.OptRanges([(0, 8, 0.01, 1.0)], 8)
+    x = torch.zeros(8)
+    with pytest.raises(ValueError, match="weight_decay comes from the range table"):
+        lib.adamw_step(x, x, x, x, x[:1], torch.zeros(1, dtype=torch.int32), weight_decay=0.01, ranges=t)
+    with pytest.raises(RuntimeError, match="device tensors"):                   # no CPU fallback, with or without a table
+        lib.adamw_step(x, x, x, x, x[:1], torch.zeros(1, dtype=torch.int32), ranges=t)
 
 
 # ---- checkpoint ------------------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
-"""Optimizer parameter groups on the MI355X: mrmt3_adamw_step_groups / mrmt3_grad_norm_ranges alone, then the
+"""Optimizer parameter groups on the MI355X: mrmt3_adamw_step / mrmt3_grad_norm over a range table alone, then the
 trainer with frozen weights, no-decay sets and EMA weights — against tests/optim_groups_ref.py (torch.optim.AdamW with real
-param groups, a float64 EMA loop), against the existing one-group kernels bit for bit, eager against graph replay."""
+param groups, a float64 EMA loop), against the flat form of the same entry points bit for bit, eager against graph replay."""
 import socket
 
 import numpy as np
@@ -56,7 +56,7 @@ def _table(dev, ranges=RANGES, n=N):
 # ---- 1. the kernel alone ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("clipped", [False, True])
 def test_grouped_step_equals_the_one_group_kernel_per_range_and_leaves_frozen_bits(dev, clipped):
-    """Inside each range P, M, V and the bf16 shadow are bit-equal to mrmt3_adamw_step (clipped: mrmt3_adamw_step_clipped,
+    """Inside each range P, M, V and the bf16 shadow are bit-equal to the flat mrmt3_adamw_step (clipped: with stat_dev,
     coefficient 0.5 and a clamp) run on a copy of that range with the range's weight decay and lr * lr_scale; every element
     outside the ranges keeps its sentinel bits in p, m, v, shadow and ema; the EMA moved inside the ranges."""
     from mrmt3 import lib
@@ -67,8 +67,8 @@ def test_grouped_step_equals_the_one_group_kernel_per_range_and_leaves_frozen_bi
     lr = torch.full((1,), 1e-2, device=dev)
     step = torch.full((1,), 6, device=dev, dtype=torch.int32)
     stat = torch.tensor([3.0, 0.5, 0.0, 0.0], device=dev) if clipped else None
-    lib.adamw_step_groups(b["p"], b["g"], b["m"], b["v"], tab, lr, step, grad_scale=1.0 / 3, ema=b["ema"], ema_decay=0.9,
-                          stat=stat, clip_value=0.2 if clipped else 0.0, shadow=b["s"])
+    lib.adamw_step(b["p"], b["g"], b["m"], b["v"], lr, step, grad_scale=1.0 / 3, ranges=tab, ema=b["ema"], ema_decay=0.9,
+                   stat=stat, clip_value=0.2 if clipped else 0.0, shadow=b["s"])
     torch.cuda.synchronize()
     assert int(step.item()) == 7
     for k in ("p", "m", "v", "ema", "s"):
@@ -79,7 +79,7 @@ def test_grouped_step_equals_the_one_group_kernel_per_range_and_leaves_frozen_bi
         lr_r = lr * torch.tensor(sc, device=dev)                                  # the kernel's f32 product
         st = torch.full((1,), 6, device=dev, dtype=torch.int32)
         if clipped:
-            lib.adamw_step_clipped(P, G, M, V, lr_r, st, stat, weight_decay=wd, grad_scale=1.0 / 3, clip_value=0.2, shadow=S)
+            lib.adamw_step(P, G, M, V, lr_r, st, weight_decay=wd, grad_scale=1.0 / 3, stat=stat, clip_value=0.2, shadow=S)
         else:
             lib.adamw_step(P, G, M, V, lr_r, st, weight_decay=wd, grad_scale=1.0 / 3, shadow=S)
         torch.cuda.synchronize()
@@ -91,8 +91,8 @@ def test_grouped_step_equals_the_one_group_kernel_per_range_and_leaves_frozen_bi
     # without an EMA buffer: the same P, and ema is not touched anywhere
     c = {k: t.clone() for k, t in before.items()}
     step.fill_(6)
-    lib.adamw_step_groups(c["p"], c["g"], c["m"], c["v"], tab, lr, step, grad_scale=1.0 / 3, stat=stat,
-                          clip_value=0.2 if clipped else 0.0, shadow=c["s"])
+    lib.adamw_step(c["p"], c["g"], c["m"], c["v"], lr, step, grad_scale=1.0 / 3, ranges=tab, stat=stat,
+                   clip_value=0.2 if clipped else 0.0, shadow=c["s"])
     torch.cuda.synchronize()
     assert torch.equal(_bits(c["p"]), _bits(b["p"])) and torch.equal(_bits(c["ema"]), _bits(before["ema"]))
 
@@ -111,7 +111,7 @@ def test_one_range_over_the_buffer_equals_the_one_group_step_and_norm_bitwise(de
         P, M, V, S = p.clone(), m.clone(), v.clone(), torch.zeros(n, device=dev, dtype=torch.bfloat16)
         step = torch.full((1,), 2, device=dev, dtype=torch.int32)
         if grouped:
-            lib.adamw_step_groups(P, g, M, V, tab, lr, step, grad_scale=0.25, shadow=S)
+            lib.adamw_step(P, g, M, V, lr, step, grad_scale=0.25, ranges=tab, shadow=S)
         else:
             lib.adamw_step(P, g, M, V, lr, step, grad_scale=0.25, shadow=S)
         out.append((P, M, V, S))
@@ -122,7 +122,7 @@ def test_one_range_over_the_buffer_equals_the_one_group_step_and_norm_bitwise(de
     s1, s2 = torch.zeros(4, device=dev), torch.zeros(4, device=dev)
     sk = torch.zeros(1, device=dev, dtype=torch.int32)
     lib.grad_norm(g, 0.5, 1.0, False, ws, s1, sk)
-    lib.grad_norm_ranges(g, tab, 0.5, 1.0, False, ws, s2, sk)
+    lib.grad_norm(g, 0.5, 1.0, False, ws, s2, sk, ranges=tab)
     torch.cuda.synchronize()
     assert torch.equal(_bits(s1), _bits(s2)) and float(s1[0]) > 0
 
@@ -143,7 +143,7 @@ def test_ema_after_eight_steps_against_float64(dev):
     gen = torch.Generator(device=dev).manual_seed(4)
     for _ in range(steps):
         b["g"][~frozen] = torch.randn(int((~frozen).sum()), device=dev, generator=gen)
-        lib.adamw_step_groups(b["p"], b["g"], b["m"], b["v"], tab, lr, step, ema=b["ema"], ema_decay=decay)
+        lib.adamw_step(b["p"], b["g"], b["m"], b["v"], lr, step, ranges=tab, ema=b["ema"], ema_decay=decay)
         torch.cuda.synchronize()
         traj.append(b["p"].double().cpu().numpy()[keep])
     want = ema64(traj, decay, ema0[keep])
@@ -173,9 +173,9 @@ def test_nonfinite_gradient_skips_everything_only_when_it_is_trainable(dev):
         before = {k: t.clone() for k, t in b.items()}
         stat, skipped = torch.zeros(4, device=dev), torch.zeros(1, device=dev, dtype=torch.int32)
         step = torch.full((1,), 3, device=dev, dtype=torch.int32)
-        lib.grad_norm_ranges(b["g"], tab, 0.5, 1.0, True, ws, stat, skipped)
-        lib.adamw_step_groups(b["p"], b["g"], b["m"], b["v"], tab, lr, step, grad_scale=0.5, ema=b["ema"], ema_decay=0.99,
-                              stat=stat, shadow=b["s"])
+        lib.grad_norm(b["g"], 0.5, 1.0, True, ws, stat, skipped, ranges=tab)
+        lib.adamw_step(b["p"], b["g"], b["m"], b["v"], lr, step, grad_scale=0.5, ranges=tab, ema=b["ema"], ema_decay=0.99,
+                       stat=stat, shadow=b["s"])
         torch.cuda.synchronize()
         st = stat.cpu().numpy()
         assert int(step.item()) == 4 and int(skipped.item()) == skipped_want
@@ -220,7 +220,7 @@ def test_norm_over_ranges_equals_float64_within_one_ulp(dev):
         got = []
         for _ in range(2):
             stat, skipped = torch.full((4,), -7.0, device=dev), torch.zeros(1, device=dev, dtype=torch.int32)
-            lib.grad_norm_ranges(g, tab, scale, float(want) / 2, False, ws, stat, skipped)
+            lib.grad_norm(g, scale, float(want) / 2, False, ws, stat, skipped, ranges=tab)
             torch.cuda.synchronize()
             got.append(stat.cpu().numpy())
         print("n = %d, %d ranges: norm %.9g, float64 %.9g" % (n, len(ranges), got[0][0], want))
@@ -545,7 +545,8 @@ def test_checkpoint_resume_restores_groups_and_ema(dev, tmp_path):
 
 
 def test_default_trainer_is_the_one_group_step_of_before(dev, monkeypatch):
-    """None of the new options: the grouped entry points are never called, the launches per family are those of the model's
+    """None of the options: the norm is never called, no range table is built, lib.adamw_step gets no `stat`, `ranges` or
+    `ema`, the launches per family are those of the model's
     structure (what the step launched before), and two steps give exactly the weights of a by-hand loop of lib.adamw_step
     over the same gradients."""
     from mrmt3 import lib
@@ -553,8 +554,15 @@ def test_default_trainer_is_the_one_group_step_of_before(dev, monkeypatch):
 
     def boom(*a, **k):
         raise AssertionError("no option is on: no grouped launch, no range table")
-    for name in ("adamw_step_groups", "grad_norm_ranges", "OptRanges"):
+    for name in ("grad_norm", "grad_norm_workspace", "OptRanges"):
         monkeypatch.setattr(lib, name, boom)
+    plain_step, plain_calls = lib.adamw_step, []
+
+    def spy(*a, stat=None, ranges=None, ema=None, **k):
+        assert stat is None and ranges is None and ema is None and len(a) <= 12, "no option is on: the plain step"
+        plain_calls.append(1)
+        return plain_step(*a, **k)
+    monkeypatch.setattr(lib, "adamw_step", spy)
     data = [_batch(dev, 600 + 10 * i) for i in range(2)]
     m = _model(torch.bfloat16, dev)
     tr = Trainer(m, lr=1e-3, graph=False)
@@ -570,6 +578,7 @@ def test_default_trainer_is_the_one_group_step_of_before(dev, monkeypatch):
         assert c["attn_fwd"] + c["attn_fwd_varlen"] == n_enc + 2 * n_dec, c
         lib.adamw_step(P, m.flat.G, M, V, lr, step, shadow=S)
     torch.cuda.synchronize()
+    assert len(plain_calls) == 2 * len(data)                                       # the trainer's and the by-hand loop's
     for got, want in ((m.flat.P, P), (m.flat.M, M), (m.flat.V, V), (m.flat.S, S)):
         assert torch.equal(_bits(got), _bits(want))
 
