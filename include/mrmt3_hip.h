@@ -73,7 +73,9 @@ void mrmt3_host_free(void* p);
 #define MRMT3_CNT_GEMM_NT_GEGLUBWD 14 /* wo data gradient + gated-GELU backward in one launch (mrmt3_gemm_nt_geglubwd) */
 #define MRMT3_CNT_ATTN_FWD_VARLEN 15  /* packed-row attention forward, bf16 or exact f32 (mrmt3_attn_fwd_varlen) */
 #define MRMT3_CNT_ATTN_BWD_VARLEN 16  /* packed-row attention backward, bf16 or exact f32 (mrmt3_attn_bwd_varlen) */
-#define MRMT3_CNT_N 17
+#define MRMT3_CNT_LOGMEL_WAVE 17      /* log-mel, wave-per-frame kernel (the model's configuration) */
+#define MRMT3_CNT_LOGMEL_GENERAL 18   /* log-mel, workgroup-per-frame kernel (every other configuration, MRMT3_LOGMEL=0) */
+#define MRMT3_CNT_N 19
 int mrmt3_dispatch_counts(unsigned long long* out, int n, int reset);
 
 /* Dispatch / tuning switches ("knobs").  Which kernel or tile shape a call takes is a function of its arguments; a few

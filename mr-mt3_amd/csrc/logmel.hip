@@ -435,6 +435,7 @@ static int logmel_launch(const float* audio, int batch, int n_samples, int hop, 
         hipLaunchKernelGGL(logmel_wave_kernel<false>, grid, dim3(LMW_THREADS), 0, s, audio, n_samples, n_frames, hop, fpw, window,
                            twiddle, fb_start, fb_cnt, fb_w, max_taps, valid_frames, seg_start, total_samples, lo, hi, normalize, out);
       MR_CHECK_LAUNCH("logmel_fwd");
+      mrmt3_count(MRMT3_CNT_LOGMEL_WAVE);
       return MRMT3_OK;
     }
   }
@@ -448,6 +449,7 @@ static int logmel_launch(const float* audio, int batch, int n_samples, int hop, 
                        fb_start, fb_cnt, fb_w, n_mels, max_taps, valid_frames, seg_start, total_samples, lo, hi, normalize,
                        out);
   MR_CHECK_LAUNCH("logmel_fwd");
+  mrmt3_count(MRMT3_CNT_LOGMEL_GENERAL);
   return MRMT3_OK;
 }
 

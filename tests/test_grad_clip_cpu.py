@@ -68,7 +68,7 @@ def test_new_entry_points_are_declared_bound_and_exported():
     assert so.mrmt3_version() >= 121 and lib.MIN_VERSION >= 121
     assert so.mrmt3_grad_norm_workspace_elems() >= 2 and so.mrmt3_grad_norm_workspace_elems() % 2 == 0
     assert callable(lib.grad_norm) and callable(lib.adamw_step)
-    assert "grad_norm" not in lib.COUNTER_NAMES and len(lib.COUNTER_NAMES) == 17
+    assert "grad_norm" not in lib.COUNTER_NAMES and len(lib.COUNTER_NAMES) == 19      # 17 families + the two log-mel kernels
     # argument errors come back as codes with a message, before anything is launched (no device needed)
     buf = (ctypes.c_double * 8)()
     a = (ctypes.addressof(buf) + 15) & ~15
