@@ -117,6 +117,32 @@ int mrmt3_logmel_crops_fwd(const float* audio, long long total_samples, const lo
                            const float* fb_w, int n_mels, int max_taps, const int* valid_frames,
                            int normalize, int out_bf16, void* out, void* stream);
 
+/* Same frontend for rows that are MIXED, inside the load that fills the frame, out of stems resident in one device buffer
+ * (stem-mix training batches: a random sub-mix of a track's stems at random gains; neither the mix nor the crops are ever
+ * materialised).  pool[pool_samples] f32 holds many stems end to end, possibly of several tracks; src_start, src_end
+ * (int64) and src_gain (f32) are DEVICE tables [batch][n_src], 1 <= n_src <= 64.  The contract:
+ *  - row b, source k: src_start is the pool offset of the crop's first sample, src_end one past the last sample of THAT
+ *    STEM.  The source contributes pool[start + i], 0 <= i < n_samples, only while start + i < end: never its neighbour's
+ *    samples.
+ *  - a source with src_gain == 0.0f is NOT READ AT ALL and its start and end are ignored: this is how a row uses fewer
+ *    than n_src stems.
+ *  - the kernel never reads outside [0, pool_samples) WHATEVER the tables hold: end is clamped to pool_samples, a source
+ *    with start < 0 or start >= end is silent.  A property of the kernel, not a precondition.
+ *  - sample i of the row is computed in f32, in source order, the product rounded before the addition (no fused
+ *    multiply-add):  acc = 0.f;  for k = 0 .. n_src-1, contributing sources only:  acc = acc + fl(gain_k * sample_k);
+ *    one defined f32 value that a sequential numpy restatement reproduces bit for bit.
+ *  - the sample is zero for i >= valid_frames[b]*hop and output frames >= valid_frames[b] are zero, as in the crops entry
+ *    (valid_frames may be NULL).
+ *  - from the mixed sample on it is the frontend above: window, FFT, filterbank, safe log, clamp / scale, f32 or bf16; the
+ *    same two kernels by the same argument rule, so with n_src = 1 and gain 1 the output equals mrmt3_logmel_crops_fwd's
+ *    bit for bit.
+ * MRMT3_ERR_INVALID_ARG before any launch: a null pointer (valid_frames excepted), n_src outside [1, 64], a size <= 0. */
+int mrmt3_logmel_mix_fwd(const float* pool, long long pool_samples, const long long* src_start,
+                         const long long* src_end, const float* src_gain, int n_src, int batch, int n_samples,
+                         int hop, const float* window, const float* twiddle, const int* fb_start,
+                         const int* fb_cnt, const float* fb_w, int n_mels, int max_taps,
+                         const int* valid_frames, int normalize, int out_bf16, void* out, void* stream);
+
 /* ---- K2/K4/K6/K7/K9: bias-free Linear layers (nn.Linear(bias=False) inside HF T5Block,
  * models/t5.py:51,72,487-490) ----------------------------------------------------------------------
  * NT:  C[M,N] (+)= A[M,K] . B[N,K]^T      forward y = x W^T, and dgrad with a pre-transposed W.

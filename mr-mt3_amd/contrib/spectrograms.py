@@ -151,6 +151,26 @@ def logmel_crops(audio: torch.Tensor, start_frames: torch.Tensor, n_frames: int,
                             out_bf16=out_bf16)
 
 
+def logmel_mix(pool: torch.Tensor, start_frames: torch.Tensor, src_end: torch.Tensor, src_gain: torch.Tensor,
+               n_frames: int, cfg: SpectrogramConfig = SpectrogramConfig(), normalize=True, valid_frames=None,
+               out_bf16=False) -> torch.Tensor:
+    """Rows mixed out of stems resident on the GPU -> [B, n_frames, n_mels], without materialising the mix or the
+    crops (`mrmt3_logmel_mix_fwd`).  `pool` [total] f32 holds the stems end to end; `start_frames` [B, n_src] (int64,
+    in hops of the pool, like `logmel_crops`) is where each source's crop starts, `src_end` [B, n_src] (int64, in
+    SAMPLES) one past the last sample of the stem it is cut from, `src_gain` [B, n_src] f32 its gain — 0 for a source
+    the row does not use, which is then not read at all.  A row is the f32 sum, in source order, of gain * sample;
+    frames >= valid_frames[b] come out zero."""
+    if not pool.is_cuda:
+        raise RuntimeError("logmel_mix needs a device tensor (no CPU fallback)")
+    dev = pool.device
+    starts = (start_frames.to(device=dev, dtype=torch.int64) * cfg.hop_width).contiguous()
+    ends = src_end.to(device=dev, dtype=torch.int64).contiguous()
+    gains = src_gain.to(device=dev, dtype=torch.float32).contiguous()
+    vf = None if valid_frames is None else valid_frames.to(device=dev, dtype=torch.int32).contiguous()
+    return lib.logmel_mix(pool.contiguous().float().view(-1), starts, ends, gains, n_frames * cfg.hop_width,
+                          kernel_tables(cfg, dev), valid_frames=vf, normalize=normalize, out_bf16=out_bf16)
+
+
 def compute_spectrogram(samples, spectrogram_config, device=None):
     """[N] samples (numpy) -> [ceil(N/hop), n_mels] log-mel (numpy, un-normalised), like the
     reference function; runs on `device` (default cuda:0)."""

@@ -36,7 +36,35 @@ __device__ __forceinline__ c2 twiddle(const c2* tw, int idx) {
   return t;
 }
 
-template <bool OUT_BF16>
+// ---- stem mix (mrmt3_logmel_mix_fwd): a row's samples are a gain-weighted sum of up to 64 sources of one pool ----------
+// The MIX instances of both kernels read `audio` as the pool, `seg_start` as src_start [batch][n_src] and `total_samples`
+// as pool_samples; the two other tables travel in MixTab<true>.  MixTab<false> is empty: the instances of the plain and
+// the crops entry points carry no argument and no instruction of this.
+#define LM_MAX_SRC 64
+template <bool MIX> struct MixTab {};
+template <> struct MixTab<true> {
+  const long long* src_end;   // [batch][n_src] one past the last sample of the stem the source is cut from
+  const float* src_gain;      // [batch][n_src] 0.0f: the source is not read at all
+  int n_src;
+};
+// Source k of a row under the header's contract: false when it is silent (gain 0: nothing of it is even looked at;
+// start < 0 or start >= min(end, pool_samples)), else its first sample, how many it has from there, and its gain.
+// p[i] is inside [0, pool_samples) for every 0 <= i < avail, whatever the tables hold.
+__device__ __forceinline__ bool mix_source(const float* pool, long long pool_samples, const long long* src_start,
+                                           const MixTab<true>& mix, int row, int k, const float*& p, long long& avail, float& g) {
+  const size_t e = (size_t)row * mix.n_src + k;
+  g = mix.src_gain[e];
+  if (g == 0.0f) return false;
+  const long long st = src_start[e];
+  long long en = mix.src_end[e];
+  if (en > pool_samples) en = pool_samples;
+  if (st < 0 || st >= en) return false;
+  p = pool + st;
+  avail = en - st;
+  return true;
+}
+
+template <bool OUT_BF16, bool MIX>
 __global__ __launch_bounds__(LM_THREADS) void logmel_kernel(
     const float* __restrict__ audio, int n_samples, int n_frames, int hop,
     const float* __restrict__ window,      // [2048]
@@ -48,7 +76,7 @@ __global__ __launch_bounds__(LM_THREADS) void logmel_kernel(
     const int* __restrict__ valid_frames,  // [B] or null
     const long long* __restrict__ seg_start,  // [B] sample offsets into one long recording, or null
     long long total_samples,
-    float lo, float hi, int normalize, void* __restrict__ out) {
+    float lo, float hi, int normalize, void* __restrict__ out, MixTab<MIX> mix) {
   __shared__ __attribute__((aligned(16))) c2 buf0[CFFT_N];
   __shared__ __attribute__((aligned(16))) c2 buf1[CFFT_N];
   __shared__ __attribute__((aligned(16))) c2 tw[CFFT_N];
@@ -70,24 +98,59 @@ __global__ __launch_bounds__(LM_THREADS) void logmel_kernel(
   // windowed frame -> LDS as 1024 complex (even sample = re, odd = im); zero beyond n_samples
   // batched rows, or crops gathered straight out of one recording: a crop sees zeros past its own end
   // (its valid frames / the end of the recording), never its neighbour's samples
-  const float* src = audio + (size_t)seg * n_samples;
-  if (seg_start != nullptr) {
-    const long long st = seg_start[seg];
-    src = audio + st;
-    long long lim = total_samples - st;
-    if (lim > n_samples) lim = n_samples;
-    if (valid_frames != nullptr && (long long)valid_frames[seg] * hop < lim) lim = (long long)valid_frames[seg] * hop;
-    n_samples = lim > 0 ? (int)lim : 0;
-  }
-  const int base = frame * hop;
+  if constexpr (MIX) {
+    // stem mix: sample i of the row = sum over the contributing sources, in source order, of fl(gain * sample) — f32,
+    // the product rounded before the addition (no FMA), zero from valid_frames * hop on
+    if (valid_frames != nullptr && (long long)valid_frames[seg] * hop < n_samples) n_samples = valid_frames[seg] * hop;
+    const int base = frame * hop;
+    float acc[2 * CFFT_N / LM_THREADS];
 #pragma unroll
-  for (int r = 0; r < CFFT_N / LM_THREADS; ++r) {
-    int c = tid + r * LM_THREADS;  // complex index
-    int s = base + 2 * c;
-    float2 w = *(const float2*)(window + 2 * c);
-    float x0 = (s < n_samples) ? src[s] : 0.f;
-    float x1 = (s + 1 < n_samples) ? src[s + 1] : 0.f;
-    buf0[c] = {x0 * w.x, x1 * w.y};
+    for (int r = 0; r < 2 * CFFT_N / LM_THREADS; ++r) acc[r] = 0.f;
+    for (int k = 0; k < mix.n_src; ++k) {
+#pragma clang fp contract(off)
+      const float* p; long long avail; float g;
+      if (!mix_source(audio, total_samples, seg_start, mix, seg, k, p, avail, g)) continue;
+      const int cnt = avail < n_samples ? (int)avail : n_samples;
+      if (cnt <= base) continue;
+      // (loads at indices clamped into the source's own samples [0, cnt), pinned before the first is used: all in flight
+      // at once; what lies at or past cnt is not added)
+      float x[2 * CFFT_N / LM_THREADS];
+#pragma unroll
+      for (int r = 0; r < 2 * CFFT_N / LM_THREADS; ++r) x[r] = p[min(base + 2 * (tid + (r >> 1) * LM_THREADS) + (r & 1), cnt - 1)];
+#pragma unroll
+      for (int r = 0; r < 2 * CFFT_N / LM_THREADS; ++r) asm volatile("" : "+v"(x[r]));
+#pragma unroll
+      for (int r = 0; r < 2 * CFFT_N / LM_THREADS; ++r) {
+        const float v = g * x[r];
+        acc[r] = base + 2 * (tid + (r >> 1) * LM_THREADS) + (r & 1) < cnt ? acc[r] + v : acc[r];
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < CFFT_N / LM_THREADS; ++r) {
+      const int c = tid + r * LM_THREADS;
+      const float2 w = *(const float2*)(window + 2 * c);
+      buf0[c] = {acc[2 * r] * w.x, acc[2 * r + 1] * w.y};
+    }
+  } else {
+    const float* src = audio + (size_t)seg * n_samples;
+    if (seg_start != nullptr) {
+      const long long st = seg_start[seg];
+      src = audio + st;
+      long long lim = total_samples - st;
+      if (lim > n_samples) lim = n_samples;
+      if (valid_frames != nullptr && (long long)valid_frames[seg] * hop < lim) lim = (long long)valid_frames[seg] * hop;
+      n_samples = lim > 0 ? (int)lim : 0;
+    }
+    const int base = frame * hop;
+#pragma unroll
+    for (int r = 0; r < CFFT_N / LM_THREADS; ++r) {
+      int c = tid + r * LM_THREADS;  // complex index
+      int s = base + 2 * c;
+      float2 w = *(const float2*)(window + 2 * c);
+      float x0 = (s < n_samples) ? src[s] : 0.f;
+      float x1 = (s + 1 < n_samples) ? src[s + 1] : 0.f;
+      buf0[c] = {x0 * w.x, x1 * w.y};
+    }
   }
   __syncthreads();
 
@@ -209,13 +272,13 @@ __device__ __forceinline__ void fft16(c2 x[16]) {
 }
 #define LMW_WAVE_SYNC() do { asm volatile("" ::: "memory"); __builtin_amdgcn_wave_barrier(); asm volatile("" ::: "memory"); } while (0)
 
-template <bool OUT_BF16>
+template <bool OUT_BF16, bool MIX>
 __global__ __launch_bounds__(LMW_THREADS, 2) void logmel_wave_kernel(
     const float* __restrict__ audio, int n_samples, int n_frames, int hop, int fpw /* frames per workgroup */,
     const float* __restrict__ window, const float* __restrict__ twid, const int* __restrict__ fb_start,
     const int* __restrict__ fb_cnt, const float* __restrict__ fb_w, int max_taps,
     const int* __restrict__ valid_frames, const long long* __restrict__ seg_start, long long total_samples,
-    float lo, float hi, int normalize, void* __restrict__ out) {
+    float lo, float hi, int normalize, void* __restrict__ out, MixTab<MIX> mix) {
   __shared__ __attribute__((aligned(32))) unsigned char lds[LMW_LDS_BYTES];
   float* const strip = (float*)lds;                                              // [LMW_STRIP_FLOATS]
   c2* const twl = (c2*)(lds + LMW_STRIP_FLOATS * 4);                             // [1024]
@@ -230,7 +293,7 @@ __global__ __launch_bounds__(LMW_THREADS, 2) void logmel_wave_kernel(
 
   // a crop sees zeros past its own end (its valid frames / the end of the recording), never its neighbour's samples
   const float* src = audio + (size_t)seg * n_samples;
-  if (seg_start != nullptr) {
+  if (!MIX && seg_start != nullptr) {
     const long long st = seg_start[seg];
     src = audio + st;
     long long lim = total_samples - st;
@@ -242,7 +305,45 @@ __global__ __launch_bounds__(LMW_THREADS, 2) void logmel_wave_kernel(
   // ---- once per workgroup: the frames' samples, the unpack twiddles, the filterbank weights [tap][mel]
   {
     const int s0 = f0 * hop, ns = (nf - 1) * hop + FFT_N;
-    for (int i = tid; i < ns; i += LMW_THREADS) strip[i] = (s0 + i < n_samples) ? src[s0 + i] : 0.f;
+    if constexpr (MIX) {
+      // stem mix: strip sample i = sum over the contributing sources, in source order, of fl(gain * sample) — f32, the
+      // product rounded before the addition (no FMA), zero from valid_frames * hop on.  A source's table entries are
+      // workgroup-uniform: read once per workgroup; a thread keeps its (at most 20) strip samples in registers meanwhile.
+      if ((long long)vf * hop < n_samples) n_samples = vf * hop;
+      constexpr int PER = (LMW_STRIP_FLOATS + LMW_THREADS - 1) / LMW_THREADS;
+      float acc[PER];
+#pragma unroll
+      for (int r = 0; r < PER; ++r) acc[r] = 0.f;
+      for (int k = 0; k < mix.n_src; ++k) {
+#pragma clang fp contract(off)
+        const float* p; long long avail; float g;
+        if (!mix_source(audio, total_samples, seg_start, mix, seg, k, p, avail, g)) continue;
+        const long long left = (avail < n_samples ? avail : (long long)n_samples) - s0;   // of the source, from the strip's start
+        const int cnt = left < ns ? (int)left : ns;
+        if (cnt <= 0) continue;
+        p += s0;
+        // (every load is issued, at an index clamped into the source's own samples [0, cnt), and pinned before the first
+        // is used: all of a thread's loads in flight at once instead of a branch and a wait per sample; what lies at or
+        // past cnt is not added)
+        float x[PER];
+#pragma unroll
+        for (int r = 0; r < PER; ++r) x[r] = p[min(tid + r * LMW_THREADS, cnt - 1)];
+#pragma unroll
+        for (int r = 0; r < PER; ++r) asm volatile("" : "+v"(x[r]));
+#pragma unroll
+        for (int r = 0; r < PER; ++r) {
+          const float v = g * x[r];
+          acc[r] = tid + r * LMW_THREADS < cnt ? acc[r] + v : acc[r];
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < PER; ++r) {
+        const int i = tid + r * LMW_THREADS;
+        if (i < ns) strip[i] = acc[r];
+      }
+    } else {
+      for (int i = tid; i < ns; i += LMW_THREADS) strip[i] = (s0 + i < n_samples) ? src[s0 + i] : 0.f;
+    }
     for (int i = tid; i < CFFT_N; i += LMW_THREADS) twl[i] = ((const c2*)twid)[i];
     for (int i = tid; i < max_taps * 512; i += LMW_THREADS) {     // coalesced read of [mel][tap], transposed into LDS
       const int m = i / max_taps, q = i - m * max_taps;
@@ -403,10 +504,11 @@ __global__ __launch_bounds__(LMW_THREADS, 2) void logmel_wave_kernel(
   }
 }
 
+template <bool MIX>
 static int logmel_launch(const float* audio, int batch, int n_samples, int hop, const float* window,
                          const float* twiddle, const int* fb_start, const int* fb_cnt, const float* fb_w, int n_mels,
                          int max_taps, const int* valid_frames, const long long* seg_start, long long total_samples,
-                         int normalize, int out_bf16, void* out, void* stream) {
+                         int normalize, int out_bf16, void* out, void* stream, MixTab<MIX> mix = {}) {
   const int n_frames = ceil_div(n_samples, hop);  // pad_end: ceil(n/hop) full windows
   const float lo = -12.f, hi = 5.f;  // MIN_LOG_MEL / MAX_LOG_MEL
   hipStream_t s = (hipStream_t)stream;
@@ -429,11 +531,11 @@ static int logmel_launch(const float* audio, int batch, int n_samples, int hop, 
       if (fpw > n_frames) fpw = n_frames;
       const dim3 grid((unsigned)(batch * ceil_div(n_frames, fpw)));
       if (out_bf16)
-        hipLaunchKernelGGL(logmel_wave_kernel<true>, grid, dim3(LMW_THREADS), 0, s, audio, n_samples, n_frames, hop, fpw, window,
-                           twiddle, fb_start, fb_cnt, fb_w, max_taps, valid_frames, seg_start, total_samples, lo, hi, normalize, out);
+        hipLaunchKernelGGL((logmel_wave_kernel<true, MIX>), grid, dim3(LMW_THREADS), 0, s, audio, n_samples, n_frames, hop, fpw, window,
+                           twiddle, fb_start, fb_cnt, fb_w, max_taps, valid_frames, seg_start, total_samples, lo, hi, normalize, out, mix);
       else
-        hipLaunchKernelGGL(logmel_wave_kernel<false>, grid, dim3(LMW_THREADS), 0, s, audio, n_samples, n_frames, hop, fpw, window,
-                           twiddle, fb_start, fb_cnt, fb_w, max_taps, valid_frames, seg_start, total_samples, lo, hi, normalize, out);
+        hipLaunchKernelGGL((logmel_wave_kernel<false, MIX>), grid, dim3(LMW_THREADS), 0, s, audio, n_samples, n_frames, hop, fpw, window,
+                           twiddle, fb_start, fb_cnt, fb_w, max_taps, valid_frames, seg_start, total_samples, lo, hi, normalize, out, mix);
       MR_CHECK_LAUNCH("logmel_fwd");
       mrmt3_count(MRMT3_CNT_LOGMEL_WAVE);
       return MRMT3_OK;
@@ -441,13 +543,13 @@ static int logmel_launch(const float* audio, int batch, int n_samples, int hop, 
   }
   dim3 grid((unsigned)(batch * n_frames)), block(LM_THREADS);
   if (out_bf16)
-    hipLaunchKernelGGL(logmel_kernel<true>, grid, block, 0, s, audio, n_samples, n_frames, hop, window, twiddle,
+    hipLaunchKernelGGL((logmel_kernel<true, MIX>), grid, block, 0, s, audio, n_samples, n_frames, hop, window, twiddle,
                        fb_start, fb_cnt, fb_w, n_mels, max_taps, valid_frames, seg_start, total_samples, lo, hi, normalize,
-                       out);
+                       out, mix);
   else
-    hipLaunchKernelGGL(logmel_kernel<false>, grid, block, 0, s, audio, n_samples, n_frames, hop, window, twiddle,
+    hipLaunchKernelGGL((logmel_kernel<false, MIX>), grid, block, 0, s, audio, n_samples, n_frames, hop, window, twiddle,
                        fb_start, fb_cnt, fb_w, n_mels, max_taps, valid_frames, seg_start, total_samples, lo, hi, normalize,
-                       out);
+                       out, mix);
   MR_CHECK_LAUNCH("logmel_fwd");
   mrmt3_count(MRMT3_CNT_LOGMEL_GENERAL);
   return MRMT3_OK;
@@ -460,7 +562,7 @@ extern "C" int mrmt3_logmel_fwd(const float* audio, int batch, int n_samples, in
                                 void* stream) {
   MR_CHECK_ARG(audio && window && twiddle && fb_start && fb_cnt && fb_w && out, "logmel_fwd: null pointer");
   MR_CHECK_ARG(batch > 0 && n_samples > 0 && hop > 0 && n_mels > 0 && max_taps > 0, "logmel_fwd: bad sizes");
-  return logmel_launch(audio, batch, n_samples, hop, window, twiddle, fb_start, fb_cnt, fb_w, n_mels, max_taps,
+  return logmel_launch<false>(audio, batch, n_samples, hop, window, twiddle, fb_start, fb_cnt, fb_w, n_mels, max_taps,
                        valid_frames, nullptr, 0, normalize, out_bf16, out, stream);
 }
 
@@ -473,6 +575,21 @@ extern "C" int mrmt3_logmel_crops_fwd(const float* audio, long long total_sample
                "logmel_crops_fwd: null pointer");
   MR_CHECK_ARG(total_samples > 0 && batch > 0 && n_samples > 0 && hop > 0 && n_mels > 0 && max_taps > 0,
                "logmel_crops_fwd: bad sizes");
-  return logmel_launch(audio, batch, n_samples, hop, window, twiddle, fb_start, fb_cnt, fb_w, n_mels, max_taps,
+  return logmel_launch<false>(audio, batch, n_samples, hop, window, twiddle, fb_start, fb_cnt, fb_w, n_mels, max_taps,
                        valid_frames, seg_start, total_samples, normalize, out_bf16, out, stream);
+}
+
+extern "C" int mrmt3_logmel_mix_fwd(const float* pool, long long pool_samples, const long long* src_start,
+                                    const long long* src_end, const float* src_gain, int n_src, int batch, int n_samples,
+                                    int hop, const float* window, const float* twiddle, const int* fb_start,
+                                    const int* fb_cnt, const float* fb_w, int n_mels, int max_taps,
+                                    const int* valid_frames, int normalize, int out_bf16, void* out, void* stream) {
+  MR_CHECK_ARG(pool && src_start && src_end && src_gain && window && twiddle && fb_start && fb_cnt && fb_w && out,
+               "logmel_mix_fwd: null pointer");
+  MR_CHECK_ARG(n_src >= 1 && n_src <= LM_MAX_SRC, "logmel_mix_fwd: n_src must be in [1, %d], got %d", LM_MAX_SRC, n_src);
+  MR_CHECK_ARG(pool_samples > 0 && batch > 0 && n_samples > 0 && hop > 0 && n_mels > 0 && max_taps > 0,
+               "logmel_mix_fwd: bad sizes");
+  return logmel_launch<true>(pool, batch, n_samples, hop, window, twiddle, fb_start, fb_cnt, fb_w, n_mels, max_taps,
+                             valid_frames, src_start, pool_samples, normalize, out_bf16, out, stream,
+                             MixTab<true>{src_end, src_gain, n_src});
 }

@@ -108,3 +108,199 @@ class DeviceBatcher:
         tg = pad_targets([targets_for_crop(int(s), int(v)) for s, v in zip(plan.start_frame, plan.valid_frames)],
                          self.event_length)
         return mel, tg.to(self.device, non_blocking=True)
+
+
+# ---- stem-mix rows -------------------------------------------------------------------------------------------
+
+@dataclass
+class StemMixPlan:
+    """`CropPlan` of the track plus, per row, which stems sound and how loud."""
+    crops: CropPlan
+    keep: np.ndarray             # bool [B, S]
+    gain: np.ndarray             # float32 [B, S], 0 where a stem is not kept
+
+
+def plan_stem_mix(n_frames: int, n_stems: int, mel_length: int = 256, num_rows_per_batch: int = 12,
+                  split_frame_length: int = 2000, keep_prob: float = 0.75, min_stems: int = 1, gain_db: float = 6.0,
+                  is_deterministic: bool = False, rng=None) -> StemMixPlan:
+    """Row plan of one track.  `rng` is anything with `randint(a, b)` inclusive, `random()` and `uniform(a, b)` (default:
+    the `random` module) and is consumed in this order:
+      1. the crop draws of `plan_crops`, unchanged: one for the run of chunks, then one per row;
+      2. then row by row: one `random()` per stem in stem order (kept iff < keep_prob); while fewer than
+         min(min_stems, n_stems) are kept, one `randint(0, len(dropped) - 1)` picking a dropped stem (in stem order) to
+         keep; then one `uniform(-gain_db, gain_db)` per KEPT stem in stem order, the gain being 10^(dB / 20) in f32.
+    `is_deterministic`: every stem at gain 1 and no draw at all (the validation form)."""
+    rng = rng or _random
+    crops = plan_crops(n_frames, mel_length, num_rows_per_batch, split_frame_length, is_deterministic, rng)
+    B = len(crops.start_frame)
+    keep = np.ones((B, n_stems), bool)
+    gain = np.ones((B, n_stems), np.float32)
+    if is_deterministic:
+        return StemMixPlan(crops, keep, gain)
+    need = min(int(min_stems), n_stems)
+    for b in range(B):
+        keep[b] = [rng.random() < keep_prob for _ in range(n_stems)]
+        while keep[b].sum() < need:
+            dropped = np.nonzero(~keep[b])[0]
+            keep[b, dropped[rng.randint(0, len(dropped) - 1)]] = True
+        for s in range(n_stems):
+            gain[b, s] = np.float32(10.0 ** (rng.uniform(-gain_db, gain_db) / 20.0)) if keep[b, s] else np.float32(0)
+    return StemMixPlan(crops, keep, gain)
+
+
+def stem_pool_layout(lengths, hop: int):
+    """Stems end to end in one pool, each starting on a whole hop: (offsets int64 [S], pool_samples)."""
+    padded = [-(-int(n) // hop) * hop for n in lengths]
+    offsets = np.concatenate([[0], np.cumsum(padded)[:-1]]).astype(np.int64)
+    return offsets, int(sum(padded))
+
+
+def mix_tables(plan: StemMixPlan, offsets, lengths, hop: int):
+    """The kernel's tables for a plan over a pool laid out by `stem_pool_layout`: (start_frames int64 [B, S] in hops of
+    the pool, src_end int64 [B, S] in samples, src_gain float32 [B, S]).  A crop that starts at or behind the end of a
+    (shorter) stem has nothing of that stem to read: the source's table gain is 0, which the kernel does not read at all
+    (its start is left at the stem's last hop).  The plan's own `gain` and `keep` — the labels — are untouched."""
+    offsets, lengths = np.asarray(offsets, np.int64), np.asarray(lengths, np.int64)
+    end = np.broadcast_to(offsets + lengths, plan.gain.shape).copy()
+    start = offsets[None, :] // hop + plan.crops.start_frame[:, None]
+    over = start * hop >= end
+    start = np.where(over, end // hop, start)
+    gain = np.where(over, np.float32(0), plan.gain).astype(np.float32)
+    return start.astype(np.int64), end, np.ascontiguousarray(gain)
+
+
+def check_mix_tables(start_frames, src_end, src_gain, pool_samples: int, hop: int):
+    """Host check of the tables before they are uploaded: every gain finite; for every source that sounds (gain != 0)
+    0 <= start <= end <= pool_samples.  A ValueError names the row.  (The kernel is safe without it — it clamps — but a
+    table that needs clamping is a planning bug, and the host is where it can be reported.)"""
+    start = np.asarray(start_frames, np.int64) * hop
+    end, gain = np.asarray(src_end, np.int64), np.asarray(src_gain, np.float32)
+    if not (start.shape == end.shape == gain.shape and gain.ndim == 2):
+        raise ValueError("stem mix tables: start, end and gain must share one [rows, sources] shape, got %s %s %s"
+                         % (start.shape, end.shape, gain.shape))
+    if not 1 <= gain.shape[1] <= 64:
+        raise ValueError("stem mix tables: %d sources per row, the kernel takes 1 to 64" % gain.shape[1])
+    for b in range(gain.shape[0]):
+        if not np.isfinite(gain[b]).all():
+            raise ValueError("stem mix tables: row %d has a gain that is not finite: %s" % (b, gain[b].tolist()))
+        on = gain[b] != 0
+        if (start[b][on] < 0).any() or (end[b][on] > pool_samples).any():
+            raise ValueError("stem mix tables: row %d points outside the pool of %d samples (start %s, end %s)"
+                             % (b, pool_samples, start[b][on].tolist(), end[b][on].tolist()))
+        if (start[b][on] > end[b][on]).any():
+            raise ValueError("stem mix tables: row %d starts behind its stem's end (start %s, end %s)"
+                             % (b, start[b][on].tolist(), end[b][on].tolist()))
+
+
+class StemMixBatcher:
+    """A track's stems on the GPU + a row plan -> `(mel [B, mel_length, 512], targets [B, event_length])`: every row a
+    random sub-mix of the stems at random gains, mixed inside the log-mel kernel's load (`mrmt3_logmel_mix_fwd`, one
+    launch, nothing materialised), labelled with the notes of exactly the stems that sound.
+
+    The targets of a row are BY DEFINITION `Tokenizer.row_targets` of the tokenisation of
+    `mrmt3.stems.merged_note_sequence(track, kept)` at the track's length; tokenisations are cached per (track, subset)
+    (tests hold the cached path to the definition).  `plan` / `row_targets` are host code and run without a GPU; `build`
+    needs one (no CPU fallback).  Stems are uploaded once per track through pinned staging and kept in a device cache of
+    at most `cache_bytes` (least recently used track dropped first; the track in use always stays)."""
+
+    def __init__(self, device, mel_length: int = 256, event_length: int = 1024, num_rows_per_batch: int = 12,
+                 split_frame_length: int = 2000, keep_prob: float = 0.75, min_stems: int = 1, gain_db: float = 6.0,
+                 is_deterministic: bool = False, tokenizer=None, rng=None, cache_bytes: int = 8 << 30,
+                 spectrogram_config=None, out_bf16: bool = False):
+        from collections import OrderedDict
+        from contrib import spectrograms
+        from mrmt3.tokenizer import Tokenizer
+        if not 0.0 <= keep_prob <= 1.0:
+            raise ValueError("keep_prob must be in [0, 1], got %r" % (keep_prob,))
+        if min_stems < 1:
+            raise ValueError("min_stems must be at least 1, got %r" % (min_stems,))
+        if not (gain_db >= 0 and np.isfinite(gain_db)):
+            raise ValueError("gain_db must be finite and >= 0, got %r" % (gain_db,))
+        self.device = torch.device(device)
+        self.cfg = spectrogram_config or spectrograms.SpectrogramConfig()
+        self.mel_length, self.event_length = mel_length, event_length
+        self.num_rows, self.split_len = num_rows_per_batch, split_frame_length
+        self.keep_prob, self.min_stems, self.gain_db = float(keep_prob), int(min_stems), float(gain_db)
+        self.is_deterministic, self.out_bf16, self.rng = is_deterministic, out_bf16, rng
+        self.tokenizer = tokenizer or Tokenizer(spectrogram_config=self.cfg)
+        self.cache_bytes = int(cache_bytes)
+        self._pools = OrderedDict()          # track.name -> (pool on the device, offsets, lengths), least recent first
+        self._feats = OrderedDict()          # (track.name, kept) -> Tokenizer.tokenize(...)
+        self.uploads = 0                     # tracks copied to the device so far (a cache hit does not count)
+        self._sp = spectrograms
+
+    # ---- host ----------------------------------------------------------------------------------------------------
+    def n_frames(self, track) -> int:
+        return -(-track.n_samples // self.cfg.hop_width)
+
+    def plan(self, track) -> StemMixPlan:
+        return plan_stem_mix(self.n_frames(track), len(track.audio), self.mel_length, self.num_rows, self.split_len,
+                             self.keep_prob, self.min_stems, self.gain_db, self.is_deterministic, self.rng)
+
+    def _tokenized(self, track, kept):
+        from mrmt3.stems import merged_note_sequence
+        key = (track.name, kept)
+        if key in self._feats:
+            self._feats.move_to_end(key)
+            return self._feats[key]
+        feats = self.tokenizer.tokenize(merged_note_sequence(track, kept), track.n_samples)
+        self._feats[key] = feats
+        while len(self._feats) > 64:
+            self._feats.popitem(last=False)
+        return feats
+
+    def row_targets(self, track, plan: StemMixPlan):
+        """Token ids of every row of the plan (a list of 1-D int arrays, before `pad_targets`)."""
+        out = []
+        for b in range(len(plan.crops.start_frame)):
+            kept = tuple(int(s) for s in np.nonzero(plan.keep[b])[0])
+            out.append(self.tokenizer.row_targets(self._tokenized(track, kept), int(plan.crops.start_frame[b]),
+                                                  int(plan.crops.valid_frames[b])))
+        return out
+
+    def tables(self, track, plan: StemMixPlan):
+        """(start_frames, src_end, src_gain, pool_samples) of the plan on the host, checked."""
+        hop = self.cfg.hop_width
+        lengths = [len(a) for a in track.audio]
+        offsets, total = stem_pool_layout(lengths, hop)
+        start, end, gain = mix_tables(plan, offsets, lengths, hop)
+        check_mix_tables(start, end, gain, total, hop)
+        return start, end, gain, total
+
+    # ---- device --------------------------------------------------------------------------------------------------
+    def pool(self, track) -> torch.Tensor:
+        """The track's stems end to end on the device (each padded to whole hops), uploaded once and cached."""
+        if self.device.type != "cuda":
+            raise RuntimeError("StemMixBatcher builds batches on the GPU (no CPU fallback)")
+        if track.name in self._pools:
+            self._pools.move_to_end(track.name)
+            return self._pools[track.name]
+        hop = self.cfg.hop_width
+        offsets, total = stem_pool_layout([len(a) for a in track.audio], hop)
+        host = torch.zeros(total, dtype=torch.float32).pin_memory()
+        for off, a in zip(offsets, track.audio):
+            host[int(off):int(off) + len(a)] = torch.from_numpy(np.ascontiguousarray(a, np.float32))
+        dev = host.to(self.device, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()          # (the pinned buffer is released on return)
+        self._pools[track.name] = dev
+        self.uploads += 1
+        while len(self._pools) > 1 and sum(p.numel() * 4 for p in self._pools.values()) > self.cache_bytes:
+            self._pools.popitem(last=False)
+        return dev
+
+    def cached_tracks(self) -> list:
+        return list(self._pools)
+
+    def mel(self, track, plan: StemMixPlan) -> torch.Tensor:
+        start, end, gain, total = self.tables(track, plan)
+        pool = self.pool(track)
+        assert pool.numel() == total
+        return self._sp.logmel_mix(pool, torch.from_numpy(start), torch.from_numpy(end), torch.from_numpy(gain),
+                                   self.mel_length, self.cfg, normalize=True,
+                                   valid_frames=torch.from_numpy(plan.crops.valid_frames), out_bf16=self.out_bf16)
+
+    def build(self, track, plan: StemMixPlan | None = None):
+        plan = plan or self.plan(track)
+        mel = self.mel(track, plan)
+        tg = pad_targets(self.row_targets(track, plan), self.event_length)
+        return mel, tg.to(self.device, non_blocking=True)

@@ -106,7 +106,7 @@ def load():
     return lib
 
 
-MIN_VERSION = 122
+MIN_VERSION = 123
 COUNTER_NAMES = ("gemm_nt_tile", "gemm_nt8", "gemm_nt_geglu", "tn_group", "tn8", "tn_tile", "attn_fwd", "attn_bwd",
                  "attn_bwd_onepass", "attn_f32", "tn_f32", "gemm_nt_splitk", "gemm_nt_addnorm", "gemm_nt_normbwd",
                  "gemm_nt_geglubwd", "attn_fwd_varlen", "attn_bwd_varlen", "logmel_wave", "logmel_general")
@@ -219,6 +219,30 @@ def logmel_crops(audio, seg_start, n_samples, tables, valid_frames=None, normali
                                              _p(tables["fb_cnt"]), _p(tables["fb_w"]), n_mels, tables["max_taps"],
                                              _p(valid_frames), int(normalize), int(out_bf16), _p(out), _stream()),
                "logmel_crops_fwd")
+    return out
+
+
+def logmel_mix(pool, src_start, src_end, src_gain, n_samples, tables, valid_frames=None, normalize=True, out_bf16=False):
+    """pool [total] f32 (stems end to end); src_start / src_end [B, n_src] int64 pool offsets (first sample of the crop,
+    one past the stem's last sample), src_gain [B, n_src] f32 (0: the source is not read) -> [B, ceil(n/hop), n_mels]:
+    the log-mel of the rows' gain-weighted stem sums (include/mrmt3_hip.h: mrmt3_logmel_mix_fwd)."""
+    _dev(pool, src_start, src_end, src_gain, valid_frames)
+    assert pool.dim() == 1 and pool.dtype == torch.float32 and pool.is_contiguous()
+    assert src_start.dim() == 2 and src_start.dtype == torch.int64 and src_start.is_contiguous()
+    assert src_end.shape == src_start.shape and src_end.dtype == torch.int64 and src_end.is_contiguous()
+    assert src_gain.shape == src_start.shape and src_gain.dtype == torch.float32 and src_gain.is_contiguous()
+    B, n_src = src_start.shape
+    assert valid_frames is None or (valid_frames.dtype == torch.int32 and valid_frames.is_contiguous()
+                                    and valid_frames.numel() == B)
+    hop, n_mels = tables["hop"], tables["n_mels"]
+    frames = -(-n_samples // hop)
+    out = torch.empty(B, frames, n_mels, device=pool.device, dtype=torch.bfloat16 if out_bf16 else torch.float32)
+    with _Timed("logmel", B * n_samples * 4 * n_src + out.numel() * out.element_size(), "B"):
+        _check(load().mrmt3_logmel_mix_fwd(_p(pool), pool.numel(), _p(src_start), _p(src_end), _p(src_gain), n_src, B,
+                                           n_samples, hop, _p(tables["window"]), _p(tables["twiddle"]),
+                                           _p(tables["fb_start"]), _p(tables["fb_cnt"]), _p(tables["fb_w"]), n_mels,
+                                           tables["max_taps"], _p(valid_frames), int(normalize), int(out_bf16), _p(out),
+                                           _stream()), "logmel_mix_fwd")
     return out
 
 

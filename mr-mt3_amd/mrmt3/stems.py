@@ -1,0 +1,109 @@
+"""Multi-stem tracks for stem-mix training: a folder of tracks, each a set of stems with their own MIDI.
+
+A track is a directory with `stems/<name>.wav` (mono, the config's sample rate, read with `contrib.audio_io`) and
+`MIDI/<name>.mid` (read with `contrib.midi_io`) — the layout of a Slakh track after resampling and WAV conversion.  A
+stem's program and drum flag come from its MIDI file (the first instrument that has notes); an optional `programs.json`
+next to the two directories, `{name: {"program": int, "is_drum": bool}}`, overrides them.  Nothing here knows an
+instrument-class table: the programs are whatever the files say.
+
+`merged_note_sequence(track, kept)` is the DEFINITION of a mixed row's label: the notes of exactly the kept stems, the
+instrument index a stem's place among the kept ones, the length the track's.  `mrmt3.batching.StemMixBatcher` tokenises
+that sequence with `mrmt3.tokenizer.Tokenizer`.  Host code (numpy); no third-party dataset package.
+"""
+from __future__ import annotations
+
+import dataclasses
+import json
+import os
+import random as _random
+
+import numpy as np
+
+from contrib import audio_io, midi_io
+from contrib.note_sequences import Note, NoteSequence
+
+
+@dataclasses.dataclass
+class StemTrack:
+    name: str                    # the track directory (the device cache's key)
+    stem_names: list             # [S] file stems, sorted
+    audio: list                  # [S] float32 [n_s] mono samples, unequal lengths allowed
+    notes: list                  # [S] NoteSequence of the stem alone (program / is_drum set on every note)
+    programs: list               # [S] (program, is_drum)
+
+    @property
+    def n_samples(self) -> int:
+        """The track's length: its longest stem."""
+        return max(len(a) for a in self.audio)
+
+    @property
+    def total_time(self) -> float:
+        return max([ns.total_time for ns in self.notes] + [0.0])
+
+
+def merged_note_sequence(track: StemTrack, kept) -> NoteSequence:
+    """The NoteSequence of the sub-mix `kept` (stem indices, ascending): exactly those stems' notes (copies), stem after
+    stem, instrument = the stem's index among the kept ones, total_time = the whole track's."""
+    out = NoteSequence(total_time=track.total_time)
+    for j, s in enumerate(kept):
+        for n in track.notes[s].notes:
+            out.notes.append(dataclasses.replace(n, instrument=j))
+    return out
+
+
+def load_track(path: str, sample_rate: int = 16000) -> StemTrack:
+    stem_dir, midi_dir = os.path.join(path, "stems"), os.path.join(path, "MIDI")
+    names = sorted(f[:-4] for f in os.listdir(stem_dir) if f.lower().endswith(".wav"))
+    if not names:
+        raise ValueError(f"{stem_dir}: no .wav stems")
+    override = {}
+    if os.path.exists(os.path.join(path, "programs.json")):
+        with open(os.path.join(path, "programs.json")) as f:
+            override = json.load(f)
+    audio, notes, programs = [], [], []
+    for name in names:
+        wav, mid = os.path.join(stem_dir, name + ".wav"), os.path.join(midi_dir, name + ".mid")
+        x, rate = audio_io.read_wav(wav)
+        if rate != sample_rate:
+            raise ValueError(f"{wav}: sample rate {rate}, the config's is {sample_rate} (resample the stems first)")
+        if not os.path.exists(mid):
+            raise ValueError(f"{wav}: the stem has no MIDI file ({mid} is missing)")
+        midi = midi_io.read_midi(mid)
+        first = next((i for i in midi.instruments if i.notes), None)
+        program, is_drum = (first.program, first.is_drum) if first is not None else (0, False)
+        if name in override:
+            program = int(override[name].get("program", program))
+            is_drum = bool(override[name].get("is_drum", is_drum))
+        ns = NoteSequence(ticks_per_quarter=midi.resolution)
+        for inst in midi.instruments:
+            for n in inst.notes:
+                ns.notes.append(Note(n.start, n.end, n.pitch, n.velocity, program, is_drum, 0))
+                ns.total_time = max(ns.total_time, n.end)
+        audio.append(x)
+        notes.append(ns)
+        programs.append((program, is_drum))
+    return StemTrack(path, names, audio, notes, programs)
+
+
+def load_stem_folder(root: str, sample_rate: int = 16000) -> list:
+    """Every track directory under `root` (one that holds `stems/`), in name order."""
+    dirs = sorted(d for d in os.listdir(root) if os.path.isdir(os.path.join(root, d, "stems")))
+    if not dirs:
+        raise ValueError(f"{root}: no track directories (a track holds stems/<name>.wav and MIDI/<name>.mid)")
+    return [load_track(os.path.join(root, d), sample_rate) for d in dirs]
+
+
+def epoch_order(n_tracks: int, seed: int, epoch: int) -> list:
+    """The order in which an epoch visits the tracks: a function of (seed, epoch) alone, the same on every rank."""
+    order = list(range(n_tracks))
+    _random.Random(int(seed) * 1000003 + int(epoch)).shuffle(order)
+    return order
+
+
+def rank_shard(order: list, rank: int, world: int) -> list:
+    """Rank `rank`'s tracks of an epoch: every world-th entry of the order.  The shards are disjoint; the order is cut to
+    a multiple of `world` first so that every rank takes the same number of steps (at most world - 1 tracks wait for an
+    epoch whose order places them earlier)."""
+    if world > 1:
+        order = order[:len(order) // world * world]
+    return order[rank::world]

@@ -18,6 +18,15 @@ The Slakh/ComMU dataset classes themselves are the reference's `dataset/` packag
 scope): put it on PYTHONPATH.  If it cannot be imported the driver STOPS with that message — it
 never silently substitutes synthetic data.
 
+Stem folders.  `+stem_root=DIR` trains from a folder of multi-stem tracks (`DIR/<track>/stems/<name>.wav`,
+`DIR/<track>/MIDI/<name>.mid`, 16 kHz; `mrmt3/stems.py`) with no dataset package at all: every row is a random sub-mix
+of a track's stems at random gains, mixed inside the log-mel kernel, labelled with the notes of the stems that sound
+(`mrmt3.batching.StemMixBatcher`).  `+stem_keep=` (0.75) is the probability that a stem sounds in a row, `+stem_min=` (1)
+the least number that do, `+stem_gain_db=` (6) the gain range in dB.  Row geometry is the config's (`mel_length`,
+`event_length`, `num_rows_per_batch`, `split_frame_length`, `dataloader.train.batch_size` tracks per step); the track
+order is a function of (seed, epoch) and the ranks take disjoint shards of it.  `+stem_val_root=DIR` gives `val_loss` on
+the deterministic full mix of those tracks.  The rows carry no `targets_prev`: a `*WithPrev` model is refused.
+
 Gradient accumulation: `cfg.trainer.accumulate_grad_batches` (the reference's `${grad_accum}`), else a top-level
 `grad_accum`, else 1 — Lightning's semantics (mrmt3/trainer.py): the optimizer steps after every N-th batch and after an
 epoch's last one; `+max_steps`, `trainer.log_every_n_steps`, the LR schedule and checkpoint steps count optimizer steps.
@@ -120,6 +129,93 @@ class SkippingBatchSampler(torch.utils.data.BatchSampler):
         import itertools
         skip, self.skip = self.skip, 0
         return itertools.islice(super().__iter__(), skip, None)
+
+
+def stem_options(cfg, with_prev=False):
+    """None without `+stem_root`; else dict(root, val_root, keep, gain_db, min_stems) from `+stem_root=DIR`,
+    `+stem_val_root=DIR`, `+stem_keep=` (default 0.75), `+stem_gain_db=` (6.0) and `+stem_min=` (1), validated like the
+    other options: a ValueError names the key.  Stem-mix rows carry no `targets_prev`: a `*WithPrev` model is refused."""
+    root = cfg.get("stem_root")
+    if root is None or str(root).lower() in ("", "none", "null"):
+        return None
+    if with_prev:
+        raise ValueError("+stem_root builds (mel, targets) rows only: targets_prev, which the *WithPrev models train "
+                         "on, is not built by the stem batcher (DESIGN 4j, out of scope) — train them through "
+                         "cfg.dataset or +synthetic=True")
+    val_root = cfg.get("stem_val_root")
+    val_root = None if val_root is None or str(val_root).lower() in ("", "none", "null") else str(val_root)
+    out = {"root": str(root), "val_root": val_root}
+    for key, name, default, cast in (("stem_keep", "keep", 0.75, float), ("stem_gain_db", "gain_db", 6.0, float),
+                                     ("stem_min", "min_stems", 1, int)):
+        raw = cfg.get(key)
+        try:
+            if isinstance(raw, bool):
+                raise ValueError
+            out[name] = default if raw is None else cast(raw)
+        except (TypeError, ValueError):
+            raise ValueError("%s must be a number, got %r" % (key, raw)) from None
+    if not 0.0 <= out["keep"] <= 1.0:
+        raise ValueError("stem_keep must be in [0, 1], got %r" % (out["keep"],))
+    if not 0.0 <= out["gain_db"] < float("inf"):
+        raise ValueError("stem_gain_db must be finite and >= 0, got %r" % (out["gain_db"],))
+    if out["min_stems"] < 1:
+        raise ValueError("stem_min must be at least 1, got %r" % (out["min_stems"],))
+    return out
+
+
+class StemLoader:
+    """The training (or validation) "loader" of `+stem_root`: an epoch visits this rank's shard of the tracks,
+    `tracks_per_step` per batch, every track one `StemMixBatcher.build` — `(mel [rows, mel_length, 512], targets
+    [rows, event_length])` already on the device.  The track order is `mrmt3.stems.epoch_order(seed, epoch)`, the ranks
+    take disjoint shards of it (`rank_shard`), and the batcher's draws restart from (seed, epoch, rank) with every
+    epoch.  `shuffle=False` (validation: the deterministic full mix) keeps the folder's order.  Has what
+    `loader_batches` asks of a loader and of a sampler: `len()`, iteration, `set_epoch`."""
+
+    def __init__(self, tracks, batcher, tracks_per_step, seed, rank=0, world=1, shuffle=True):
+        from mrmt3 import stems
+        self.tracks, self.batcher, self.per = tracks, batcher, max(1, int(tracks_per_step))
+        self.seed, self.rank, self.world, self.shuffle, self.epoch = int(seed), rank, world, shuffle, 0
+        self._stems = stems
+        if not stems.rank_shard(list(range(len(tracks))), rank, world):
+            raise ValueError("%d stem tracks cannot be sharded over %d ranks" % (len(tracks), world))
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def shard(self):
+        n = len(self.tracks)
+        order = self._stems.epoch_order(n, self.seed, self.epoch) if self.shuffle else list(range(n))
+        return self._stems.rank_shard(order, self.rank, self.world)
+
+    def __len__(self):
+        return -(-len(self.shard()) // self.per)
+
+    def __iter__(self):
+        import random
+        shard = self.shard()
+        self.batcher.rng = random.Random((self.seed * 1000003 + self.epoch) * 4099 + self.rank)
+        for i in range(0, len(shard), self.per):
+            built = [self.batcher.build(self.tracks[t]) for t in shard[i:i + self.per]]
+            yield torch.cat([b[0] for b in built]), torch.cat([b[1] for b in built])
+
+
+def stem_loaders(cfg, opts, device, world=1, rank=0):
+    """(train StemLoader, validation StemLoader or None) over `+stem_root` / `+stem_val_root`; the row geometry is the
+    config's (`mel_length`, `event_length`, `num_rows_per_batch`, `split_frame_length`, `dataloader.train.batch_size`
+    tracks per step)."""
+    from mrmt3 import stems
+    from mrmt3.batching import StemMixBatcher
+    geom = dict(mel_length=int(cfg.mel_length), event_length=int(cfg.event_length),
+                num_rows_per_batch=int(cfg.num_rows_per_batch), split_frame_length=int(cfg.get("split_frame_length", 2000)))
+    per = int(cfg.dataloader.train.batch_size)
+    train = StemLoader(stems.load_stem_folder(opts["root"]),
+                       StemMixBatcher(device, keep_prob=opts["keep"], min_stems=opts["min_stems"], gain_db=opts["gain_db"], **geom),
+                       per, cfg.seed, rank, world)
+    val = None
+    if opts["val_root"] is not None:
+        val = StemLoader(stems.load_stem_folder(opts["val_root"]), StemMixBatcher(device, is_deterministic=True, **geom),
+                         1, cfg.seed, rank, world, shuffle=False)
+    return train, val
 
 
 def accumulate_grad_batches(cfg) -> int:
@@ -312,7 +408,11 @@ def main(argv=None):
     max_steps = cfg.get("max_steps")
     max_steps = None if max_steps is None else int(max_steps)
     train_loader = val_loader = sampler = None
-    if not synthetic:
+    stem = None if synthetic else stem_options(cfg, with_prev)
+    if stem is not None:
+        train_loader, val_loader = stem_loaders(cfg, stem, device, world, rank)
+        sampler = train_loader                   # (`set_epoch`: the track order is a function of (seed, epoch))
+    elif not synthetic:
         train_loader, val_loader, sampler = real_loaders(cfg, world, rank)
     start, start_epoch, skip, resumed = 0, 0, 0, False
     path = cfg.get("path")
@@ -350,6 +450,8 @@ def main(argv=None):
 
         def validate(ep):
             """val_loss = mean over the batches of ALL ranks (each rank holds a shard of the validation set)."""
+            if val_loader is None:               # (+stem_root without +stem_val_root)
+                return
             acc = torch.zeros(2, device=device, dtype=torch.float64)
             for b in val_loader:
                 prev = b[2].to(device) if len(b) > 2 else None
