@@ -37,6 +37,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "rowmath.h"
 
 #define G8_OOB 0x7FFF0000
 // kernel knock-outs (MRMT3_GEMM8_DBG) and the start skew exist in the diagnostics build only (common.h: MR_DIAG)
@@ -313,29 +314,17 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8_kernel(G8Params P) {
                                  pack_bf2(acc[i][1][0], acc[i][1][1]), pack_bf2(acc[i][1][2], acc[i][1][3])};
         const unsigned h1p[4] = {pack_bf2(acc[i][2][0], acc[i][2][1]), pack_bf2(acc[i][2][2], acc[i][2][3]),
                                  pack_bf2(acc[i][3][0], acc[i][3][1]), pack_bf2(acc[i][3][2], acc[i][3][3])};
-        float o[8];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float a_lo = __uint_as_float(h0p[e] << 16), a_hi = __uint_as_float(h0p[e] & 0xFFFF0000u);
-          const float b_lo = __uint_as_float(h1p[e] << 16), b_hi = __uint_as_float(h1p[e] & 0xFFFF0000u);
-          o[2 * e] = gelu_new_f(a_lo) * b_lo;
-          o[2 * e + 1] = gelu_new_f(a_hi) * b_hi;
-        }
-        if (dc.thresh) {
-          float mk[8];
-          const unsigned long long e8 = ((unsigned long long)row * P.dff + f0) >> 2;
-          drop_mask4(dc, e8, mk);
-          drop_mask4(dc, e8 + 1, mk + 4);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] *= mk[e];
-        }
+        float a[8], b[8], o[8];
+        unpack8(u32x4{h0p[0], h0p[1], h0p[2], h0p[3]}, a);
+        unpack8(u32x4{h1p[0], h1p[1], h1p[2], h1p[3]}, b);
+        geglu_fwd8(dc, ((unsigned long long)row * P.dff + f0) >> 2, a, b, o);
         if (row < P.M) {
           bf16_t* hp = (bf16_t*)P.C + (size_t)row * P.ldc + f0;
           if (!(G8_DBG(64))) {
             __builtin_nontemporal_store((u32x4{h0p[0], h0p[1], h0p[2], h0p[3]}), (u32x4*)hp);
             __builtin_nontemporal_store((u32x4{h1p[0], h1p[1], h1p[2], h1p[3]}), (u32x4*)(hp + P.dff));
           }
-          const u32x4 gv = {pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3]), pack_bf2(o[4], o[5]), pack_bf2(o[6], o[7])};
+          const u32x4 gv = pack8(o);
           u32x4* gp = (u32x4*)((bf16_t*)P.C2 + (size_t)row * P.ldc2 + f0);
           if (G8_DBG(128)) {}
           else if (P.nt_c & 2) __builtin_nontemporal_store(gv, gp);      // (h: only the backward reads it again; g: the next kernel)

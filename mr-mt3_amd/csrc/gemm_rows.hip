@@ -18,7 +18,7 @@
 //   hand-off the tile is rounded to bf16 — exactly what the stand-alone product writes — into an LDS image
 //            [64 rows][512 columns] (row stride 1040 B: conflict-free 8-byte writes), the staging memory being free.
 //   rows     each wave then runs the ROW kernel's body on 8 rows of the tile, reading y from LDS instead of HBM: the
-//            same per-lane column assignment, the same arithmetic in the same order as rowops.hip, so the results equal
+//            same per-lane column assignment and the same functions (rowmath.h) inlined as in rowops.hip, so the results equal
 //            the two-kernel form bit for bit (forward; the norm-weight partial sums are grouped by 64 rows instead of 32).
 //            All of a wave's global loads (8 rows x 2 KiB) are requested before the first is used.
 //
@@ -32,8 +32,9 @@
 #include <type_traits>
 
 #include "common.h"
+#include "rowmath.h"
 
-// no implicit FMA formation: the row phases restate rowops.hip's arithmetic and must land on the same bits
+// no implicit FMA formation in this file (the row phases' arithmetic is rowmath.h's and carries its own setting)
 #pragma clang fp contract(off)
 
 #define GR_OOB 0x7FFF0000
@@ -91,22 +92,6 @@ __device__ __forceinline__ u32x4 gr_img_pair(const unsigned char* p) {
   u32x4 r;
   asm volatile("ds_read2st64_b64 %0, %1 offset1:1\n\ts_waitcnt lgkmcnt(0)" : "=v"(r) : "v"((unsigned)(uintptr_t)p) : "memory");
   return r;
-}
-__device__ __forceinline__ void gr_unpack4(u32x2 t, float v[4]) {
-  v[0] = __uint_as_float(t.x << 16); v[1] = __uint_as_float(t.x & 0xFFFF0000u);
-  v[2] = __uint_as_float(t.y << 16); v[3] = __uint_as_float(t.y & 0xFFFF0000u);
-}
-template <bool BF> __device__ __forceinline__ void gr_load4(const void* p, size_t idx, float v[4]) {
-  if constexpr (BF) {
-    gr_unpack4(*(const u32x2*)((const bf16_t*)p + idx), v);
-  } else {
-    const f32x4 t = *(const f32x4*)((const float*)p + idx);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  }
-}
-template <bool BF> __device__ __forceinline__ void gr_store4(void* p, size_t idx, const float v[4]) {
-  if constexpr (BF) *(u32x2*)((bf16_t*)p + idx) = u32x2{pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])};
-  else *(f32x4*)((float*)p + idx) = f32x4{v[0], v[1], v[2], v[3]};
 }
 
 // RI / RO: the residual gradient in / out is bf16 (NORMBWD only).  BM: rows of a tile — 64 (8 waves x 64 accumulator
@@ -297,7 +282,7 @@ __global__ __launch_bounds__(512, BM == 64 ? 4 : 2) void gemm_rows_kernel(GRPara
     const DropCfg dy = dc0, dout = dc1;
     float wv[2][4];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) gr_load4<false>(P.wn, i * 256 + lane * 4, wv[i]);
+    for (int i = 0; i < 2; ++i) load4<float>(P.wn + i * 256 + lane * 4, wv[i]);
     constexpr int G = RPW;                       // rows per group: all of the wave's rows (8 or 16)
     // the wave's pieces of the tile image first (LDS reads while none of this wave's global loads are in flight)
     u32x4 yimg[G];
@@ -324,24 +309,16 @@ __global__ __launch_bounds__(512, BM == 64 ? 4 : 2) void gemm_rows_kernel(GRPara
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int col = i * 256 + lane * 4;
-        float v[4] = {xv[t][i].x, xv[t][i].y, xv[t][i].z, xv[t][i].w};
-        float yv[4];
-        gr_unpack4(i == 0 ? u32x2{y4.x, y4.y} : u32x2{y4.z, y4.w}, yv);
-        if (dy.thresh) {
-          float m[4];
-          drop_mask4(dy, (base + col) >> 2, m);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) yv[e] *= m[e];
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] += yv[e];
+        float v[4], yv[4];
+        unpack4(xv[t][i], v);
+        unpack4(i == 0 ? u32x2{y4.x, y4.y} : u32x2{y4.z, y4.w}, yv);
+        norm_fwd_add(dy, (base + col) >> 2, v, yv);
         xv[t][i] = f32x4{v[0], v[1], v[2], v[3]};
         if (P.x1 != nullptr) {
           if (P.cache_mode & 1) __builtin_nontemporal_store(xv[t][i], (f32x4*)(P.x1 + base + col));
           else *(f32x4*)(P.x1 + base + col) = xv[t][i];
         }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) ss[t] = fmaf(v[e], v[e], ss[t]);
+        ss[t] = norm_fwd_sumsq(v, ss[t]);
       }
     }
     // wave_sum of every row, the rows' butterflies interleaved (per row: the same six steps in the same order)
@@ -354,22 +331,15 @@ __global__ __launch_bounds__(512, BM == 64 ? 4 : 2) void gemm_rows_kernel(GRPara
       const int row = m0 + w + 8 * t;
       if (row >= P.M) continue;
       const size_t base = (size_t)row * 512;
-      const float rstd = rsqrtf(ss[t] / 512.0f + P.eps);
+      const float rstd = norm_rstd(ss[t], 512.0f, P.eps);
       if (lane == 0 && P.rstd != nullptr) P.rstd[row] = rstd;
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int col = i * 256 + lane * 4;
-        const float v[4] = {xv[t][i].x, xv[t][i].y, xv[t][i].z, xv[t][i].w};
-        float o[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = wv[i][e] * (v[e] * rstd);
-        if (P.out_drop && dout.thresh) {
-          float m[4];
-          drop_mask4(dout, (base + col) >> 2, m);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] *= m[e];
-        }
-        gr_store4<true>(P.xn, base + col, o);
+        float v[4], o[4];
+        unpack4(xv[t][i], v);
+        norm_fwd_out(wv[i], v, rstd, dout, P.out_drop, (base + col) >> 2, o);
+        store4<bf16_t>(P.xn + base + col, o);
       }
     }
   } else if constexpr (EPI == GR_NORMBWD) {
@@ -377,7 +347,7 @@ __global__ __launch_bounds__(512, BM == 64 ? 4 : 2) void gemm_rows_kernel(GRPara
     float wv[2][4], dwp[2][4];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      gr_load4<false>(P.wn, i * 256 + lane * 4, wv[i]);
+      load4<float>(P.wn + i * 256 + lane * 4, wv[i]);
 #pragma unroll
       for (int e = 0; e < 4; ++e) dwp[i][e] = 0.f;
     }
@@ -387,6 +357,7 @@ __global__ __launch_bounds__(512, BM == 64 ? 4 : 2) void gemm_rows_kernel(GRPara
 #pragma unroll
     for (int grp = 0; grp < RPW / G; ++grp) {
       typedef typename std::conditional<RI, u32x2, f32x4>::type RawR;
+      typedef typename std::conditional<RO, bf16_t, float>::type TRO;
       f32x4 xv[G][2];
       RawR rr[G][2];
       float rs[G];
@@ -412,15 +383,10 @@ __global__ __launch_bounds__(512, BM == 64 ? 4 : 2) void gemm_rows_kernel(GRPara
         const u32x4 g4 = gr_img_pair(lds + lr * GR_YLD + lane * 8);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-          gr_unpack4(i == 0 ? u32x2{g4.x, g4.y} : u32x2{g4.z, g4.w}, g[t][i]);
-          float xh[4] = {xv[t][i].x, xv[t][i].y, xv[t][i].z, xv[t][i].w};
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            xh[e] *= rstd;
-            dwp[i][e] = fmaf(g[t][i][e], xh[e], dwp[i][e]);
-            g[t][i][e] *= wv[i][e];
-            dot[t] = fmaf(g[t][i][e], xh[e], dot[t]);
-          }
+          unpack4(i == 0 ? u32x2{g4.x, g4.y} : u32x2{g4.z, g4.w}, g[t][i]);
+          float xh[4];
+          unpack4(xv[t][i], xh);
+          dot[t] = norm_bwd_acc(g[t][i], xh, wv[i], rstd, dwp[i], dot[t]);
           xv[t][i] = f32x4{xh[0], xh[1], xh[2], xh[3]};
         }
       }
@@ -433,28 +399,20 @@ __global__ __launch_bounds__(512, BM == 64 ? 4 : 2) void gemm_rows_kernel(GRPara
         const int row = m0 + w + 8 * (grp * G + t);
         if (row >= P.M) continue;
         const size_t base = (size_t)row * 512;
-        const float rstd = rs[t], dt = dot[t] / 512.0f;
+        const float rstd = rs[t], dt = norm_bwd_mean(dot[t], 512.0f);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
           const int col = i * 256 + lane * 4;
-          const float xh[4] = {xv[t][i].x, xv[t][i].y, xv[t][i].z, xv[t][i].w};
-          float d[4];
+          float xh[4], rv[4], d[4];
+          unpack4(xv[t][i], xh);
+          unpack4(rr[t][i], rv);
 #pragma unroll
-          for (int e = 0; e < 4; ++e) d[e] = rstd * fmaf(-xh[e], dt, g[t][i][e]);
-          float rv[4];
-          if constexpr (RI) gr_unpack4(rr[t][i], rv);
-          else { rv[0] = rr[t][i].x; rv[1] = rr[t][i].y; rv[2] = rr[t][i].z; rv[3] = rr[t][i].w; }
-#pragma unroll
-          for (int e = 0; e < 4; ++e) d[e] += rv[e];
-          gr_store4<RO>(P.dx1, base + col, d);
+          for (int e = 0; e < 4; ++e) d[e] = norm_bwd_dx(g[t][i][e], xh[e], rstd, dt);
+          add4(d, rv);
+          store4<TRO>((TRO*)P.dx1 + base + col, d);
           if (P.dy != nullptr) {
-            if (ddy.thresh) {
-              float m[4];
-              drop_mask4(ddy, (base + col) >> 2, m);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) d[e] *= m[e];
-            }
-            gr_store4<true>(P.dy, base + col, d);
+            mask4(ddy, (base + col) >> 2, d);
+            store4<bf16_t>(P.dy + base + col, d);
           }
         }
       }
@@ -494,27 +452,14 @@ __global__ __launch_bounds__(512, BM == 64 ? 4 : 2) void gemm_rows_kernel(GRPara
         if (row >= P.M) continue;
         const u32x4 gv = *(const u32x4*)(lds + lr * GR_YLD + lane * 16);
         float a[8], b[8], go[8], da[8], db[8];
-        gr_unpack4(u32x2{hv[t][0].x, hv[t][0].y}, a); gr_unpack4(u32x2{hv[t][0].z, hv[t][0].w}, a + 4);
-        gr_unpack4(u32x2{hv[t][1].x, hv[t][1].y}, b); gr_unpack4(u32x2{hv[t][1].z, hv[t][1].w}, b + 4);
-        gr_unpack4(u32x2{gv.x, gv.y}, go); gr_unpack4(u32x2{gv.z, gv.w}, go + 4);
-        if (d.thresh) {
-          float m[8];
-          const unsigned long long i8 = ((unsigned long long)row * dff + n0 + lane * 8) >> 3;
-          drop_mask4(d, 2 * i8, m);
-          drop_mask4(d, 2 * i8 + 1, m + 4);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) go[e] *= m[e];
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          float f, fd;
-          gelu_new_fd(a[e], &f, &fd);
-          da[e] = go[e] * b[e] * fd;
-          db[e] = go[e] * f;
-        }
+        unpack8(hv[t][0], a);
+        unpack8(hv[t][1], b);
+        unpack8(gv, go);
+        const unsigned long long i8 = ((unsigned long long)row * dff + n0 + lane * 8) >> 3;
+        geglu_bwd8(d, 2 * i8, a, b, go, da, db);
         bf16_t* pd = P.dh + (size_t)row * 2 * dff + n0 + lane * 8;
-        *(u32x4*)pd = u32x4{pack_bf2(da[0], da[1]), pack_bf2(da[2], da[3]), pack_bf2(da[4], da[5]), pack_bf2(da[6], da[7])};
-        *(u32x4*)(pd + dff) = u32x4{pack_bf2(db[0], db[1]), pack_bf2(db[2], db[3]), pack_bf2(db[4], db[5]), pack_bf2(db[6], db[7])};
+        *(u32x4*)pd = pack8(da);
+        *(u32x4*)(pd + dff) = pack8(db);
       }
     }
   }

@@ -7,48 +7,11 @@
 // entry point.
 #include "common.h"
 #include "opt_ranges.h"
+#include "rowmath.h"
 
-// no implicit FMA formation in this file: gemm_rows.hip restates these kernels' arithmetic and must land on the same bits
+// no implicit FMA formation in this file: cross-entropy, AdamW and the optimizer tail have their bits pinned under this
+// setting (the arithmetic shared with the fused GEMM epilogues carries its own, rowmath.h)
 #pragma clang fp contract(off)
-
-template <typename T> __device__ __forceinline__ void load4(const T* p, float v[4]);
-template <> __device__ __forceinline__ void load4<float>(const float* p, float v[4]) {
-  f32x4 t = *(const f32x4*)p;
-  v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-}
-template <> __device__ __forceinline__ void load4<bf16_t>(const bf16_t* p, float v[4]) {
-  u32x2 t = *(const u32x2*)p;
-  v[0] = __uint_as_float(t.x << 16); v[1] = __uint_as_float(t.x & 0xFFFF0000u);
-  v[2] = __uint_as_float(t.y << 16); v[3] = __uint_as_float(t.y & 0xFFFF0000u);
-}
-template <typename T> __device__ __forceinline__ void store4(T* p, const float v[4]);
-template <> __device__ __forceinline__ void store4<float>(float* p, const float v[4]) {
-  *(f32x4*)p = f32x4{v[0], v[1], v[2], v[3]};
-}
-template <> __device__ __forceinline__ void store4<bf16_t>(bf16_t* p, const float v[4]) {
-  *(u32x2*)p = u32x2{pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])};
-}
-
-// streaming (non-temporal) forms: for operands a kernel reads once and nobody reads again soon (the saved activations of
-// the backward), and for outputs whose reader is several kernels away (the residual stream) — they then do not push
-// the tensors the NEXT kernel wants out of the 256 MB Infinity Cache
-template <typename T> __device__ __forceinline__ void load4_nt(const T* p, float v[4]);
-template <> __device__ __forceinline__ void load4_nt<float>(const float* p, float v[4]) {
-  const f32x4 t = __builtin_nontemporal_load((const f32x4*)p);
-  v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-}
-template <> __device__ __forceinline__ void load4_nt<bf16_t>(const bf16_t* p, float v[4]) {
-  const u32x2 t = __builtin_nontemporal_load((const u32x2*)p);
-  v[0] = __uint_as_float(t.x << 16); v[1] = __uint_as_float(t.x & 0xFFFF0000u);
-  v[2] = __uint_as_float(t.y << 16); v[3] = __uint_as_float(t.y & 0xFFFF0000u);
-}
-template <typename T> __device__ __forceinline__ void store4_nt(T* p, const float v[4]);
-template <> __device__ __forceinline__ void store4_nt<float>(float* p, const float v[4]) {
-  __builtin_nontemporal_store((f32x4{v[0], v[1], v[2], v[3]}), (f32x4*)p);
-}
-template <> __device__ __forceinline__ void store4_nt<bf16_t>(bf16_t* p, const float v[4]) {
-  __builtin_nontemporal_store((u32x2{pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])}), (u32x2*)p);
-}
 
 // ------------------------------------------------------------------------------------------------
 // fused add + dropout + RMS norm, forward.   one wave per row, 4 rows per workgroup
@@ -79,25 +42,16 @@ __global__ __launch_bounds__(256) void add_rmsnorm_fwd_kernel(const float* __res
       if (y != nullptr) {
         float yv[4];
         load4<TY>(y + base + col, yv);
-        if (dy.thresh) {
-          float m[4];
-          drop_mask4(dy, (base + col) >> 2, m);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) yv[e] *= m[e];
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[i][e] += yv[e];
+        norm_fwd_add(dy, (base + col) >> 2, v[i], yv);
       }
       if (x1 != nullptr) {
         if (cache_mode & 1) store4_nt<float>(x1 + base + col, v[i]);
         else store4<float>(x1 + base + col, v[i]);
       }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) ss = fmaf(v[i][e], v[i][e], ss);
+      ss = norm_fwd_sumsq(v[i], ss);
     }
   }
-  ss = wave_sum(ss);
-  const float rstd = rsqrtf(ss / (float)cols + eps);
+  const float rstd = norm_rstd(wave_sum(ss), (float)cols, eps);
   if (lane == 0 && rstd_out != nullptr) rstd_out[row] = rstd;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
@@ -105,14 +59,7 @@ __global__ __launch_bounds__(256) void add_rmsnorm_fwd_kernel(const float* __res
       const int col = i * 256 + lane * 4;
       float wv[4], o[4];
       load4<float>(w + col, wv);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = wv[e] * (v[i][e] * rstd);
-      if (out_drop && dout.thresh) {
-        float m[4];
-        drop_mask4(dout, (base + col) >> 2, m);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] *= m[e];
-      }
+      norm_fwd_out(wv, v[i], rstd, dout, out_drop, (base + col) >> 2, o);
       store4<TN>(xn + base + col, o);
     }
   }
@@ -200,44 +147,25 @@ __global__ __launch_bounds__(256) void add_rmsnorm_bwd_kernel(const TG* __restri
       if (i < nv) {
         const int col = i * 256 + lane * 4;
         load4<TG>(dxn + base + col, g[i]);
-        if (out_drop && dout.thresh) {
-          float m[4];
-          drop_mask4(dout, (base + col) >> 2, m);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) g[i][e] *= m[e];
-        }
+        if (out_drop) mask4(dout, (base + col) >> 2, g[i]);     // (the site dropped its output: the stand-alone kernel only)
         if (cache_mode & 1) load4_nt<float>(x1 + base + col, xh[i]);
         else load4<float>(x1 + base + col, xh[i]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          xh[i][e] *= rstd;
-          dwp[i][e] = fmaf(g[i][e], xh[i][e], dwp[i][e]);
-          g[i][e] *= wv[i][e];
-          dot = fmaf(g[i][e], xh[i][e], dot);
-        }
+        dot = norm_bwd_acc(g[i], xh[i], wv[i], rstd, dwp[i], dot);
       }
     }
-    dot = wave_sum(dot) / (float)cols;
+    dot = norm_bwd_mean(wave_sum(dot), (float)cols);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       if (i < nv) {
         const int col = i * 256 + lane * 4;
         float d[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) d[e] = rstd * fmaf(-xh[i][e], dot, g[i][e]);
-        if (dres != nullptr) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) d[e] += rr[i][e];
-        }
+        for (int e = 0; e < 4; ++e) d[e] = norm_bwd_dx(g[i][e], xh[i][e], rstd, dot);
+        if (dres != nullptr) add4(d, rr[i]);
         if (cache_mode & 2) store4_nt<TRO>(dx1 + base + col, d);
         else store4<TRO>(dx1 + base + col, d);
         if (dy != nullptr) {
-          if (ddy.thresh) {
-            float m[4];
-            drop_mask4(ddy, (base + col) >> 2, m);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) d[e] *= m[e];
-          }
+          mask4(ddy, (base + col) >> 2, d);
           store4<bf16_t>(dy + base + col, d);
         }
       }
@@ -415,9 +343,6 @@ extern "C" int mrmt3_add_rmsnorm_bwd(const void* dxn, int dxn_dtype, const void*
 // ------------------------------------------------------------------------------------------------
 // gated GELU (HF T5DenseGatedGeluDense + NewGELUActivation)
 // ------------------------------------------------------------------------------------------------
-// (fast_tanh / gelu_new_f live in common.h: the GEGLU epilogue of gemm8.hip uses the same arithmetic)
-// (gelu_new_fd lives in common.h too: the GEGLU-backward epilogue of gemm_rows.hip uses the same arithmetic)
-
 // Both kernels move 8 elements (two dropout quads) per thread and iteration: 16-byte accesses for bf16.
 template <typename T>
 __global__ void geglu_fwd_kernel(const T* __restrict__ h, T* __restrict__ g, int rows, int dff, DropCfg d) {
@@ -432,15 +357,7 @@ __global__ void geglu_fwd_kernel(const T* __restrict__ h, T* __restrict__ g, int
     load4<T>(h + row * 2 * dff + col + 4, a + 4);
     load4<T>(h + row * 2 * dff + dff + col, b);
     load4<T>(h + row * 2 * dff + dff + col + 4, b + 4);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = gelu_new_f(a[e]) * b[e];
-    if (d.thresh) {
-      float m[8];
-      drop_mask4(d, 2 * i, m);
-      drop_mask4(d, 2 * i + 1, m + 4);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] *= m[e];
-    }
+    geglu_fwd8(d, 2 * i, a, b, o);
     store4<T>(g + row * dff + col, o);
     store4<T>(g + row * dff + col + 4, o + 4);
   }
@@ -469,20 +386,7 @@ __global__ void geglu_bwd_kernel(const T* __restrict__ h, const T* __restrict__ 
     }
     load4<T>(dg + row * dff + col, go);
     load4<T>(dg + row * dff + col + 4, go + 4);
-    if (d.thresh) {
-      float m[8];
-      drop_mask4(d, 2 * i, m);
-      drop_mask4(d, 2 * i + 1, m + 4);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) go[e] *= m[e];
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float f, fd;
-      gelu_new_fd(a[e], &f, &fd);
-      da[e] = go[e] * b[e] * fd;
-      db[e] = go[e] * f;
-    }
+    geglu_bwd8(d, 2 * i, a, b, go, da, db);
     store4<T>(dh + row * 2 * dff + col, da);
     store4<T>(dh + row * 2 * dff + col + 4, da + 4);
     store4<T>(dh + row * 2 * dff + dff + col, db);

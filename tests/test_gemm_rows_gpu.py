@@ -2,8 +2,8 @@
 ABI: mrmt3_gemm_nt_addnorm (o / co / wo projection -> residual add + dropout + T5LayerNorm, HF T5LayerSelfAttention /
 T5LayerFF as called at models/t5.py:636-648), mrmt3_gemm_nt_normbwd (data gradient -> backward of that norm),
 mrmt3_gemm_nt_geglubwd (wo data gradient -> gated-GELU backward).  The forward fusion and the GEGLU backward promise the
-SAME BITS as the two-kernel form (the tile is rounded to bf16 exactly as the stand-alone product writes it and the row
-arithmetic is restated in the same order); the norm backward promises the same bits for dx1 / dy and the same norm-weight
+SAME BITS as the two-kernel form (the tile is rounded to bf16 exactly as the stand-alone product writes it and both forms
+inline the same functions of csrc/rowmath.h for the row arithmetic); the norm backward promises the same bits for dx1 / dy and the same norm-weight
 gradient up to the grouping of its f32 partial sums (64 rows per partial row instead of 32).  Each case is also held to an
 f32 torch reference of the whole chain, so that the pair cannot be wrong together.
 
