@@ -133,8 +133,8 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(AttnParams P, AttnVarl
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int t = uw * 2 + i;
-      blds_rows8(kres, k_lane, on ? (kv0 + t * 8) * P.ldk * 2 : BUF_OOB, base + t * 1024);
-      blds_rows8(vres, v_lane, on ? (kv0 + t * 8) * P.ldv * 2 : BUF_OOB, base + 8192 + t * 1024);
+      blds_rows8(kres, k_lane, on ? (kv0 + t * 8) * P.ldk * 2 : LDS_DMA_OOB, base + t * 1024);
+      blds_rows8(vres, v_lane, on ? (kv0 + t * 8) * P.ldv * 2 : LDS_DMA_OOB, base + 8192 + t * 1024);
     }
   };
   stage(0, 0, true);
@@ -388,8 +388,8 @@ __global__ __launch_bounds__(256, RT == 1 ? 3 : 2) void attn_bwd_dkdv_kernel(Att
   // (the statistics are simply read again), so the loop below prefetches and waits without a branch.
   auto stage = [&](int buf, int qb0, bool on) {
     unsigned char* base = lds + buf * QD_STAGE_BYTES;
-    blds_rows8(qres, q_lane, on ? (qb0 + uw * 8) * P.ldq * 2 : BUF_OOB, base + uw * 1024);
-    blds_rows8(dores, do_lane, on ? (qb0 + uw * 8) * P.lddo * 2 : BUF_OOB, base + 4096 + uw * 1024);
+    blds_rows8(qres, q_lane, on ? (qb0 + uw * 8) * P.ldq * 2 : LDS_DMA_OOB, base + uw * 1024);
+    blds_rows8(dores, do_lane, on ? (qb0 + uw * 8) * P.lddo * 2 : LDS_DMA_OOB, base + 4096 + uw * 1024);
     const float* sp = (lane < 32 ? lse : dlt) + min(qb0 + (lane & 31), Lq_rs - 1);
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)sp,
                                      (__attribute__((address_space(3))) void*)(base + 8192), 4, 0, 0);
@@ -612,8 +612,8 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(AttnParams P, AttnV
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int t = uw * 2 + i;
-      blds_rows8(kres, k_lane, on ? (kv0 + t * 8) * P.ldk * 2 : BUF_OOB, base + t * 1024);
-      blds_rows8(vres, v_lane, on ? (kv0 + t * 8) * P.ldv * 2 : BUF_OOB, base + 8192 + t * 1024);
+      blds_rows8(kres, k_lane, on ? (kv0 + t * 8) * P.ldk * 2 : LDS_DMA_OOB, base + t * 1024);
+      blds_rows8(vres, v_lane, on ? (kv0 + t * 8) * P.ldv * 2 : LDS_DMA_OOB, base + 8192 + t * 1024);
     }
   };
   stage(0, 0, true);

@@ -105,11 +105,11 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_onepass_kernel(AttnParams P) 
   auto stage = [&](int buf, int qb0, bool on) {
     unsigned char* base = ldsS + buf * OP_STAGE_BYTES;
     if (uw < 4) {
-      blds_rows8(qres, q_lane, on ? (qb0 + uw * 8) * P.ldq * 2 : BUF_OOB, base + uw * 1024);
-      blds_rows8(dores, do_lane, on ? (qb0 + uw * 8) * P.lddo * 2 : BUF_OOB, base + 4096 + uw * 1024);
+      blds_rows8(qres, q_lane, on ? (qb0 + uw * 8) * P.ldq * 2 : LDS_DMA_OOB, base + uw * 1024);
+      blds_rows8(dores, do_lane, on ? (qb0 + uw * 8) * P.lddo * 2 : LDS_DMA_OOB, base + 4096 + uw * 1024);
     } else {
-      blds_rows8(ores, o_lane, on ? (qb0 + (uw - 4) * 8) * P.ldo * 2 : BUF_OOB, base + 8192 + (uw - 4) * 1024);
-      blds_rows8(olres, o_lane, (on && have_lo) ? (qb0 + (uw - 4) * 8) * P.ldo * 2 : BUF_OOB, base + 12288 + (uw - 4) * 1024);
+      blds_rows8(ores, o_lane, on ? (qb0 + (uw - 4) * 8) * P.ldo * 2 : LDS_DMA_OOB, base + 8192 + (uw - 4) * 1024);
+      blds_rows8(olres, o_lane, (on && have_lo) ? (qb0 + (uw - 4) * 8) * P.ldo * 2 : LDS_DMA_OOB, base + 12288 + (uw - 4) * 1024);
     }
     const float* sp = lse + min(qb0 + (lane & 31), P.Lq - 1);
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)sp,

@@ -3,12 +3,10 @@
 // attention-probability dropout generator, the launch parameter block.
 #pragma once
 #include "common.h"
+#include "lds_dma.h"
 
 #define HD 64          // head dim (d_kv)
 
-__device__ __forceinline__ s16x4 lds_tr16(const unsigned char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-}
 __device__ __forceinline__ bf16x8 cat8(s16x4 lo, s16x4 hi) {
   return bf16x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
 }
@@ -211,17 +209,16 @@ static inline int attn_grid_x(int L, bool paired) {
 // for the whole kernel, the tile offset is a scalar, and rows past the end of the tensor (or a whole tile that is
 // switched off by an out-of-range scalar offset) come back as zeros without touching memory — so the loop needs no
 // address arithmetic, no row clamp and no branch around the prefetch.
-#define BUF_OOB 0x7FFF0000
+// (LDS_DMA_OOB, lds_dma.h, is that out-of-range scalar offset.)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rows_rsrc(const bf16_t* base, int nrows, int ld) {
-  return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, ((nrows - 1) * ld + HD) * 2, 0x00020000);
+  return lds_dma_rsrc(base, (size_t)(((nrows - 1) * ld + HD) * 2));
 }
 __device__ __forceinline__ unsigned rows8_lane_off(int ld, int lane) {     // row lane>>3, swizzled 16-B chunk
   return (unsigned)(((lane >> 3) * ld + (((lane & 7) ^ (lane >> 3)) << 3)) * 2);
 }
 __device__ __forceinline__ void blds_rows8(__amdgpu_buffer_rsrc_t r, unsigned lane_off, int tile_byte_off, unsigned char* dst) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)dst, 16, lane_off, tile_byte_off, 0, 0);
+  lds_dma16(r, dst, lane_off, tile_byte_off);
 }
-#define VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
 
 // attention_onepass.hip: the backward in one pass when a workgroup can own all keys of a (batch, head); 1 = launched
 int mrmt3_attn_bwd_onepass_try(const AttnParams& P, hipStream_t s);

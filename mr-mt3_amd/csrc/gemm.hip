@@ -27,6 +27,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "lds_dma.h"
 
 #define TILE 128
 #define ROWB 128  // bytes per LDS row
@@ -328,10 +329,6 @@ extern "C" int mrmt3_gemm_nt_ws(const void* A, int lda, const void* B, int ldb, 
 
 __device__ __attribute__((aligned(256))) unsigned char g_zero_page[256];  // source of out-of-range rows
 
-__device__ __forceinline__ s16x4 lds_tr16(const unsigned char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-}
-
 __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const bf16_t* __restrict__ A, int lda,
                                                          const bf16_t* __restrict__ B, int ldb,
                                                          float* __restrict__ slab, int M, int N1, int N2,
@@ -346,8 +343,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const bf16_t* __restric
   {
     // work items in split-major order (all tiles of token range 0, then of range 1, ...); XCD x (= blockIdx % 8) takes
     // the contiguous eighth [x*n/8, (x+1)*n/8) of them, in dispatch order.  The grid is padded to a multiple of 8.
-    const int n = (int)gridDim.x, per = n >> 3;
-    const int w = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
+    const int w = xcd_major_index();
     const int n_work = n_tiles * n_splits;
     if (w >= n_work) return;
     split = w / n_tiles;

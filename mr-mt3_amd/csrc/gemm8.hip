@@ -2,34 +2,18 @@
 // (M = 16 K .. 64 K token rows, N and K = 384 .. 2048), bf16 operands, f32 accumulation.
 //
 // Stands for the same nn.Linear(bias=False) layers as gemm.hip (HF T5Attention q/k/v/o, T5DenseGatedGeluDense
-// wi_0/wi_1/wo, models/t5.py:51 proj, :72 lm_head, and their dgrad).  What round 1's kernel left on the table
-// (profiles/r01_pmc_gemm_sq.txt: waves parked on s_waitcnt / s_barrier 39 %, MFMA pipe busy ~30 %) was its
-// schedule — one barrier per K step, the fragment reads of a step starting only behind that barrier, two
-// workgroup-wide stages — not its traffic.  This kernel is built around the schedule instead:
+// wi_0/wi_1/wo, models/t5.py:51 proj, :72 lm_head, and their dgrad).  The schedule is pingpong.h's (read that header
+// first), shared with gemm_tn8.hip.  What is this kernel's own:
 //
-//   * 512 threads = 8 waves = 2 per SIMD; the two waves of a SIMD (wave w and w + 4: "group" 0 and 1) run the SAME
-//     program one s_barrier apart, so while one of them issues its 16 MFMAs of a phase the other reads fragments
-//     from LDS and issues the next LDS-DMA loads (ping-pong; MI355X_MICROARCH "two waves per SIMD").
-//   * a 256 x 256 (or 128 x 256) tile, K step 64 (128-byte rows), two LDS buffers of four 16-KiB half-tiles each.
-//     A half-tile is what ONE phase reads: HA0 / HA1 = the first / second half of every wave's rows, HB0 / HB1 the
-//     first / second half of every wave's columns.  A K step is four phases of 16 (8) MFMAs per wave:
-//         ph1 reads HA0, HB0   (r0 x c0)      ph2 reads HB1   (r0 x c1)
-//         ph3 reads HA1        (r1 x c1)      ph4 reads none  (r1 x c0)
-//     and every phase issues ONE half-tile of LDS-DMA (buffer_load ... lds) two K steps ahead, into the slot whose
-//     last reader finished two phases ago:  ph1: HB1(u+1)  ph2: HA1(u+1)  ph3: HA0(u+2)  ph4: HB0(u+2).
-//     Each load therefore has ~5 phases to land, and the only wait in the loop is a counted vmcnt that leaves the
-//     four youngest half-tiles in flight (never 0), placed one phase before the half-tile is read.
+//   * a 256 x 256 (or 128 x 256) tile, K step 64 (128-byte rows).
 //   * persistent workgroups: the K-step stream runs on across output tiles (the first K steps of the next tile are
 //     in flight while the current one finishes); XCD x owns a contiguous range of (m-tile, n-tile) pairs.
 //   * the MFMAs are issued transposed (weights as the A operand), with the weight rows of a wave's 64 columns
 //     permuted on the LDS-DMA source address, so that a lane's accumulators hold runs of consecutive columns of one
 //     C row and the four lanes of a row write one contiguous 64-byte segment per store instruction: the epilogue
 //     stores straight from registers, 16 bytes per lane, no LDS transposition.
-//   * (tried, not kept: all 160 KiB of LDS — a third B buffer, B requested three K steps ahead, 7 instead of 4 half-tiles
-//     in flight per CU.  Same results, 917 against 945 TF over the step's shapes: the K loop is not waiting for bytes in
-//     flight.  A side lesson of that variant: when the K-step body grew a second lambda, hipcc stopped inlining it, the
-//     accumulators it captures by reference went to scratch memory and the kernel ran 50x slower — if a lambda here is
-//     ever not inlined, force it with __attribute__((always_inline)).)
+//   * the epilogue leaves in four batches inside the read segments of the K loop (store_rows), and the counted waits
+//     allow for them (wait_young).
 //   * N need only be a multiple of 128: the last column tile is shifted left to end at N and masks the columns the
 //     tile before it owns.
 #include <stdlib.h>
@@ -37,13 +21,11 @@
 #include <type_traits>
 
 #include "common.h"
+#include "pingpong.h"
 #include "rowmath.h"
 
-#define G8_OOB 0x7FFF0000
 // kernel knock-outs (MRMT3_GEMM8_DBG) and the start skew exist in the diagnostics build only (common.h: MR_DIAG)
 #define G8_DBG(bit) MR_DIAG(P.dbg & (bit))
-#define G8_HALF 16384
-#define G8_BUF (4 * G8_HALF)
 
 struct G8Params {
   const bf16_t* A;
@@ -71,18 +53,6 @@ struct G8Params {
 // 1 25.77, 2 25.61, 0 25.63 — the consumer of C is the next kernel and finds it in the Infinity Cache.
 static int g8_store_mode() { return MR_KNOB("MRMT3_GEMM8_NT", 2) & 3; }
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t g8_rsrc(const void* base, size_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-}
-
-// (kept in a __device__ function: called from a lambda inside the kernel template, the builtin makes hipcc's host
-// pass drop the kernel's launch stub without a diagnostic)
-__device__ __forceinline__ void g8_dma16(__amdgpu_buffer_rsrc_t r, unsigned char* dst, unsigned voff, int soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)dst, 16, voff, soff, 0, 0);
-}
-
-#define G8_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-
 // RT = 16-row tiles per wave (8: 256-row workgroup tile, 4: 128-row).  NST = global stores (and loads, ACCUM) the
 // epilogue of one tile issues per lane: they sit in the vmcnt queue behind the loads the next K step waits for.
 template <typename TOUT, bool ACCUM, int RT, int EPI = 0>
@@ -93,7 +63,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8_kernel(G8Params P) {
   constexpr int NA = RT / 4;                   // LDS-DMA instructions per thread and A half-tile (2 or 1)
   constexpr int A_HALF_ROWS = GROUP_ROWS;      // rows in HA0 (= RT*8 per group x 2 groups)
   constexpr int YOUNG = 2 * NA + 4;            // loads of the four youngest half-tiles (2 A halves, 2 B halves)
-  __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * G8_BUF];
+  __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * PP_BUF];
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = w >> 2, wc = w & 3;
@@ -155,8 +125,8 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8_kernel(G8Params P) {
     return P.M;
   };
   const int kcols = SPLITK ? P.kfull : P.K;                   // (columns of the operands; P.K is the depth of a tile)
-  const __amdgpu_buffer_rsrc_t ra = g8_rsrc(P.A, ((size_t)(P.M - 1) * P.lda + kcols) * 2);
-  const __amdgpu_buffer_rsrc_t rb = g8_rsrc(P.B, ((size_t)(P.N - 1) * P.ldb + kcols) * 2);
+  const __amdgpu_buffer_rsrc_t ra = lds_dma_rsrc(P.A, ((size_t)(P.M - 1) * P.lda + kcols) * 2);
+  const __amdgpu_buffer_rsrc_t rb = lds_dma_rsrc(P.B, ((size_t)(P.N - 1) * P.ldb + kcols) * 2);
 
   // ---- LDS-DMA source offsets.  One wave-instruction = 1 KiB = 8 rows x 128 B of a half-tile; lane p fills
   // (row 8*piece + p/8, chunk p%8) with the row's 16-byte chunk (p%8) ^ (p/8) (bank swizzle on the SOURCE side).
@@ -188,22 +158,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8_kernel(G8Params P) {
   }
   const unsigned a1_delta = (unsigned)(RT * 8 * P.lda * 2);
   const unsigned b1_delta = EPI == 1 ? (unsigned)(P.dff * P.ldb * 2) : (unsigned)(32 * P.ldb * 2);
-  const int piece0 = w * 1024;                              // LDS offset of this wave's piece inside a half-tile
-
-  auto load_a = [&](int buf, int half, int soff) {          // half 0: HA0, 1: HA1
-    if (G8_DBG(16)) soff = G8_OOB;
-    unsigned char* base = lds + buf * G8_BUF + half * G8_HALF + piece0;
-#pragma unroll
-    for (int i = 0; i < NA; ++i)
-      g8_dma16(ra, base + i * 8192, voffA[i] + (half ? a1_delta : 0u), soff);
-  };
-  auto load_b = [&](int buf, int half, int soff) {          // half 0: HB0, 1: HB1
-    if (G8_DBG(16)) soff = G8_OOB;
-    unsigned char* base = lds + buf * G8_BUF + (2 + half) * G8_HALF + piece0;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-      g8_dma16(rb, base + i * 8192, voffB[i] + (half ? b1_delta : 0u), soff);
-  };
+  const int piece0 = w * PP_PIECE;                          // LDS offset of this wave's piece inside a half-tile
 
   // ---- load cursor: the K step whose half-tiles are being requested (two ahead of the one being computed)
   int l_it = 0, l_k = 0, l_sa, l_sb;
@@ -212,7 +167,21 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8_kernel(G8Params P) {
     tile_origin(0, m0, n0, cm);
     src_off(m0, n0, l_sa, l_sb);
   }
-  auto cursor_next = [&]() {
+  auto load_a = [&](int buf, int half) PP_INLINE {          // half 0: HA0, 1: HA1
+    const int soff = G8_DBG(16) ? LDS_DMA_OOB : l_sa;
+    unsigned char* base = lds + buf * PP_BUF + half * PP_HALF + piece0;
+#pragma unroll
+    for (int i = 0; i < NA; ++i)
+      lds_dma16(ra, base + i * PP_STRIDE, voffA[i] + (half ? a1_delta : 0u), soff);
+  };
+  auto load_b = [&](int buf, int half) PP_INLINE {          // half 0: HB0, 1: HB1
+    const int soff = G8_DBG(16) ? LDS_DMA_OOB : l_sb;
+    unsigned char* base = lds + buf * PP_BUF + (2 + half) * PP_HALF + piece0;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      lds_dma16(rb, base + i * PP_STRIDE, voffB[i] + (half ? b1_delta : 0u), soff);
+  };
+  auto cursor_next = [&]() PP_INLINE {
     ++l_k;
     if (l_k < nk) { if (!(G8_DBG(4))) { l_sa += 128; l_sb += 128; } return; }
     l_k = 0;
@@ -222,14 +191,14 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8_kernel(G8Params P) {
       tile_origin(l_it, m0, n0, cm);
       src_off(m0, n0, l_sa, l_sb);
     } else {
-      l_sa = l_sb = G8_OOB;                                  // switched off: zero fill, no memory traffic
+      l_sa = l_sb = LDS_DMA_OOB;                                  // switched off: zero fill, no memory traffic
     }
   };
 
   // ---- fragment read offsets (bytes inside a buffer); ks = 1 is the same address ^ 64
   const int fsw = (fg ^ (fr & 7)) << 4;
-  const int a_off0 = g * (RT * 8 * 128) + fr * 128 + fsw;    // + half * G8_HALF + (rt % (RT/2)) * 2048
-  const int b_off0 = 2 * G8_HALF + wc * 4096 + fr * 128 + fsw;  // + half * G8_HALF + (ct & 1) * 2048
+  const int a_off0 = g * (RT * 8 * 128) + fr * 128 + fsw;    // + half * PP_HALF + (rt % (RT/2)) * 2048
+  const int b_off0 = 2 * PP_HALF + wc * 4096 + fr * 128 + fsw;  // + half * PP_HALF + (ct & 1) * 2048
   const int a_off1 = a_off0 ^ 64, b_off1 = b_off0 ^ 64;
 
   constexpr int RH = RT / 2;                                 // row tiles per half
@@ -240,18 +209,18 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8_kernel(G8Params P) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  auto read_a = [&](int buf, int half) {
+  auto read_a = [&](int buf, int half) PP_INLINE {
     if (G8_DBG(8)) return;
-    const unsigned char* p = lds + buf * G8_BUF + half * G8_HALF;
+    const unsigned char* p = lds + buf * PP_BUF + half * PP_HALF;
 #pragma unroll
     for (int i = 0; i < RH; ++i) {
       af[i][0] = *(const bf16x8*)(p + a_off0 + i * 2048);
       af[i][1] = *(const bf16x8*)(p + a_off1 + i * 2048);
     }
   };
-  auto read_b = [&](int buf, int half) {
+  auto read_b = [&](int buf, int half) PP_INLINE {
     if (G8_DBG(8)) return;
-    const unsigned char* p = lds + buf * G8_BUF + half * G8_HALF;
+    const unsigned char* p = lds + buf * PP_BUF + half * PP_HALF;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       bf_[half * 2 + j][0] = *(const bf16x8*)(p + b_off0 + j * 2048);
@@ -260,7 +229,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8_kernel(G8Params P) {
   };
   // 16 (8) MFMAs: row half rh x column half ch, both k-steps.  Weights are the A operand: D = W_frag . X_frag^T.
   // FIRST (the first K step of an output tile): the accumulators start from zero instead of being cleared.
-  auto mma = [&](int rh, int ch, bool first) {
+  auto mma = [&](int rh, int ch, bool first) PP_INLINE {
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
@@ -271,25 +240,10 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8_kernel(G8Params P) {
           acc[rh * RH + i][ch * 2 + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf_[ch * 2 + j][ks], af[i][ks], c, 0, 0, 0);
         }
   };
-  // (Tried: issuing a phase's LDS-DMA requests between its MFMAs instead of in the read segment.  A wave issues in
-  // order and an LDS-DMA instruction takes 60+ cycles to issue, so the MFMAs behind it wait: barriers + MFMAs alone
-  // went from 1.03 to 1.30 us per K step.  In the read segment the same issue time runs beside the partner's MFMAs.)
-#define G8_SEG_END()                            \
-  __builtin_amdgcn_sched_barrier(0);            \
-  __builtin_amdgcn_s_barrier();                 \
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-  __builtin_amdgcn_sched_barrier(0);            \
-  __builtin_amdgcn_s_setprio(1)
-#define G8_MMA_END()                            \
-  __builtin_amdgcn_s_setprio(0);                \
-  __builtin_amdgcn_sched_barrier(0);            \
-  __builtin_amdgcn_s_barrier();                 \
-  __builtin_amdgcn_sched_barrier(0)
-
   // ---- the epilogue, two row tiles at a time.  A tile's 128 KiB of C issued in one go cost 5-7 us per tile (the K
   // loop of a K = 512 tile: 11 us) — not HBM bandwidth (de-phasing the workgroups did not help) but the store path of
   // the CU: HALF the stores cost 1.3 us, the second half 5.7, and what an instruction costs goes with the number of
-  // cache lines it touches.  So (a) the lanes of rows r and r + 8 (lane ^ 8: one DPP row rotate) exchange halves, which
+  // cache lines it touches.  So (a) the lanes of rows r and r + 8 exchange halves (pp_exchange_f32 / _bf16), which
   // makes a store instruction 8 rows x 128 contiguous bytes (whole lines) instead of 16 rows x 64; (b) the tile leaves in
   // four batches, in the read segments of four consecutive phases:
   //     row tiles 0,1 (final after ph2 of the tile's last K step) -> its ph3      row tiles 2,3 -> its ph4
@@ -350,10 +304,8 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8_kernel(G8Params P) {
         const f32x4 s0 = up ? acc[i][0] : acc[i][2], s1 = up ? acc[i][1] : acc[i][3];
         const u32x4 keep = {pack_bf2(k0[0], k0[1]), pack_bf2(k0[2], k0[3]), pack_bf2(k1[0], k1[1]), pack_bf2(k1[2], k1[3])};
         const u32x4 send = {pack_bf2(s0[0], s0[1]), pack_bf2(s0[2], s0[3]), pack_bf2(s1[0], s1[1]), pack_bf2(s1[2], s1[3])};
-        u32x4 recv;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) recv[e] = (unsigned)__builtin_amdgcn_mov_dpp((int)send[e], 0x128, 0xf, 0xf, false);   // row_ror:8
-        const u32x4 v1 = up ? recv : keep, v2 = up ? keep : recv;
+        u32x4 v1, v2;
+        pp_exchange_bf16(keep, send, up, v1, v2);
         bf16_t* p = (bf16_t*)C + n0 + wc * 64 + (up ? 32 : 0) + fg * 8;
         // C is written once and not read by this kernel: streaming stores keep it from flushing the operand panels out
         // of the XCD's L2 (a round of 32 tiles is 4 MB, the whole L2)
@@ -372,13 +324,8 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8_kernel(G8Params P) {
         // f32: column tiles (0,1) and (2,3) each make one 128-byte line per row
 #pragma unroll
         for (int cp = 0; cp < 2; ++cp) {
-          const f32x4 lo = acc[i][2 * cp], hi = acc[i][2 * cp + 1];
-          const f32x4 send = up ? lo : hi;
-          f32x4 recv;
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            recv[e] = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(send[e]), 0x128, 0xf, 0xf, false));
-          f32x4 v1 = up ? recv : lo, v2 = up ? hi : recv;
+          f32x4 v1, v2;
+          pp_exchange_f32(acc[i][2 * cp], acc[i][2 * cp + 1], up, v1, v2);
           float* p = (float*)C + n0 + wc * 64 + cp * 32 + (up ? 16 : 0) + fg * 4;
           if (row1 < mlim) { float* q1 = p + (size_t)row1 * P.ldc; if (ACCUM) v1 += *(const f32x4*)q1; *(f32x4*)q1 = v1; }
           if (row2 < mlim) { float* q2 = p + (size_t)row2 * P.ldc; if (ACCUM) v2 += *(const f32x4*)q2; *(f32x4*)q2 = v2; }
@@ -391,17 +338,17 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8_kernel(G8Params P) {
   // (The immediates must be compile-time constants and a chain of scalar branches per wait is not free: computing the
   // allowance from a running request counter cost 0.45 us per K step.  The five cases below cover the schedule.)
   constexpr int SQ = ACCUM ? 0 : (RH / 2) * (EPI == 1 ? 3 : (sizeof(TOUT) == 2 ? 2 : 4));   // stores per lane and batch (0: not counted)
-  auto wait_young = [&](int extra) {
-    if (SQ == 0 || extra == 0) { if (YOUNG == 8) G8_VMCNT(8); else G8_VMCNT(6); return; }
+  auto wait_young = [&](int extra) PP_INLINE {
+    if (SQ == 0 || extra == 0) { if (YOUNG == 8) VMCNT(8); else VMCNT(6); return; }
 #define G8_W(k)                                                                               \
   do {                                                                                        \
     constexpr int n_ = YOUNG + (k) * SQ;                                                      \
-    if (n_ == 8) G8_VMCNT(8); else if (n_ == 10) G8_VMCNT(10); else if (n_ == 12) G8_VMCNT(12);           \
-    else if (n_ == 14) G8_VMCNT(14); else if (n_ == 16) G8_VMCNT(16); else if (n_ == 18) G8_VMCNT(18);     \
-    else if (n_ == 20) G8_VMCNT(20); else if (n_ == 22) G8_VMCNT(22); else if (n_ == 24) G8_VMCNT(24);     \
-    else if (n_ == 32) G8_VMCNT(32); else if (n_ == 40) G8_VMCNT(40);                                      \
-    else if (n_ > 40) G8_VMCNT(40); else if (n_ > 32) G8_VMCNT(32); else if (n_ > 24) G8_VMCNT(24);        \
-    else G8_VMCNT(6);                                                                         \
+    if (n_ == 8) VMCNT(8); else if (n_ == 10) VMCNT(10); else if (n_ == 12) VMCNT(12);           \
+    else if (n_ == 14) VMCNT(14); else if (n_ == 16) VMCNT(16); else if (n_ == 18) VMCNT(18);     \
+    else if (n_ == 20) VMCNT(20); else if (n_ == 22) VMCNT(22); else if (n_ == 24) VMCNT(24);     \
+    else if (n_ == 32) VMCNT(32); else if (n_ == 40) VMCNT(40);                                      \
+    else if (n_ > 40) VMCNT(40); else if (n_ > 32) VMCNT(32); else if (n_ > 24) VMCNT(24);        \
+    else VMCNT(6);                                                                         \
   } while (0)
     if (extra == 1) G8_W(1);
     else if (extra == 2) G8_W(2);
@@ -409,16 +356,8 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8_kernel(G8Params P) {
     else G8_W(4);
 #undef G8_W
   };
-  auto ld_a = [&](int buf, int half, int soff) { load_a(buf, half, soff); };
-  auto ld_b = [&](int buf, int half, int soff) { load_b(buf, half, soff); };
-
-  // ---- prologue: K steps 0 and (half of) 1
-  ld_a(0, 0, l_sa); ld_b(0, 0, l_sb); ld_b(0, 1, l_sb); ld_a(0, 1, l_sa);
-  cursor_next();
-  ld_a(1, 0, l_sa); ld_b(1, 0, l_sb);
-  wait_young(0);                                             // HA0(0), HB0(0) landed; four half-tiles behind them
-  __builtin_amdgcn_s_barrier();
-  if (g == 1) __builtin_amdgcn_s_barrier();                  // group 1 runs one barrier behind group 0
+  auto wait_first = [&]() PP_INLINE { wait_young(0); };
+  pp_prologue(g, load_a, load_b, cursor_next, wait_first);
 
   int c_it = 0, c_m0, c_n0, c_cmin;
   tile_origin(0, c_m0, c_n0, c_cmin);
@@ -437,38 +376,19 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8_kernel(G8Params P) {
     const bool full = c_m0 + BM <= row_limit(c_m0) && c_n0 >= c_cmin && !ACCUM && !(G8_DBG(1));
     const bool pf = p_pending && p_full;                      // the previous tile's batches were issued in full
     const int x4 = (last && full ? 2 : 0) + (first && pf ? 2 : 0);
-    // ph1: r0 x c0
-    read_a(buf, 0);
-    read_b(buf, 0);
-    if (first && p_pending) store_rows(RH, p_m0, p_n0, p_cmin, p_full);
-    ld_b(buf ^ 1, 1, l_sb);
-    wait_young(first ? (pf ? 3 : 0) : (second && p_second_full ? 1 : 0));     // HB1 of this K step (read in ph2)
-    G8_SEG_END();
-    mma(0, 0, first);
-    G8_MMA_END();
-    // ph2: r0 x c1
-    read_b(buf, 1);
-    if (first && p_pending) store_rows(RH + RH / 2, p_m0, p_n0, p_cmin, p_full);
-    ld_a(buf ^ 1, 1, l_sa);
-    wait_young(first && pf ? 4 : 0);                                          // HA1 of this K step (read in ph3)
-    G8_SEG_END();
-    mma(0, 1, first);
-    G8_MMA_END();
-    // ph3: r1 x c1
-    read_a(buf, 1);
-    if (last) store_rows(0, c_m0, c_n0, c_cmin, full);
-    cursor_next();
-    ld_a(buf, 0, l_sa);
-    G8_SEG_END();
-    mma(1, 1, first);
-    G8_MMA_END();
-    // ph4: r1 x c0
-    if (last) store_rows(RH / 2, c_m0, c_n0, c_cmin, full);
-    ld_b(buf, 0, l_sb);
-    wait_young(x4);                                                           // HA0, HB0 of the next K step
-    G8_SEG_END();
-    mma(1, 0, first);
-    G8_MMA_END();
+    auto stores = [&](int ph) PP_INLINE {
+      if (ph == 1) { if (first && p_pending) store_rows(RH, p_m0, p_n0, p_cmin, p_full); }
+      else if (ph == 2) { if (first && p_pending) store_rows(RH + RH / 2, p_m0, p_n0, p_cmin, p_full); }
+      else if (ph == 3) { if (last) store_rows(0, c_m0, c_n0, c_cmin, full); }
+      else { if (last) store_rows(RH / 2, c_m0, c_n0, c_cmin, full); }
+    };
+    auto wait = [&](int ph) PP_INLINE {
+      if (ph == 1) wait_young(first ? (pf ? 3 : 0) : (second && p_second_full ? 1 : 0));
+      else if (ph == 2) wait_young(first && pf ? 4 : 0);
+      else wait_young(x4);
+    };
+    auto mma_k = [&](int rh, int ch) PP_INLINE { mma(rh, ch, first); };
+    pp_kstep<buf>(read_a, read_b, load_a, load_b, mma_k, cursor_next, stores, wait);
     if (first) { p_second_full = pf; p_pending = false; }
     if (last) {
       p_m0 = c_m0; p_n0 = c_n0; p_cmin = c_cmin; p_pending = true; p_full = full;
@@ -488,9 +408,37 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8_kernel(G8Params P) {
     }
   }
   if (p_pending) { store_rows(RH, p_m0, p_n0, p_cmin, false); store_rows(RH + RH / 2, p_m0, p_n0, p_cmin, false); }
-  G8_VMCNT(0);
-  if (g == 0) __builtin_amdgcn_s_barrier();                  // pairs with group 1's extra barrier at the start
+  pp_exit(g);
 }
+
+// ---- host side: one launch plan ----------------------------------------------------------------------------------------
+// Tile height, tile count and grid of a launch over M rows x tiles_n column tiles.  Plain products take 128-row tiles when
+// there are not enough 256-row tiles to fill the chip; the fused wi + GEGLU launch has a rule of its own and passes its
+// choice in (force128 = 0 / 1; -1: the plain rule).  The grid is one workgroup per CU, or the tile count rounded up to a
+// multiple of 8 (one eighth per XCD) when that is less.
+struct G8Plan { bool small; int n_tiles, grid, cus; };
+static G8Plan g8_plan(int M, int tiles_n, int force128 = -1) {
+  G8Plan pl;
+  pl.cus = mrmt3_cu_count() & ~7;
+  const int tiles256 = ceil_div(M, 256) * tiles_n;
+  pl.small = force128 < 0 ? tiles256 < pl.cus : force128 != 0;
+  pl.n_tiles = pl.small ? ceil_div(M, 128) * tiles_n : tiles256;
+  pl.grid = pl.n_tiles < pl.cus ? ((pl.n_tiles + 7) & ~7) : pl.cus;
+  return pl;
+}
+// What every launch fills the same way: operands, strides, no split K, the store mode, the diagnostics switches.
+static G8Params g8_params_base(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K) {
+  G8Params P = {};
+  P.A = (const bf16_t*)A; P.B = (const bf16_t*)B; P.C = C;
+  P.lda = lda; P.ldb = ldb; P.ldc = ldc; P.M = M; P.N = N; P.K = K;
+  P.ksplit = 1; P.kfull = K;
+  P.nt_c = g8_store_mode();
+#ifdef MRMT3_DIAG
+  P.dbg = mrmt3_diag_env("MRMT3_GEMM8_DBG");
+#endif
+  return P;
+}
+static bool g8_operands_fit(int M, int lda, int N, int ldb, int K) { return lds_dma_fits(M, lda, K) && lds_dma_fits(N, ldb, K); }
 
 // Returns 1 if the shape was launched on the second-generation kernel, 0 if the caller should use gemm.hip's.
 int mrmt3_gemm_nt8_try(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K,
@@ -504,33 +452,22 @@ int mrmt3_gemm_nt8_try(const void* A, int lda, const void* B, int ldb, void* C, 
   // at most one wave (short inputs: 12 segments per GPU, the encoder), or a tile count that fills >= 80 % of the
   // last wave's slots.  A last column tile that is half overlap (N = 384 / 1152: 11-33 % of the MFMAs redone) still
   // wins cold (qkv 115 -> 96 us).  Not: the accumulate form (one launch per decoder layer).
-  {
-    if (MR_KNOB("MRMT3_GEMM8_ALL", 0) != 1) {                   // (1: tuning / tests, take every admissible shape)
-      if (accumulate) return 0;
-      const int cu = mrmt3_cu_count() & ~7, tn = ceil_div(N, 256), t256 = ceil_div(M, 256) * tn;
-      const int nt = t256 < cu ? ceil_div(M, 128) * tn : t256;
-      const int waves = ceil_div(nt, cu);
-      if (nt > cu && nt * 5 < waves * cu * 4) return 0;        // a last wave of workgroups less than 80 % full
-    }
+  const G8Plan pl = g8_plan(M, ceil_div(N, 256));
+  if (MR_KNOB("MRMT3_GEMM8_ALL", 0) != 1) {                     // (1: tuning / tests, take every admissible shape)
+    if (accumulate) return 0;
+    const int waves = ceil_div(pl.n_tiles, pl.cus);
+    if (pl.n_tiles > pl.cus && pl.n_tiles * 5 < waves * pl.cus * 4) return 0;   // a last wave of workgroups less than 80 % full
   }
-  if (((size_t)M * lda + K) * 2 >= 0x7FFF0000ull || ((size_t)N * ldb + K) * 2 >= 0x7FFF0000ull) return 0;
-  G8Params P;
-  P.A = (const bf16_t*)A; P.B = (const bf16_t*)B; P.C = C;
-  P.lda = lda; P.ldb = ldb; P.ldc = ldc; P.M = M; P.N = N; P.K = K;
-  P.ksplit = 1; P.mpad = 0; P.kfull = K;
-  P.dbg = 0; P.skew_ticks = 0;
-  P.nt_c = g8_store_mode();
+  if (!g8_operands_fit(M, lda, N, ldb, K)) return 0;
+  G8Params P = g8_params_base(A, lda, B, ldb, C, ldc, M, N, K);
   P.tiles_n = ceil_div(N, 256);
-  const int cus = mrmt3_cu_count() & ~7;
-  const int tiles256 = ceil_div(M, 256) * P.tiles_n;
-  const bool small = tiles256 < cus;                         // not enough 256-row tiles to fill the chip: 128-row tiles
-  P.n_tiles = small ? ceil_div(M, 128) * P.tiles_n : tiles256;
-  int grid = P.n_tiles < cus ? ((P.n_tiles + 7) & ~7) : cus;
-  if (grid > P.n_tiles) grid = (P.n_tiles + 7) & ~7;
+  P.n_tiles = pl.n_tiles;
+  const bool small = pl.small;
+  const int cus = pl.cus;
+  int grid = pl.grid;
 #ifdef MRMT3_DIAG
   {
     // (experiment, closed: start skew) one tile ~ nk x 1.4 us (0.7 for 128-row tiles) + the stores; eight start phases across that period
-    P.dbg = mrmt3_diag_env("MRMT3_GEMM8_DBG");
     const int skew_pct = MR_KNOB("MRMT3_GEMM8_SKEW", 0);
     const double tile_us = (K / 64) * (small ? 0.7 : 1.4) + 1.5;
     const int tiles_per_wg = ceil_div(P.n_tiles, cus);
@@ -604,17 +541,11 @@ int mrmt3_gemm_nt8_splitk_try(const void* A, int lda, const void* B, int ldb, vo
   if (sp <= 1 || !workspace) return 0;
   const int mpad = ceil_div(M, 128) * 128;
   if (workspace_bytes < (size_t)sp * mpad * N * sizeof(float) || ((uintptr_t)workspace & 15)) return 0;
-  if (((size_t)M * lda + K) * 2 >= 0x7FFF0000ull || ((size_t)N * ldb + K) * 2 >= 0x7FFF0000ull) return 0;
-  G8Params P;
-  memset(&P, 0, sizeof(P));
-  P.A = (const bf16_t*)A; P.B = (const bf16_t*)B; P.C = workspace;
-  P.lda = lda; P.ldb = ldb; P.ldc = N; P.M = M; P.N = N;
-  P.K = K / sp; P.kfull = K; P.ksplit = sp; P.mpad = mpad;
+  if (!g8_operands_fit(M, lda, N, ldb, K)) return 0;
+  G8Params P = g8_params_base(A, lda, B, ldb, workspace, N, M, N, K / sp);          // C = the slab, a tile walks K / sp
+  P.kfull = K; P.ksplit = sp; P.mpad = mpad;
   P.tiles_n = ceil_div(N, 256);
-  P.n_tiles = sp * (mpad / 128) * P.tiles_n;
-#ifdef MRMT3_DIAG
-  P.dbg = mrmt3_diag_env("MRMT3_GEMM8_DBG");
-#endif
+  P.n_tiles = sp * (mpad / 128) * P.tiles_n;                 // 128-row tiles over the virtual rows, at most one wave
   const int grid = (P.n_tiles + 7) & ~7;
   hipLaunchKernelGGL((gemm_nt8_kernel<float, false, 4>), dim3((unsigned)grid), dim3(512), 0, s, P);
   const size_t total = (size_t)M * (N >> 2);
@@ -649,8 +580,7 @@ extern "C" int mrmt3_gemm_nt_geglu(const void* x, int ldx, const void* wi, int l
   const int min_rows = MR_KNOB("MRMT3_GEGLU_FUSED_MIN_ROWS", 2048);
   bool fused = rows >= min_rows && dff % 128 == 0 && K % 128 == 0 && ldx % 8 == 0 && ldw % 8 == 0 && ldh % 8 == 0 &&
                ldg % 8 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)wi % 16) == 0 && ((uintptr_t)h % 16) == 0 &&
-               ((uintptr_t)g % 16) == 0 && ((size_t)rows * ldx + K) * 2 < 0x7FFF0000ull &&
-               ((size_t)2 * dff * ldw + K) * 2 < 0x7FFF0000ull;
+               ((uintptr_t)g % 16) == 0 && g8_operands_fit(rows, ldx, 2 * dff, ldw, K);
   if (MR_KNOB("MRMT3_GEGLU_FUSED", 1) == 0) fused = false;
   if (!fused) {
     int rc = mrmt3_gemm_nt(x, ldx, wi, ldw, h, ldh, rows, 2 * dff, K, MRMT3_BF16, MRMT3_BF16, 0, stream);
@@ -658,12 +588,8 @@ extern "C" int mrmt3_gemm_nt_geglu(const void* x, int ldx, const void* wi, int l
     MR_CHECK_ARG(ldh == 2 * dff && ldg == dff, "gemm_nt_geglu: the unfused path needs dense h and g");
     return mrmt3_geglu_fwd(h, g, rows, dff, MRMT3_BF16, p_drop, seed, step_dev, stream_id, stream);
   }
-  G8Params P;
-  P.A = (const bf16_t*)x; P.B = (const bf16_t*)wi; P.C = h; P.C2 = g;
-  P.lda = ldx; P.ldb = ldw; P.ldc = ldh; P.ldc2 = ldg; P.dff = dff;
-  P.M = rows; P.N = 2 * dff; P.K = K;
-  P.ksplit = 1; P.mpad = 0; P.kfull = K;
-  P.nt_c = g8_store_mode();
+  G8Params P = g8_params_base(x, ldx, wi, ldw, h, ldh, rows, 2 * dff, K);
+  P.C2 = g; P.ldc2 = ldg; P.dff = dff;
   P.drop = make_drop(p_drop, seed, stream_id, step_dev);
   P.tiles_n = dff / 128;
   const int cus = mrmt3_cu_count() & ~7;
@@ -672,15 +598,10 @@ extern "C" int mrmt3_gemm_nt_geglu(const void* x, int ldx, const void* wi, int l
   // the 128-row tiling does not (12 segments per GPU: 384 tiles = 1.5 waves against 768 = 3 waves)
   auto fill = [&](int nt) { return (double)nt / ((double)ceil_div(nt, cus) * cus); };
   const bool small = tiles256 < cus || (tiles256 < 4 * cus && fill(tiles128) > fill(tiles256) + 0.15);
-  P.n_tiles = small ? tiles128 : tiles256;
-  P.dbg = 0;
-#ifdef MRMT3_DIAG
-  P.dbg = mrmt3_diag_env("MRMT3_GEMM8_DBG");
-#endif
-  P.skew_ticks = 0;
-  int grid = P.n_tiles < cus ? ((P.n_tiles + 7) & ~7) : cus;
-  if (small) hipLaunchKernelGGL((gemm_nt8_kernel<bf16_t, false, 4, 1>), dim3((unsigned)grid), dim3(512), 0, s, P);
-  else hipLaunchKernelGGL((gemm_nt8_kernel<bf16_t, false, 8, 1>), dim3((unsigned)grid), dim3(512), 0, s, P);
+  const G8Plan pl = g8_plan(rows, P.tiles_n, small ? 1 : 0);
+  P.n_tiles = pl.n_tiles;
+  if (small) hipLaunchKernelGGL((gemm_nt8_kernel<bf16_t, false, 4, 1>), dim3((unsigned)pl.grid), dim3(512), 0, s, P);
+  else hipLaunchKernelGGL((gemm_nt8_kernel<bf16_t, false, 8, 1>), dim3((unsigned)pl.grid), dim3(512), 0, s, P);
   MR_CHECK_LAUNCH("gemm_nt_geglu");
   mrmt3_count(MRMT3_CNT_GEMM_NT_GEGLU);
   return MRMT3_OK;

@@ -32,12 +32,12 @@
 #include <type_traits>
 
 #include "common.h"
+#include "lds_dma.h"
 #include "rowmath.h"
 
 // no implicit FMA formation in this file (the row phases' arithmetic is rowmath.h's and carries its own setting)
 #pragma clang fp contract(off)
 
-#define GR_OOB 0x7FFF0000
 #define GR_YLD 1040                       // bytes per row of the LDS image of the output tile
 #define GR_B_BYTES 65536                  // 8 waves x 2 slots x 4 KiB of private weight rows
 
@@ -77,14 +77,6 @@ struct GRParams {
 #else
 #define GR_DBG(bit) 0
 #endif
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t gr_rsrc(const void* base, size_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ void gr_dma16(__amdgpu_buffer_rsrc_t r, unsigned char* dst, unsigned voff, int soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)dst, 16, voff, soff, 0, 0);
-}
-#define GR_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
 
 // The lane's two 8-byte pieces of an image row (columns 4 lane .. + 3 and 256 + 4 lane .. + 3, 512 bytes apart) in ONE
 // ds_read2st64_b64.
@@ -151,8 +143,8 @@ __global__ __launch_bounds__(512, BM == 64 ? 4 : 2) void gemm_rows_kernel(GRPara
   DropCfg dc0 = P.d0, dc1 = P.d1;
   DROP_STEP(dc0);
   if (EPI == GR_ADDNORM) DROP_STEP(dc1);
-  const __amdgpu_buffer_rsrc_t ra = gr_rsrc(P.A, ((size_t)(P.M - 1) * P.lda + P.K) * 2);
-  const __amdgpu_buffer_rsrc_t rb = gr_rsrc(P.B, ((size_t)(P.n_ctiles * 512 - 1) * P.ldb + P.K) * 2);
+  const __amdgpu_buffer_rsrc_t ra = lds_dma_rsrc(P.A, ((size_t)(P.M - 1) * P.lda + P.K) * 2);
+  const __amdgpu_buffer_rsrc_t rb = lds_dma_rsrc(P.B, ((size_t)(P.n_ctiles * 512 - 1) * P.ldb + P.K) * 2);
   // LDS-DMA sources: WHOLE 128-byte lines only.  (The first version staged the weights in 64-byte K steps, half a line
   // per row and request: a CU's memory path moves lines, used in full or not.)  A piece q of wave w = tile rows
   // 64 q + 8 w .. + 7 x 128 B; B piece q of wave w and column half ch = its columns 32 ch + 8 q .. + 7 x 128 B.
@@ -181,14 +173,14 @@ __global__ __launch_bounds__(512, BM == 64 ? 4 : 2) void gemm_rows_kernel(GRPara
     const bool on = chunk < np && !GR_DBG(32);
 #pragma unroll
     for (int q = 0; q < NAP; ++q)
-      gr_dma16(ra, ldsA + slot * A_SLOT + q * 8192, voffA, on ? koff(chunk) + q * astride : GR_OOB);
+      lds_dma16(ra, ldsA + slot * A_SLOT + q * 8192, voffA, on ? koff(chunk) + q * astride : LDS_DMA_OOB);
   };
   // B of K chunk `chunk` (64 deep), column half ch -> this wave's slot ch
   auto ldB = [&](int ch, int chunk) __attribute__((always_inline)) {
     const bool on = chunk < np && !GR_DBG(16);
 #pragma unroll
     for (int q = 0; q < 4; ++q)
-      gr_dma16(rb, ldsB + ch * 4096 + q * 1024, voffB, on ? koff(chunk) + (ch * 4 + q) * qstride : GR_OOB);
+      lds_dma16(rb, ldsB + ch * 4096 + q * 1024, voffB, on ? koff(chunk) + (ch * 4 + q) * qstride : LDS_DMA_OOB);
   };
 
   // fragment read offsets (128-byte rows, chunk c of row r at c ^ (r & 7); the second 32-deep K step is the offset ^ 64)
@@ -232,13 +224,13 @@ __global__ __launch_bounds__(512, BM == 64 ? 4 : 2) void gemm_rows_kernel(GRPara
   };
   auto chunk = [&](int aslot, int p) __attribute__((always_inline)) {
     // outstanding, oldest first: A(p + LA - 1) x NAP, B(p, 0) x 4, B(p, 1) x 4
-    GR_VMCNT(4);
+    VMCNT(4);
     __builtin_amdgcn_s_barrier();               // every wave's pieces of A(p) have landed; all are done reading A(p-1)
     __builtin_amdgcn_sched_barrier(0);
     ldA((aslot + LA) % NSLOT, p + LA);          // (into the slot of chunk p - 1)
     phase(aslot, 0, p);
     // outstanding: B(p, 1) x 4, A(p + LA) x NAP, B(p+1, 0) x 4
-    if (NAP == 1) GR_VMCNT(5); else GR_VMCNT(6);
+    if (NAP == 1) VMCNT(5); else VMCNT(6);
     __builtin_amdgcn_sched_barrier(0);
     phase(aslot, 1, p);
   };
@@ -258,7 +250,7 @@ __global__ __launch_bounds__(512, BM == 64 ? 4 : 2) void gemm_rows_kernel(GRPara
     for (; p + 4 <= np; p += 4) { chunk(0, p); chunk(1, p + 1); chunk(2, p + 2); chunk(3, p + 3); }
     if (p < np) { chunk(0, p); chunk(1, p + 1); }   // (np is even)
   }
-  GR_VMCNT(0);                                   // (the switched-off tail loads still write zeros into their slots)
+  VMCNT(0);                                   // (the switched-off tail loads still write zeros into their slots)
   __builtin_amdgcn_s_barrier();
   GR_STAMP(2);
 
@@ -482,7 +474,7 @@ extern "C" int mrmt3_gemm_rows_ok(int M, int N, int K, int lda, int ldw) {
   if (M <= 0 || N <= 0 || K < 128 || K % 128 != 0 || N % 512 != 0 || (N != 512 && N != 1024)) return 0;
   if (lda % 8 != 0 || ldw % 8 != 0 || lda < K || ldw < K) return 0;
   const size_t mpad = (size_t)ceil_div(M, 128) * 128;
-  if ((mpad * lda + K) * 2 >= 0x7FFF0000ull || ((size_t)N * ldw + K) * 2 >= 0x7FFF0000ull) return 0;
+  if (!lds_dma_fits(mpad, lda, K) || !lds_dma_fits(N, ldw, K)) return 0;
   return 1;
 }
 

@@ -2,9 +2,8 @@
 // bf16 operands, f32 accumulation — the autograd backward of every nn.Linear(bias=False) of the T5 stack with respect
 // to its weight (dW = dY^T X; reference: torch autograd through HF T5Attention / T5DenseGatedGeluDense, models/t5.py:51,72).
 //
-// Same schedule as gemm8.hip (read that header first): 512 threads, the two waves of a SIMD one barrier apart, a
-// 256 x 256 tile of dW per workgroup, 64 token rows per K step, two LDS buffers of four 16-KiB half-tiles, one half-tile
-// of LDS-DMA requested per phase two K steps ahead, counted vmcnt.  What differs:
+// The schedule is pingpong.h's (read that header first), shared with gemm8.hip: a 256 x 256 tile of dW per workgroup,
+// 64 token rows per K step, no stores inside the K loop and a constant wait of 8.  What is this kernel's own:
 //   * the reduction runs over the TOKEN rows, the slow index of both operands: a half-tile is stored
 //     [64 tokens][128 features] (256-byte rows, 32-byte units XOR-swizzled by token & 7 on the LDS-DMA source address) and
 //     the MFMA fragments are read with ds_read_b64_tr_b16 (hardware transpose), two reads per 16 x 32 fragment — the
@@ -25,11 +24,7 @@
 #include <vector>
 
 #include "common.h"
-
-#define T8_OOB 0x7FFF0000
-#define T8_HALF 16384
-#define T8_BUF (4 * T8_HALF)
-#define T8_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
+#include "pingpong.h"
 
 struct T8Params {
   const bf16_t* A;     // dY [M][lda]   (N1 features)
@@ -60,9 +55,6 @@ struct T8RTile {
 };
 static_assert(sizeof(T8RTile) == 48, "reduce record layout");
 
-__device__ __forceinline__ void t8_dma16(__amdgpu_buffer_rsrc_t r, unsigned char* dst, unsigned voff, int soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)dst, 16, voff, soff, 0, 0);
-}
 // one 16 x 32 MFMA operand: features of one 32-byte unit, the lane group's 4 + 4 token rows (rows R and R + 16).
 // The transposed reads are INLINE ASM on purpose: hipcc (ROCm 7.2) puts `s_waitcnt vmcnt(0)` in front of every
 // __builtin_amdgcn_ds_read_tr16_b64 while an LDS-DMA load is outstanding (it cannot prove the two do not alias; plain
@@ -86,10 +78,8 @@ __device__ __forceinline__ void t8_run_item(const T8Item& P, unsigned char* lds)
   const int rmin = P.rmin, cmin = P.cmin;                  // rows / columns below belong to the neighbouring tile
   const int nk = P.nk;                                     // even
 
-  const __amdgpu_buffer_rsrc_t ra =
-      __builtin_amdgcn_make_buffer_rsrc((void*)P.A, 0, (int)(((size_t)(P.M - 1) * P.lda + P.N1) * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rb =
-      __builtin_amdgcn_make_buffer_rsrc((void*)P.B, 0, (int)(((size_t)(P.M - 1) * P.ldb + P.N2) * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t ra = lds_dma_rsrc(P.A, ((size_t)(P.M - 1) * P.lda + P.N1) * 2);
+  const __amdgpu_buffer_rsrc_t rb = lds_dma_rsrc(P.B, ((size_t)(P.M - 1) * P.ldb + P.N2) * 2);
 
   // ---- LDS-DMA source offsets.  A half-tile = 64 token rows x 256 B; one wave-instruction = 1 KiB = 4 token rows;
   // lane p fills (token 4*piece + p/16, 16-byte chunk p%16) with the token row's chunk whose 32-byte unit is
@@ -104,31 +94,31 @@ __device__ __forceinline__ void t8_run_item(const T8Item& P, unsigned char* lds)
     voffA[i] = (unsigned)((tk * P.lda + (v >> 6) * 128 + (v & 63)) * 2);
     voffB[i] = (unsigned)((tk * P.ldb + (v >> 5) * 64 + (v & 31)) * 2);
   }
-  const int piece0 = w * 1024;
-  auto load_a = [&](int buf, int half, int soff) {
-    unsigned char* base = lds + buf * T8_BUF + half * T8_HALF + piece0;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) t8_dma16(ra, base + i * 8192, voffA[i] + (half ? 128u : 0u), soff);
-  };
-  auto load_b = [&](int buf, int half, int soff) {
-    unsigned char* base = lds + buf * T8_BUF + (2 + half) * T8_HALF + piece0;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) t8_dma16(rb, base + i * 8192, voffB[i] + (half ? 64u : 0u), soff);
-  };
-  int l_k = 0;
+  const int piece0 = w * PP_PIECE;
+  int l_k = 0;                                               // the load cursor: the K step being requested
   int l_sa = (P.row0 * P.lda + a0) * 2, l_sb = (P.row0 * P.ldb + b0) * 2;
+  auto load_a = [&](int buf, int half) PP_INLINE {
+    unsigned char* base = lds + buf * PP_BUF + half * PP_HALF + piece0;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) lds_dma16(ra, base + i * PP_STRIDE, voffA[i] + (half ? 128u : 0u), l_sa);
+  };
+  auto load_b = [&](int buf, int half) PP_INLINE {
+    unsigned char* base = lds + buf * PP_BUF + (2 + half) * PP_HALF + piece0;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) lds_dma16(rb, base + i * PP_STRIDE, voffB[i] + (half ? 64u : 0u), l_sb);
+  };
   const int step_a = 64 * P.lda * 2, step_b = 64 * P.ldb * 2;
-  auto cursor_next = [&]() {
+  auto cursor_next = [&]() PP_INLINE {
     ++l_k;
     if (l_k < nk) { l_sa += step_a; l_sb += step_b; }
-    else { l_sa = l_sb = T8_OOB; }                          // past the token range: zero fill, no memory traffic
+    else { l_sa = l_sb = LDS_DMA_OOB; }                     // past the token range: zero fill, no memory traffic
   };
 
   // ---- fragment addresses: token row ks*32 + 4 fg + fq (and + 16), unit U stored at U ^ (row & 7), 8-byte piece fp
   const int rrow = fg * 4 + fq, rx = rrow & 7;
   const int f_lane = rrow * 256 + (fp >> 1) * 16 + (fp & 1) * 8;
   const int a_addr = f_lane + (((g * 4) ^ rx) << 5);                        // ^ (i << 5) for row tile i, + ks * 8192
-  const int b_addr = 2 * T8_HALF + f_lane + (((wc * 2) ^ rx) << 5);         // ^ (j << 5) for column tile j
+  const int b_addr = 2 * PP_HALF + f_lane + (((wc * 2) ^ rx) << 5);         // ^ (j << 5) for column tile j
 
   bf16x8 af[4][2], bf_[4][2];
   f32x4 acc[8][4];
@@ -137,16 +127,16 @@ __device__ __forceinline__ void t8_run_item(const T8Item& P, unsigned char* lds)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   const unsigned lds0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) unsigned char*)lds);
-  auto read_a = [&](int buf, int half) {
-    const unsigned p = lds0 + buf * T8_BUF + half * T8_HALF;
+  auto read_a = [&](int buf, int half) PP_INLINE {
+    const unsigned p = lds0 + buf * PP_BUF + half * PP_HALF;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       af[i][0] = t8_frag<0>(p + (a_addr ^ (i << 5)));
       af[i][1] = t8_frag<8192>(p + (a_addr ^ (i << 5)));
     }
   };
-  auto read_b = [&](int buf, int half) {
-    const unsigned p = lds0 + buf * T8_BUF + half * T8_HALF;
+  auto read_b = [&](int buf, int half) PP_INLINE {
+    const unsigned p = lds0 + buf * PP_BUF + half * PP_HALF;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       bf_[half * 2 + j][0] = t8_frag<0>(p + (b_addr ^ (j << 5)));
@@ -154,7 +144,7 @@ __device__ __forceinline__ void t8_run_item(const T8Item& P, unsigned char* lds)
     }
   };
   // X fragments are the MFMA's first operand: a lane ends up with 4 consecutive n2 columns of one n1 row per tile
-  auto mma = [&](int rh, int ch) {
+  auto mma = [&](int rh, int ch) PP_INLINE {
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
@@ -164,61 +154,20 @@ __device__ __forceinline__ void t8_run_item(const T8Item& P, unsigned char* lds)
           acc[rh * 4 + i][ch * 2 + j] =
               __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf_[ch * 2 + j][ks], af[i][ks], acc[rh * 4 + i][ch * 2 + j], 0, 0, 0);
   };
-#define T8_SEG_END()                            \
-  __builtin_amdgcn_sched_barrier(0);            \
-  __builtin_amdgcn_s_barrier();                 \
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-  __builtin_amdgcn_sched_barrier(0);            \
-  __builtin_amdgcn_s_setprio(1)
-#define T8_MMA_END()                            \
-  __builtin_amdgcn_s_setprio(0);                \
-  __builtin_amdgcn_sched_barrier(0);            \
-  __builtin_amdgcn_s_barrier();                 \
-  __builtin_amdgcn_sched_barrier(0)
-
-  // ---- prologue: K steps 0 and (half of) 1
-  load_a(0, 0, l_sa); load_b(0, 0, l_sb); load_b(0, 1, l_sb); load_a(0, 1, l_sa);
-  cursor_next();
-  load_a(1, 0, l_sa); load_b(1, 0, l_sb);
-  T8_VMCNT(8);
-  __builtin_amdgcn_s_barrier();
-  if (g == 1) __builtin_amdgcn_s_barrier();                  // group 1 runs one barrier behind group 0
-
-  auto kstep = [&](int buf) {
-    read_a(buf, 0);
-    read_b(buf, 0);
-    load_b(buf ^ 1, 1, l_sb);
-    T8_VMCNT(8);
-    T8_SEG_END();
-    mma(0, 0);
-    T8_MMA_END();
-    read_b(buf, 1);
-    load_a(buf ^ 1, 1, l_sa);
-    T8_VMCNT(8);
-    T8_SEG_END();
-    mma(0, 1);
-    T8_MMA_END();
-    read_a(buf, 1);
-    cursor_next();
-    load_a(buf, 0, l_sa);
-    T8_SEG_END();
-    mma(1, 1);
-    T8_MMA_END();
-    load_b(buf, 0, l_sb);
-    T8_VMCNT(8);
-    T8_SEG_END();
-    mma(1, 0);
-    T8_MMA_END();
-  };
+  // pingpong.h's K loop: nothing is stored inside it, so every wait leaves the 8 requests of the four youngest
+  // half-tiles in flight
+  auto no_stores = [&](int) PP_INLINE {};
+  auto wait8 = [&](int) PP_INLINE { VMCNT(8); };
+  auto wait_first = [&]() PP_INLINE { VMCNT(8); };
+  pp_prologue(g, load_a, load_b, cursor_next, wait_first);
   for (int u = 0; u < nk; u += 2) {
-    kstep(0);
-    kstep(1);
+    pp_kstep<0>(read_a, read_b, load_a, load_b, mma, cursor_next, no_stores, wait8);
+    pp_kstep<1>(read_a, read_b, load_a, load_b, mma, cursor_next, no_stores, wait8);
   }
-  T8_VMCNT(0);                                               // the switched-off requests of the last steps
-  if (g == 0) __builtin_amdgcn_s_barrier();                  // pairs with group 1's extra barrier at the start
+  pp_exit(g);
 
-  // ---- epilogue: lane holds slab[n1 = row tile i, row fr][n2 = 16 ct + 4 fg + r].  The lanes of rows r and r + 8
-  // exchange halves (DPP row rotate) so that a store instruction writes 8 rows x 128 contiguous bytes.
+  // ---- epilogue: lane holds slab[n1 = row tile i, row fr][n2 = 16 ct + 4 fg + r]; stored in 8 rows x 128 contiguous
+  // bytes per instruction (pp_exchange_f32).
   if (b0 + wc * 64 < cmin || a0 + g * 128 < rmin) return;    // owned by the neighbouring tile (wave-uniform)
   float* out = P.out;
   const bool up = fr >= 8;
@@ -227,13 +176,8 @@ __device__ __forceinline__ void t8_run_item(const T8Item& P, unsigned char* lds)
     const int row1 = a0 + g * 128 + i * 16 + (fr & 7), row2 = row1 + 8;
 #pragma unroll
     for (int cp = 0; cp < 2; ++cp) {
-      const f32x4 lo = acc[i][2 * cp], hi = acc[i][2 * cp + 1];
-      const f32x4 send = up ? lo : hi;
-      f32x4 recv;
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        recv[e] = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(send[e]), 0x128, 0xf, 0xf, false));
-      const f32x4 v1 = up ? recv : lo, v2 = up ? hi : recv;
+      f32x4 v1, v2;
+      pp_exchange_f32(acc[i][2 * cp], acc[i][2 * cp + 1], up, v1, v2);
       float* p = out + b0 + wc * 64 + cp * 32 + (up ? 16 : 0) + fg * 4;
       __builtin_nontemporal_store(v1, (f32x4*)(p + (size_t)row1 * P.ldo));
       __builtin_nontemporal_store(v2, (f32x4*)(p + (size_t)row2 * P.ldo));
@@ -242,10 +186,9 @@ __device__ __forceinline__ void t8_run_item(const T8Item& P, unsigned char* lds)
 }
 
 __global__ __launch_bounds__(512, 2) void gemm_tn8_kernel(T8Params P) {
-  __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * T8_BUF];
+  __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * PP_BUF];
   // work item: all tiles of one token range run on one XCD (they share the range's rows of dY and X in its L2)
-  const int n = (int)gridDim.x, per = n >> 3;
-  const int wi = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
+  const int wi = xcd_major_index();
   if (wi >= P.n_tiles * P.n_splits) return;
   const int split = wi / P.n_tiles, tile = wi - split * P.n_tiles;
   const int t1 = tile / P.tiles_n2, t2 = tile - t1 * P.tiles_n2;
@@ -271,9 +214,8 @@ __global__ __launch_bounds__(512, 2) void gemm_tn8_kernel(T8Params P) {
 __global__ __launch_bounds__(512, 2) void gemm_tn8_group_kernel(const T8Item* __restrict__ items,
                                                                   const int* __restrict__ cta_start,
                                                                   const int* __restrict__ cta_items, int* sync) {
-  __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * T8_BUF];
-  const int n = (int)gridDim.x, per = n >> 3;
-  const int l = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
+  __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * PP_BUF];
+  const int l = xcd_major_index();
   const int q1 = cta_start[l + 1];
   for (int q = cta_start[l]; q < q1; ++q) {
     const T8Item I = items[cta_items[q]];
@@ -325,7 +267,7 @@ int mrmt3_tn8_plan(int M, int N1, int N2, int* tiles, int* splits, int* rows_per
   // mrmt3_tn_group_ok).  Other widths go to gemm_tn_kernel (found by tests/test_fuzz_gpu.py: N1 = 576 was admitted
   // with % 8 and came back wrong in rows 512..575).
   if (M < 8192 || N1 < 256 || N2 < 256 || N1 % 128 != 0 || N2 % 64 != 0) return 0;
-  if ((size_t)M * (size_t)(N1 > N2 ? N1 : N2) * 2 >= 0x7FFF0000ull) return 0;
+  if (!lds_dma_fits((size_t)M, (size_t)(N1 > N2 ? N1 : N2), 0)) return 0;
   const int cus = mrmt3_cu_count();
   const int t = ceil_div(N1, 256) * ceil_div(N2, 256);
   int s = cus / t;                                           // one workgroup per CU (128 KiB of LDS each)
@@ -364,7 +306,7 @@ static int t8_cus() {
 
 extern "C" int mrmt3_tn_group_ok(int M, int N1, int N2, int lda, int ldb, int ldc) {
   return M >= 1024 && N1 >= 256 && N2 >= 256 && N1 % 128 == 0 && N2 % 64 == 0 && lda % 8 == 0 && ldb % 8 == 0 &&
-         ldc % 4 == 0 && ((size_t)M + 128) * (size_t)(lda > ldb ? lda : ldb) * 2 < 0x7FFF0000ull;
+         ldc % 4 == 0 && lds_dma_fits((size_t)M + 128, (size_t)(lda > ldb ? lda : ldb), 0);
 }
 
 // Units of 128 token rows (two K steps).  For every candidate item length the gradients are cut into R_s token ranges
