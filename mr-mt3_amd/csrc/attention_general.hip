@@ -10,9 +10,6 @@
 
 namespace {
 
-template <typename T> __device__ __forceinline__ float ld1(const T* p);
-template <> __device__ __forceinline__ float ld1<float>(const float* p) { return *p; }
-template <> __device__ __forceinline__ float ld1<bf16_t>(const bf16_t* p) { return bf2f(*p); }
 template <typename T> __device__ __forceinline__ f32x4 ld4(const T* p);
 template <> __device__ __forceinline__ f32x4 ld4<float>(const float* p) { return *(const f32x4*)p; }
 template <> __device__ __forceinline__ f32x4 ld4<bf16_t>(const bf16_t* p) {
@@ -20,9 +17,6 @@ template <> __device__ __forceinline__ f32x4 ld4<bf16_t>(const bf16_t* p) {
   return f32x4{__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xFFFF0000u), __uint_as_float(w.y << 16),
                __uint_as_float(w.y & 0xFFFF0000u)};
 }
-template <typename T> __device__ __forceinline__ void st1(T* p, float v);
-template <> __device__ __forceinline__ void st1<float>(float* p, float v) { *p = v; }
-template <> __device__ __forceinline__ void st1<bf16_t>(bf16_t* p, float v) { *p = f2bf(v); }
 
 // element (q, key) of head-matrix bh kept?  (the generator of the bf16 kernels, one element at a time)
 __device__ __forceinline__ bool attn_keep1(const AttnDrop& d, unsigned drop_bh, int q, int key) {

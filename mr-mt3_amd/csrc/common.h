@@ -89,6 +89,13 @@ __device__ __forceinline__ unsigned pack_bf2(float lo, float hi) {
   typedef float f32x2_t __attribute__((ext_vector_type(2)));
   return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{lo, hi}, bf16x2_t));
 }
+// one element of an f32 or a bf16 buffer as f32 (decode.hip, attention_general.hip)
+template <typename T> __device__ __forceinline__ float ld1(const T* p);
+template <> __device__ __forceinline__ float ld1<float>(const float* p) { return *p; }
+template <> __device__ __forceinline__ float ld1<bf16_t>(const bf16_t* p) { return bf2f(*p); }
+template <typename T> __device__ __forceinline__ void st1(T* p, float v);
+template <> __device__ __forceinline__ void st1<float>(float* p, float v) { *p = v; }
+template <> __device__ __forceinline__ void st1<bf16_t>(bf16_t* p, float v) { *p = f2bf(v); }
 
 // ---- wave / block reductions (wave = 64) -----------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {

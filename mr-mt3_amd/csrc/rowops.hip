@@ -1032,7 +1032,7 @@ extern "C" int mrmt3_ce_fwd_bwd_reg(const float* logits, const int64_t* targets,
 // ------------------------------------------------------------------------------------------------
 // log-probability of one target per row (teacher-forced scoring; forward only).  One wave per row; the row (up to
 // 64 * TLP_REGS logits; longer rows are refused) stays in registers, so it is read once.  Same arithmetic and
-// summation order as the greedy decoder's tail (decode.hip dec_argmax<., true>): NaN-propagating maximum, exp(l - max)
+// summation order as the greedy decoder's tail (decode_tail.hip dec_argmax<., true>): NaN-propagating maximum, exp(l - max)
 // summed per lane in ascending column then the xor tree, (l[target] - max) - log(sum).
 // ------------------------------------------------------------------------------------------------
 #define TLP_REGS 32

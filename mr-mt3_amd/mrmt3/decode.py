@@ -1,4 +1,4 @@
-"""Greedy generation on the MI355X decoder (csrc/decode.hip) with the reference's output contract.
+"""Greedy generation on the MI355X decoder (csrc/decode.hip, decode_tail.hip, decode_grammar.hip) with the reference's output contract.
 
   * `T5ForConditionalGeneration.generate` (models/t5.py:251-302): batched; returns int64
     [B, 1 + steps] starting with token 0, finished rows padded with 0, stops when every row has
@@ -43,12 +43,12 @@ from . import lib
 from .grammar import ACTIVE_BYTES, EventGrammar, resolve as _grammar
 
 
-MAX_DECODE_BATCH = 256     # DEC_MAXB of csrc/decode.hip: sequences decoded together (one wave per row x sequence)
-MAX_BEAMS = 8              # BEAM_MAXK of csrc/decode.hip
-BEAM_HREC = 32             # int32 per group of the hypothesis record (csrc/decode.hip, include/mrmt3_hip.h)
+MAX_DECODE_BATCH = 256     # DEC_MAXB of csrc/decode.h: sequences decoded together (one wave per row x sequence)
+MAX_BEAMS = 8              # BEAM_MAXK of csrc/decode_tail.hip
+BEAM_HREC = 32             # int32 per group of the hypothesis record (csrc/decode_tail.hip, include/mrmt3_hip.h)
 
 
-MAX_SAMPLE_VOCAB = 2048   # 64 * LOGP_REGS of csrc/decode.hip: the sampled tail keeps a vocabulary row in one wave's registers
+MAX_SAMPLE_VOCAB = 2048   # 64 * LOGP_REGS of csrc/decode.h: the sampled tail keeps a vocabulary row in one wave's registers
 
 
 @dataclass(frozen=True)

@@ -3,7 +3,7 @@
 
 `EventGrammar` is the descriptor the device state machine reads (`mrmt3_grammar` of include/mrmt3_hip.h): the id ranges of a
 codec in MODEL ids (the 3 special tokens included), the longest time a shift run may reach and whether a row starts in the tie
-section.  The rules themselves live in csrc/decode.hip (`gram_push`, `gram_allowed`); tests/grammar_ref.py restates them on the
+section.  The rules themselves live in csrc/decode_grammar.hip (`gram_push`, `gram_allowed`); tests/grammar_ref.py restates them on the
 host.  `ACTIVE_BYTES` is the size of a row's `active` / `carry` bit set over (program, pitch): bit `program * 128 + pitch`.
 """
 from __future__ import annotations

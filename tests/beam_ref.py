@@ -1,4 +1,4 @@
-"""Host restatement (float64) of the beam search the decoder runs on the GPU (csrc/decode.hip dec_beam_select /
+"""Host restatement (float64) of the beam search the decoder runs on the GPU (csrc/decode_tail.hip dec_beam_select /
 dec_beam_finalize_kernel): HF 4.18 `beam_search` + `BeamSearchScorer` with early_stopping=False and one hypothesis kept,
 `max_length` counting new tokens.  Used by tests/test_beam_decode_{cpu,gpu}.py; not a test module itself.
 

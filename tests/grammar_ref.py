@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE ONLY: host restatement of the MT3 event grammar the decoder enforces on the device (csrc/decode.hip
+"""TEST INFRASTRUCTURE ONLY: host restatement of the MT3 event grammar the decoder enforces on the device (csrc/decode_grammar.hip
 `gram_push` / `gram_allowed`), next to tests/beam_ref.py and tests/sample_ref.py.  Plain Python sets and numpy;
 nothing here shares code with the kernel or with mrmt3/grammar.py: the id ranges come from the codec, the rules from the table.
 

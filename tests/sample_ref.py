@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE ONLY: host restatement of the decoder's sampling rule (csrc/decode.hip `sample_draw`), next
+"""TEST INFRASTRUCTURE ONLY: host restatement of the decoder's sampling rule (csrc/decode_tail.hip `sample_draw`), next
 to tests/beam_ref.py.  float64 over given f32 logits; nothing here shares code with the kernel.
 
 The rule, per row (HF 4.18 `sample()`: NoBadWords -> TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper ->

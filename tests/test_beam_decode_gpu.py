@@ -1,4 +1,4 @@
-"""Beam search and banned tokens on the MI355X decoder (csrc/decode.hip dec_beam_select / dec_beam_reorder /
+"""Beam search and banned tokens on the MI355X decoder (csrc/decode_tail.hip dec_beam_select / dec_beam_reorder /
 dec_beam_finalize_kernel, dec_argmax<true>), scored against the float64 host restatement of HF 4.18's beam search
 (tests/beam_ref.py) and the float64 teacher-forced decoder (oracle.t5_ref.decode_step_logits).
 

@@ -1,4 +1,4 @@
-"""Greedy decode (csrc/decode.hip) scored step by step: every step's lm_head logits, copied out of the decoder
+"""Greedy decode (csrc/decode.hip, the greedy tail in csrc/decode_tail.hip) scored step by step: every step's lm_head logits, copied out of the decoder
 (`Decoder.run(logits_out=...)`, mrmt3_decoder_logits), against a float64 teacher-forced reference run on the tokens the
 decoder itself emitted (`oracle.t5_ref.decode_step_logits`, cross-attention K/V = the decoder's own buffer, so only the
 token loop is under test).
