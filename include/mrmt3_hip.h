@@ -14,7 +14,9 @@
  * Conventions
  *  - Plain C: pointers are raw DEVICE pointers into caller-owned allocations (torch tensors); sizes
  *    and strides are explicit, in ELEMENTS unless a name ends in _bytes.  No torch types.
- *  - dtype codes: MRMT3_F32 (float) or MRMT3_BF16 (raw bfloat16 bits, uint16_t).
+ *  - dtype codes: MRMT3_F32 (float) or MRMT3_BF16 (raw bfloat16 bits, uint16_t).  The row, embedding, loss and layout
+ *    entry points (norm, geglu, addpos, dropmask_cast, ce, lmhead, cast, transpose) refuse any other code with
+ *    MRMT3_ERR_INVALID_ARG before they launch or write anything, also for an operand that is NULL: pass MRMT3_F32 there.
  *  - Every call is asynchronous on the hipStream_t passed as `void* stream`, re-entrant across
  *    streams, never synchronises the device and never allocates (graph-capture safe).  The only
  *    library-owned objects are the opaque mrmt3_decoder handles.

@@ -169,7 +169,7 @@ __host__ inline DropCfg make_drop(float p, unsigned long long seed, unsigned str
 // instructions; with the activations served from the Infinity Cache the GEGLU kernels were as much VALU as memory).
 // Saturates cleanly (exp -> inf gives 1, exp -> 0 gives -1); absolute error <= 2e-7.
 // Every a * b + c of the activation helpers is an EXPLICIT fmaf and contraction is off around them (as it is at the top of
-// rowops.hip / gemm_rows.hip): the fused kernels promise the SAME BITS as the element-wise kernels they replace, and which
+// rowops.hip and its four siblings, and of gemm_rows.hip): the fused kernels promise the SAME BITS as the element-wise kernels they replace, and which
 // a * b + c becomes an FMA is otherwise the compiler's choice per call site — it differed between two files as soon as the
 // build flags changed.  Written out, the helpers are also shorter than what either setting gave: gelu_new 9 vector
 // instructions + v_exp + v_rcp (contraction off, no fmaf: 13 + 2), gelu_new with its derivative 17 + 2 (was 29 + 2); the
@@ -200,8 +200,38 @@ __device__ __forceinline__ void gelu_new_fd(float x, float* f, float* d) {
   *d = fmaf(hx * q * c, w, p);
 }
 
-// norm-weight gradient: per-workgroup partial rows are summed by DW_CHUNKS row chunks (rowops.hip: dw_reduce_body);
-// the workspace of a norm site is [partial rows | DW_CHUNKS chunk sums][cols] f32 + one arrival counter per 64 columns
+// norm-weight gradient: per-workgroup partial rows are summed by DW_CHUNKS row chunks (rowops.hip: dw_reduce_body; the
+// fused norm backward of gemm_rows.hip leaves the same rows); the workspace of a norm site is
+// [partial rows | DW_CHUNKS chunk sums][cols] f32 + one arrival counter per 64 columns
 #define DW_CHUNKS 16
 
 __host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+// workgroups of 256 lanes for a grid-stride loop over n_items (rowops / embed / optim / layout.hip): at most 4096
+static inline int ew_blocks(size_t n_items) {
+  size_t b = (n_items + 255) / 256;
+  return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
+}
+
+// ---- run-time dtype code / width -> compile-time type / constant (the row, loss and layout entry points) ---------------
+// mr_dtype(code, f) calls the generic lambda f with a tag (`typename decltype(tag)::type` is the element type) for MRMT3_F32
+// and MRMT3_BF16 and returns true; for any other code it calls nothing and returns false.  mr_const<A, B, ...>(v, f) does
+// the same for an int among a fixed list (`decltype(tag)::value`).  Nested calls instantiate the cross product of kernels.
+template <typename T> struct MrType { typedef T type; };
+template <int N> struct MrInt { static constexpr int value = N; };
+template <typename F> static inline bool mr_dtype(int code, F&& f) {
+  if (code == MRMT3_F32) { f(MrType<float>{}); return true; }
+  if (code == MRMT3_BF16) { f(MrType<bf16_t>{}); return true; }
+  return false;
+}
+template <int... Ns, typename F> static inline bool mr_const(int v, F&& f) {
+  return ((v == Ns ? (f(MrInt<Ns>{}), true) : false) || ...);
+}
+// bytes per element of a dtype code, 0 for a code that is neither
+static inline size_t mr_dtype_bytes(int code) {
+  size_t b = 0;
+  mr_dtype(code, [&](auto t) { b = sizeof(typename decltype(t)::type); });
+  return b;
+}
+// an entry point refuses an unknown dtype code before it launches or writes anything, whether or not the operand is null
+#define MR_CHECK_DTYPE(who, arg) \
+  MR_CHECK_ARG(mr_dtype_bytes(arg) != 0, "%s: %s = %d is neither MRMT3_F32 nor MRMT3_BF16", who, #arg, (int)(arg))

@@ -1,4 +1,4 @@
-// Host-side planner of the grouped optimizer step (mrmt3_opt_ranges_plan): plain C++, no HIP — csrc/rowops.hip includes it,
+// Host-side planner of the grouped optimizer step (mrmt3_opt_ranges_plan): plain C++, no HIP — csrc/optim.hip alone includes it,
 // and a CPU build with a main() of its own can too (a sanitizer run of the planner needs no GPU).
 //
 // The caller describes the trainable part of the flat parameter buffer as sorted, disjoint element ranges, each with its own

@@ -1,5 +1,5 @@
-"""Constructions, fp64 references and checkers of the per-element tests of the row-wise kernels of csrc/rowops.hip
-(tests/test_exact_rows_gpu.py; proven on the CPU by tests/test_exact_rows_cpu.py).  Plain torch on whatever device the
+"""Constructions, fp64 references and checkers of the per-element tests of the row-wise kernels of csrc/rowops.hip, embed.hip,
+loss.hip, optim.hip and layout.hip (tests/test_exact_rows_gpu.py; proven on the CPU by tests/test_exact_rows_cpu.py).  Plain torch on whatever device the
 tensors live on; nothing here touches the library.
 
 A. Data movement: position-coded operands whose every value is exact in bf16, so a copy, a cast, a transpose or a gather
@@ -10,7 +10,7 @@ C. RMSNorm, gated GELU, cross-entropy, token log-probability and AdamW against f
    EVERY element held to a bound derived from the kernel's operation chain.  All bounds are worst-case counts in units of
    u = 2^-24 (the unit roundoff of f32: one correctly rounded operation errs by at most u |result|; the hardware's exp, log
    and rsqrt are taken at one ulp = 2u) and of the project's own constants.  `TREE(n)` is the depth of a sum of n terms
-   per lane followed by the 64-lane xor tree, the shape every row reduction of rowops.hip has.
+   per lane followed by the 64-lane xor tree, the shape every row reduction of those sources has.
 """
 import math
 
@@ -22,9 +22,9 @@ U = 2.0 ** -24                          # unit roundoff of f32
 BF16_MIN_NORMAL_EXP = -126
 F32_MIN_NORMAL = 2.0 ** -126            # results below it may be flushed or keep only a few bits
 FAST_TANH_T = 2e-7                      # csrc/common.h: "fast_tanh ... absolute error <= 2e-7"
-EW_GRID = 256 * 4096                    # rowops.hip ew_blocks(): a launch has at most 4096 workgroups of 256 lanes
+EW_GRID = 256 * 4096                    # common.h ew_blocks(): a launch has at most 4096 workgroups of 256 lanes
 EW_SIZES = (4, 4 * (EW_GRID + 3))       # one quad; a grid-stride loop that wraps (with a ragged last pass)
-EB_CHUNK = 32                           # rowops.hip: sorted rows summed per workgroup of the embedding gradient
+EB_CHUNK = 32                           # embed.hip: sorted rows summed per workgroup of the embedding gradient
 
 
 def TREE(n_per_lane):
@@ -155,7 +155,7 @@ def check_bf16_conversion(got, src, what, subnormal=False):
 
 
 def token_ids(labels, seq_len, shift, start_id, pad_id, vocab):
-    """rowops.hip token_at(): the id row r embeds (shifted right inside its sequence, -100 -> pad, clamped to the table)."""
+    """embed.hip token_at(): the id row r embeds (shifted right inside its sequence, -100 -> pad, clamped to the table)."""
     ids = labels.reshape(-1).clone()
     if shift:
         prev = torch.cat([ids[:1], ids[:-1]])
@@ -522,7 +522,7 @@ def logits_case(rows, V, first_kind=0, seed=0, device="cpu", ignore_every=5, ins
 
 def ce_reference(logits, targets, weighted, inst_lo, inst_hi, grad_scale=1.0, eps=0.0, z=0.0, grad_bf16=False):
     """fp64 loss, NLL and dlogits of tasks/mt3_net.py's (weighted) cross-entropy with label smoothing eps and z-loss z
-    (rowops.hip, REG): per scored row r = (1 - eps) nll + eps (lse - mean l) + z lse^2, loss = sum w r / denom,
+    (loss.hip, REG): per scored row r = (1 - eps) nll + eps (lse - mean l) + z lse^2, loss = sum w r / denom,
     dlogits = g0 (p (1 + 2 z lse) - (1 - eps) [j = t] - eps / V), g0 = w grad_scale / denom; ignored rows: exactly zero.
 
     Bounds of the f32 kernels (mx = row maximum, se = sum exp(l - mx), p = exp(l - mx) / se, A = sum_j p_j |l_j - mx|):
@@ -615,7 +615,7 @@ TLP_ROWS = [1, 6]
 
 def logprob_reference(logits, targets, ignore_index=-100):
     """fp64 log_softmax(l)[t] (0 at an ignored row, NaN for a row that holds a NaN) and the bound of
-    rowops.hip token_logprob = (l_t - mx) - log(se): the subtraction u |l_t - mx|, se as in ce_reference with a chain of
+    loss.hip token_logprob = (l_t - mx) - log(se): the subtraction u |l_t - mx|, se as in ce_reference with a chain of
     32 terms per lane and the wave tree, log one ulp, the last subtraction u |result|:
       |d| <= u (2 |l_t - mx| + A + TREE(32) + 4 + 2 |log se| + |result|)."""
     l = logits.double()
@@ -668,7 +668,7 @@ def adam_case(n, step0, n_steps, device="cpu", seed=0):
 
 def adam_reference(p0, m0, v0, grads, step0, wd, gscale):
     """torch.optim.AdamW on float64 copies, given the SAME numbers the kernel is given (the f32 values of lr, the betas,
-    eps, the weight decay and grad_scale), and per-element bounds of rowops.hip adamw_kernel carried along the steps:
+    eps, the weight decay and grad_scale), and per-element bounds of optim.hip adamw_kernel carried along the steps:
       gr = g gscale                                   u |gr|
       m' = m + (gr - m) c1   (c1 = 1 - beta1, exact)  em' = beta1 em + u (c1 |gr| + 2 c1 |gr - m| + |m'|)
       v' = v beta2 + (c2 gr) gr                       relative: rv' = rv + 5u   (a sum of non-negative terms; below
@@ -704,7 +704,7 @@ def adam_reference(p0, m0, v0, grads, step0, wd, gscale):
 
 
 def adam_restated(p0, m0, v0, grads, step0, wd, gscale, fault=None):
-    """rowops.hip adamw_kernel in torch f32.  Faults: 'no_bias2' (the second-moment bias correction left out; it matters in the
+    """optim.hip adamw_kernel in torch f32.  Faults: 'no_bias2' (the second-moment bias correction left out; it matters in the
     first steps only), 'eps_inside' (eps added under the square root)."""
     lr, b1, b2 = torch.tensor(ADAM["lr"], dtype=torch.float32), torch.tensor(ADAM["beta1"], dtype=torch.float32), \
         torch.tensor(ADAM["beta2"], dtype=torch.float32)
@@ -729,5 +729,5 @@ def adam_restated(p0, m0, v0, grads, step0, wd, gscale, fault=None):
 
 
 def adam_decay_f32(wd):
-    """decay = 1 - lr * wd as the kernel forms it in f32 (a product and a subtraction; contraction is off in rowops.hip)."""
+    """decay = 1 - lr * wd as the kernel forms it in f32 (a product and a subtraction; contraction is off in optim.hip)."""
     return 1.0 - torch.tensor(ADAM["lr"], dtype=torch.float32) * torch.tensor(wd, dtype=torch.float32)

@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE ONLY: float64 restatement of the cross-entropy with label smoothing and z-loss (csrc/rowops.hip
+"""TEST INFRASTRUCTURE ONLY: float64 restatement of the cross-entropy with label smoothing and z-loss (csrc/loss.hip
 `ce_wave_kernel<., ., true>` / `ce_kernel<., true>`), next to tests/sample_ref.py.  Plain torch on the CPU;
 nothing here shares code with the kernels.
 

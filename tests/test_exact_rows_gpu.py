@@ -1,4 +1,4 @@
-"""Per-element tests of the row-wise kernels of csrc/rowops.hip on a real MI355X (constructions, fp64 references and bounds:
+"""Per-element tests of the row-wise kernels of csrc/rowops.hip, embed.hip, loss.hip, optim.hip and layout.hip on a real MI355X (constructions, fp64 references and bounds:
 tests/_exact_rows.py, proven on the CPU by tests/test_exact_rows_cpu.py).
 
 A. Data movement and the f32 -> bf16 conversion: bit-exact on position-coded operands, the dropout mask of every site equal
@@ -532,7 +532,7 @@ def test_cross_entropy_per_element_against_fp64(dev, rows, V):
 
 def test_cross_entropy_at_24577_rows_where_a_wave_walks_three_rows_and_the_last_walk_is_cut_short(dev):
     rows, V = er.CE_BIG
-    assert rows // (4 * 2048) == 3 and rows % 12 != 0                   # rowops.hip ce_rows_per_wave
+    assert rows // (4 * 2048) == 3 and rows % 12 != 0                   # loss.hip ce_rows_per_wave
     worst = dict(loss=0.0, nll=0.0)
     _ce_check(dev, rows, V, 0, False, F32, False, worst)
     for k in ("dlogits", "loss"):

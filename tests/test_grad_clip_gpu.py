@@ -198,7 +198,7 @@ def test_coefficient_one_is_the_unclipped_step_bit_for_bit(dev, monkeypatch):
 
 @pytest.mark.parametrize("scale", [0.25, 1.0 / 3.0])
 def test_abi_clipped_step_with_coefficient_one_equals_adamw_step_bitwise(dev, scale):
-    """adamw_step(stat=[., 1, 0]) (adamw_kernel<true>) against adamw_step() (adamw_kernel<false>).  Also with an inexact grad_scale (1/3: three micro-batches or ranks): rowops.hip is compiled with fp contract off, so
+    """adamw_step(stat=[., 1, 0]) (adamw_kernel<true>) against adamw_step() (adamw_kernel<false>).  Also with an inexact grad_scale (1/3: three micro-batches or ranks): optim.hip is compiled with fp contract off, so
     neither kernel fuses g * scale into the next operation and the extra `* 1.0f` changes no bit."""
     from mrmt3 import lib
     n = 4 * 70001

@@ -945,7 +945,7 @@ def test_transpose_cast(dev):
 
 
 def test_transpose_batched_even_and_odd_shapes(dev):
-    """One launch, several matrices laid out back to back in flat buffers.  Which path each takes (csrc/rowops.hip
+    """One launch, several matrices laid out back to back in flat buffers.  Which path each takes (csrc/layout.hip
     transpose_batched_kernel): (384, 512) at offset 0 moves 16 bytes per lane; (70, 130) has even dimensions and an even
     offset and moves pairs, with overhanging tiles; (33, 7) has odd dimensions and moves single elements.  Its 231 elements
     leave EVERY later matrix at an odd offset, so (64, 64), (5, 1000), (136, 72), (2048, 512) and (72, 200) move single
