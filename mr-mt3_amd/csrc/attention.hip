@@ -29,9 +29,6 @@
 // ------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------
-#define KV_STAGES 3
-#define KV_STAGE_BYTES 16384   // K tile 8 KiB + V tile 8 KiB
-
 static int attn_tile_mode() { return MR_KNOB("MRMT3_ATTN_TILE_MODE", 5); }      // tuning only
 
 // One template per kernel serves dense and packed rows: VL picks, at compile time, how the prologue finds the workgroup's row,
@@ -49,57 +46,30 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(AttnParams P, AttnVarl
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int uw = __builtin_amdgcn_readfirstlane(wave);
   const int fr = lane & 15, fg = lane >> 4, fq = fr >> 2, fp = lane & 3;
-  int tile_, h, b;
-  int Lq, Lk;
-  size_t qr0, kr0;            // first row of this (batch) row's queries / keys
-  size_t st0;                 // first lse element of this (row, head)
-  if constexpr (VL == 0) {
-    attn_tile(tile_, h, b, P.tile_mode);
-    Lq = P.Lq; Lk = P.Lk;
-    qr0 = (size_t)b * Lq; kr0 = (size_t)b * Lk;
-    st0 = ((size_t)b * P.H + h) * Lq;
-  } else {
-    const int e = blockIdx.x / P.H;
-    h = blockIdx.x % P.H;
-    b = V.tiles[2 + 2 * e];
-    tile_ = V.tiles[3 + 2 * e];
-    if (b < 0) {
-      int r0, r1;
-      if (varlen_tail_rows(V, e, r0, r1)) {
+  AttnRow R;
+  if (!attn_locate<VL>(P, V, R, [&](int h, int r0, int r1) {
         varlen_zero_rows(P.out, P.ldo, h, r0, r1);
         varlen_zero_rows(P.o_lo_out, P.ldo, h, r0, r1);
         if (P.lse)
           for (int r = r0 + tid; r < r1; r += 256) P.lse[(size_t)h * V.Tcap + r] = 0.f;
-      }
-      return;
-    }
-    const int o0 = V.row_off[b];
-    Lq = V.row_off[b + 1] - o0;
-    qr0 = (size_t)o0;
-    if constexpr (VL == 1) { Lk = Lq; kr0 = qr0; }
-    else { Lk = P.Lk; kr0 = (size_t)b * P.Lk; }
-    st0 = (size_t)h * V.Tcap + o0;
-  }
+      }))
+    return;
+  const int tile_ = R.tile, h = R.h, b = R.b, Lq = R.Lq, Lk = R.Lk;
+  const size_t qr0 = R.qr0, kr0 = R.kr0, st0 = R.st0;
   const bf16_t* qb = P.q + qr0 * P.ldq + h * HD;
   const bf16_t* kb = P.k + kr0 * P.ldk + h * HD;
   const bf16_t* vb = P.v + kr0 * P.ldv + h * HD;
   const unsigned drop_bh = P.drop.seed + step_salt(P.drop.step) + (unsigned)(b * P.H + h) * DROP_CB;
   const int n_qt = ceil_div(Lq, 64 * RT);
-  const __amdgpu_buffer_rsrc_t kres = rows_rsrc(kb, Lk, P.ldk), vres = rows_rsrc(vb, Lk, P.ldv);
-  const unsigned k_lane = rows8_lane_off(P.ldk, lane), v_lane = rows8_lane_off(P.ldv, lane);
+  const KvSrc kv = kv_src(kb, vb, Lk, P.ldk, P.ldv, lane);
   // 16-byte output rows need 16-byte aligned rows (kernel-uniform)
   const bool wide_rows = (P.ldo & 7) == 0 && (((uintptr_t)P.out | (uintptr_t)P.o_lo_out) & 15) == 0;
 
-  // causal: query tile t needs 2(t+1) key tiles, so a workgroup takes the PAIR (n_qt-1-t, t) — every workgroup
-  // of the launch then does the same amount of work and the launch has no tail of heavy tiles
+  // causal: the PAIR of query tiles (n_qt-1-t, t), see attn_pass_tile
 #pragma nounroll
   for (int pass = 0; pass < (PAIR ? 2 : 1); ++pass) {
-  int q_tile = tile_;
-  if (PAIR) {
-    q_tile = pass == 0 ? n_qt - 1 - tile_ : tile_;
-    if (pass == 1 && 2 * tile_ == n_qt - 1) break;
-    if (pass == 1) __syncthreads();      // every wave is done reading the previous tile's LDS stages
-  }
+  int q_tile;
+  if (!attn_pass_tile<PAIR>(pass, tile_, n_qt, true, q_tile)) break;
   const int q0 = q_tile * (64 * RT);
 
   // Q fragments (B operand): lane holds Q[q = qrow(qt)][d = 32ks + 8g .. +7]
@@ -126,29 +96,13 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(AttnParams P, AttnVarl
 
   int n_kv = ceil_div(Lk, 64);
   if (P.causal) n_kv = min(n_kv, (min(q0 + 64 * RT - 1, Lq - 1)) / 64 + 1);
-  // each wave stages 16 rows of K and of V per tile (2 + 2 wave-instructions); `on` = false turns the tile into
-  // four zero-fills that never leave the CU, which keeps the vmcnt arithmetic of the loop uniform
-  auto stage = [&](int buf, int kv0, bool on) {
-    unsigned char* base = lds + buf * KV_STAGE_BYTES;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int t = uw * 2 + i;
-      blds_rows8(kres, k_lane, on ? (kv0 + t * 8) * P.ldk * 2 : LDS_DMA_OOB, base + t * 1024);
-      blds_rows8(vres, v_lane, on ? (kv0 + t * 8) * P.ldv * 2 : LDS_DMA_OOB, base + 8192 + t * 1024);
-    }
-  };
-  stage(0, 0, true);
-  stage(1, 64, n_kv > 1);
+  kv_prime(lds, kv, uw, n_kv);
   int cur = 0;
 
   for (int j = 0; j < n_kv; ++j) {
     const int kv0 = j * 64;
-    VMCNT(4);                                       // tile j landed (tile j+1 may still be in flight)
-    __builtin_amdgcn_s_barrier();
-    stage(cur == 0 ? 2 : cur - 1, kv0 + 128, j + 2 < n_kv);
-    const unsigned char* lk = lds + cur * KV_STAGE_BYTES;
+    const unsigned char* lk = kv_step(lds, kv, uw, cur, j, n_kv);
     const unsigned char* lv = lk + 8192;
-    cur = cur == KV_STAGES - 1 ? 0 : cur + 1;
 
     // (causal: the last key tile of a query tile lies entirely above the 32 rows of waves 0 and 1.  They run it anyway,
     // fully masked: a per-wave skip made the accumulators loop-carried through two paths and hipcc copied all of them
@@ -234,7 +188,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(AttnParams P, AttnVarl
       }
     }
   }
-  VMCNT(0);      // the switched-off prefetches of the last two iterations still write their zeros
+  VMCNT(0);      // (kv_step: the switched-off prefetches)
 
 #pragma unroll
   for (int qt = 0; qt < RT; ++qt) {
@@ -292,47 +246,23 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(AttnParams P, AttnVarl
 #define QD_STAGES 4
 #define QD_STAGE_BYTES 8448   // Q 4 KiB + dO 4 KiB + 64 floats
 
-// Packed (VL != 0, PAIR = false, RT = 1): self-attention takes the (row, 64-key tile) entries of the tile list in reverse order
-// (key tile t of a causal row is seen by the queries from 64 t on: the low tiles are the heavy ones); cross-attention keeps the
-// dense grid over the Lc keys of every row and loops over that row's packed queries (none for an empty row: zeros).
+// Packed (VL != 0, PAIR = false, RT = 1): self-attention takes the (row, 64-key tile) entries of the tile list in reverse order,
+// cross-attention keeps the dense grid over the Lc keys of every row (attn_locate, KEY_TILES) and loops over that row's packed
+// queries (none for an empty row: zeros).
 template <bool PAIR, bool DROP, int RT = 2, int VL = 0>
 __global__ __launch_bounds__(256, RT == 1 ? 3 : 2) void attn_bwd_dkdv_kernel(AttnParams P, AttnVarlen V) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[QD_STAGES * QD_STAGE_BYTES];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int uw = __builtin_amdgcn_readfirstlane(wave);
   const int fr = lane & 15, fg = lane >> 4, fq = fr >> 2, fp = lane & 3;
-  int tile_, h, b;
-  int Lq, Lk;
-  size_t qr0, kr0, st0;
-  if constexpr (VL == 0) {
-    attn_tile(tile_, h, b, P.tile_mode);
-    Lq = P.Lq; Lk = P.Lk;
-    qr0 = (size_t)b * Lq; kr0 = (size_t)b * Lk;
-    st0 = ((size_t)b * P.H + h) * Lq;
-  } else {
-    if constexpr (VL == 2) {
-      attn_tile(tile_, h, b, P.tile_mode);
-    } else {
-      const int e = V.n_ent - 1 - (int)(blockIdx.x / P.H);
-      h = blockIdx.x % P.H;
-      b = V.tiles[2 + 2 * e];
-      tile_ = V.tiles[3 + 2 * e];
-      if (b < 0) {
-        int r0, r1;
-        if (varlen_tail_rows(V, e, r0, r1)) {
-          varlen_zero_rows(P.dk, P.lddk, h, r0, r1);
-          varlen_zero_rows(P.dv, P.lddv, h, r0, r1);
-        }
-        return;
-      }
-    }
-    const int o0 = V.row_off[b];
-    Lq = V.row_off[b + 1] - o0;
-    qr0 = (size_t)o0;
-    if constexpr (VL == 1) { Lk = Lq; kr0 = qr0; }
-    else { Lk = P.Lk; kr0 = (size_t)b * P.Lk; }
-    st0 = Lq > 0 ? (size_t)h * V.Tcap + o0 : 0;     // (an empty row reads no statistics; keep the address inside the buffer)
-  }
+  AttnRow R;
+  if (!attn_locate<VL, true>(P, V, R, [&](int h, int r0, int r1) {
+        varlen_zero_rows(P.dk, P.lddk, h, r0, r1);
+        varlen_zero_rows(P.dv, P.lddv, h, r0, r1);
+      }))
+    return;
+  const int tile_ = R.tile, h = R.h, b = R.b, Lq = R.Lq, Lk = R.Lk;
+  const size_t qr0 = R.qr0, kr0 = R.kr0, st0 = R.st0;
   const bf16_t* qb = P.q + qr0 * P.ldq + h * HD;
   const bf16_t* dob = P.d_o + qr0 * P.lddo + h * HD;
   const bf16_t* kb = P.k + kr0 * P.ldk + h * HD;
@@ -347,15 +277,11 @@ __global__ __launch_bounds__(256, RT == 1 ? 3 : 2) void attn_bwd_dkdv_kernel(Att
   const __amdgpu_buffer_rsrc_t qres = rows_rsrc(qb, Lq_rs, P.ldq), dores = rows_rsrc(dob, Lq_rs, P.lddo);
   const unsigned q_lane = rows8_lane_off(P.ldq, lane), do_lane = rows8_lane_off(P.lddo, lane);
 
-  // causal: key tile t is seen by the queries from 128 t on, so the pair (t, n_kt-1-t) balances the launch
+  // causal: the pair of key tiles (t, n_kt-1-t), see attn_pass_tile
 #pragma nounroll
   for (int pass = 0; pass < (PAIR ? 2 : 1); ++pass) {
-  int k_tile = tile_;
-  if (PAIR) {
-    k_tile = pass == 0 ? tile_ : n_kt - 1 - tile_;
-    if (pass == 1 && 2 * tile_ == n_kt - 1) break;
-    if (pass == 1) __syncthreads();
-  }
+  int k_tile;
+  if (!attn_pass_tile<PAIR>(pass, tile_, n_kt, false, k_tile)) break;
   const int k0 = k_tile * (64 * RT);
 
   bf16x8 kf[RT][2], vf[RT][2];
@@ -445,16 +371,8 @@ __global__ __launch_bounds__(256, RT == 1 ? 3 : 2) void attn_bwd_dkdv_kernel(Att
           }
         }
         float pk[4] = {pv[0], pv[1], pv[2], pv[3]}, dk_[4] = {dp[0], dp[1], dp[2], dp[3]};
-        if (DROP && P.drop.thresh8) {    // run-time test on purpose, see the forward kernel
-          // this lane's word: query (fp-th of its quad's four), key group key >> 2; the quad's other three by DPP
-          const unsigned w = mix24(drop_k[nt] + (unsigned)(qb0 + qt * 16) * DROP_CQ);
-          const bool k0_ = (quad_word<0>(w) & drop_bmask) >= drop_bthr, k1_ = (quad_word<1>(w) & drop_bmask) >= drop_bthr;
-          const bool k2_ = (quad_word<2>(w) & drop_bmask) >= drop_bthr, k3_ = (quad_word<3>(w) & drop_bmask) >= drop_bthr;
-          pk[0] = k0_ ? pk[0] : 0.f; dk_[0] = k0_ ? dk_[0] : 0.f;
-          pk[1] = k1_ ? pk[1] : 0.f; dk_[1] = k1_ ? dk_[1] : 0.f;
-          pk[2] = k2_ ? pk[2] : 0.f; dk_[2] = k2_ ? dk_[2] : 0.f;
-          pk[3] = k3_ ? pk[3] : 0.f; dk_[3] = k3_ ? dk_[3] : 0.f;
-        }
+        if (DROP && P.drop.thresh8)      // run-time test on purpose, see the forward kernel
+          drop_quad(mix24(drop_k[nt] + (unsigned)(qb0 + qt * 16) * DROP_CQ), drop_bmask, drop_bthr, pk, dk_);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           pd[qt][nt][r] = pk[r];                                           // keep scale: applied to dV at the end
@@ -487,9 +405,9 @@ __global__ __launch_bounds__(256, RT == 1 ? 3 : 2) void attn_bwd_dkdv_kernel(Att
     bf16_t* dvrow = P.dv + (kr0 + key[nt]) * P.lddv + h * HD;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
-      f32x4 a = dkT[nt][dt], c = dvT[nt][dt] * P.drop.scale;
-      *(u32x2*)(dkrow + dt * 16 + fg * 4) = u32x2{pack_bf2(a[0], a[1]), pack_bf2(a[2], a[3])};
-      *(u32x2*)(dvrow + dt * 16 + fg * 4) = u32x2{pack_bf2(c[0], c[1]), pack_bf2(c[2], c[3])};
+      const f32x4 c = dvT[nt][dt] * P.drop.scale;
+      store_row_bf16(dkrow, dt, fg, dkT[nt][dt]);
+      store_row_bf16(dvrow, dt, fg, c);
     }
   }
   }  // pass
@@ -509,52 +427,27 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(AttnParams P, AttnV
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int uw = __builtin_amdgcn_readfirstlane(wave);
   const int fr = lane & 15, fg = lane >> 4, fq = fr >> 2, fp = lane & 3;
-  int tile_, h, b;
-  int Lq, Lk;
-  size_t qr0, kr0, st0;
-  if constexpr (VL == 0) {
-    attn_tile(tile_, h, b, P.tile_mode);
-    Lq = P.Lq; Lk = P.Lk;
-    qr0 = (size_t)b * Lq; kr0 = (size_t)b * Lk;
-    st0 = ((size_t)b * P.H + h) * Lq;
-  } else {
-    const int e = blockIdx.x / P.H;
-    h = blockIdx.x % P.H;
-    b = V.tiles[2 + 2 * e];
-    tile_ = V.tiles[3 + 2 * e];
-    if (b < 0) {
-      int r0, r1;
-      if (varlen_tail_rows(V, e, r0, r1)) {
+  AttnRow R;
+  if (!attn_locate<VL>(P, V, R, [&](int h, int r0, int r1) {
         varlen_zero_rows(P.dq, P.lddq, h, r0, r1);
         for (int r = r0 + tid; r < r1; r += 256) P.delta[(size_t)h * V.Tcap + r] = 0.f;
-      }
-      return;
-    }
-    const int o0 = V.row_off[b];
-    Lq = V.row_off[b + 1] - o0;
-    qr0 = (size_t)o0;
-    if constexpr (VL == 1) { Lk = Lq; kr0 = qr0; }
-    else { Lk = P.Lk; kr0 = (size_t)b * P.Lk; }
-    st0 = (size_t)h * V.Tcap + o0;
-  }
+      }))
+    return;
+  const int tile_ = R.tile, h = R.h, b = R.b, Lq = R.Lq, Lk = R.Lk;
+  const size_t qr0 = R.qr0, kr0 = R.kr0, st0 = R.st0;
   const bf16_t* qb = P.q + qr0 * P.ldq + h * HD;
   const bf16_t* dob = P.d_o + qr0 * P.lddo + h * HD;
   const bf16_t* kb = P.k + kr0 * P.ldk + h * HD;
   const bf16_t* vb = P.v + kr0 * P.ldv + h * HD;
   const unsigned drop_bh = P.drop.seed + step_salt(P.drop.step) + (unsigned)(b * P.H + h) * DROP_CB;
   const int n_qt = ceil_div(Lq, 64 * RT);
-  const __amdgpu_buffer_rsrc_t kres = rows_rsrc(kb, Lk, P.ldk), vres = rows_rsrc(vb, Lk, P.ldv);
-  const unsigned k_lane = rows8_lane_off(P.ldk, lane), v_lane = rows8_lane_off(P.ldv, lane);
+  const KvSrc kv = kv_src(kb, vb, Lk, P.ldk, P.ldv, lane);
 
   // causal: the pair of query tiles (n_qt-1-t, t), as in the forward kernel
 #pragma nounroll
   for (int pass = 0; pass < (PAIR ? 2 : 1); ++pass) {
-  int q_tile = tile_;
-  if (PAIR) {
-    q_tile = pass == 0 ? n_qt - 1 - tile_ : tile_;
-    if (pass == 1 && 2 * tile_ == n_qt - 1) break;
-    if (pass == 1) __syncthreads();
-  }
+  int q_tile;
+  if (!attn_pass_tile<PAIR>(pass, tile_, n_qt, true, q_tile)) break;
   const int q0 = q_tile * (64 * RT);
   // (per pass, the lane's coordinates are re-derived from an opaque copy of the lane id: everything that depends only on the
   // lane is otherwise hoisted out of the pass loop and held across both passes in registers of its own — at the 168 registers
@@ -607,27 +500,13 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(AttnParams P, AttnV
 
   int n_kv = ceil_div(Lk, 64);
   if (P.causal) n_kv = min(n_kv, (min(q0 + 64 * RT - 1, Lq - 1)) / 64 + 1);
-  auto stage = [&](int buf, int kv0, bool on) {      // as in the forward kernel
-    unsigned char* base = lds + buf * KV_STAGE_BYTES;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int t = uw * 2 + i;
-      blds_rows8(kres, k_lane, on ? (kv0 + t * 8) * P.ldk * 2 : LDS_DMA_OOB, base + t * 1024);
-      blds_rows8(vres, v_lane, on ? (kv0 + t * 8) * P.ldv * 2 : LDS_DMA_OOB, base + 8192 + t * 1024);
-    }
-  };
-  stage(0, 0, true);
-  stage(1, 64, n_kv > 1);
+  kv_prime(lds, kv, uw, n_kv);
   int cur = 0;
 
   for (int j = 0; j < n_kv; ++j) {
     const int kv0 = j * 64;
-    VMCNT(4);
-    __builtin_amdgcn_s_barrier();
-    stage(cur == 0 ? 2 : cur - 1, kv0 + 128, j + 2 < n_kv);
-    const unsigned char* lk = lds + cur * KV_STAGE_BYTES;
+    const unsigned char* lk = kv_step(lds, kv, uw, cur, j, n_kv);
     const unsigned char* lv = lk + 8192;
-    cur = cur == KV_STAGES - 1 ? 0 : cur + 1;
     // (no per-wave skip of the fully masked last causal tile: see the forward kernel)
     const bool need_mask = (kv0 + 64 > Lk) || (P.causal && kv0 + 63 > q0 + uw * (16 * RT));
     f32x4 dsT[RT][4];  // [qt][kt] : dS^T[key = kt*16+4g+r][q = fr]
@@ -689,10 +568,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(AttnParams P, AttnV
     if (qr >= Lq) continue;
     bf16_t* row = P.dq + (qr0 + qr) * P.lddq + h * HD;
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      f32x4 a = dqT[qt][dt];
-      *(u32x2*)(row + dt * 16 + fg * 4) = u32x2{pack_bf2(a[0], a[1]), pack_bf2(a[2], a[3])};
-    }
+    for (int dt = 0; dt < 4; ++dt) store_row_bf16(row, dt, fg, dqT[qt][dt]);
   }
   }  // pass
 }
@@ -738,6 +614,42 @@ static AttnParams attn_bwd_params(const void* q, int ldq, const void* k, int ldk
   return P;
 }
 
+// The one launch ladder of the three flash kernels: (pair, drop, RT, VL) -> the instantiation.  Five shapes exist per kernel and
+// dropout switch — paired 128-row tiles (PAIR implies RT = 2, VL = 0), unpaired 128-row tiles, 64-row tiles, packed self- and
+// packed cross-attention (VL != 0 implies RT = 1) — 30 instantiations in all; any other combination is refused.
+enum AttnKernel { ATTN_FWD, ATTN_DQ, ATTN_DKDV };
+template <AttnKernel K, bool PAIR, bool DROP, int RT, int VL>
+static void attn_launch_as(dim3 grid, hipStream_t s, const AttnParams& P, const AttnVarlen& V) {
+  if constexpr (K == ATTN_FWD) hipLaunchKernelGGL((attn_fwd_kernel<PAIR, DROP, RT, VL>), grid, dim3(256), 0, s, P, V);
+  else if constexpr (K == ATTN_DQ) hipLaunchKernelGGL((attn_bwd_dq_kernel<PAIR, DROP, RT, VL>), grid, dim3(256), 0, s, P, V);
+  else hipLaunchKernelGGL((attn_bwd_dkdv_kernel<PAIR, DROP, RT, VL>), grid, dim3(256), 0, s, P, V);
+}
+template <AttnKernel K>
+static bool attn_launch(bool pair, int RT, int VL, dim3 grid, hipStream_t s, const AttnParams& P, const AttnVarlen& V) {
+  bool known = true;
+  mr_bool(P.drop.thresh8 != 0, [&](auto drop) {
+    constexpr bool D = decltype(drop)::value;
+    if (pair && RT == 2 && VL == 0) attn_launch_as<K, true, D, 2, 0>(grid, s, P, V);
+    else if (!pair && RT == 2 && VL == 0) attn_launch_as<K, false, D, 2, 0>(grid, s, P, V);
+    else if (!pair && RT == 1 && VL == 0) attn_launch_as<K, false, D, 1, 0>(grid, s, P, V);
+    else if (!pair && RT == 1 && VL == 1) attn_launch_as<K, false, D, 1, 1>(grid, s, P, V);
+    else if (!pair && RT == 1 && VL == 2) attn_launch_as<K, false, D, 1, 2>(grid, s, P, V);
+    else known = false;
+  });
+  return known;
+}
+// a dense launch over the L rows (queries, or keys for dK/dV) of every (batch, head): which tiles it takes and its grid
+struct AttnTiles {
+  bool pair;
+  int RT;
+  dim3 grid;
+};
+static AttnTiles attn_tiles(int L, int causal, int H, int B) {
+  const bool pair = attn_paired(L, causal, H, B);
+  if (attn_fine(L, pair, causal, H, B)) return {false, 1, dim3(ceil_div(L, 64), H, B)};      // small launch: 64-row tiles
+  return {pair, 2, dim3(attn_grid_x(L, pair), H, B)};
+}
+
 extern "C" int mrmt3_attn_fwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o,
                               int ldo, void* o_lo, float* lse, int B, int H, int Lq, int Lk, int causal, int dtype, float p_drop,
                               uint64_t seed, const int32_t* step_dev, uint32_t stream_id, void* stream) {
@@ -752,21 +664,8 @@ extern "C" int mrmt3_attn_fwd(const void* q, int ldq, const void* k, int ldk, co
   AttnParams P = attn_fwd_params(q, ldq, k, ldk, v, ldv, o, ldo, o_lo, lse, B, H, Lq, Lk, causal,
                                  make_attn_drop(p_drop, seed, stream_id, step_dev));
   P.tile_mode = attn_tile_mode();
-  const AttnVarlen V{};
-  const bool pair = attn_paired(Lq, causal, H, B);
-  if (attn_fine(Lq, pair, causal, H, B)) {                          // small launch: 64-row tiles
-    const dim3 gf(ceil_div(Lq, 64), H, B);
-    if (P.drop.thresh8) hipLaunchKernelGGL((attn_fwd_kernel<false, true, 1>), gf, dim3(256), 0, s, P, V);
-    else hipLaunchKernelGGL((attn_fwd_kernel<false, false, 1>), gf, dim3(256), 0, s, P, V);
-    MR_CHECK_LAUNCH("attn_fwd");
-    mrmt3_count(MRMT3_CNT_ATTN_FWD);
-    return MRMT3_OK;
-  }
-  const dim3 grid(attn_grid_x(Lq, pair), H, B);
-  if (pair && P.drop.thresh8) hipLaunchKernelGGL((attn_fwd_kernel<true, true>), grid, dim3(256), 0, s, P, V);
-  else if (pair) hipLaunchKernelGGL((attn_fwd_kernel<true, false>), grid, dim3(256), 0, s, P, V);
-  else if (P.drop.thresh8) hipLaunchKernelGGL((attn_fwd_kernel<false, true>), grid, dim3(256), 0, s, P, V);
-  else hipLaunchKernelGGL((attn_fwd_kernel<false, false>), grid, dim3(256), 0, s, P, V);
+  const AttnTiles tq = attn_tiles(Lq, causal, H, B);
+  MR_CHECK_ARG(attn_launch<ATTN_FWD>(tq.pair, tq.RT, 0, tq.grid, s, P, AttnVarlen{}), "attn_fwd: no such kernel");
   MR_CHECK_LAUNCH("attn_fwd");
   mrmt3_count(MRMT3_CNT_ATTN_FWD);
   return MRMT3_OK;
@@ -789,31 +688,11 @@ extern "C" int mrmt3_attn_bwd(const void* q, int ldq, const void* k, int ldk, co
     mrmt3_count(MRMT3_CNT_ATTN_BWD_ONEPASS);
     return MRMT3_OK;
   }
-  const AttnVarlen V{};
   // dQ first: it derives delta = rowsum(dO * O) from operands it loads anyway and leaves it for dK/dV
-  const bool pair_q = attn_paired(Lq, causal, H, B), pair_k = attn_paired(Lk, causal, H, B);
-  const dim3 gq(attn_grid_x(Lq, pair_q), H, B), gk(attn_grid_x(Lk, pair_k), H, B);
-  const bool drop = P.drop.thresh8 != 0;
-  const bool fine_q = attn_fine(Lq, pair_q, causal, H, B), fine_k = attn_fine(Lk, pair_k, causal, H, B);
-  if (fine_q) {
-    const dim3 gf(ceil_div(Lq, 64), H, B);
-    if (drop) hipLaunchKernelGGL((attn_bwd_dq_kernel<false, true, 1>), gf, dim3(256), 0, s, P, V);
-    else hipLaunchKernelGGL((attn_bwd_dq_kernel<false, false, 1>), gf, dim3(256), 0, s, P, V);
-  } else
-  if (pair_q && drop) hipLaunchKernelGGL((attn_bwd_dq_kernel<true, true>), gq, dim3(256), 0, s, P, V);
-  else if (pair_q) hipLaunchKernelGGL((attn_bwd_dq_kernel<true, false>), gq, dim3(256), 0, s, P, V);
-  else if (drop) hipLaunchKernelGGL((attn_bwd_dq_kernel<false, true>), gq, dim3(256), 0, s, P, V);
-  else hipLaunchKernelGGL((attn_bwd_dq_kernel<false, false>), gq, dim3(256), 0, s, P, V);
+  const AttnTiles tq = attn_tiles(Lq, causal, H, B), tk = attn_tiles(Lk, causal, H, B);
+  MR_CHECK_ARG(attn_launch<ATTN_DQ>(tq.pair, tq.RT, 0, tq.grid, s, P, AttnVarlen{}), "attn_bwd: no such dq kernel");
   MR_CHECK_LAUNCH("attn_bwd dq");
-  if (fine_k) {
-    const dim3 gf(ceil_div(Lk, 64), H, B);
-    if (drop) hipLaunchKernelGGL((attn_bwd_dkdv_kernel<false, true, 1>), gf, dim3(256), 0, s, P, V);
-    else hipLaunchKernelGGL((attn_bwd_dkdv_kernel<false, false, 1>), gf, dim3(256), 0, s, P, V);
-  } else
-  if (pair_k && drop) hipLaunchKernelGGL((attn_bwd_dkdv_kernel<true, true>), gk, dim3(256), 0, s, P, V);
-  else if (pair_k) hipLaunchKernelGGL((attn_bwd_dkdv_kernel<true, false>), gk, dim3(256), 0, s, P, V);
-  else if (drop) hipLaunchKernelGGL((attn_bwd_dkdv_kernel<false, true>), gk, dim3(256), 0, s, P, V);
-  else hipLaunchKernelGGL((attn_bwd_dkdv_kernel<false, false>), gk, dim3(256), 0, s, P, V);
+  MR_CHECK_ARG(attn_launch<ATTN_DKDV>(tk.pair, tk.RT, 0, tk.grid, s, P, AttnVarlen{}), "attn_bwd: no such dkdv kernel");
   MR_CHECK_LAUNCH("attn_bwd dkdv");
   mrmt3_count(MRMT3_CNT_ATTN_BWD);
   return MRMT3_OK;
@@ -844,14 +723,8 @@ extern "C" int mrmt3_attn_fwd_varlen(const void* q, int ldq, const void* k, int 
   MR_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0, "attn_fwd_varlen: bf16 strides must be multiples of 8");
   const AttnParams P = attn_fwd_params(q, ldq, k, ldk, v, ldv, o, ldo, o_lo, lse, B, H, Lmax, Lk, causal, drop);
   const AttnVarlen V{row_off, tiles, mrmt3_pack_tile_entries(B, Tcap), Tcap};
-  const dim3 grid(V.n_ent * H);
-  if (Lk == 0) {
-    if (drop.thresh8) hipLaunchKernelGGL((attn_fwd_kernel<false, true, 1, 1>), grid, dim3(256), 0, s, P, V);
-    else hipLaunchKernelGGL((attn_fwd_kernel<false, false, 1, 1>), grid, dim3(256), 0, s, P, V);
-  } else {
-    if (drop.thresh8) hipLaunchKernelGGL((attn_fwd_kernel<false, true, 1, 2>), grid, dim3(256), 0, s, P, V);
-    else hipLaunchKernelGGL((attn_fwd_kernel<false, false, 1, 2>), grid, dim3(256), 0, s, P, V);
-  }
+  const int VL = Lk == 0 ? 1 : 2;
+  MR_CHECK_ARG(attn_launch<ATTN_FWD>(false, 1, VL, dim3(V.n_ent * H), s, P, V), "attn_fwd_varlen: no such kernel");
   MR_CHECK_LAUNCH("attn_fwd_varlen");
   mrmt3_count(MRMT3_CNT_ATTN_FWD_VARLEN);
   return MRMT3_OK;
@@ -879,23 +752,13 @@ extern "C" int mrmt3_attn_bwd_varlen(const void* q, int ldq, const void* k, int 
   const AttnParams P = attn_bwd_params(q, ldq, k, ldk, v, ldv, o, ldo, o_lo, d_o, lddo, lse, delta, dq, lddq, dk, lddk, dv,
                                        lddv, B, H, Lmax, Lk, causal, drop);
   const AttnVarlen V{row_off, tiles, mrmt3_pack_tile_entries(B, Tcap), Tcap};
-  const dim3 grid(V.n_ent * H);
-  const bool dr = drop.thresh8 != 0;
+  const int VL = Lk == 0 ? 1 : 2;
+  // the tile list; cross-attention dK/dV: the dense grid over the Lk keys of every row
+  const dim3 grid(V.n_ent * H), gk = Lk == 0 ? grid : dim3(ceil_div(Lk, VARLEN_TILE), H, B);
   // dQ first: it writes delta for dK/dV (and zeroes the tail rows of dQ and delta)
-  if (Lk == 0) {
-    if (dr) hipLaunchKernelGGL((attn_bwd_dq_kernel<false, true, 1, 1>), grid, dim3(256), 0, s, P, V);
-    else hipLaunchKernelGGL((attn_bwd_dq_kernel<false, false, 1, 1>), grid, dim3(256), 0, s, P, V);
-    MR_CHECK_LAUNCH("attn_bwd_varlen dq");
-    if (dr) hipLaunchKernelGGL((attn_bwd_dkdv_kernel<false, true, 1, 1>), grid, dim3(256), 0, s, P, V);
-    else hipLaunchKernelGGL((attn_bwd_dkdv_kernel<false, false, 1, 1>), grid, dim3(256), 0, s, P, V);
-  } else {
-    if (dr) hipLaunchKernelGGL((attn_bwd_dq_kernel<false, true, 1, 2>), grid, dim3(256), 0, s, P, V);
-    else hipLaunchKernelGGL((attn_bwd_dq_kernel<false, false, 1, 2>), grid, dim3(256), 0, s, P, V);
-    MR_CHECK_LAUNCH("attn_bwd_varlen dq");
-    const dim3 gk(ceil_div(Lk, VARLEN_TILE), H, B);
-    if (dr) hipLaunchKernelGGL((attn_bwd_dkdv_kernel<false, true, 1, 2>), gk, dim3(256), 0, s, P, V);
-    else hipLaunchKernelGGL((attn_bwd_dkdv_kernel<false, false, 1, 2>), gk, dim3(256), 0, s, P, V);
-  }
+  MR_CHECK_ARG(attn_launch<ATTN_DQ>(false, 1, VL, grid, s, P, V), "attn_bwd_varlen: no such dq kernel");
+  MR_CHECK_LAUNCH("attn_bwd_varlen dq");
+  MR_CHECK_ARG(attn_launch<ATTN_DKDV>(false, 1, VL, gk, s, P, V), "attn_bwd_varlen: no such dkdv kernel");
   MR_CHECK_LAUNCH("attn_bwd_varlen dkdv");
   mrmt3_count(MRMT3_CNT_ATTN_BWD_VARLEN);
   return MRMT3_OK;

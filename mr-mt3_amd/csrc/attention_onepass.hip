@@ -157,6 +157,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_onepass_kernel(AttnParams P) 
       acc = mfma16(kt_, ds_, acc);
     }
     const int q = qb0 + c_qt * 16 + fr;
+    // (not store_row_bf16: with the row address formed before the pack, the block loop is scheduled differently)
     if (q < P.Lq)
       *(u32x2*)(P.dq + ((size_t)b * P.Lq + q) * P.lddq + h * HD + c_dt * 16 + fg * 4) =
           u32x2{pack_bf2(acc[0], acc[1]), pack_bf2(acc[2], acc[3])};
@@ -226,15 +227,8 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_onepass_kernel(AttnParams P) 
             for (int r = 0; r < 4; ++r) pv[r] = 0.f;
           }
           float pk[4] = {pv[0], pv[1], pv[2], pv[3]}, dk_[4] = {dp[0], dp[1], dp[2], dp[3]};
-          if (DROP && P.drop.thresh8) {
-            const unsigned w = mix24(drop_k[nt] + (unsigned)(qb0 + qt * 16) * DROP_CQ);
-            const bool k0_ = (quad_word<0>(w) & drop_bmask) >= drop_bthr, k1_ = (quad_word<1>(w) & drop_bmask) >= drop_bthr;
-            const bool k2_ = (quad_word<2>(w) & drop_bmask) >= drop_bthr, k3_ = (quad_word<3>(w) & drop_bmask) >= drop_bthr;
-            pk[0] = k0_ ? pk[0] : 0.f; dk_[0] = k0_ ? dk_[0] : 0.f;
-            pk[1] = k1_ ? pk[1] : 0.f; dk_[1] = k1_ ? dk_[1] : 0.f;
-            pk[2] = k2_ ? pk[2] : 0.f; dk_[2] = k2_ ? dk_[2] : 0.f;
-            pk[3] = k3_ ? pk[3] : 0.f; dk_[3] = k3_ ? dk_[3] : 0.f;
-          }
+          if (DROP && P.drop.thresh8)
+            drop_quad(mix24(drop_k[nt] + (unsigned)(qb0 + qt * 16) * DROP_CQ), drop_bmask, drop_bthr, pk, dk_);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             pd[qt][c][r] = pk[r];
@@ -288,9 +282,9 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_onepass_kernel(AttnParams P) 
     bf16_t* dvrow = P.dv + ((size_t)b * P.Lk + key[nt]) * P.lddv + h * HD;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
-      const f32x4 a = dkT[nt][dt], c = dvT[nt][dt] * P.drop.scale;
-      *(u32x2*)(dkrow + dt * 16 + fg * 4) = u32x2{pack_bf2(a[0], a[1]), pack_bf2(a[2], a[3])};
-      *(u32x2*)(dvrow + dt * 16 + fg * 4) = u32x2{pack_bf2(c[0], c[1]), pack_bf2(c[2], c[3])};
+      const f32x4 c = dvT[nt][dt] * P.drop.scale;
+      store_row_bf16(dkrow, dt, fg, dkT[nt][dt]);
+      store_row_bf16(dvrow, dt, fg, c);
     }
   }
 }
@@ -303,17 +297,13 @@ int mrmt3_attn_bwd_onepass_try(const AttnParams& P, hipStream_t s) {
   const int m = MR_KNOB("MRMT3_ATTN_ONEPASS_MIN_BH", 0);
   if (m > 0) min_bh = m;
   if (!enabled || P.causal || P.B * P.H < min_bh || P.Lq < 32) return 0;
-  const dim3 grid((unsigned)P.H, (unsigned)P.B);
-  if (P.Lk == 256) {
-    if (P.drop.thresh8) hipLaunchKernelGGL((attn_bwd_onepass_kernel<true, 2>), grid, dim3(512), 0, s, P);
-    else hipLaunchKernelGGL((attn_bwd_onepass_kernel<false, 2>), grid, dim3(512), 0, s, P);
-    return 1;
-  }
-  // 256 < Lk <= 320 (MR-MT3's own model: 256 encoder frames + 64 memory slots): the 3 + 2 tile form, key tail masked
-  if (P.Lk > 256 && P.Lk <= 320 && MR_KNOB("MRMT3_ATTN_ONEPASS_320", 1) != 0) {
-    if (P.drop.thresh8) hipLaunchKernelGGL((attn_bwd_onepass_kernel<true, 3>), grid, dim3(512), 0, s, P);
-    else hipLaunchKernelGGL((attn_bwd_onepass_kernel<false, 3>), grid, dim3(512), 0, s, P);
-    return 1;
-  }
-  return 0;
+  // 256 keys: NT = 2.  256 < Lk <= 320 (MR-MT3's own model: 256 encoder frames + 64 memory slots): the 3 + 2 tile form, key
+  // tail masked
+  const int NT = P.Lk == 256 ? 2 : (P.Lk > 256 && P.Lk <= 320 && MR_KNOB("MRMT3_ATTN_ONEPASS_320", 1) != 0) ? 3 : 0;
+  return mr_const<2, 3>(NT, [&](auto nt) {
+    mr_bool(P.drop.thresh8 != 0, [&](auto drop) {
+      hipLaunchKernelGGL((attn_bwd_onepass_kernel<decltype(drop)::value, decltype(nt)::value>), dim3((unsigned)P.H, (unsigned)P.B),
+                         dim3(512), 0, s, P);
+    });
+  });
 }

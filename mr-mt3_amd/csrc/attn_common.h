@@ -1,6 +1,7 @@
 // Helpers shared by the attention kernels (attention.hip: forward, two-pass backward, exact-f32 kernels;
 // attention_onepass.hip: the one-pass backward): fragment reads, the swizzled LDS tile image and its LDS-DMA fill, the
-// attention-probability dropout generator, the launch parameter block.
+// attention-probability dropout generator, the launch parameter block, and what the flash kernels share: the row prologue
+// (attn_locate), the pair passes (attn_pass_tile), the K/V staging of forward and dQ (kv_stage / kv_prime / kv_step).
 #pragma once
 #include "common.h"
 #include "lds_dma.h"
@@ -69,6 +70,17 @@ template <int R>
 __device__ __forceinline__ unsigned quad_word(unsigned w) {
   return (unsigned)__builtin_amdgcn_mov_dpp((int)w, R * 0x55, 0xF, 0xF, true);
 }
+// ... and the quad's mask applied to the lane's four probabilities and four dP values.  `w` is this lane's word: query (fp-th of
+// its quad's four), key group key >> 2; the lane's own element sits in byte (key & 3) = fp of every word of the quad:
+// bmask = 0xFF << 8 fp, bthr = thresh8 << 8 fp.
+__device__ __forceinline__ void drop_quad(unsigned w, unsigned bmask, unsigned bthr, float (&pk)[4], float (&dk_)[4]) {
+  const bool k0_ = (quad_word<0>(w) & bmask) >= bthr, k1_ = (quad_word<1>(w) & bmask) >= bthr;
+  const bool k2_ = (quad_word<2>(w) & bmask) >= bthr, k3_ = (quad_word<3>(w) & bmask) >= bthr;
+  pk[0] = k0_ ? pk[0] : 0.f; dk_[0] = k0_ ? dk_[0] : 0.f;
+  pk[1] = k1_ ? pk[1] : 0.f; dk_[1] = k1_ ? dk_[1] : 0.f;
+  pk[2] = k2_ ? pk[2] : 0.f; dk_[2] = k2_ ? dk_[2] : 0.f;
+  pk[3] = k3_ ? pk[3] : 0.f; dk_[3] = k3_ ? dk_[3] : 0.f;
+}
 // max over the four 16-lane rows of a wave (lanes l, l^16, l^32, l^48): gfx950's v_permlane16/32_swap are
 // plain VALU moves, so the reduction has no LDS (ds_bpermute) round trip in the softmax's dependency chain
 typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
@@ -93,6 +105,10 @@ __device__ __forceinline__ void widen_rows(const u32x2 c[4], u32x4 out[2]) {
   }
 }
 __device__ __forceinline__ int widen_off(int fg) { return (fg & 1) * 16 + (fg >> 1) * 8; }
+// the gradient kernels' 8-byte row stores: accumulator tile dt of the lane's row -> bf16 features 16 dt + 4 fg .. + 3 of `row`
+__device__ __forceinline__ void store_row_bf16(bf16_t* row, int dt, int fg, f32x4 a) {
+  *(u32x2*)(row + dt * 16 + fg * 4) = u32x2{pack_bf2(a[0], a[1]), pack_bf2(a[2], a[3])};
+}
 #define LOG2E 1.4426950408889634f
 #define LN2 0.6931471805599453f
 
@@ -218,6 +234,104 @@ __device__ __forceinline__ unsigned rows8_lane_off(int ld, int lane) {     // ro
 }
 __device__ __forceinline__ void blds_rows8(__amdgpu_buffer_rsrc_t r, unsigned lane_off, int tile_byte_off, unsigned char* dst) {
   lds_dma16(r, dst, lane_off, tile_byte_off);
+}
+
+// ---- the prologue of the flash kernels (attention.hip), written once: which (batch) row, head and tile the workgroup owns, the
+// row's lengths and its base offsets.  VL = 0: the grid and attn_tile.  VL = 1 / 2: entry blockIdx.x / H of the tile list for
+// head blockIdx.x % H; a surplus entry calls zero_tail(h, r0, r1) for the tail rows [r0, r1) it owns and the workgroup is done
+// (attn_locate returns false).  KEY_TILES (the dK/dV kernel, a workgroup owns keys): packed self-attention takes the list in
+// reverse (key tile t of a causal row is seen by the queries from 64 t on: the low tiles are the heavy ones), packed
+// cross-attention keeps the dense grid over the Lk keys of every row and an empty row (Lq = 0) gets st0 = 0 (it reads no
+// statistics; keep the address inside the buffer).
+struct AttnRow {
+  int tile, h, b;
+  int Lq, Lk;
+  size_t qr0, kr0;            // first row of this (batch) row's queries / keys
+  size_t st0;                 // first lse / delta element of this (row, head)
+};
+template <int VL, bool KEY_TILES = false, typename ZeroTail>
+__device__ __forceinline__ bool attn_locate(const AttnParams& P, const AttnVarlen& V, AttnRow& R, ZeroTail&& zero_tail) {
+  if constexpr (VL == 0 || (VL == 2 && KEY_TILES)) {
+    attn_tile(R.tile, R.h, R.b, P.tile_mode);
+  } else {
+    const int w = blockIdx.x / P.H;
+    const int e = KEY_TILES ? V.n_ent - 1 - w : w;
+    R.h = blockIdx.x % P.H;
+    R.b = V.tiles[2 + 2 * e];
+    R.tile = V.tiles[3 + 2 * e];
+    if (R.b < 0) {
+      int r0, r1;
+      if (varlen_tail_rows(V, e, r0, r1)) zero_tail(R.h, r0, r1);
+      return false;
+    }
+  }
+  if constexpr (VL == 0) {
+    R.Lq = P.Lq; R.Lk = P.Lk;
+    R.qr0 = (size_t)R.b * R.Lq; R.kr0 = (size_t)R.b * R.Lk;
+    R.st0 = ((size_t)R.b * P.H + R.h) * R.Lq;
+  } else {
+    const int o0 = V.row_off[R.b];
+    R.Lq = V.row_off[R.b + 1] - o0;
+    R.qr0 = (size_t)o0;
+    if constexpr (VL == 1) { R.Lk = R.Lq; R.kr0 = R.qr0; }
+    else { R.Lk = P.Lk; R.kr0 = (size_t)R.b * P.Lk; }
+    R.st0 = (size_t)R.h * V.Tcap + o0;
+    if constexpr (KEY_TILES) R.st0 = R.Lq > 0 ? R.st0 : 0;
+  }
+  return true;
+}
+// causal launches pair the 128-row tiles: a workgroup takes tiles (n-1-t, t) in two passes — query tile t needs 2(t+1) key tiles
+// (key tile t is seen by the queries from 128 t on), so every workgroup of the launch does the same amount of work and the
+// launch has no tail of heavy tiles.  far_first: pass 0 takes n-1-t.  Returns false when pass 1 has nothing left (odd n: the
+// middle tile is its own partner); pass 1 starts once every wave is done reading the previous tile's LDS stages.
+template <bool PAIR>
+__device__ __forceinline__ bool attn_pass_tile(int pass, int tile, int n, bool far_first, int& t) {
+  t = tile;
+  if (PAIR) {
+    t = (pass == 0) == far_first ? n - 1 - tile : tile;
+    if (pass == 1 && 2 * tile == n - 1) return false;
+    if (pass == 1) __syncthreads();
+  }
+  return true;
+}
+
+// ---- K/V staging of the forward and dQ kernels: 64-key tiles, KV_STAGES LDS stages of K tile | V tile, two tiles in flight.
+#define KV_STAGES 3
+#define KV_STAGE_BYTES 16384   // K tile 8 KiB + V tile 8 KiB
+struct KvSrc {
+  __amdgpu_buffer_rsrc_t kres, vres;
+  unsigned k_lane, v_lane;
+  int ldk, ldv;
+};
+__device__ __forceinline__ KvSrc kv_src(const bf16_t* kb, const bf16_t* vb, int Lk, int ldk, int ldv, int lane) {
+  return KvSrc{rows_rsrc(kb, Lk, ldk), rows_rsrc(vb, Lk, ldv), rows8_lane_off(ldk, lane), rows8_lane_off(ldv, lane), ldk, ldv};
+}
+// each wave (uw) stages 16 rows of K and of V per tile (2 + 2 wave-instructions); `on` = false turns the tile into
+// four zero-fills that never leave the CU, which keeps the vmcnt arithmetic of the loop uniform
+__device__ __forceinline__ void kv_stage(unsigned char* lds, const KvSrc& S, int uw, int buf, int kv0, bool on) {
+  unsigned char* base = lds + buf * KV_STAGE_BYTES;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int t = uw * 2 + i;
+    blds_rows8(S.kres, S.k_lane, on ? (kv0 + t * 8) * S.ldk * 2 : LDS_DMA_OOB, base + t * 1024);
+    blds_rows8(S.vres, S.v_lane, on ? (kv0 + t * 8) * S.ldv * 2 : LDS_DMA_OOB, base + 8192 + t * 1024);
+  }
+}
+// before the loop: tiles 0 and 1
+__device__ __forceinline__ void kv_prime(unsigned char* lds, const KvSrc& S, int uw, int n_kv) {
+  kv_stage(lds, S, uw, 0, 0, true);
+  kv_stage(lds, S, uw, 1, 64, n_kv > 1);
+}
+// top of iteration j (`cur` = its stage, 0 at j = 0): wait for tile j, prefetch tile j + 2 into the stage tile j - 1 left,
+// rotate `cur`; returns tile j's K image, its V image follows at + 8192.  After the loop VMCNT(0): the switched-off
+// prefetches of the last two iterations still write their zeros.
+__device__ __forceinline__ const unsigned char* kv_step(unsigned char* lds, const KvSrc& S, int uw, int& cur, int j, int n_kv) {
+  VMCNT(4);                                       // tile j landed (tile j+1 may still be in flight)
+  __builtin_amdgcn_s_barrier();
+  kv_stage(lds, S, uw, cur == 0 ? 2 : cur - 1, j * 64 + 128, j + 2 < n_kv);
+  const unsigned char* lk = lds + cur * KV_STAGE_BYTES;
+  cur = cur == KV_STAGES - 1 ? 0 : cur + 1;
+  return lk;
 }
 
 // attention_onepass.hip: the backward in one pass when a workgroup can own all keys of a (batch, head); 1 = launched

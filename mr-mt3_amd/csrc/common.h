@@ -215,9 +215,11 @@ static inline int ew_blocks(size_t n_items) {
 // ---- run-time dtype code / width -> compile-time type / constant (the row, loss and layout entry points) ---------------
 // mr_dtype(code, f) calls the generic lambda f with a tag (`typename decltype(tag)::type` is the element type) for MRMT3_F32
 // and MRMT3_BF16 and returns true; for any other code it calls nothing and returns false.  mr_const<A, B, ...>(v, f) does
-// the same for an int among a fixed list (`decltype(tag)::value`).  Nested calls instantiate the cross product of kernels.
+// the same for an int among a fixed list (`decltype(tag)::value`), mr_bool(v, f) for a bool (always calls).  Nested calls
+// instantiate the cross product of kernels.
 template <typename T> struct MrType { typedef T type; };
 template <int N> struct MrInt { static constexpr int value = N; };
+template <bool B> struct MrBool { static constexpr bool value = B; };
 template <typename F> static inline bool mr_dtype(int code, F&& f) {
   if (code == MRMT3_F32) { f(MrType<float>{}); return true; }
   if (code == MRMT3_BF16) { f(MrType<bf16_t>{}); return true; }
@@ -225,6 +227,10 @@ template <typename F> static inline bool mr_dtype(int code, F&& f) {
 }
 template <int... Ns, typename F> static inline bool mr_const(int v, F&& f) {
   return ((v == Ns ? (f(MrInt<Ns>{}), true) : false) || ...);
+}
+template <typename F> static inline void mr_bool(bool v, F&& f) {
+  if (v) f(MrBool<true>{});
+  else f(MrBool<false>{});
 }
 // bytes per element of a dtype code, 0 for a code that is neither
 static inline size_t mr_dtype_bytes(int code) {
