@@ -145,6 +145,40 @@ int mrmt3_logmel_mix_fwd(const float* pool, long long pool_samples, const long l
                          const int* fb_cnt, const float* fb_w, int n_mels, int max_taps,
                          const int* valid_frames, int normalize, int out_bf16, void* out, void* stream);
 
+/* Windowed-sinc resampler at arbitrary ratio that mixes as it goes (pitch-shift rows of stem-mix training, stems at their
+ * native rate, inference on audio at another rate).  It writes rows of f32 SAMPLES, out [batch][n_samples]; the rows then go
+ * through mrmt3_logmel_fwd.  pool[pool_samples] f32 as in mrmt3_logmel_mix_fwd; every table below is a DEVICE table
+ * [batch][n_src], 1 <= n_src <= 64: src_pos (int64, 32.32 fixed point: the absolute pool position of output sample 0),
+ * src_begin / src_end (int64: first sample of the stem, one past its last), src_step (int64, 32.32: input samples per
+ * output sample), src_gain (f32), src_filt (int32: which table, or -1).  filt[n_filt][513][n_taps] f32 holds the polyphase
+ * tables: P = 512 phases (an ABI constant), row p the taps at a fraction of p/512, row 512 = row 0 shifted by one sample;
+ * n_taps is even.  valid_samples [batch] (int64) may be NULL.  The contract, every output one defined f32 value
+ * (fl = one rounding to f32; no fused multiply-add, no packed f32):
+ *  - output i of source k of row b:  pos = src_pos + i*src_step in int64 (wrapping), n = pos >> 32, fr = pos & 0xffffffff,
+ *    j = fr >> 23, w = float(fr & 0x7fffff) * 2^-23 (23 bits: exact).
+ *  - tap t has the coefficient  c = fl(h[j][t] + fl(w * fl(h[j+1][t] - h[j][t])))  and reads  idx = n + t - n_taps/2 + 1.
+ *  - acc = +0;  for t = 0 .. n_taps-1 in order, only where max(begin, 0) <= idx < min(end, pool_samples):
+ *    acc = fl(acc + fl(c * pool[idx])).  A tap outside those bounds is NOT READ and adds nothing (a select, not a product
+ *    with zero): what lies between the stems may be NaN.
+ *  - the row:  row = +0;  for k = 0 .. n_src-1, sounding sources only:  row = fl(row + fl(gain_k * acc_k)).
+ *  - src_filt == -1: no filter.  The source contributes pool[n + i] under the same bounds, the fraction and the step
+ *    ignored:  row = fl(row + fl(gain * pool[n + i]))  where that sample exists.  A row whose sources are all -1 is the
+ *    mixed row of mrmt3_logmel_mix_fwd bit for bit.
+ *  - a source with src_gain == 0.0f is NOT READ AT ALL.  A src_filt outside [-1, n_filt), a step <= 0 or begin >= end makes
+ *    the source silent.  Whatever the tables hold, the kernel reads nothing outside [0, pool_samples).
+ *  - outputs i >= valid_samples[b] are 0.
+ * MRMT3_ERR_INVALID_ARG before any launch: a null pointer (valid_samples excepted), n_src outside [1, 64], n_taps odd or
+ * outside [2, 160], n_filt < 0, a size <= 0, filt not 8-byte aligned.  Checks that name rows are the host's
+ * (mrmt3.resample.check_resample_tables). */
+int mrmt3_resample_mix_fwd(const float* pool, long long pool_samples, const long long* src_pos,
+                           const long long* src_begin, const long long* src_end, const long long* src_step,
+                           const float* src_gain, const int* src_filt, int n_src, int batch, int n_samples,
+                           const float* filt, int n_filt, int n_taps, const long long* valid_samples, float* out,
+                           void* stream);
+/* Launches of mrmt3_resample_mix_fwd since the process started (or since the last call with reset != 0): its dispatch
+ * counter, kept apart from mrmt3_dispatch_counts so that MRMT3_CNT_N and the counters of an untouched step stay as they are. */
+unsigned long long mrmt3_resample_launches(int reset);
+
 /* ---- K2/K4/K6/K7/K9: bias-free Linear layers (nn.Linear(bias=False) inside HF T5Block,
  * models/t5.py:51,72,487-490) ----------------------------------------------------------------------
  * NT:  C[M,N] (+)= A[M,K] . B[N,K]^T      forward y = x W^T, and dgrad with a pre-transposed W.

@@ -155,6 +155,15 @@ class InferenceHandler:
         mel = spectrograms.logmel_segments(x, self.spectrogram_config, normalize=self.mel_norm, valid_frames=vf)
         return mel, raw
 
+    def _at_model_rate(self, audio, sample_rate):
+        """`audio` at `sample_rate` -> audio at the model's rate: uploaded and resampled on the device
+        (mrmt3_resample_mix_fwd).  None, or the model's rate: `audio` itself."""
+        if sample_rate is None or sample_rate == self.SAMPLE_RATE:
+            return audio
+        from mrmt3.resample import resample
+        x = torch.from_numpy(np.ascontiguousarray(np.asarray(audio, np.float32).reshape(-1))).to(self.device)
+        return resample(x, sample_rate, self.SAMPLE_RATE).cpu().numpy()
+
     def _preprocess(self, audio):
         frames, frame_times = self._audio_to_frames(audio)
         frames, frame_times, paddings = self._split_token_into_length(frames, frame_times)
@@ -209,8 +218,11 @@ class InferenceHandler:
     @torch.no_grad()
     def inference(self, audio, audio_path=None, outpath=None, valid_programs=None, num_beams=1, batch_size=5,
                   max_length=1024, verbose=False, return_tokens=False, with_confidence=False, min_confidence=None,
-                  do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, best_of=1, constrained=False):
+                  do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, best_of=1, constrained=False,
+                  sample_rate=None):
         """audio -> note sequence (and a MIDI file when `outpath` is given, like inference.py:149-204).
+        `sample_rate`: the rate of `audio` when it is not the model's 16 kHz (a quarter to four times that): the audio is
+        resampled on the device first; None is the 16 kHz path, untouched.
         `return_tokens=True` returns (post-processed token arrays per batch, frame times) instead.
         `with_confidence` (implied by `min_confidence`): every note carries `confidence` in (0, 1], notes below
         `min_confidence` are dropped; with `return_tokens` a third item holds the log-probability arrays.
@@ -221,7 +233,7 @@ class InferenceHandler:
         segment-memory models hand the sounding notes from segment to segment within a batch."""
         scored = with_confidence or min_confidence is not None
         sample = self._sample_options(do_sample, temperature, top_k, top_p, seed, best_of)
-        inputs, frame_times = self._preprocess(audio)
+        inputs, frame_times = self._preprocess(self._at_model_rate(audio, sample_rate))
         batches, ft = self._batching(inputs, frame_times, batch_size=batch_size)
         if self.contiguous_inference:
             batches = [torch.cat(batches, dim=0)]
@@ -251,8 +263,9 @@ class InferenceHandler:
     @torch.no_grad()
     def inference_many(self, audios, outpaths=None, max_length=1024, return_tokens=False, valid_programs=None,
                        num_beams=1, with_confidence=False, min_confidence=None, do_sample=False, temperature=1.0, top_k=0,
-                       top_p=1.0, seed=0, best_of=1, constrained=False):
-        """Several recordings in one go.  Segment-memory models decode them in lockstep (one batch row per
+                       top_p=1.0, seed=0, best_of=1, constrained=False, sample_rate=None):
+        """Several recordings in one go (`sample_rate` as in `inference`, the same for every recording).
+        Segment-memory models decode them in lockstep (one batch row per
         recording, `model.generate_songs`); the plain T5 simply batches all segments.  Returns one note sequence
         (or, with `return_tokens`, one `(token arrays, frame times)` pair) per recording, like `inference`.
         `valid_programs` / `num_beams` are honoured as given (length penalty 0.4, as `inference` under decode_options).
@@ -264,7 +277,7 @@ class InferenceHandler:
         if sample is not None and best_of > 1 and hasattr(self.model, "generate_songs"):
             raise ValueError("best_of > 1 is for the plain T5 model (MT3Net); the segment-memory models decode one sample "
                              "per segment")
-        pre = [self._preprocess(a) for a in audios]
+        pre = [self._preprocess(self._at_model_rate(a, sample_rate)) for a in audios]
         opts = valid_programs is not None or num_beams != 1
         scored = with_confidence or min_confidence is not None
         ban = None if valid_programs is None else program_ban_ids(valid_programs, self.codec)

@@ -118,6 +118,8 @@ class StemMixPlan:
     crops: CropPlan
     keep: np.ndarray             # bool [B, S]
     gain: np.ndarray             # float32 [B, S], 0 where a stem is not kept
+    shift: int = 0               # pitch shift of the whole plan in semitones; 0: the track as it is
+    step: int = 1 << 32          # 32.32 input samples per output sample, ratio_step(2 ** (shift / 12))
 
 
 def plan_stem_mix(n_frames: int, n_stems: int, mel_length: int = 256, num_rows_per_batch: int = 12,
@@ -169,6 +171,27 @@ def mix_tables(plan: StemMixPlan, offsets, lengths, hop: int):
     return start.astype(np.int64), end, np.ascontiguousarray(gain)
 
 
+def resample_tables(plan: StemMixPlan, offsets, lengths, hop: int):
+    """The resampler's tables for a pitch-shifted plan over a pool laid out by `stem_pool_layout`:
+    (src_pos, src_begin, src_end, src_step int64 [B, S], src_gain float32 [B, S], src_filt int32 [B, S] all 0,
+    valid_samples int64 [B]).  Source s of row b starts at (offset_s << 32) + start_frame_b * hop * step and is bounded by
+    its own stem.  The stretched stem has `out_length(len_s, step)` samples; a crop that starts at or behind them has
+    nothing of that stem to read and gets table gain 0 as in `mix_tables` (its position is left at the stem's start) —
+    which covers every source whose first tap lies at or behind its stem's end."""
+    from mrmt3.resample import out_length
+    offsets, lengths = np.asarray(offsets, np.int64), np.asarray(lengths, np.int64)
+    shape = plan.gain.shape
+    step = int(plan.step)
+    begin = np.broadcast_to(offsets, shape).copy()
+    end = np.broadcast_to(offsets + lengths, shape).copy()
+    start = plan.crops.start_frame.astype(np.int64)[:, None] * hop                      # in stretched samples
+    over = start >= np.array([out_length(int(n), step) for n in lengths], np.int64)[None, :]
+    pos = np.where(over, begin << 32, (begin << 32) + start * step)
+    gain = np.where(over, np.float32(0), plan.gain).astype(np.float32)
+    return (pos.astype(np.int64), begin, end, np.full(shape, step, np.int64), np.ascontiguousarray(gain),
+            np.zeros(shape, np.int32), plan.crops.valid_frames.astype(np.int64) * hop)
+
+
 def check_mix_tables(start_frames, src_end, src_gain, pool_samples: int, hop: int):
     """Host check of the tables before they are uploaded: every gain finite; for every source that sounds (gain != 0)
     0 <= start <= end <= pool_samples.  A ValueError names the row.  (The kernel is safe without it — it clamps — but a
@@ -201,15 +224,23 @@ class StemMixBatcher:
     `mrmt3.stems.merged_note_sequence(track, kept)` at the track's length; tokenisations are cached per (track, subset)
     (tests hold the cached path to the definition).  `plan` / `row_targets` are host code and run without a GPU; `build`
     needs one (no CPU fallback).  Stems are uploaded once per track through pinned staging and kept in a device cache of
-    at most `cache_bytes` (least recently used track dropped first; the track in use always stays)."""
+    at most `cache_bytes` (least recently used track dropped first; the track in use always stays).
+
+    `pitch_shift=S` > 0: every plan first draws one shift of k semitones in [-S, S], clamped so that no label
+    leaves the codec's pitches; the whole track visit is played at 2^(k/12) times its speed — the rows are resampled and
+    mixed by `mrmt3_resample_mix_fwd` and go through `mrmt3_logmel_fwd`, the labels are those of
+    `mrmt3.stems.speed_note_sequence`.  k = 0 and `pitch_shift=0` are the launch above, untouched.  A stem whose
+    `track.rates` entry is not the config's rate is resampled on the device, once, when the track is uploaded."""
 
     def __init__(self, device, mel_length: int = 256, event_length: int = 1024, num_rows_per_batch: int = 12,
                  split_frame_length: int = 2000, keep_prob: float = 0.75, min_stems: int = 1, gain_db: float = 6.0,
                  is_deterministic: bool = False, tokenizer=None, rng=None, cache_bytes: int = 8 << 30,
-                 spectrogram_config=None, out_bf16: bool = False):
+                 spectrogram_config=None, out_bf16: bool = False, pitch_shift: int = 0):
         from collections import OrderedDict
         from contrib import spectrograms
         from mrmt3.tokenizer import Tokenizer
+        if isinstance(pitch_shift, bool) or not isinstance(pitch_shift, (int, np.integer)) or not 0 <= pitch_shift <= 24:
+            raise ValueError("pitch_shift must be an int in [0, 24] (semitones), got %r" % (pitch_shift,))
         if not 0.0 <= keep_prob <= 1.0:
             raise ValueError("keep_prob must be in [0, 1], got %r" % (keep_prob,))
         if min_stems < 1:
@@ -222,28 +253,54 @@ class StemMixBatcher:
         self.num_rows, self.split_len = num_rows_per_batch, split_frame_length
         self.keep_prob, self.min_stems, self.gain_db = float(keep_prob), int(min_stems), float(gain_db)
         self.is_deterministic, self.out_bf16, self.rng = is_deterministic, out_bf16, rng
+        self.pitch_shift = int(pitch_shift)
         self.tokenizer = tokenizer or Tokenizer(spectrogram_config=self.cfg)
         self.cache_bytes = int(cache_bytes)
         self._pools = OrderedDict()          # track.name -> (pool on the device, offsets, lengths), least recent first
-        self._feats = OrderedDict()          # (track.name, kept) -> Tokenizer.tokenize(...)
+        self._feats = OrderedDict()          # (track.name, kept, shift) -> Tokenizer.tokenize(...)
         self.uploads = 0                     # tracks copied to the device so far (a cache hit does not count)
         self._sp = spectrograms
 
     # ---- host ----------------------------------------------------------------------------------------------------
-    def n_frames(self, track) -> int:
-        return -(-track.n_samples // self.cfg.hop_width)
+    def lengths(self, track, step: int = 1 << 32) -> list:
+        """Samples of every stem at the config's rate, played at step / 2^32 times its speed."""
+        from mrmt3.resample import out_length
+        lengths = track.lengths(self.cfg.sample_rate)
+        return lengths if step == 1 << 32 else [out_length(n, step) for n in lengths]
+
+    def n_samples(self, track, step: int = 1 << 32) -> int:
+        """The (stretched) track's length: its longest stem."""
+        return max(self.lengths(track, step))
+
+    def n_frames(self, track, step: int = 1 << 32) -> int:
+        return -(-self.n_samples(track, step) // self.cfg.hop_width)
 
     def plan(self, track) -> StemMixPlan:
-        return plan_stem_mix(self.n_frames(track), len(track.audio), self.mel_length, self.num_rows, self.split_len,
+        """With `pitch_shift` S > 0 (and not deterministic) ONE `randint(-S, S)` comes first: the shift of the whole
+        track visit, clamped into `mrmt3.stems.shift_range(track)`; every draw of `plan_stem_mix` follows unchanged, over
+        the frames of the stretched track."""
+        shift, step = 0, 1 << 32
+        if self.pitch_shift > 0 and not self.is_deterministic:
+            from mrmt3.resample import ratio_step
+            from mrmt3.stems import shift_range
+            lo, hi = shift_range(track)
+            shift = max(lo, min(hi, int((self.rng or _random).randint(-self.pitch_shift, self.pitch_shift))))
+            step = ratio_step(2.0 ** (shift / 12.0))
+        plan = plan_stem_mix(self.n_frames(track, step), len(track.audio), self.mel_length, self.num_rows, self.split_len,
                              self.keep_prob, self.min_stems, self.gain_db, self.is_deterministic, self.rng)
+        plan.shift, plan.step = shift, step
+        return plan
 
-    def _tokenized(self, track, kept):
-        from mrmt3.stems import merged_note_sequence
-        key = (track.name, kept)
+    def _tokenized(self, track, kept, shift: int = 0, step: int = 1 << 32):
+        from mrmt3.stems import merged_note_sequence, speed_note_sequence
+        key = (track.name, kept, int(shift))
         if key in self._feats:
             self._feats.move_to_end(key)
             return self._feats[key]
-        feats = self.tokenizer.tokenize(merged_note_sequence(track, kept), track.n_samples)
+        ns = merged_note_sequence(track, kept)
+        if shift != 0:
+            ns = speed_note_sequence(ns, shift, step)
+        feats = self.tokenizer.tokenize(ns, self.n_samples(track, step))
         self._feats[key] = feats
         while len(self._feats) > 64:
             self._feats.popitem(last=False)
@@ -254,18 +311,29 @@ class StemMixBatcher:
         out = []
         for b in range(len(plan.crops.start_frame)):
             kept = tuple(int(s) for s in np.nonzero(plan.keep[b])[0])
-            out.append(self.tokenizer.row_targets(self._tokenized(track, kept), int(plan.crops.start_frame[b]),
+            out.append(self.tokenizer.row_targets(self._tokenized(track, kept, plan.shift, plan.step), int(plan.crops.start_frame[b]),
                                                   int(plan.crops.valid_frames[b])))
         return out
 
     def tables(self, track, plan: StemMixPlan):
         """(start_frames, src_end, src_gain, pool_samples) of the plan on the host, checked."""
         hop = self.cfg.hop_width
-        lengths = [len(a) for a in track.audio]
+        lengths = self.lengths(track)
         offsets, total = stem_pool_layout(lengths, hop)
         start, end, gain = mix_tables(plan, offsets, lengths, hop)
         check_mix_tables(start, end, gain, total, hop)
         return start, end, gain, total
+
+    def shifted_tables(self, track, plan: StemMixPlan):
+        """(src_pos, src_begin, src_end, src_step, src_gain, src_filt, valid_samples, pool_samples) of a pitch-shifted plan
+        on the host, checked: the resampler's tables over the same pool (one filter table, index 0)."""
+        from mrmt3.resample import check_resample_tables
+        hop = self.cfg.hop_width
+        lengths = self.lengths(track)
+        offsets, total = stem_pool_layout(lengths, hop)
+        tabs = resample_tables(plan, offsets, lengths, hop)
+        check_resample_tables(*tabs[:6], total, 1)
+        return tabs + (total,)
 
     # ---- device --------------------------------------------------------------------------------------------------
     def pool(self, track) -> torch.Tensor:
@@ -276,11 +344,20 @@ class StemMixBatcher:
             self._pools.move_to_end(track.name)
             return self._pools[track.name]
         hop = self.cfg.hop_width
-        offsets, total = stem_pool_layout([len(a) for a in track.audio], hop)
+        rate = self.cfg.sample_rate
+        rates = track.rates or [rate] * len(track.audio)
+        offsets, total = stem_pool_layout(self.lengths(track), hop)
         host = torch.zeros(total, dtype=torch.float32).pin_memory()
-        for off, a in zip(offsets, track.audio):
-            host[int(off):int(off) + len(a)] = torch.from_numpy(np.ascontiguousarray(a, np.float32))
+        for off, a, r in zip(offsets, track.audio, rates):
+            if r == rate:
+                host[int(off):int(off) + len(a)] = torch.from_numpy(np.ascontiguousarray(a, np.float32))
         dev = host.to(self.device, non_blocking=True)
+        for off, a, r, n in zip(offsets, track.audio, rates, self.lengths(track)):
+            if r != rate:                    # a stem at its native rate: resampled on the device into its slot, once
+                from mrmt3.resample import resample
+                y = resample(torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(self.device), r, rate)
+                assert y.numel() == n
+                dev[int(off):int(off) + n] = y
         torch.cuda.current_stream(self.device).synchronize()          # (the pinned buffer is released on return)
         self._pools[track.name] = dev
         self.uploads += 1
@@ -292,12 +369,29 @@ class StemMixBatcher:
         return list(self._pools)
 
     def mel(self, track, plan: StemMixPlan) -> torch.Tensor:
+        if plan.shift != 0:
+            return self._shifted_mel(track, plan)
         start, end, gain, total = self.tables(track, plan)
         pool = self.pool(track)
         assert pool.numel() == total
         return self._sp.logmel_mix(pool, torch.from_numpy(start), torch.from_numpy(end), torch.from_numpy(gain),
                                    self.mel_length, self.cfg, normalize=True,
                                    valid_frames=torch.from_numpy(plan.crops.valid_frames), out_bf16=self.out_bf16)
+
+    def _shifted_mel(self, track, plan: StemMixPlan) -> torch.Tensor:
+        """A pitch-shifted plan: one `resample_mix` launch writes the mixed rows, one `logmel` launch transforms them."""
+        from mrmt3 import lib
+        from mrmt3.resample import device_filter
+        pos, begin, end, step, gain, filt, valid, total = self.shifted_tables(track, plan)
+        pool = self.pool(track)
+        assert pool.numel() == total
+        dev = pool.device
+        rows = lib.resample_mix(pool, *(torch.from_numpy(t).to(dev) for t in (pos, begin, end, step, gain, filt)),
+                                self.mel_length * self.cfg.hop_width, device_filter(plan.step, dev),
+                                valid_samples=torch.from_numpy(valid).to(dev))
+        return lib.logmel(rows, self._sp.kernel_tables(self.cfg, dev),
+                          valid_frames=torch.from_numpy(plan.crops.valid_frames).to(dev), normalize=True,
+                          out_bf16=self.out_bf16)
 
     def build(self, track, plan: StemMixPlan | None = None):
         plan = plan or self.plan(track)

@@ -106,7 +106,7 @@ def load():
     return lib
 
 
-MIN_VERSION = 123
+MIN_VERSION = 124
 COUNTER_NAMES = ("gemm_nt_tile", "gemm_nt8", "gemm_nt_geglu", "tn_group", "tn8", "tn_tile", "attn_fwd", "attn_bwd",
                  "attn_bwd_onepass", "attn_f32", "tn_f32", "gemm_nt_splitk", "gemm_nt_addnorm", "gemm_nt_normbwd",
                  "gemm_nt_geglubwd", "attn_fwd_varlen", "attn_bwd_varlen", "logmel_wave", "logmel_general")
@@ -244,6 +244,36 @@ def logmel_mix(pool, src_start, src_end, src_gain, n_samples, tables, valid_fram
                                            tables["max_taps"], _p(valid_frames), int(normalize), int(out_bf16), _p(out),
                                            _stream()), "logmel_mix_fwd")
     return out
+
+
+def resample_mix(pool, src_pos, src_begin, src_end, src_step, src_gain, src_filt, n_samples, filt, valid_samples=None):
+    """pool [total] f32 (stems end to end); src_pos / src_begin / src_end / src_step [B, n_src] int64 (32.32 position of
+    output 0, the stem's first sample, one past its last, 32.32 input samples per output sample), src_gain [B, n_src] f32
+    (0: not read), src_filt [B, n_src] int32 (table index, -1: pass-through); filt [n_filt, 513, n_taps] f32 polyphase
+    tables; valid_samples [B] int64 or None -> [B, n_samples] f32 rows, resampled and mixed
+    (include/mrmt3_hip.h: mrmt3_resample_mix_fwd)."""
+    _dev(pool, src_pos, src_begin, src_end, src_step, src_gain, src_filt, filt, valid_samples)
+    assert pool.dim() == 1 and pool.dtype == torch.float32 and pool.is_contiguous()
+    assert src_pos.dim() == 2 and src_pos.dtype == torch.int64 and src_pos.is_contiguous()
+    for t in (src_begin, src_end, src_step):
+        assert t.shape == src_pos.shape and t.dtype == torch.int64 and t.is_contiguous()
+    assert src_gain.shape == src_pos.shape and src_gain.dtype == torch.float32 and src_gain.is_contiguous()
+    assert src_filt.shape == src_pos.shape and src_filt.dtype == torch.int32 and src_filt.is_contiguous()
+    assert filt.dim() == 3 and filt.shape[1] == 513 and filt.dtype == torch.float32 and filt.is_contiguous()
+    B, n_src = src_pos.shape
+    assert valid_samples is None or (valid_samples.dtype == torch.int64 and valid_samples.is_contiguous()
+                                     and valid_samples.numel() == B)
+    out = torch.empty(B, int(n_samples), device=pool.device, dtype=torch.float32)
+    _check(load().mrmt3_resample_mix_fwd(_p(pool), pool.numel(), _p(src_pos), _p(src_begin), _p(src_end), _p(src_step),
+                                         _p(src_gain), _p(src_filt), n_src, B, int(n_samples), _p(filt), filt.shape[0],
+                                         filt.shape[2], _p(valid_samples), _p(out), _stream()), "resample_mix_fwd")
+    return out
+
+
+def resample_launches(reset: bool = False) -> int:
+    """Launches of `resample_mix` since the process started / the last reset (mrmt3_resample_launches): the resampler's
+    dispatch counter, kept apart from `dispatch_counts` so that an untouched step counts exactly as before."""
+    return int(load().mrmt3_resample_launches(int(reset)))
 
 
 def gemm_nt(a, b, out=None, out_dtype=None, accumulate=False):

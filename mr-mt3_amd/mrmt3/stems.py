@@ -1,6 +1,7 @@
 """Multi-stem tracks for stem-mix training: a folder of tracks, each a set of stems with their own MIDI.
 
-A track is a directory with `stems/<name>.wav` (mono, the config's sample rate, read with `contrib.audio_io`) and
+A track is a directory with `stems/<name>.wav` (mono, the config's sample rate — or, with `any_rate=True`, any rate from a
+quarter to four times that: the batcher resamples such a stem on the device when it uploads the track) and
 `MIDI/<name>.mid` (read with `contrib.midi_io`) — the layout of a Slakh track after resampling and WAV conversion.  A
 stem's program and drum flag come from its MIDI file (the first instrument that has notes); an optional `programs.json`
 next to the two directories, `{name: {"program": int, "is_drum": bool}}`, overrides them.  Nothing here knows an
@@ -8,7 +9,8 @@ instrument-class table: the programs are whatever the files say.
 
 `merged_note_sequence(track, kept)` is the DEFINITION of a mixed row's label: the notes of exactly the kept stems, the
 instrument index a stem's place among the kept ones, the length the track's.  `mrmt3.batching.StemMixBatcher` tokenises
-that sequence with `mrmt3.tokenizer.Tokenizer`.  Host code (numpy); no third-party dataset package.
+that sequence with `mrmt3.tokenizer.Tokenizer`.  `speed_note_sequence(ns, shift, step)` is the DEFINITION of the label of a
+pitch-shifted row: the track played at step / 2^32 times its speed.  Host code (numpy); no third-party dataset package.
 """
 from __future__ import annotations
 
@@ -30,11 +32,21 @@ class StemTrack:
     audio: list                  # [S] float32 [n_s] mono samples, unequal lengths allowed
     notes: list                  # [S] NoteSequence of the stem alone (program / is_drum set on every note)
     programs: list               # [S] (program, is_drum)
+    rates: list | None = None    # [S] sample rate of each stem's audio; None: every stem is at the config's rate
+
+    def lengths(self, sample_rate: int = 16000) -> list:
+        """Samples of every stem at `sample_rate`: its own length, or what `mrmt3.resample.resample` makes of it."""
+        if self.rates is None:
+            return [len(a) for a in self.audio]
+        from fractions import Fraction
+        from mrmt3.resample import out_length, ratio_step
+        return [len(a) if r == sample_rate else out_length(len(a), ratio_step(Fraction(int(r), int(sample_rate))))
+                for a, r in zip(self.audio, self.rates)]
 
     @property
     def n_samples(self) -> int:
-        """The track's length: its longest stem."""
-        return max(len(a) for a in self.audio)
+        """The track's length: its longest stem (at 16 kHz; `max(track.lengths(rate))` for another config)."""
+        return max(self.lengths())
 
     @property
     def total_time(self) -> float:
@@ -51,7 +63,26 @@ def merged_note_sequence(track: StemTrack, kept) -> NoteSequence:
     return out
 
 
-def load_track(path: str, sample_rate: int = 16000) -> StemTrack:
+def speed_note_sequence(ns: NoteSequence, shift: int, step: int) -> NoteSequence:
+    """`ns` played at step / 2^32 times its speed (32.32 fixed point, `mrmt3.resample.ratio_step(2 ** (shift / 12))`):
+    every start and end time and total_time multiplied by 2^32 / step in float64, every note that is not a drum note
+    transposed by `shift` semitones (drum notes keep their pitch: it names the instrument).  Copies; `ns` is untouched."""
+    scale = float(1 << 32) / float(int(step))
+    out = NoteSequence(total_time=ns.total_time * scale, ticks_per_quarter=ns.ticks_per_quarter)
+    for n in ns.notes:
+        out.notes.append(dataclasses.replace(n, start_time=n.start_time * scale, end_time=n.end_time * scale,
+                                             pitch=n.pitch if n.is_drum else n.pitch + int(shift)))
+    return out
+
+
+def shift_range(track: StemTrack):
+    """(lowest, highest) pitch shift in semitones that keeps every non-drum note of the track inside the codec's 0..127:
+    (-min_pitch, 127 - max_pitch); (-127, 127) for a track without pitched notes.  A function of the track alone."""
+    pitches = [n.pitch for ns in track.notes for n in ns.notes if not n.is_drum]
+    return (-min(pitches), 127 - max(pitches)) if pitches else (-127, 127)
+
+
+def load_track(path: str, sample_rate: int = 16000, any_rate: bool = False) -> StemTrack:
     stem_dir, midi_dir = os.path.join(path, "stems"), os.path.join(path, "MIDI")
     names = sorted(f[:-4] for f in os.listdir(stem_dir) if f.lower().endswith(".wav"))
     if not names:
@@ -60,12 +91,14 @@ def load_track(path: str, sample_rate: int = 16000) -> StemTrack:
     if os.path.exists(os.path.join(path, "programs.json")):
         with open(os.path.join(path, "programs.json")) as f:
             override = json.load(f)
-    audio, notes, programs = [], [], []
+    audio, notes, programs, rates = [], [], [], []
     for name in names:
         wav, mid = os.path.join(stem_dir, name + ".wav"), os.path.join(midi_dir, name + ".mid")
         x, rate = audio_io.read_wav(wav)
-        if rate != sample_rate:
+        if rate != sample_rate and not any_rate:
             raise ValueError(f"{wav}: sample rate {rate}, the config's is {sample_rate} (resample the stems first)")
+        if not sample_rate <= 4 * rate <= 16 * sample_rate:
+            raise ValueError(f"{wav}: sample rate {rate} is outside 1/4 to 4 times the config's {sample_rate}")
         if not os.path.exists(mid):
             raise ValueError(f"{wav}: the stem has no MIDI file ({mid} is missing)")
         midi = midi_io.read_midi(mid)
@@ -82,15 +115,16 @@ def load_track(path: str, sample_rate: int = 16000) -> StemTrack:
         audio.append(x)
         notes.append(ns)
         programs.append((program, is_drum))
-    return StemTrack(path, names, audio, notes, programs)
+        rates.append(int(rate))
+    return StemTrack(path, names, audio, notes, programs, rates if any(r != sample_rate for r in rates) else None)
 
 
-def load_stem_folder(root: str, sample_rate: int = 16000) -> list:
+def load_stem_folder(root: str, sample_rate: int = 16000, any_rate: bool = False) -> list:
     """Every track directory under `root` (one that holds `stems/`), in name order."""
     dirs = sorted(d for d in os.listdir(root) if os.path.isdir(os.path.join(root, d, "stems")))
     if not dirs:
         raise ValueError(f"{root}: no track directories (a track holds stems/<name>.wav and MIDI/<name>.mid)")
-    return [load_track(os.path.join(root, d), sample_rate) for d in dirs]
+    return [load_track(os.path.join(root, d), sample_rate, any_rate) for d in dirs]
 
 
 def epoch_order(n_tracks: int, seed: int, epoch: int) -> list:

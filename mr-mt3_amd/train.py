@@ -26,6 +26,10 @@ the least number that do, `+stem_gain_db=` (6) the gain range in dB.  Row geomet
 `event_length`, `num_rows_per_batch`, `split_frame_length`, `dataloader.train.batch_size` tracks per step); the track
 order is a function of (seed, epoch) and the ranks take disjoint shards of it.  `+stem_val_root=DIR` gives `val_loss` on
 the deterministic full mix of those tracks.  The rows carry no `targets_prev`: a `*WithPrev` model is refused.
+`+stem_pitch_shift=N` (0) plays every track visit at 2^(k/12) times its speed, k drawn from [-N, N] semitones:
+audio resampled on the device, labels transposed and rescaled in time; `+stem_native_rate=true` accepts stems at a quarter
+to four times the config's rate (Slakh's 44.1 kHz) and resamples them on the device when a track is uploaded.  Validation
+batches stay deterministic and unshifted.  With either on the run ends with `resample_launches K`.
 
 Gradient accumulation: `cfg.trainer.accumulate_grad_batches` (the reference's `${grad_accum}`), else a top-level
 `grad_accum`, else 1 — Lightning's semantics (mrmt3/trainer.py): the optimizer steps after every N-th batch and after an
@@ -133,8 +137,10 @@ class SkippingBatchSampler(torch.utils.data.BatchSampler):
 
 def stem_options(cfg, with_prev=False):
     """None without `+stem_root`; else dict(root, val_root, keep, gain_db, min_stems) from `+stem_root=DIR`,
-    `+stem_val_root=DIR`, `+stem_keep=` (default 0.75), `+stem_gain_db=` (6.0) and `+stem_min=` (1), validated like the
-    other options: a ValueError names the key.  Stem-mix rows carry no `targets_prev`: a `*WithPrev` model is refused."""
+    `+stem_val_root=DIR`, `+stem_keep=` (default 0.75), `+stem_gain_db=` (6.0) and `+stem_min=` (1), plus `pitch_shift`
+    and `native_rate` when `+stem_pitch_shift=` (semitones, default 0) / `+stem_native_rate=` (default false) are given,
+    validated like the other options: a ValueError names the key.  Stem-mix rows carry no `targets_prev`: a `*WithPrev`
+    model is refused."""
     root = cfg.get("stem_root")
     if root is None or str(root).lower() in ("", "none", "null"):
         return None
@@ -146,20 +152,31 @@ def stem_options(cfg, with_prev=False):
     val_root = None if val_root is None or str(val_root).lower() in ("", "none", "null") else str(val_root)
     out = {"root": str(root), "val_root": val_root}
     for key, name, default, cast in (("stem_keep", "keep", 0.75, float), ("stem_gain_db", "gain_db", 6.0, float),
-                                     ("stem_min", "min_stems", 1, int)):
+                                     ("stem_min", "min_stems", 1, int), ("stem_pitch_shift", "pitch_shift", 0, int)):
         raw = cfg.get(key)
+        if raw is None and key == "stem_pitch_shift":
+            continue                         # (the two newer keys appear in the result only when they are given)
         try:
-            if isinstance(raw, bool):
+            if isinstance(raw, bool) or (key == "stem_pitch_shift" and isinstance(raw, float) and raw != int(raw)):
                 raise ValueError
             out[name] = default if raw is None else cast(raw)
         except (TypeError, ValueError):
             raise ValueError("%s must be a number, got %r" % (key, raw)) from None
+    native = cfg.get("stem_native_rate")
+    if native is not None:
+        if isinstance(native, str) and native.lower() in ("true", "false"):
+            native = native.lower() == "true"
+        if not isinstance(native, bool):
+            raise ValueError("stem_native_rate must be true or false, got %r" % (native,))
+        out["native_rate"] = native
     if not 0.0 <= out["keep"] <= 1.0:
         raise ValueError("stem_keep must be in [0, 1], got %r" % (out["keep"],))
     if not 0.0 <= out["gain_db"] < float("inf"):
         raise ValueError("stem_gain_db must be finite and >= 0, got %r" % (out["gain_db"],))
     if out["min_stems"] < 1:
         raise ValueError("stem_min must be at least 1, got %r" % (out["min_stems"],))
+    if not 0 <= out.get("pitch_shift", 0) <= 24:
+        raise ValueError("stem_pitch_shift must be an int in [0, 24] (semitones), got %r" % (out["pitch_shift"],))
     return out
 
 
@@ -208,12 +225,14 @@ def stem_loaders(cfg, opts, device, world=1, rank=0):
     geom = dict(mel_length=int(cfg.mel_length), event_length=int(cfg.event_length),
                 num_rows_per_batch=int(cfg.num_rows_per_batch), split_frame_length=int(cfg.get("split_frame_length", 2000)))
     per = int(cfg.dataloader.train.batch_size)
-    train = StemLoader(stems.load_stem_folder(opts["root"]),
-                       StemMixBatcher(device, keep_prob=opts["keep"], min_stems=opts["min_stems"], gain_db=opts["gain_db"], **geom),
+    native = dict(any_rate=True) if opts.get("native_rate") else {}
+    train = StemLoader(stems.load_stem_folder(opts["root"], **native),
+                       StemMixBatcher(device, keep_prob=opts["keep"], min_stems=opts["min_stems"], gain_db=opts["gain_db"],
+                                      pitch_shift=opts.get("pitch_shift", 0), **geom),
                        per, cfg.seed, rank, world)
     val = None
     if opts["val_root"] is not None:
-        val = StemLoader(stems.load_stem_folder(opts["val_root"]), StemMixBatcher(device, is_deterministic=True, **geom),
+        val = StemLoader(stems.load_stem_folder(opts["val_root"], **native), StemMixBatcher(device, is_deterministic=True, **geom),
                          1, cfg.seed, rank, world, shuffle=False)
     return train, val
 
@@ -504,6 +523,9 @@ def main(argv=None):
         skipped = trainer.skipped_steps          # (every rank skips the same steps: the norm is of the exchanged gradient)
         if skipped > 0:
             print(f"skipped_steps {skipped}", flush=True)
+    if rank == 0 and stem is not None and (stem.get("pitch_shift") or stem.get("native_rate")):
+        from mrmt3 import lib
+        print(f"resample_launches {lib.resample_launches()}", flush=True)      # (this rank's: shifted rows + uploaded stems)
     if rank == 0:
         out_dir = os.path.join(str(cfg.get("output_dir", ".")), f"{cfg.model_type}_{cfg.dataset_type}",
                                "version_0", "checkpoints")
