@@ -179,6 +179,65 @@ int mrmt3_resample_mix_fwd(const float* pool, long long pool_samples, const long
  * counter, kept apart from mrmt3_dispatch_counts so that MRMT3_CNT_N and the counters of an untouched step stay as they are. */
 unsigned long long mrmt3_resample_launches(int reset);
 
+/* Stem-mix labels built on the device: the padded target row of every training row, straight from the track's
+ * note table, one launch for the whole batch.  A row's targets are by definition Tokenizer.row_targets of the tokenisation
+ * of the merged, speed-changed track (mrmt3/stems.py); they are a function of the kept stems' notes, the row's frame window
+ * and the speed factor alone, and this entry computes that function.  mrmt3.labels.label_rows_host restates it on the host.
+ *
+ * The note table (DEVICE, one per track, every stem's notes in stem order; mrmt3.labels.note_table):
+ *   note_times [n_notes][2] f64: start and end in seconds, exactly as loaded, finite and >= 0;
+ *   note_meta  [n_notes][4] int32, 16-byte aligned: pitch (0..127), velocity bin, program | is_drum << 8 | stem << 16, and
+ *     `next`: the index of the note's successor in its (pitch, program, is_drum) group ordered by (start, index) over ALL
+ *     stems, -1 for the group's last note.
+ * Per row, DEVICE arrays [batch]: keep (uint64, bit s: stem s sounds), start_frame, n_frames, total_frames (int64; the
+ * tokenizer's frame count of the stretched track, (n + hop - n % hop) / hop), scale (f64, 2^32 / step), shift (int32,
+ * semitones).  The codec and the frames are passed by value: the first token of the pitch, velocity, program and drum
+ * ranges and the tie token, max_shift_steps, steps_per_second (sps), sample_rate and hop (frames per second, fps, is their
+ * f64 quotient), event_length, num_special_tokens.
+ * Nothing bars a different scale and shift in every row.
+ *
+ * The row (tokens are codec ids; a shift of k steps is the id k):
+ *  - Notes: the kept stems' notes in table order.  With shift != 0 a time becomes t * scale in f64, one rounding, and
+ *    pitch + shift applies to notes that are not drum notes; with shift == 0 both are untouched.
+ *  - Trim: in every (pitch, program, is_drum) group, ordered by start time (equal starts in table order), a note whose end
+ *    is greater than its successor's start ends at that start; then notes with start >= end are dropped.  The successor is
+ *    the one AMONG THE KEPT STEMS (the kernel follows `next` to the first kept note).
+ *  - Events: every note that is not a drum note gives an off event (velocity bin 0) at its end, every note an on event at
+ *    its start; ordered by scaled f64 time, off before on, pitched before drum, program, pitch, table index.  The step of
+ *    an event is rint(time * steps_per_second), half to even, in f64.
+ *  - Window: s0(f) = the largest step s with s / sps <= f / fps, both quotients in f64.  The row's events are those with
+ *    s0(start_frame) <= step, and step < s0(start_frame + n_frames) if start_frame + n_frames < total_frames: a row that
+ *    ends on the track's last frame takes everything up to the end.
+ *  - Tie section: the (program, pitch) pairs whose last event with step < min(s0(start_frame), S_last) is an on event,
+ *    S_last the step of the subset's last event, ordered by (program, pitch), emitted as `program, pitch`, then `tie`.
+ *    The min restates a quirk of the reference's encode_and_index_events: its state mark stops advancing in the trailing
+ *    loop, so a row behind the last note repeats the state before the last step's first event (one note 0.1-0.5 s gives
+ *    `program, pitch, tie` for every row after it).
+ *  - Walk: the tie section at time 0, then every event emits `program, velocity, pitch`, a drum note `velocity, drum`.  A
+ *    velocity or program token equal to the one in force is skipped (the tie section's program tokens count).  Before the
+ *    first token an event emits after time has advanced, the shift is written: the time since the row's first step, in
+ *    chunks of max_shift_steps, largest first.  Trailing shifts do not exist.
+ *  - A kept subset without any event gives `tie` alone (the host tokenizer raises IndexError there).
+ *  - targets [batch][event_length] int64 in pad_targets form: truncated to event_length, + num_special_tokens, EOS (1) only
+ *    where there is room, -100 behind it.
+ * Capacity: a row holds at most 2048 events in its window and 2048 tie pairs (LDS).  A row that needs more is NOT exact
+ * and says so: status [batch] int32 is 0 for a row built as above, else a sum of 1 (events over capacity), 2 (tie pairs
+ * over capacity), 4 (scaling made two start times of a group equal, so that `next` no longer gives the group's order),
+ * 8 (a shifted pitch, a program or a velocity bin outside 0..127; the note is left out).  The caller rebuilds such a row on
+ * the host.  Whatever the table holds, the kernel reads nothing outside it and follows at most n_notes links per note.
+ * MRMT3_ERR_INVALID_ARG before any launch: a null pointer (the table's two excepted when n_notes == 0), n_stems outside
+ * [1, 64], n_notes < 0, batch, event_length, max_shift_steps, steps_per_second, sample_rate or hop <= 0, a negative
+ * token base, note_meta not 16-byte aligned. */
+int mrmt3_label_rows_fwd(const double* note_times, const int* note_meta, int n_notes, int n_stems,
+                         const unsigned long long* keep, const long long* start_frame, const long long* n_frames,
+                         const long long* total_frames, const double* scale, const int* shift, int batch,
+                         int pitch_base, int velocity_base, int tie_token, int program_base, int drum_base,
+                         int max_shift_steps, int steps_per_second, int sample_rate, int hop, int event_length,
+                         int num_special_tokens, long long* targets, int* status, void* stream);
+/* Launches of mrmt3_label_rows_fwd since the process started (or since the last call with reset != 0); kept apart from
+ * mrmt3_dispatch_counts like the resampler's. */
+unsigned long long mrmt3_label_launches(int reset);
+
 /* ---- K2/K4/K6/K7/K9: bias-free Linear layers (nn.Linear(bias=False) inside HF T5Block,
  * models/t5.py:51,72,487-490) ----------------------------------------------------------------------
  * NT:  C[M,N] (+)= A[M,K] . B[N,K]^T      forward y = x W^T, and dgrad with a pre-transposed W.

@@ -230,12 +230,20 @@ class StemMixBatcher:
     leaves the codec's pitches; the whole track visit is played at 2^(k/12) times its speed — the rows are resampled and
     mixed by `mrmt3_resample_mix_fwd` and go through `mrmt3_logmel_fwd`, the labels are those of
     `mrmt3.stems.speed_note_sequence`.  k = 0 and `pitch_shift=0` are the launch above, untouched.  A stem whose
-    `track.rates` entry is not the config's rate is resampled on the device, once, when the track is uploaded."""
+    `track.rates` entry is not the config's rate is resampled on the device, once, when the track is uploaded.
+
+    `device_labels=True`: `build` makes the targets with one launch of `mrmt3_label_rows_fwd` over the track's
+    note table, which lives on the device beside the pool; no tokenisation of the whole track, and the same targets.  It
+    accepts only the tokenizer configuration the kernel implements (ties, no onsets-only, training trim, no token-order
+    augmentation, the codec's own velocity bins): a ValueError names the option.  `with_prev=True` (needs
+    `device_labels`) adds `targets_prev`, `Tokenizer.row_targets_prev` row by row, for the `*WithPrev` models.  With both
+    off every call and every bit is what it was."""
 
     def __init__(self, device, mel_length: int = 256, event_length: int = 1024, num_rows_per_batch: int = 12,
                  split_frame_length: int = 2000, keep_prob: float = 0.75, min_stems: int = 1, gain_db: float = 6.0,
                  is_deterministic: bool = False, tokenizer=None, rng=None, cache_bytes: int = 8 << 30,
-                 spectrogram_config=None, out_bf16: bool = False, pitch_shift: int = 0):
+                 spectrogram_config=None, out_bf16: bool = False, pitch_shift: int = 0, device_labels: bool = False,
+                 with_prev: bool = False):
         from collections import OrderedDict
         from contrib import spectrograms
         from mrmt3.tokenizer import Tokenizer
@@ -255,6 +263,14 @@ class StemMixBatcher:
         self.is_deterministic, self.out_bf16, self.rng = is_deterministic, out_bf16, rng
         self.pitch_shift = int(pitch_shift)
         self.tokenizer = tokenizer or Tokenizer(spectrogram_config=self.cfg)
+        self.device_labels, self.with_prev = bool(device_labels), bool(with_prev)
+        if self.with_prev and not self.device_labels:
+            raise ValueError("with_prev=True needs device_labels=True: targets_prev is built by the label kernel only")
+        if self.device_labels:
+            from mrmt3.labels import label_codec
+            self._codec = label_codec(self.tokenizer)        # ValueError: a tokenizer option the kernel does not implement
+        self._notes = {}                     # track.name -> (NoteTable on the device), beside the track's pool
+        self.host_label_rows = 0             # rows the label kernel handed back (status != 0), rebuilt on the host
         self.cache_bytes = int(cache_bytes)
         self._pools = OrderedDict()          # track.name -> (pool on the device, offsets, lengths), least recent first
         self._feats = OrderedDict()          # (track.name, kept, shift) -> Tokenizer.tokenize(...)
@@ -306,14 +322,18 @@ class StemMixBatcher:
             self._feats.popitem(last=False)
         return feats
 
+    def _host_row(self, track, plan: StemMixPlan, b: int, prev: bool = False):
+        """Token ids of row b of the plan, or of its previous window, by the host tokenizer."""
+        kept = tuple(int(s) for s in np.nonzero(plan.keep[b])[0])
+        feats = self._tokenized(track, kept, plan.shift, plan.step)
+        if prev:
+            return self.tokenizer.row_targets_prev(feats, int(plan.crops.start_frame[b]), int(plan.crops.chunk_start[b]),
+                                                   self.mel_length)
+        return self.tokenizer.row_targets(feats, int(plan.crops.start_frame[b]), int(plan.crops.valid_frames[b]))
+
     def row_targets(self, track, plan: StemMixPlan):
         """Token ids of every row of the plan (a list of 1-D int arrays, before `pad_targets`)."""
-        out = []
-        for b in range(len(plan.crops.start_frame)):
-            kept = tuple(int(s) for s in np.nonzero(plan.keep[b])[0])
-            out.append(self.tokenizer.row_targets(self._tokenized(track, kept, plan.shift, plan.step), int(plan.crops.start_frame[b]),
-                                                  int(plan.crops.valid_frames[b])))
-        return out
+        return [self._host_row(track, plan, b) for b in range(len(plan.crops.start_frame))]
 
     def tables(self, track, plan: StemMixPlan):
         """(start_frames, src_end, src_gain, pool_samples) of the plan on the host, checked."""
@@ -360,10 +380,20 @@ class StemMixBatcher:
                 dev[int(off):int(off) + n] = y
         torch.cuda.current_stream(self.device).synchronize()          # (the pinned buffer is released on return)
         self._pools[track.name] = dev
+        if self.device_labels:               # the note table travels, counts and leaves with the pool
+            from mrmt3.labels import note_table
+            tab = note_table(track, self._codec.num_velocity_bins)
+            self._notes[track.name] = (torch.from_numpy(tab.times).to(self.device), torch.from_numpy(tab.meta).to(self.device),
+                                       tab.n_stems)
         self.uploads += 1
-        while len(self._pools) > 1 and sum(p.numel() * 4 for p in self._pools.values()) > self.cache_bytes:
-            self._pools.popitem(last=False)
+        while len(self._pools) > 1 and self.cached_bytes() > self.cache_bytes:
+            self._notes.pop(self._pools.popitem(last=False)[0], None)
         return dev
+
+    def cached_bytes(self) -> int:
+        """Device bytes the cache holds: every track's pool and, with `device_labels`, its note table."""
+        return (sum(p.numel() * 4 for p in self._pools.values())
+                + sum(t.numel() * 8 + m.numel() * 4 for t, m, _ in self._notes.values()))
 
     def cached_tracks(self) -> list:
         return list(self._pools)
@@ -393,8 +423,52 @@ class StemMixBatcher:
                           valid_frames=torch.from_numpy(plan.crops.valid_frames).to(dev), normalize=True,
                           out_bf16=self.out_bf16)
 
+    def prev_windows(self, plan: StemMixPlan) -> np.ndarray:
+        """bool [B]: the rows that have a previous window, frames [start - mel_length, start) of their own chunk
+        (`Tokenizer.row_targets_prev`); the others carry the placeholder."""
+        return plan.crops.start_frame - plan.crops.chunk_start - self.mel_length > 0
+
+    def row_targets_prev(self, track, plan: StemMixPlan):
+        """Token ids of every row's previous window on the host (a list of 1-D int arrays, before `pad_targets`)."""
+        return [self._host_row(track, plan, b, prev=True) for b in range(len(plan.crops.start_frame))]
+
+    def device_targets(self, track, plan: StemMixPlan):
+        """`targets` — and with `with_prev` `targets_prev` — of the plan by ONE launch of the label kernel,
+        already padded and on the device.  The previous windows are further rows of the same launch; a row without one has
+        an empty stem mask, for which the kernel writes `tie` alone: the placeholder's encoded form.  The status words are
+        read back once; a row the kernel could not hold is rebuilt by the host path, and only that row."""
+        from mrmt3 import lib
+        from mrmt3.labels import keep_masks, tokenizer_frames
+        self.pool(track)                                                     # (uploads the note table with the audio)
+        times, meta, n_stems = self._notes[track.name]
+        B = len(plan.crops.start_frame)
+        n = 2 * B if self.with_prev else B
+        arg = np.zeros((5, n), np.int64)                                     # keep, start_frame, n_frames, total_frames, scale
+        arg[0, :B] = keep_masks(plan.keep).view(np.int64)
+        arg[1, :B], arg[2, :B] = plan.crops.start_frame, plan.crops.valid_frames
+        if self.with_prev:
+            has = self.prev_windows(plan)
+            arg[0, B:] = np.where(has, arg[0, :B], 0)
+            arg[1, B:], arg[2, B:] = np.where(has, plan.crops.start_frame - self.mel_length, 0), self.mel_length
+        arg[3] = tokenizer_frames(self.n_samples(track, plan.step), self.cfg.hop_width)
+        arg[4] = np.full(n, float(1 << 32) / float(int(plan.step)), np.float64).view(np.int64)
+        raw = np.concatenate([arg.reshape(-1).view(np.uint8), np.full(n, plan.shift, np.int32).view(np.uint8)])
+        dev = torch.from_numpy(raw).to(self.device)                          # one copy for the six arrays
+        a = dev[:40 * n].view(torch.int64).view(5, n)
+        tg, status = lib.label_rows(times, meta, n_stems, a[0], a[1], a[2], a[3], a[4].view(torch.float64),
+                                    dev[40 * n:].view(torch.int32), self._codec, self.event_length)
+        bad = np.nonzero(status.cpu().numpy())[0]
+        if len(bad):
+            self.host_label_rows += len(bad)
+            fixed = pad_targets([self._host_row(track, plan, int(b) % B, prev=b >= B) for b in bad], self.event_length)
+            tg[torch.from_numpy(bad).to(self.device)] = fixed.to(self.device)
+        return (tg[:B], tg[B:]) if self.with_prev else (tg,)
+
     def build(self, track, plan: StemMixPlan | None = None):
+        """`(mel, targets)`; `(mel, targets, targets_prev)` with `with_prev`."""
         plan = plan or self.plan(track)
         mel = self.mel(track, plan)
+        if self.device_labels:
+            return (mel,) + self.device_targets(track, plan)
         tg = pad_targets(self.row_targets(track, plan), self.event_length)
         return mel, tg.to(self.device, non_blocking=True)

@@ -106,7 +106,7 @@ def load():
     return lib
 
 
-MIN_VERSION = 124
+MIN_VERSION = 125
 COUNTER_NAMES = ("gemm_nt_tile", "gemm_nt8", "gemm_nt_geglu", "tn_group", "tn8", "tn_tile", "attn_fwd", "attn_bwd",
                  "attn_bwd_onepass", "attn_f32", "tn_f32", "gemm_nt_splitk", "gemm_nt_addnorm", "gemm_nt_normbwd",
                  "gemm_nt_geglubwd", "attn_fwd_varlen", "attn_bwd_varlen", "logmel_wave", "logmel_general")
@@ -274,6 +274,40 @@ def resample_launches(reset: bool = False) -> int:
     """Launches of `resample_mix` since the process started / the last reset (mrmt3_resample_launches): the resampler's
     dispatch counter, kept apart from `dispatch_counts` so that an untouched step counts exactly as before."""
     return int(load().mrmt3_resample_launches(int(reset)))
+
+
+LABEL_CAPACITY = 2048        # events of one row's window, and tie pairs, that mrmt3_label_rows_fwd holds (an ABI constant)
+
+
+def label_rows(note_times, note_meta, n_stems, keep, start_frame, n_frames, total_frames, scale, shift, codec,
+               event_length=1024):
+    """note_times [N, 2] f64 and note_meta [N, 4] int32 (a `mrmt3.labels.NoteTable` on the device); keep [B] int64 holding
+    the uint64 stem masks, start_frame / n_frames / total_frames [B] int64, scale [B] f64, shift [B] int32; `codec` a
+    `mrmt3.labels.LabelCodec` -> (targets [B, event_length] int64 in `pad_targets` form, status [B] int32, 0 where the row
+    is exact) (include/mrmt3_hip.h: mrmt3_label_rows_fwd)."""
+    _dev(note_times, note_meta, keep, start_frame, n_frames, total_frames, scale, shift)
+    N = note_meta.shape[0]
+    assert note_times.shape == (N, 2) and note_times.dtype == torch.float64 and note_times.is_contiguous()
+    assert note_meta.shape == (N, 4) and note_meta.dtype == torch.int32 and note_meta.is_contiguous()
+    B = keep.numel()
+    for t in (keep, start_frame, n_frames, total_frames):
+        assert t.shape == (B,) and t.dtype == torch.int64 and t.is_contiguous()
+    assert scale.shape == (B,) and scale.dtype == torch.float64 and scale.is_contiguous()
+    assert shift.shape == (B,) and shift.dtype == torch.int32 and shift.is_contiguous()
+    targets = torch.empty(B, int(event_length), device=keep.device, dtype=torch.int64)
+    status = torch.empty(B, device=keep.device, dtype=torch.int32)
+    _check(load().mrmt3_label_rows_fwd(
+        _p(note_times) if N else None, _p(note_meta) if N else None, N, int(n_stems), _p(keep), _p(start_frame),
+        _p(n_frames), _p(total_frames), _p(scale), _p(shift), B, codec.pitch_base, codec.velocity_base, codec.tie_token,
+        codec.program_base, codec.drum_base, codec.max_shift_steps,
+        codec.steps_per_second, codec.sample_rate, codec.hop, int(event_length), codec.num_special_tokens, _p(targets),
+        _p(status), _stream()), "label_rows_fwd")
+    return targets, status
+
+
+def label_launches(reset: bool = False) -> int:
+    """Launches of `label_rows` since the process started / the last reset (mrmt3_label_launches)."""
+    return int(load().mrmt3_label_launches(int(reset)))
 
 
 def gemm_nt(a, b, out=None, out_dtype=None, accumulate=False):

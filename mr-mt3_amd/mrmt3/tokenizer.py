@@ -142,6 +142,18 @@ class Tokenizer:
             row = self.remove_redundant_tokens(self.randomize_tokens(row, rng))
         return row
 
+    def row_targets_prev(self, feats: dict, start_frame: int, chunk_start: int, mel_length: int) -> np.ndarray:
+        """`targets_prev` of a row (reference dataset/dataset_2_random_segmem_prev.py:73-94, 147-153): a previous window
+        exists iff the row starts more than `mel_length` frames into its chunk (`start_length - mel_length > 0`); it is then
+        the frames [start_frame - mel_length, start_frame) with their own tie section.  Every other row — a deterministic
+        one always — carries the placeholder `[tie, shift 1]` (the reference's raw ids 1131, 1 in its codec), which goes
+        through the same run-length encoding: the trailing shift is dropped."""
+        if start_frame - chunk_start - mel_length > 0:
+            return self.row_targets(feats, start_frame - mel_length, mel_length)
+        if self.tie_token is None:
+            raise ValueError("row_targets_prev: the placeholder is the tie token, the tokenizer has include_ties=False")
+        return self.run_length_encode_shifts([self.tie_token, self.codec.encode_event(event_codec.Event("shift", 1))])
+
     def targets_for_crop(self, feats: dict, rng=None):
         """`(start_frame, n_frames) -> token ids` for `mrmt3.batching.DeviceBatcher.build`."""
         return lambda start_frame, n_frames: self.row_targets(feats, start_frame, n_frames, rng)

@@ -25,7 +25,9 @@ of a track's stems at random gains, mixed inside the log-mel kernel, labelled wi
 the least number that do, `+stem_gain_db=` (6) the gain range in dB.  Row geometry is the config's (`mel_length`,
 `event_length`, `num_rows_per_batch`, `split_frame_length`, `dataloader.train.batch_size` tracks per step); the track
 order is a function of (seed, epoch) and the ranks take disjoint shards of it.  `+stem_val_root=DIR` gives `val_loss` on
-the deterministic full mix of those tracks.  The rows carry no `targets_prev`: a `*WithPrev` model is refused.
+the deterministic full mix of those tracks.  `+stem_device_labels=true` builds the targets on the device, one
+launch per track visit, instead of tokenising whole tracks on the host: the same targets, and `targets_prev` with them,
+so a `*WithPrev` model trains from stems (without the option it is refused); the run then ends with `label_launches K`.
 `+stem_pitch_shift=N` (0) plays every track visit at 2^(k/12) times its speed, k drawn from [-N, N] semitones:
 audio resampled on the device, labels transposed and rescaled in time; `+stem_native_rate=true` accepts stems at a quarter
 to four times the config's rate (Slakh's 44.1 kHz) and resamples them on the device when a track is uploaded.  Validation
@@ -139,12 +141,19 @@ def stem_options(cfg, with_prev=False):
     """None without `+stem_root`; else dict(root, val_root, keep, gain_db, min_stems) from `+stem_root=DIR`,
     `+stem_val_root=DIR`, `+stem_keep=` (default 0.75), `+stem_gain_db=` (6.0) and `+stem_min=` (1), plus `pitch_shift`
     and `native_rate` when `+stem_pitch_shift=` (semitones, default 0) / `+stem_native_rate=` (default false) are given,
-    validated like the other options: a ValueError names the key.  Stem-mix rows carry no `targets_prev`: a `*WithPrev`
-    model is refused."""
+    validated like the other options: a ValueError names the key; likewise `device_labels` when
+    `+stem_device_labels=` (default false) is given.  Only the label kernel builds `targets_prev`: without
+    `+stem_device_labels=true` a `*WithPrev` model is refused."""
     root = cfg.get("stem_root")
     if root is None or str(root).lower() in ("", "none", "null"):
         return None
-    if with_prev:
+    labels = cfg.get("stem_device_labels")
+    if labels is not None:
+        if isinstance(labels, str) and labels.lower() in ("true", "false"):
+            labels = labels.lower() == "true"
+        if not isinstance(labels, bool):
+            raise ValueError("stem_device_labels must be true or false, got %r" % (labels,))
+    if with_prev and not labels:
         raise ValueError("+stem_root builds (mel, targets) rows only: targets_prev, which the *WithPrev models train "
                          "on, is not built by the stem batcher (DESIGN 4j, out of scope) — train them through "
                          "cfg.dataset or +synthetic=True")
@@ -169,6 +178,8 @@ def stem_options(cfg, with_prev=False):
         if not isinstance(native, bool):
             raise ValueError("stem_native_rate must be true or false, got %r" % (native,))
         out["native_rate"] = native
+    if labels is not None:
+        out["device_labels"] = labels
     if not 0.0 <= out["keep"] <= 1.0:
         raise ValueError("stem_keep must be in [0, 1], got %r" % (out["keep"],))
     if not 0.0 <= out["gain_db"] < float("inf"):
@@ -183,7 +194,7 @@ def stem_options(cfg, with_prev=False):
 class StemLoader:
     """The training (or validation) "loader" of `+stem_root`: an epoch visits this rank's shard of the tracks,
     `tracks_per_step` per batch, every track one `StemMixBatcher.build` — `(mel [rows, mel_length, 512], targets
-    [rows, event_length])` already on the device.  The track order is `mrmt3.stems.epoch_order(seed, epoch)`, the ranks
+    [rows, event_length])`, and `targets_prev` behind them when the batcher builds it, already on the device.  The track order is `mrmt3.stems.epoch_order(seed, epoch)`, the ranks
     take disjoint shards of it (`rank_shard`), and the batcher's draws restart from (seed, epoch, rank) with every
     epoch.  `shuffle=False` (validation: the deterministic full mix) keeps the folder's order.  Has what
     `loader_batches` asks of a loader and of a sampler: `len()`, iteration, `set_epoch`."""
@@ -213,10 +224,10 @@ class StemLoader:
         self.batcher.rng = random.Random((self.seed * 1000003 + self.epoch) * 4099 + self.rank)
         for i in range(0, len(shard), self.per):
             built = [self.batcher.build(self.tracks[t]) for t in shard[i:i + self.per]]
-            yield torch.cat([b[0] for b in built]), torch.cat([b[1] for b in built])
+            yield tuple(torch.cat([b[k] for b in built]) for k in range(len(built[0])))
 
 
-def stem_loaders(cfg, opts, device, world=1, rank=0):
+def stem_loaders(cfg, opts, device, world=1, rank=0, with_prev=False):
     """(train StemLoader, validation StemLoader or None) over `+stem_root` / `+stem_val_root`; the row geometry is the
     config's (`mel_length`, `event_length`, `num_rows_per_batch`, `split_frame_length`, `dataloader.train.batch_size`
     tracks per step)."""
@@ -226,6 +237,8 @@ def stem_loaders(cfg, opts, device, world=1, rank=0):
                 num_rows_per_batch=int(cfg.num_rows_per_batch), split_frame_length=int(cfg.get("split_frame_length", 2000)))
     per = int(cfg.dataloader.train.batch_size)
     native = dict(any_rate=True) if opts.get("native_rate") else {}
+    if opts.get("device_labels"):
+        geom.update(device_labels=True, with_prev=with_prev)
     train = StemLoader(stems.load_stem_folder(opts["root"], **native),
                        StemMixBatcher(device, keep_prob=opts["keep"], min_stems=opts["min_stems"], gain_db=opts["gain_db"],
                                       pitch_shift=opts.get("pitch_shift", 0), **geom),
@@ -429,7 +442,7 @@ def main(argv=None):
     train_loader = val_loader = sampler = None
     stem = None if synthetic else stem_options(cfg, with_prev)
     if stem is not None:
-        train_loader, val_loader = stem_loaders(cfg, stem, device, world, rank)
+        train_loader, val_loader = stem_loaders(cfg, stem, device, world, rank, with_prev)
         sampler = train_loader                   # (`set_epoch`: the track order is a function of (seed, epoch))
     elif not synthetic:
         train_loader, val_loader, sampler = real_loaders(cfg, world, rank)
@@ -526,6 +539,9 @@ def main(argv=None):
     if rank == 0 and stem is not None and (stem.get("pitch_shift") or stem.get("native_rate")):
         from mrmt3 import lib
         print(f"resample_launches {lib.resample_launches()}", flush=True)      # (this rank's: shifted rows + uploaded stems)
+    if rank == 0 and stem is not None and stem.get("device_labels"):
+        from mrmt3 import lib
+        print(f"label_launches {lib.label_launches()}", flush=True)            # (this rank's: one per track visit)
     if rank == 0:
         out_dir = os.path.join(str(cfg.get("output_dir", ".")), f"{cfg.model_type}_{cfg.dataset_type}",
                                "version_0", "checkpoints")
