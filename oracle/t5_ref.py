@@ -268,7 +268,7 @@ def generate_t5_cached(sd, cfg, mel, max_length=1024):
     return ids
 
 
-def decode_step_logits(sd, cfg, ids, ck, cv, prefix=None, rnd=None):
+def decode_step_logits(sd, cfg, ids, ck, cv, prefix=None, rnd=None, pos=None):
     """Teacher-forced restatement of one KV-cached greedy decode (`generate_t5_cached`'s structure) in float64: the
     lm_head logits of EVERY step, [B, n_prefix + T, V], for decoder inputs `ids` [B, T] (start token first) after
     `prefix` [B, n_prefix, d] memory rows (`generate_2`; fed without the positional term, which is added here).
@@ -279,7 +279,8 @@ def decode_step_logits(sd, cfg, ids, ck, cv, prefix=None, rnd=None):
     decode's.  `rnd` (None = exact) is applied where csrc/decode.hip rounds to the weights' dtype: the normed
     activation entering every projection (lm_head included), the attention output before an O projection, the gated
     GELU output before wo, and each self-attention K/V cache entry.  The residual stream, q, the scores and the
-    softmax stay unrounded."""
+    softmax stay unrounded.  `pos` [>= n_prefix + T, d]: the positional rows to add instead of the sinusoid table (a
+    decoder handle takes its table from the caller)."""
     H, eps, L = cfg["num_heads"], cfg["layer_norm_epsilon"], cfg["num_decoder_layers"]
     r = (lambda t: t) if rnd is None else rnd
     W = lambda k: sd[k].double()
@@ -288,7 +289,7 @@ def decode_step_logits(sd, cfg, ids, ck, cv, prefix=None, rnd=None):
     if prefix is not None:
         x = torch.cat([prefix.double(), x], dim=1)
     B, T, d = x.shape
-    x = x + pos_emb(T, d)[0].double()
+    x = x + (pos_emb(T, d)[0] if pos is None else pos[:T]).double()
     dk = blk(0, "0.SelfAttention.q").shape[0] // H
     heads = lambda t: t.reshape(B, -1, H, dk).transpose(1, 2)
     causal = torch.ones(T, T, dtype=torch.bool).tril()
