@@ -749,6 +749,7 @@ typedef struct {
   int eos, pad;
   int max_shift_steps;        /* a shift run may not carry time past this many steps from the segment start */
   int tie_section;            /* 1: a row starts in the tie section, 0: in the body */
+  int steps_per_second;       /* the codec's time grid; read by mrmt3_notes_decode_fwd alone (the grammar counts steps) */
 } mrmt3_grammar;
 #define MRMT3_GRAMMAR_SET_BYTES 2048   /* a 128 x 128 bit set over (program, pitch): bit program * 128 + pitch, LSB first */
 /* Stand-alone state (the decoder owns one of its own): `state` is caller-owned device memory of
@@ -784,6 +785,62 @@ int mrmt3_decoder_set_grammar(mrmt3_decoder* dec, const mrmt3_grammar* g, const 
  * hypothesis returned).  The emitted tokens are pushed again from the start state, so the result does not depend on
  * which rows held the hypothesis' prefix along the way. */
 int mrmt3_decoder_grammar_active(mrmt3_decoder* dec, uint8_t* out, void* stream);
+
+/* ---- notes from token rows ---------------------------------------------------------------------------
+ * Token rows -> notes on the device: the inverse of mrmt3_label_rows_fwd and the last stage of inference, one
+ * launch for every segment of every recording.  The definition is the host decoder as it stands: InferenceHandler's
+ * _postprocess_batch + _to_event + contrib.metrics_utils.event_predictions_to_ns (or _scored) with NoteEncodingWithTiesSpec
+ * (or ...ScoredSpec); its quirks are reproduced, not repaired.  mrmt3.notes.decode_notes_host restates the contract below on
+ * the host.  The result equals the host decoder's note for note, f64 times and f32 scores bit for bit.
+ *
+ * Input (DEVICE): ids [rows][ld] int64 exactly as the decoder returns them, column 0 the start token; logp [rows][ld] f32
+ * beside it or NULL.  Rows are segments; the rows of one recording are contiguous and in time order, seg_first [n_rec + 1]
+ * int32 gives each recording's first row (non-decreasing from 0 to rows: the caller checks it; the kernel clamps it).
+ * Recordings are independent.  Per row: start_time f64 (the first frame's time minus its remainder mod 1 / steps_per_second)
+ * and limit f64, the next row's start_time; any limit <= 0 means "none" (a recording's last row; the host's `if max_time`).
+ * g: the id ranges in MODEL ids as for the grammar, plus steps_per_second (max_shift_steps and tie_section are not read: a
+ * row always begins in the tie section).  velocity_of_bin [g->n_velocity] int32: the velocity of every velocity id
+ * (vocabularies.bin_to_velocity).
+ *
+ * The row:
+ *  - Cut: token j is column j + 1.  The row ends before the first j whose id is g->eos or g->shift0 - 1 (the id that decodes
+ *    to -1: UNK, which the host cuts at as well).  A row with no such j contributes NO tokens (the reference's argmax quirk).
+ *  - Codec: an id outside the six ranges of g counts 1 invalid event and is skipped (PAD and the extra ids among them).
+ *  - Time: a shift of v adds v to `steps`; now = start_time + steps / steps_per_second in f64, one correctly rounded quotient
+ *    and one correctly rounded sum, no contraction.  If the row has a limit and now > limit: dropped += (tokens in the row) -
+ *    (index of this shift), and the row ends.  Every other event sets steps = 0 and leaves `now` as it is.
+ *  - State machine, one per recording, carried from row to row: contrib.note_sequences.decode_note_event exactly.  The tie
+ *    section begins at every row's start, also for a row without tokens.  time < current_time counts 1 invalid and changes
+ *    nothing; each of the six ValueError sites counts 1 invalid; a re-onset closes the running note first; `tie` ends every
+ *    sounding note that was not declared, at current_time; a note's end is max(end, start + 0.01); total_time is the maximum
+ *    of the ends; after the last row, current_time = max(current_time, onset + 0.01) over the sounding notes, which then
+ *    all end at current_time.
+ *  - Order: the host keeps the sounding notes in a dict: `tie` and the flush emit in INSERTION order, and a key that was
+ *    popped and struck again has moved to the end.  The notes come out in the host's order.
+ *  - Scored (logp != NULL): logc of a note is the f32 the host holds before math.exp: the minimum (taken left to right with
+ *    <, as Python's min) over the onset's own token, the row's latest program token, if any, and the row's latest kept
+ *    shift token, if any; fixed at the onset for notes that an off, a re-onset, `tie` or the flush emits.
+ *
+ * Output (DEVICE), per recording r: n_notes, invalid, dropped, status [n_rec] int32; total_time [n_rec] f64; the notes in
+ * order from entry seg_first[r] * (ld - 1) of times [rows * (ld - 1)][2] f64 (start, end), meta [rows * (ld - 1)][4] int32
+ * (pitch, velocity, program | is_drum << 8, 0: the fields of mrmt3.labels.NoteTable; 16-byte aligned) and, when scored,
+ * logc [rows * (ld - 1)] f32.  A recording's notes cannot outnumber its tokens, so a region never overflows; the tail of a
+ * region behind n_notes is left unwritten.
+ * Capacity: at most MRMT3_NOTES_CAPACITY notes of a recording sound at once (LDS).  A recording that needs more reports
+ * status 1 and its other outputs mean nothing: the caller decodes that recording on the host.
+ * Whatever the ids hold, the kernel reads and writes nothing outside these arrays, and every loop is bounded by ld, rows or
+ * the capacity.
+ * MRMT3_ERR_INVALID_ARG before any launch: a null pointer (logp and logc excepted, which go together), rows, ld or n_rec
+ * <= 0, ld < 2, a negative range, n_pitch or n_program > 128, n_velocity <= 0, n_velocity or n_drum > 65536,
+ * steps_per_second <= 0, meta not 16-byte aligned. */
+#define MRMT3_NOTES_CAPACITY 4096
+int mrmt3_notes_decode_fwd(const mrmt3_grammar* g, const long long* ids, const float* logp, int rows, int ld,
+                           const int* seg_first, int n_rec, const double* start_time, const double* limit,
+                           const int* velocity_of_bin, int* n_notes, int* invalid, int* dropped, int* status,
+                           double* total_time, double* times, int* meta, float* logc, void* stream);
+/* Launches of mrmt3_notes_decode_fwd since the process started (or since the last call with reset != 0); kept apart from
+ * mrmt3_dispatch_counts like the resampler's and the label kernel's. */
+unsigned long long mrmt3_notes_launches(int reset);
 
 /* ---- gradient exchange (data parallel, one process per GPU): RCCL communicators as opaque handles ----------------
  * Replaces what the reference gets from Lightning's `ddp_find_unused_parameters_false` strategy (config/config.yaml:45,

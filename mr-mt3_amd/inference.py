@@ -19,6 +19,9 @@
   * `do_sample` / `temperature` / `top_k` / `top_p` / `seed` / `best_of` (the reference's call site pins `do_sample=False`):
     honoured under `decode_options`, like `num_beams`.  Batch i of a recording draws with `seed + i`; `best_of = n` keeps, per
     segment, the most likely of n samples (`model.generate_best_of`, plain T5 only).
+  * `device_notes` (not in the reference; off by default): the token ids (and log-probabilities) of all batches stay on the
+    device and `_to_event` is replaced by ONE launch of `mrmt3_notes_decode_fwd` per call (`mrmt3.notes.decode_notes`, DESIGN
+    §4m); the note sequence is the host path's, note for note.
 """
 from __future__ import annotations
 
@@ -87,7 +90,7 @@ def postprocess_logprobs(logp: torch.Tensor):
 
 class InferenceHandler:
     def __init__(self, model=None, weight_path=None, device=torch.device('cuda'), mel_norm=True,
-                 contiguous_inference=False, use_tf_spectral_ops=False, decode_options=None) -> None:
+                 contiguous_inference=False, use_tf_spectral_ops=False, decode_options=None, device_notes=False) -> None:
         if model is None:
             from models.t5 import T5ForConditionalGeneration
             from mrmt3.synthetic import T5_SMALL
@@ -107,6 +110,8 @@ class InferenceHandler:
         # honour `valid_programs` / `num_beams` in `inference` (the reference accepts and drops them)
         self.decode_options = bool(int(os.environ.get("MRMT3_DECODE_OPTIONS", "0"))) if decode_options is None \
             else bool(decode_options)
+        # tokens -> notes on the device (`_to_notes_device`) instead of `_to_event`; `inference(device_notes=)` overrides it
+        self.device_notes = bool(device_notes)
 
     def _get_program_ids(self, valid_programs):
         """inference.py:138-147: `bad_words_ids` of the programs outside `valid_programs`, one single-token list each."""
@@ -207,6 +212,21 @@ class InferenceHandler:
                                                        encoding_spec=note_sequences.NoteEncodingWithTiesSpec)
         return result["est_ns"]
 
+    def _to_notes_device(self, ids, frame_times, logps=None, min_confidence=None, recordings=None):
+        """`_to_event` on the device: `ids` the decoder's id tensors (one per batch or recording, [rows, width] on the device,
+        the widths may differ), `frame_times` their frame times, `logps` the log-probability tensors beside them or None,
+        `recordings` the row count of every recording (None: one) -> one note sequence per recording, from one launch."""
+        from mrmt3 import notes
+        width = max(t.shape[1] for t in ids)
+        eos, pad_id = self.model.config.eos_token_id, getattr(self.model.config, "pad_token_id", 0)
+        pad = lambda t, v: t if t.shape[1] == width else torch.nn.functional.pad(t, (0, width - t.shape[1]), value=v)
+        # (a row is read up to its first EOS, and a row without one contributes nothing: the padding changes neither)
+        flat = torch.cat([pad(t, pad_id) for t in ids])
+        flat_lp = None if logps is None else torch.cat([pad(t.float(), 0.0) for t in logps])
+        arrays = notes.decode_notes(flat, np.concatenate(frame_times, axis=0), self.codec, logp=flat_lp, recordings=recordings,
+                                    eos_token_id=eos, pad_token_id=pad_id)
+        return [a.to_note_sequence(min_confidence) for a in arrays]
+
     def _sample_options(self, do_sample, temperature, top_k, top_p, seed, best_of):
         """The sampling keywords as `_generate` takes them, or None: honoured only under `decode_options`."""
         if not (isinstance(best_of, int) and best_of >= 1):
@@ -219,7 +239,7 @@ class InferenceHandler:
     def inference(self, audio, audio_path=None, outpath=None, valid_programs=None, num_beams=1, batch_size=5,
                   max_length=1024, verbose=False, return_tokens=False, with_confidence=False, min_confidence=None,
                   do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, best_of=1, constrained=False,
-                  sample_rate=None):
+                  sample_rate=None, device_notes=None):
         """audio -> note sequence (and a MIDI file when `outpath` is given, like inference.py:149-204).
         `sample_rate`: the rate of `audio` when it is not the model's 16 kHz (a quarter to four times that): the audio is
         resampled on the device first; None is the 16 kHz path, untouched.
@@ -230,15 +250,18 @@ class InferenceHandler:
         likely of that many samples per segment (plain T5 only) and implies sampling.
         `constrained` (under `decode_options`; True or an `EventGrammar`): the decoder emits only tokens the event decoder
         accepts.  The plain T5 decodes a batch's segments side by side, each knowing only its own tie section; the
-        segment-memory models hand the sounding notes from segment to segment within a batch."""
+        segment-memory models hand the sounding notes from segment to segment within a batch.
+        `device_notes` (None: the handler's): the tokens become notes on the device, one launch for the whole recording;
+        the result is the same note sequence.  `return_tokens` ignores it."""
         scored = with_confidence or min_confidence is not None
+        on_device = (self.device_notes if device_notes is None else bool(device_notes)) and not return_tokens
         sample = self._sample_options(do_sample, temperature, top_k, top_p, seed, best_of)
         inputs, frame_times = self._preprocess(self._at_model_rate(audio, sample_rate))
         batches, ft = self._batching(inputs, frame_times, batch_size=batch_size)
         if self.contiguous_inference:
             batches = [torch.cat(batches, dim=0)]
             ft = [np.concatenate(ft, axis=0)]
-        results, logps = [], []
+        results, logps, kept, kept_lp = [], [], [], []
         for i, batch in enumerate(batches):
             kw = {} if sample is None else dict(sample=dict(sample, seed=sample["seed"] + i), best_of=best_of)
             if self.decode_options and constrained is not False:
@@ -246,15 +269,24 @@ class InferenceHandler:
             if scored:
                 opts = (valid_programs, num_beams) if self.decode_options else (None, 1)
                 result, logp = self._generate(batch.to(self.device), max_length, *opts, scored=True, **kw)
-                logps.append(postprocess_logprobs(logp))
+                if on_device:
+                    kept_lp.append(logp)
+                else:
+                    logps.append(postprocess_logprobs(logp))
             elif self.decode_options:
                 result = self._generate(batch.to(self.device), max_length, valid_programs, num_beams, **kw)
             else:
                 result = self.model.generate(inputs=batch.to(self.device), max_length=max_length)
-            results.append(self._postprocess_batch(result))
+            if on_device:
+                kept.append(result)
+            else:
+                results.append(self._postprocess_batch(result))
         if return_tokens:
             return (results, ft, logps) if scored else (results, ft)
-        ns = self._to_event(results, ft, logps if scored else None, min_confidence)
+        if on_device:
+            ns = self._to_notes_device(kept, ft, kept_lp if scored else None, min_confidence)[0]
+        else:
+            ns = self._to_event(results, ft, logps if scored else None, min_confidence)
         if outpath is not None:
             os.makedirs(os.path.dirname(os.path.abspath(outpath)), exist_ok=True)
             midi_io.note_sequence_to_midi_file(ns, outpath)
@@ -263,7 +295,7 @@ class InferenceHandler:
     @torch.no_grad()
     def inference_many(self, audios, outpaths=None, max_length=1024, return_tokens=False, valid_programs=None,
                        num_beams=1, with_confidence=False, min_confidence=None, do_sample=False, temperature=1.0, top_k=0,
-                       top_p=1.0, seed=0, best_of=1, constrained=False, sample_rate=None):
+                       top_p=1.0, seed=0, best_of=1, constrained=False, sample_rate=None, device_notes=None):
         """Several recordings in one go (`sample_rate` as in `inference`, the same for every recording).
         Segment-memory models decode them in lockstep (one batch row per
         recording, `model.generate_songs`); the plain T5 simply batches all segments.  Returns one note sequence
@@ -272,7 +304,7 @@ class InferenceHandler:
         `with_confidence` / `min_confidence` as in `inference`.  The sampling keywords as in `inference` (under
         `decode_options`): the plain T5 decodes every segment in one batch under `seed`, the segment-memory models draw
         segment i of every recording under `seed + i`; `best_of` > 1 is for the plain T5.  `constrained` as in `inference`,
-        honoured as given."""
+        honoured as given.  `device_notes` as in `inference`: every recording's notes come from one launch."""
         sample = self._sample_options(do_sample, temperature, top_k, top_p, seed, best_of)
         if sample is not None and best_of > 1 and hasattr(self.model, "generate_songs"):
             raise ValueError("best_of > 1 is for the plain T5 model (MT3Net); the segment-memory models decode one sample "
@@ -312,6 +344,14 @@ class InferenceHandler:
                     lps.append(flat_lp[at:at + x.shape[0]])
                 at += x.shape[0]
         out = []
+        if (self.device_notes if device_notes is None else bool(device_notes)) and not return_tokens:
+            out = self._to_notes_device(list(ids), [ft for _, ft in pre], list(lps) if scored else None, min_confidence,
+                                        recordings=[len(ft) for _, ft in pre])
+            for k, ns in enumerate(out):
+                if outpaths is not None and outpaths[k] is not None:
+                    os.makedirs(os.path.dirname(os.path.abspath(outpaths[k])), exist_ok=True)
+                    midi_io.note_sequence_to_midi_file(ns, outpaths[k])
+            return out
         for k, (seg_ids, (_, ft)) in enumerate(zip(ids, pre)):
             results, times = [self._postprocess_batch(seg_ids)], [ft]
             logps = [postprocess_logprobs(lps[k])] if scored else None

@@ -18,7 +18,8 @@ ACTIVE_BYTES = 2048      # MRMT3_GRAMMAR_SET_BYTES
 
 class _CGrammar(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("shift0", "n_shift", "pitch0", "n_pitch", "velocity0", "n_velocity", "tie", "program0",
-                                       "n_program", "drum0", "n_drum", "eos", "pad", "max_shift_steps", "tie_section")]
+                                       "n_program", "drum0", "n_drum", "eos", "pad", "max_shift_steps", "tie_section",
+                                       "steps_per_second")]
 
 
 @dataclass(frozen=True)
@@ -38,6 +39,7 @@ class EventGrammar:
     pad: int
     max_shift_steps: int
     tie_section: bool = True
+    steps_per_second: int = vocabularies.DEFAULT_STEPS_PER_SECOND   # read by the note decoder alone (mrmt3.notes)
 
     @classmethod
     def from_codec(cls, codec, mel_length=256, spectrogram_config=None, tie_section=True, max_shift_steps=None,
@@ -60,8 +62,9 @@ class EventGrammar:
             raise ValueError(f"max_shift_steps must be >= 0, got {max_shift_steps}")
         (s0, ns), (p0, np_), (v0, nv), (t0, _), (g0, ng), (d0, nd) = (rng(n) for n in ("shift", "pitch", "velocity", "tie",
                                                                                       "program", "drum"))
+        sps = codec.steps_per_second             # a grid that is not whole becomes 0, which the note decoder refuses
         return cls(s0, ns, p0, np_, v0, nv, t0, g0, ng, d0, nd, int(eos_token_id), int(pad_token_id), max_shift_steps,
-                   bool(tie_section))
+                   bool(tie_section), int(sps) if sps == int(sps) and sps >= 1 else 0)
 
     def c_struct(self) -> _CGrammar:
         return _CGrammar(*[int(getattr(self, f.name)) for f in fields(self)])

@@ -106,7 +106,7 @@ def load():
     return lib
 
 
-MIN_VERSION = 125
+MIN_VERSION = 126
 COUNTER_NAMES = ("gemm_nt_tile", "gemm_nt8", "gemm_nt_geglu", "tn_group", "tn8", "tn_tile", "attn_fwd", "attn_bwd",
                  "attn_bwd_onepass", "attn_f32", "tn_f32", "gemm_nt_splitk", "gemm_nt_addnorm", "gemm_nt_normbwd",
                  "gemm_nt_geglubwd", "attn_fwd_varlen", "attn_bwd_varlen", "logmel_wave", "logmel_general")
@@ -308,6 +308,48 @@ def label_rows(note_times, note_meta, n_stems, keep, start_frame, n_frames, tota
 def label_launches(reset: bool = False) -> int:
     """Launches of `label_rows` since the process started / the last reset (mrmt3_label_launches)."""
     return int(load().mrmt3_label_launches(int(reset)))
+
+
+NOTES_CAPACITY = 4096        # notes of one recording that may sound at once in mrmt3_notes_decode_fwd (MRMT3_NOTES_CAPACITY)
+
+
+def notes_decode(grammar, ids, seg_first, start_time, limit, velocity_of_bin, steps_per_second, logp=None):
+    """ids [rows, ld] int64 as the decoder returns them (column 0 the start token), logp [rows, ld] f32 beside it or None;
+    seg_first [n_rec + 1] int32, start_time / limit [rows] f64, velocity_of_bin [n_velocity] int32, all on the device;
+    `grammar` a `mrmt3.grammar.EventGrammar` (the id ranges), `steps_per_second` the codec's -> dict of device tensors:
+    n_notes, invalid, dropped, status [n_rec] int32, total_time [n_rec] f64, times [rows * (ld - 1), 2] f64,
+    meta [rows * (ld - 1), 4] int32 and, with `logp`, logc [rows * (ld - 1)] f32; recording r's notes start at entry
+    seg_first[r] * (ld - 1) (include/mrmt3_hip.h: mrmt3_notes_decode_fwd)."""
+    _dev(ids, seg_first, start_time, limit, velocity_of_bin, logp)
+    assert ids.dim() == 2 and ids.dtype == torch.int64 and ids.is_contiguous()
+    rows, ld = ids.shape
+    assert logp is None or (logp.shape == ids.shape and logp.dtype == torch.float32 and logp.is_contiguous())
+    assert seg_first.dim() == 1 and seg_first.dtype == torch.int32 and seg_first.is_contiguous()
+    n_rec = seg_first.numel() - 1
+    for t in (start_time, limit):
+        assert t.shape == (rows,) and t.dtype == torch.float64 and t.is_contiguous()
+    assert velocity_of_bin.shape == (grammar.n_velocity,) and velocity_of_bin.dtype == torch.int32
+    assert velocity_of_bin.is_contiguous()
+    if steps_per_second != int(steps_per_second):
+        raise ValueError(f"notes_decode needs a whole steps_per_second, got {steps_per_second!r}")
+    g = grammar.c_struct()
+    g.steps_per_second = int(steps_per_second)
+    dev, cap = ids.device, max(rows * (ld - 1), 0)
+    out = {k: torch.empty(max(n_rec, 0), device=dev, dtype=torch.int32) for k in ("n_notes", "invalid", "dropped", "status")}
+    out["total_time"] = torch.empty(max(n_rec, 0), device=dev, dtype=torch.float64)
+    out["times"] = torch.empty(cap, 2, device=dev, dtype=torch.float64)
+    out["meta"] = torch.empty(cap, 4, device=dev, dtype=torch.int32)
+    out["logc"] = None if logp is None else torch.empty(cap, device=dev, dtype=torch.float32)
+    _check(load().mrmt3_notes_decode_fwd(C.byref(g), _p(ids), _p(logp), rows, ld, _p(seg_first), n_rec, _p(start_time),
+                                         _p(limit), _p(velocity_of_bin), _p(out["n_notes"]), _p(out["invalid"]),
+                                         _p(out["dropped"]), _p(out["status"]), _p(out["total_time"]), _p(out["times"]),
+                                         _p(out["meta"]), _p(out["logc"]), _stream()), "notes_decode_fwd")
+    return out
+
+
+def notes_launches(reset: bool = False) -> int:
+    """Launches of `notes_decode` since the process started / the last reset (mrmt3_notes_launches)."""
+    return int(load().mrmt3_notes_launches(int(reset)))
 
 
 def gemm_nt(a, b, out=None, out_dtype=None, accumulate=False):
