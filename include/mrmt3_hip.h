@@ -842,6 +842,55 @@ int mrmt3_notes_decode_fwd(const mrmt3_grammar* g, const long long* ids, const f
  * mrmt3_dispatch_counts like the resampler's and the label kernel's. */
 unsigned long long mrmt3_notes_launches(int reset);
 
+/* ---- note matching -----------------------------------------------------------------------------------
+ * The matcher of the note-level scores on the device: for every problem of one launch a maximum-cardinality matching of
+ * the bipartite graph of contrib.transcription_metrics.match_notes (mir_eval's), estimated notes on the left.  Precision,
+ * recall and F1 depend on the matching's size alone.  mrmt3.scoring.match_notes_host restates the contract below on the host.
+ *
+ * Tables (DEVICE): times [n][2] f64 (start, end) and meta [n][4] int32, 16-byte aligned (pitch, velocity,
+ * program | is_drum << 8, unused): the fields of mrmt3.labels.NoteTable and of mrmt3_notes_decode_fwd's output, so both feed
+ * this kernel as they lie.  Only the times and the pitch are read.
+ *
+ * Problems: problem p matches the reference entries ref_idx[ref_first[p] .. ref_first[p + 1]) against the estimated entries
+ * est_idx[est_first[p] .. est_first[p + 1]); each entry is an index into its table, ref_first / est_first are
+ * [n_prob + 1] int32, Lr = ref_first[n_prob], Le = est_first[n_prob].  Each list is in non-decreasing onset order, equal
+ * onsets in increasing index order.  A note may appear in many problems: filtering (pitch range, zero durations, program
+ * groups) is the caller's, done by choosing the lists; no program field is read.  prob_flags[p]: bit 0 = the offset
+ * criterion is on; bits 8 and up = the pitch table used, in [0, n_tables).
+ *
+ * Edges: f64, one rounding per operation, no contraction.  Reference entry r and estimated entry e are adjacent iff
+ *  - rint(|on_r - on_e| * 1e6) / 1e6 <= onset_tol (np.around(., 6): multiply, round half to even, divide), and
+ *  - pitch_lo[t][pitch_r] <= pitch_e <= pitch_hi[t][pitch_r], tables [n_tables][128] int32 (pitch_r outside 0..127: no edge;
+ *    a table number outside [0, n_tables): a problem without edges), and
+ *  - with bit 0: rint(|off_r - off_e| * 1e6) / 1e6 <= max(offset_ratio * (off_r - on_r), offset_min_tol).
+ * The pitch tolerance is a table the host computes with the matcher's own expression (mrmt3.scoring.pitch_tables).
+ *
+ * Output (DEVICE): matched [n_prob] int32, the size of a maximum matching of problem p (unique); match [Le] int32, for
+ * estimated entry k the POSITION in ref_idx of its partner or -1: a valid matching of that size, which one is the kernel's
+ * choice but the same on every run; status [n_prob] int32: 0 ok, 2 a list of p is not in order (the problem's matched is 0
+ * and its match entries are -1 then).
+ * An entry whose index lies outside its table, or whose onset is NaN, has no edges and is transparent to the order: the
+ * entries around it are compared with each other.  NaN offsets make no edges under bit 0.
+ *
+ * No capacity: a run of any length is matched in caller-owned device memory, `workspace` of
+ * mrmt3_note_match_workspace_bytes(Lr, Le) bytes (4 * Le + 2 * Lr int32; 0 for sizes outside [0, 2^30]), 4-byte aligned,
+ * no initial contents needed.  Memory and work are O(entries x window), never O(n_ref * n_est).
+ * Whatever the arrays hold, the kernel reads and writes nothing outside them: ref_first / est_first are clamped to
+ * [0, Lr] / [0, Le] and made non-decreasing per problem, and every loop is bounded by a list or window length.
+ * MRMT3_ERR_INVALID_ARG before any launch: a null pointer (the workspace included: pass any device pointer when its size
+ * is 0), n_prob <= 0, n_tables <= 0 or > 2^22, a note count outside [0, 2^31), a tolerance that is negative or NaN, meta
+ * not 16-byte aligned, a workspace not 4-byte aligned. */
+size_t mrmt3_note_match_workspace_bytes(long long Lr, long long Le);
+int mrmt3_note_match_fwd(const double* ref_times, const int* ref_meta, long long n_ref_notes,
+                         const double* est_times, const int* est_meta, long long n_est_notes,
+                         const int* ref_idx, const int* ref_first, const int* est_idx, const int* est_first,
+                         const int* prob_flags, int n_prob,
+                         const int* pitch_lo, const int* pitch_hi, int n_tables,
+                         double onset_tol, double offset_ratio, double offset_min_tol,
+                         int* matched, int* match, int* status, void* workspace, void* stream);
+/* Launches of mrmt3_note_match_fwd since the process started (or since the last call with reset != 0). */
+unsigned long long mrmt3_note_match_launches(int reset);
+
 /* ---- gradient exchange (data parallel, one process per GPU): RCCL communicators as opaque handles ----------------
  * Replaces what the reference gets from Lightning's `ddp_find_unused_parameters_false` strategy (config/config.yaml:45,
  * train.sh:6): torch DDP's bucketed NCCL all-reduce of the gradients.  The flat f32 gradient buffer is exchanged as a few

@@ -95,6 +95,16 @@ def match_notes(ref_intervals, ref_pitches, est_intervals, est_pitches, onset_to
     return sorted((r, e) for e, r in m.items())
 
 
+def scores_from_counts(matched: int, n_ref: int, n_est: int, beta: float = 1.0):
+    """(precision, recall, F) of a maximum matching of `matched` pairs between n_ref reference and n_est estimated notes:
+    the one place these quotients are written (the host matcher and `mrmt3.scoring` both score through it)."""
+    if n_ref == 0 or n_est == 0:
+        return 0.0, 0.0, 0.0
+    precision = matched / n_est
+    recall = matched / n_ref
+    return precision, recall, f_measure(precision, recall, beta)
+
+
 def average_overlap_ratio(ref_intervals, est_intervals, matching) -> float:
     ratios = []
     for r, e in matching:
@@ -115,9 +125,8 @@ def precision_recall_f1_overlap(ref_intervals, ref_pitches, est_intervals, est_p
         return 0.0, 0.0, 0.0, 0.0
     matching = match_notes(ref_intervals, ref_pitches, est_intervals, est_pitches, onset_tolerance, pitch_tolerance,
                            offset_ratio, offset_min_tolerance, strict)
-    precision = len(matching) / len(est_pitches)
-    recall = len(matching) / len(ref_pitches)
-    return precision, recall, f_measure(precision, recall, beta), average_overlap_ratio(ref_intervals, est_intervals, matching)
+    return scores_from_counts(len(matching), len(ref_pitches), len(est_pitches), beta) + (
+        average_overlap_ratio(ref_intervals, est_intervals, matching),)
 
 
 def sequence_to_valued_intervals(ns, min_midi_pitch=21, max_midi_pitch=108):

@@ -2,7 +2,8 @@
 counterpart of the reference's evaluate.py:16-330 without pretty_midi / note_seq / mir_eval / librosa:
 MIDI files are read by `contrib.midi_io.read_midi` (pretty_midi's conventions), note matching is
 `contrib.transcription_metrics` (mir_eval's algorithm).  Function names, arguments and result keys are
-the reference's.  CPU, host-side: nothing here touches the GPU path.
+the reference's.  CPU, host-side by default: nothing here touches the GPU path unless a `device` is named, and then only
+the matching moves (`mrmt3.scoring`): the files are read and the results assembled by the same code.
 """
 from __future__ import annotations
 
@@ -31,59 +32,31 @@ def _midi(x):
     return x if isinstance(x, midi_io.MidiData) else midi_io.read_midi(x)
 
 
-def compute_transcription_metrics(ref_mid, est_mid):
-    """evaluate.py:25-53: onset+offset and onset-only scores over all notes (pitches are passed to the matcher
-    as MIDI numbers, exactly as the reference does)."""
-    ns_ref = midi_io.midi_to_note_sequence(_midi(ref_mid))
-    ns_est = midi_io.midi_to_note_sequence(_midi(est_mid))
-    iv_r, p_r, _ = tm.sequence_to_valued_intervals(ns_ref)
-    iv_e, p_e, _ = tm.sequence_to_valued_intervals(ns_est)
-    onoff = tm.precision_recall_f1_overlap(iv_r, p_r, iv_e, p_e)
-    on = tm.precision_recall_f1_overlap(iv_r, p_r, iv_e, p_e, offset_ratio=None)
+def transcription_metrics_result(n_ref, n_est, onoff, on):
+    """The dict of `compute_transcription_metrics` from the two (precision, recall, f1, overlap) tuples."""
     keys = ("precision", "recall", "f1", "overlap")
-    out = {"len_ref_intervals": len(iv_r), "len_est_intervals": len(iv_e)}
+    out = {"len_ref_intervals": n_ref, "len_est_intervals": n_est}
     out.update({f"onoff_{k}": v for k, v in zip(keys, onoff)})
     out.update({f"on_{k}": v for k, v in zip(keys, on)})
     return out
 
 
-def mt3_program_aware_note_scores(fname1, fname2, granularity_type):
-    """evaluate.py:56-237: instrument-agnostic onset F1 plus the program-aware onset F1 of MT3 at the given
-    program granularity (per-group scores weighted by note counts)."""
-    ref_mid, est_mid = _midi(fname1), _midi(fname2)
+def program_aware_result(onset, groups, granularity_type):
+    """The dict of `mt3_program_aware_note_scores`: `onset` the instrument-agnostic (precision, recall, f1), `groups` one
+    ((program, is_drum), (precision, recall, f1), n_ref, n_est) per program group IN THE ORDER they are summed.  The host
+    scorer and `mrmt3.scoring` both assemble their result here."""
     res = {}
-    iv_r, p_r, _ = tm.sequence_to_valued_intervals(midi_io.midi_to_note_sequence(ref_mid))
-    iv_e, p_e, _ = tm.sequence_to_valued_intervals(midi_io.midi_to_note_sequence(est_mid))
-    precision, recall, f1, _ = tm.precision_recall_f1_overlap(iv_r, p_r, iv_e, p_e, offset_ratio=None)
-    res["Onset precision"], res["Onset recall"], res["Onset F1"] = precision, recall, f1
-
-    def group(mid):
-        g = collections.OrderedDict()
-        for inst in mid.instruments:
-            key = (get_granular_program(inst.program, inst.is_drum, granularity_type), inst.is_drum)
-            g.setdefault(key, []).extend(inst.notes)
-        return g
-
-    ref_g, est_g = group(ref_mid), group(est_mid)
+    res["Onset precision"], res["Onset recall"], res["Onset F1"] = onset
     sums = {True: [0.0, 0, 0.0, 0], False: [0.0, 0, 0.0, 0]}       # is_drum -> [P*n_est, n_est, R*n_ref, n_ref]
     program_f1 = {}
-    for key in set(ref_g) | set(est_g):
-        program, is_drum = key
-
-        def arrays(notes):
-            iv = np.array([[n.start, n.end] for n in notes], dtype=np.float64).reshape(-1, 2)
-            return iv, tm.midi_to_hz([n.pitch for n in notes])
-
-        r_iv, r_hz = arrays(ref_g.get(key, []))
-        e_iv, e_hz = arrays(est_g.get(key, []))
-        p, r, f, _ = tm.precision_recall_f1_overlap(r_iv, r_hz, e_iv, e_hz, offset_ratio=None)
+    for (program, is_drum), (p, r, f), n_ref, n_est in groups:
         if granularity_type == "midi_class":
             program_f1[-1 if is_drum else program] = f
         acc = sums[bool(is_drum)]
-        acc[0] += p * len(e_iv)
-        acc[1] += len(e_iv)
-        acc[2] += r * len(r_iv)
-        acc[3] += len(r_iv)
+        acc[0] += p * n_est
+        acc[1] += n_est
+        acc[2] += r * n_ref
+        acc[3] += n_ref
     p_sum, p_cnt = sums[True][0] + sums[False][0], sums[True][1] + sums[False][1]
     r_sum, r_cnt = sums[True][2] + sums[False][2], sums[True][3] + sums[False][3]
     precision = p_sum / p_cnt if p_cnt else 0
@@ -93,6 +66,79 @@ def mt3_program_aware_note_scores(fname1, fname2, granularity_type):
                 f"Onset + program F1 ({granularity_type})": tm.f_measure(precision, recall),
                 "F1 by program": program_f1})
     return res
+
+
+def group_order(ref_keys, est_keys):
+    """The order `mt3_program_aware_note_scores` visits its program groups in: the union of the two key sets, each built
+    from its keys in order of first appearance."""
+    return list(set(ref_keys) | set(est_keys))
+
+
+def _device_scores(pairs, device, families, with_overlap=True, errors="raise"):
+    from mrmt3 import scoring
+    from mrmt3.notes import DeviceNotes
+    ref = DeviceNotes.from_arrays([scoring.table_from_midi(_midi(r)) for r, _ in pairs], device)
+    est = DeviceNotes.from_arrays([scoring.table_from_midi(_midi(e)) for _, e in pairs], device)
+    return scoring.score_tables(ref, est, with_overlap=with_overlap, families=families, errors=errors)
+
+
+def compute_transcription_metrics(ref_mid, est_mid, device=None):
+    """evaluate.py:25-53: onset+offset and onset-only scores over all notes (pitches are passed to the matcher
+    as MIDI numbers, exactly as the reference does).  `device`: the notes are uploaded and matched there
+    (`mrmt3.scoring.score_tables`); None is the host matcher."""
+    if device is not None:
+        got = _device_scores([(ref_mid, est_mid)], device, ("onoff", "on"))[0]
+        return {k: got[k] for k in transcription_metrics_result(0, 0, (0,) * 4, (0,) * 4)}
+    ns_ref = midi_io.midi_to_note_sequence(_midi(ref_mid))
+    ns_est = midi_io.midi_to_note_sequence(_midi(est_mid))
+    iv_r, p_r, _ = tm.sequence_to_valued_intervals(ns_ref)
+    iv_e, p_e, _ = tm.sequence_to_valued_intervals(ns_est)
+    onoff = tm.precision_recall_f1_overlap(iv_r, p_r, iv_e, p_e)
+    on = tm.precision_recall_f1_overlap(iv_r, p_r, iv_e, p_e, offset_ratio=None)
+    return transcription_metrics_result(len(iv_r), len(iv_e), onoff, on)
+
+
+def _program_aware_from_scores(got, granularity_type):
+    keys = ["Onset precision", "Onset recall", "Onset F1"] + [f"Onset + program {k} ({granularity_type})"
+                                                              for k in ("precision", "recall", "F1")]
+    res = {k: got[k] for k in keys}
+    res["F1 by program"] = got["F1 by program (%s)" % granularity_type]
+    return res
+
+
+def mt3_program_aware_note_scores(fname1, fname2, granularity_type, device=None):
+    """evaluate.py:56-237: instrument-agnostic onset F1 plus the program-aware onset F1 of MT3 at the given
+    program granularity (per-group scores weighted by note counts).  `device` as in `compute_transcription_metrics`."""
+    ref_mid, est_mid = _midi(fname1), _midi(fname2)
+    if device is not None:
+        got = _device_scores([(ref_mid, est_mid)], device, ("on", granularity_type), with_overlap=False)[0]
+        return _program_aware_from_scores(got, granularity_type)
+    iv_r, p_r, _ = tm.sequence_to_valued_intervals(midi_io.midi_to_note_sequence(ref_mid))
+    iv_e, p_e, _ = tm.sequence_to_valued_intervals(midi_io.midi_to_note_sequence(est_mid))
+    precision, recall, f1, _ = tm.precision_recall_f1_overlap(iv_r, p_r, iv_e, p_e, offset_ratio=None)
+
+    def group(mid):
+        g = collections.OrderedDict()
+        for inst in mid.instruments:
+            key = (get_granular_program(inst.program, inst.is_drum, granularity_type), inst.is_drum)
+            g.setdefault(key, []).extend(inst.notes)
+        return g
+
+    ref_g, est_g = group(ref_mid), group(est_mid)
+
+    def scored():
+        for key in group_order(ref_g, est_g):
+
+            def arrays(notes):
+                iv = np.array([[n.start, n.end] for n in notes], dtype=np.float64).reshape(-1, 2)
+                return iv, tm.midi_to_hz([n.pitch for n in notes])
+
+            r_iv, r_hz = arrays(ref_g.get(key, []))
+            e_iv, e_hz = arrays(est_g.get(key, []))
+            p, r, f, _ = tm.precision_recall_f1_overlap(r_iv, r_hz, e_iv, e_hz, offset_ratio=None)
+            yield key, (p, r, f), len(r_iv), len(e_iv)
+
+    return program_aware_result((precision, recall, f1), scored(), granularity_type)
 
 
 def loop_transcription_eval(ref_mid, est_mid):
@@ -110,9 +156,11 @@ def loop_transcription_eval(ref_mid, est_mid):
     return float(np.mean(np.max(score, axis=-1))), len(ref_mid.instruments), len(est_mid.instruments)
 
 
-def evaluate_main(dataset_name, test_midi_dir, ground_truth_midi_dir, enable_instrument_eval=False, first_n=None):
+def evaluate_main(dataset_name, test_midi_dir, ground_truth_midi_dir, enable_instrument_eval=False, first_n=None,
+                  device=None):
     """evaluate.py:275-330: pair every transcribed file with its ground truth, score at the three program
-    granularities, print and return the means."""
+    granularities, print and return the means.  `device`: the files are read as before, their notes uploaded, and every
+    pair is scored in ONE launch of the device matcher (`mrmt3.scoring.score_tables`); None is the host matcher."""
     if dataset_name == "Slakh":
         est = sorted(glob.glob(f"{test_midi_dir}/*/mix.mid"))
         ref = [k.replace(test_midi_dir, ground_truth_midi_dir).replace("/mix.mid", "/all_src_v2.mid") for k in est]
@@ -131,13 +179,31 @@ def evaluate_main(dataset_name, test_midi_dir, ground_truth_midi_dir, enable_ins
         return out
 
     scores = collections.defaultdict(list)
-    with concurrent.futures.ThreadPoolExecutor(max_workers=8) as pool:
-        for fut in concurrent.futures.as_completed([pool.submit(score, p) for p in zip(ref, est)]):
+    if device is not None:
+        mids = []
+        for pair in zip(ref, est):
             try:
-                for k, v in fut.result().items():
-                    scores[k].append(v)
+                mids.append((_midi(pair[0]), _midi(pair[1])))
             except Exception as exc:                      # one unreadable file must not end the run
                 print(str(exc))
+        families = ("on", "flat", "full", "midi_class")
+        for got in (_device_scores(mids, device, families, with_overlap=False, errors="return") if mids else []):
+            if isinstance(got, Exception):                # a pair the host matcher would refuse
+                print(str(got))
+                continue
+            out = {}
+            for granularity in ("flat", "full", "midi_class"):
+                out.update(_program_aware_from_scores(got, granularity))
+            for k, v in out.items():
+                scores[k].append(v)
+    else:
+        with concurrent.futures.ThreadPoolExecutor(max_workers=8) as pool:
+            for fut in concurrent.futures.as_completed([pool.submit(score, p) for p in zip(ref, est)]):
+                try:
+                    for k, v in fut.result().items():
+                        scores[k].append(v)
+                except Exception as exc:                      # one unreadable file must not end the run
+                    print(str(exc))
     mean_scores = {k: float(np.mean(v)) for k, v in scores.items() if k != "F1 by program"}
     if enable_instrument_eval:
         by_prog = collections.defaultdict(list)

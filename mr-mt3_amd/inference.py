@@ -212,16 +212,20 @@ class InferenceHandler:
                                                        encoding_spec=note_sequences.NoteEncodingWithTiesSpec)
         return result["est_ns"]
 
-    def _to_notes_device(self, ids, frame_times, logps=None, min_confidence=None, recordings=None):
+    def _to_notes_device(self, ids, frame_times, logps=None, min_confidence=None, recordings=None, tables=False):
         """`_to_event` on the device: `ids` the decoder's id tensors (one per batch or recording, [rows, width] on the device,
         the widths may differ), `frame_times` their frame times, `logps` the log-probability tensors beside them or None,
-        `recordings` the row count of every recording (None: one) -> one note sequence per recording, from one launch."""
+        `recordings` the row count of every recording (None: one) -> one note sequence per recording, from one launch.
+        `tables`: the notes stay on the device, one `mrmt3.notes.DeviceNotes` for all recordings (unscored)."""
         from mrmt3 import notes
         width = max(t.shape[1] for t in ids)
         eos, pad_id = self.model.config.eos_token_id, getattr(self.model.config, "pad_token_id", 0)
         pad = lambda t, v: t if t.shape[1] == width else torch.nn.functional.pad(t, (0, width - t.shape[1]), value=v)
         # (a row is read up to its first EOS, and a row without one contributes nothing: the padding changes neither)
         flat = torch.cat([pad(t, pad_id) for t in ids])
+        if tables:
+            return notes.decode_notes_device(flat, np.concatenate(frame_times, axis=0), self.codec, recordings=recordings,
+                                             eos_token_id=eos, pad_token_id=pad_id)
         flat_lp = None if logps is None else torch.cat([pad(t.float(), 0.0) for t in logps])
         arrays = notes.decode_notes(flat, np.concatenate(frame_times, axis=0), self.codec, logp=flat_lp, recordings=recordings,
                                     eos_token_id=eos, pad_token_id=pad_id)
@@ -295,7 +299,8 @@ class InferenceHandler:
     @torch.no_grad()
     def inference_many(self, audios, outpaths=None, max_length=1024, return_tokens=False, valid_programs=None,
                        num_beams=1, with_confidence=False, min_confidence=None, do_sample=False, temperature=1.0, top_k=0,
-                       top_p=1.0, seed=0, best_of=1, constrained=False, sample_rate=None, device_notes=None):
+                       top_p=1.0, seed=0, best_of=1, constrained=False, sample_rate=None, device_notes=None,
+                       return_tables=False):
         """Several recordings in one go (`sample_rate` as in `inference`, the same for every recording).
         Segment-memory models decode them in lockstep (one batch row per
         recording, `model.generate_songs`); the plain T5 simply batches all segments.  Returns one note sequence
@@ -304,7 +309,11 @@ class InferenceHandler:
         `with_confidence` / `min_confidence` as in `inference`.  The sampling keywords as in `inference` (under
         `decode_options`): the plain T5 decodes every segment in one batch under `seed`, the segment-memory models draw
         segment i of every recording under `seed + i`; `best_of` > 1 is for the plain T5.  `constrained` as in `inference`,
-        honoured as given.  `device_notes` as in `inference`: every recording's notes come from one launch."""
+        honoured as given.  `device_notes` as in `inference`: every recording's notes come from one launch.
+        `return_tables`: the notes are decoded on the device and stay there: one `mrmt3.notes.DeviceNotes` for all
+        recordings instead of note sequences, what `mrmt3.scoring.score_tables` takes (no confidence, no files)."""
+        if return_tables and (return_tokens or with_confidence or min_confidence is not None or outpaths is not None):
+            raise ValueError("return_tables gives the device's note tables alone: no tokens, confidence or MIDI files")
         sample = self._sample_options(do_sample, temperature, top_k, top_p, seed, best_of)
         if sample is not None and best_of > 1 and hasattr(self.model, "generate_songs"):
             raise ValueError("best_of > 1 is for the plain T5 model (MT3Net); the segment-memory models decode one sample "
@@ -344,6 +353,8 @@ class InferenceHandler:
                     lps.append(flat_lp[at:at + x.shape[0]])
                 at += x.shape[0]
         out = []
+        if return_tables:
+            return self._to_notes_device(list(ids), [ft for _, ft in pre], recordings=[len(ft) for _, ft in pre], tables=True)
         if (self.device_notes if device_notes is None else bool(device_notes)) and not return_tokens:
             out = self._to_notes_device(list(ids), [ft for _, ft in pre], list(lps) if scored else None, min_confidence,
                                         recordings=[len(ft) for _, ft in pre])

@@ -62,7 +62,8 @@ def header_signatures(path: str = HEADER_PATH) -> dict:
             m = re.fullmatch(r"\s*(.*?[\s\*])\w+\s*", prm, flags=re.S)       # type, then the parameter's name
             if m is None:
                 raise TypeError(f"{name}: cannot parse the parameter '{prm.strip()}'")
-            args.append(_ctype(m.group(1), name))
+            # (an f64 by value is a parameter type only — the matcher's tolerances; `_ctype` itself does not take it)
+            args.append(C.c_double if m.group(1).split() == ["double"] else _ctype(m.group(1), name))
         sigs[name] = (_ctype(ret, name), args)
     if set(sigs) != set(header_symbols(path)):
         raise TypeError("unparsed prototypes: %s" % sorted(set(sigs) ^ set(header_symbols(path))))
@@ -106,7 +107,7 @@ def load():
     return lib
 
 
-MIN_VERSION = 126
+MIN_VERSION = 127
 COUNTER_NAMES = ("gemm_nt_tile", "gemm_nt8", "gemm_nt_geglu", "tn_group", "tn8", "tn_tile", "attn_fwd", "attn_bwd",
                  "attn_bwd_onepass", "attn_f32", "tn_f32", "gemm_nt_splitk", "gemm_nt_addnorm", "gemm_nt_normbwd",
                  "gemm_nt_geglubwd", "attn_fwd_varlen", "attn_bwd_varlen", "logmel_wave", "logmel_general")
@@ -350,6 +351,49 @@ def notes_decode(grammar, ids, seg_first, start_time, limit, velocity_of_bin, st
 def notes_launches(reset: bool = False) -> int:
     """Launches of `notes_decode` since the process started / the last reset (mrmt3_notes_launches)."""
     return int(load().mrmt3_notes_launches(int(reset)))
+
+
+def note_match(ref_times, ref_meta, est_times, est_meta, ref_idx, ref_first, est_idx, est_first, prob_flags, pitch_lo,
+               pitch_hi, onset_tol=0.05, offset_ratio=0.2, offset_min_tol=0.05):
+    """ref_times / est_times [n, 2] f64 and ref_meta / est_meta [n, 4] int32 (note tables: a `mrmt3.labels.NoteTable` on the
+    device, the output of `notes_decode`); ref_idx [Lr] / est_idx [Le] int32, the entries of every problem's two lists, each
+    in onset order; ref_first / est_first [n_prob + 1] int32; prob_flags [n_prob] int32 (bit 0: offsets on, bits 8..: the
+    pitch table); pitch_lo / pitch_hi [n_tables, 128] int32, all on the device -> (matched [n_prob] int32, match [Le] int32,
+    status [n_prob] int32).  ONE launch for every problem; Lr and Le are taken from the list tensors' lengths, no read-back
+    (include/mrmt3_hip.h: mrmt3_note_match_fwd)."""
+    _dev(ref_times, ref_meta, est_times, est_meta, ref_idx, ref_first, est_idx, est_first, prob_flags, pitch_lo, pitch_hi)
+    for times, meta in ((ref_times, ref_meta), (est_times, est_meta)):
+        n = meta.shape[0]
+        assert times.shape == (n, 2) and times.dtype == torch.float64 and times.is_contiguous()
+        assert meta.shape == (n, 4) and meta.dtype == torch.int32 and meta.is_contiguous()
+    for t in (ref_idx, est_idx, ref_first, est_first, prob_flags):
+        assert t.dim() == 1 and t.dtype == torch.int32 and t.is_contiguous()
+    n_prob = prob_flags.numel()
+    assert ref_first.numel() == n_prob + 1 and est_first.numel() == n_prob + 1
+    assert pitch_lo.dim() == 2 and pitch_lo.shape[1] == 128 and pitch_lo.dtype == torch.int32 and pitch_lo.is_contiguous()
+    assert pitch_hi.shape == pitch_lo.shape and pitch_hi.dtype == torch.int32 and pitch_hi.is_contiguous()
+    dev, Lr, Le = prob_flags.device, ref_idx.numel(), est_idx.numel()
+    matched = torch.empty(n_prob, device=dev, dtype=torch.int32)
+    status = torch.empty(n_prob, device=dev, dtype=torch.int32)
+    match = torch.empty(Le, device=dev, dtype=torch.int32)
+    lib = load()
+    words = int(lib.mrmt3_note_match_workspace_bytes(Lr, Le)) // 4
+    if words == 0 and (Lr or Le):
+        raise ValueError(f"note_match: list lengths {Lr}, {Le} are beyond the kernel's 2^30 entries")
+    ws = torch.empty(max(words, 1), device=dev, dtype=torch.int32)
+    spare = torch.empty(4, 4, device=dev, dtype=torch.int32)           # what an empty tensor's null pointer is replaced by
+    ptr = lambda t: _p(t) if t.numel() else _p(spare)
+    _check(lib.mrmt3_note_match_fwd(ptr(ref_times), ptr(ref_meta), ref_meta.shape[0], ptr(est_times), ptr(est_meta),
+                                    est_meta.shape[0], ptr(ref_idx), _p(ref_first), ptr(est_idx), _p(est_first),
+                                    ptr(prob_flags), n_prob, _p(pitch_lo), _p(pitch_hi), pitch_lo.shape[0], float(onset_tol),
+                                    float(offset_ratio), float(offset_min_tol), _p(matched), ptr(match), _p(status), _p(ws),
+                                    _stream()), "note_match_fwd")
+    return matched, match, status
+
+
+def note_match_launches(reset: bool = False) -> int:
+    """Launches of `note_match` since the process started / the last reset (mrmt3_note_match_launches)."""
+    return int(load().mrmt3_note_match_launches(int(reset)))
 
 
 def gemm_nt(a, b, out=None, out_dtype=None, accumulate=False):

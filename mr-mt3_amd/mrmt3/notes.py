@@ -9,6 +9,9 @@ kernel and runs without a GPU; tests hold it to the definition.  `decode_notes` 
 of every recording, no CPU fallback of the kernel itself — only a recording with more notes sounding at once than the
 kernel's LDS holds (`status != 0`) is decoded on the host, and that recording alone.
 
+`decode_notes_device` is `decode_notes` without the copy home: the notes of every recording stay on the device as one
+`DeviceNotes`, what `mrmt3.scoring` scores.
+
 The quirks of the definition are reproduced, not repaired: a row without EOS contributes no tokens, UNK cuts a row like EOS,
 and the sounding notes come out in the insertion order of the host's dict.
 """
@@ -245,11 +248,10 @@ def decode_notes_host(grammar: EventGrammar, ids, seg_first, start_time, limit, 
 _TABLES = {}
 
 
-def decode_notes(ids_dev, frame_times, codec, logp=None, recordings=None, eos_token_id=1, pad_token_id=0) -> List[NoteArrays]:
-    """ids_dev [rows, ld] int64 on the device as the decoder returned them (every row of every recording, a recording's rows
-    together), frame_times [rows, frames] on the host, `codec` of `vocabularies.build_codec`, logp [rows, ld] f32 on the
-    device or None, `recordings` the row count of each recording (None: one) -> one `NoteArrays` per recording.  One launch;
-    only the notes written come back.  A recording over the kernel's capacity is decoded by `decode_notes_host`."""
+def _decode_launch(ids_dev, frame_times, codec, logp, recordings, eos_token_id, pad_token_id):
+    """The launch `decode_notes` and `decode_notes_device` share: the checks, the row order, ONE `lib.notes_decode`, the
+    per-recording head read back, and the notes written gathered on the device (one copy of what is needed instead of the
+    regions whole).  Returns a dict; `redo(r)` decodes recording r on the host (a recording over the kernel's capacity)."""
     import torch
     from mrmt3 import lib
     check_codec(codec)
@@ -283,22 +285,130 @@ def decode_notes(ids_dev, frame_times, codec, logp=None, recordings=None, eos_to
     head = torch.stack([out[k] for k in ("n_notes", "invalid", "dropped", "status")]).cpu().numpy()
     total = out["total_time"].cpu().numpy()
     counts = np.where(head[3] == 0, head[0], 0)
-    # the notes written, gathered on the device: one copy of what is needed instead of the regions whole
     pick = np.concatenate([int(seg_first[r]) * (ld - 1) + np.arange(counts[r]) for r in range(n_rec)] or [np.zeros(0, int)])
     at = torch.from_numpy(pick.astype(np.int64)).to(dev)
-    times, meta = out["times"][at].cpu().numpy(), out["meta"][at].cpu().numpy()
-    logc = None if logp is None else out["logc"][at].cpu().numpy()
-    result, o = [], 0
-    for r in range(n_rec):
+
+    def redo(r):
         a, b = int(seg_first[r]), int(seg_first[r + 1])
+        arrays = decode_notes_host(grammar, ids_dev[a:b].cpu().numpy(), np.asarray([0, b - a]), start[a:b], limit[a:b],
+                                   velocity_table(codec), sps, None if logp is None else logp[a:b].cpu().numpy())[0]
+        arrays.status = int(head[3][r])
+        return arrays
+
+    return dict(n_rec=n_rec, head=head, total=total, counts=counts, redo=redo, times=out["times"][at], meta=out["meta"][at],
+                logc=None if logp is None else out["logc"][at])
+
+
+def decode_notes(ids_dev, frame_times, codec, logp=None, recordings=None, eos_token_id=1, pad_token_id=0) -> List[NoteArrays]:
+    """ids_dev [rows, ld] int64 on the device as the decoder returned them (every row of every recording, a recording's rows
+    together), frame_times [rows, frames] on the host, `codec` of `vocabularies.build_codec`, logp [rows, ld] f32 on the
+    device or None, `recordings` the row count of each recording (None: one) -> one `NoteArrays` per recording.  One launch;
+    only the notes written come back.  A recording over the kernel's capacity is decoded by `decode_notes_host`."""
+    d = _decode_launch(ids_dev, frame_times, codec, logp, recordings, eos_token_id, pad_token_id)
+    head, total, counts = d["head"], d["total"], d["counts"]
+    times, meta = d["times"].cpu().numpy(), d["meta"].cpu().numpy()
+    logc = None if d["logc"] is None else d["logc"].cpu().numpy()
+    result, o = [], 0
+    for r in range(d["n_rec"]):
         if head[3][r] != 0:                      # over capacity: this recording alone goes to the host
-            redo = decode_notes_host(grammar, ids_dev[a:b].cpu().numpy(), np.asarray([0, b - a]), start[a:b], limit[a:b],
-                                     velocity_table(codec), sps, None if logp is None else logp[a:b].cpu().numpy())[0]
-            redo.status = int(head[3][r])
-            result.append(redo)
+            result.append(d["redo"](r))
             continue
         n = int(counts[r])
         result.append(NoteArrays(times[o:o + n], meta[o:o + n], None if logc is None else logc[o:o + n], int(head[1][r]),
                                  int(head[2][r]), float(total[r])))
         o += n
     return result
+
+
+@dataclasses.dataclass
+class DeviceNotes:
+    """The notes of several recordings as tensors on one device, for `mrmt3.scoring`: times float64 [N, 2] and meta int32
+    [N, 4] in the layout of `NoteArrays` / `mrmt3.labels.NoteTable`; recording r's notes are the rows
+    [first[r], first[r] + count[r]) (int64 [R]); invalid, dropped, status int32 [R] and total_time float64 [R] as the decoder
+    reported them (zeros for tables that were not decoded).  `counts` is the host's copy of `count`, kept so that nothing
+    is read back to learn a size."""
+    times: "torch.Tensor"
+    meta: "torch.Tensor"
+    first: "torch.Tensor"
+    count: "torch.Tensor"
+    invalid: "torch.Tensor"
+    dropped: "torch.Tensor"
+    total_time: "torch.Tensor"
+    status: "torch.Tensor"
+    counts: Optional[np.ndarray] = None
+
+    def __len__(self) -> int:
+        return int(self.count.numel())
+
+    def host_counts(self) -> np.ndarray:
+        if self.counts is None:
+            self.counts = self.count.cpu().numpy().astype(np.int64)
+        return self.counts
+
+    @classmethod
+    def from_arrays(cls, tables, device) -> "DeviceNotes":
+        """`tables`: one (times [n, 2], meta [n, 4]) pair of numpy arrays (or a `NoteArrays`) per recording, uploaded."""
+        import torch
+        pairs = [(t.times, t.meta) if hasattr(t, "meta") else t for t in tables]
+        counts = np.asarray([len(m) for _, m in pairs], np.int64)
+        times = np.concatenate([np.asarray(t, np.float64).reshape(-1, 2) for t, _ in pairs] or [np.zeros((0, 2))])
+        meta = np.concatenate([np.asarray(m, np.int32).reshape(-1, 4) for _, m in pairs] or [np.zeros((0, 4), np.int32)])
+        R = len(pairs)
+        zeros = torch.zeros(R, dtype=torch.int32, device=device)
+        total = [float(t.total_time) if hasattr(t, "total_time") else 0.0 for t in tables]
+        return cls(torch.from_numpy(times).to(device), torch.from_numpy(meta).to(device),
+                   torch.from_numpy(np.cumsum(counts) - counts).to(device), torch.from_numpy(counts).to(device), zeros,
+                   zeros.clone(), torch.tensor(total, dtype=torch.float64, device=device), zeros.clone(), counts)
+
+    @classmethod
+    def from_note_table(cls, times, meta=None) -> "DeviceNotes":
+        """One recording: a track's reference, `mrmt3.labels.NoteTable` tensors already on a device (`times`, `meta`, or an
+        object that has both).  No copy."""
+        import torch
+        if meta is None:
+            times, meta = times.times, times.meta
+        n, dev = meta.shape[0], meta.device
+        zeros = torch.zeros(1, dtype=torch.int32, device=dev)
+        return cls(times, meta, torch.zeros(1, dtype=torch.int64, device=dev), torch.full((1,), n, dtype=torch.int64, device=dev),
+                   zeros, zeros.clone(), torch.zeros(1, dtype=torch.float64, device=dev), zeros.clone(),
+                   np.asarray([n], np.int64))
+
+    @classmethod
+    def concat(cls, parts) -> "DeviceNotes":
+        """Several `DeviceNotes` of one device as one, the recordings in order."""
+        import torch
+        parts = list(parts)
+        offs = np.cumsum([0] + [p.meta.shape[0] for p in parts])
+        cat = lambda name: torch.cat([getattr(p, name) for p in parts])
+        return cls(cat("times"), cat("meta"), torch.cat([p.first + int(o) for p, o in zip(parts, offs)]), cat("count"),
+                   cat("invalid"), cat("dropped"), cat("total_time"), cat("status"),
+                   np.concatenate([p.host_counts() for p in parts]))
+
+
+def decode_notes_device(ids_dev, frame_times, codec, recordings=None, eos_token_id=1, pad_token_id=0) -> DeviceNotes:
+    """`decode_notes` without the copy home: the same launch, the notes stay on the device as one `DeviceNotes` (unscored).
+    Only the per-recording head comes back.  A recording with `status != 0` is decoded on the host and uploaded, that one
+    alone."""
+    import torch
+    d = _decode_launch(ids_dev, frame_times, codec, None, recordings, eos_token_id, pad_token_id)
+    head, counts, dev = d["head"], d["counts"].astype(np.int64), ids_dev.device
+    times, meta, total = d["times"], d["meta"], d["total"].copy()
+    invalid, dropped = head[1].copy(), head[2].copy()
+    if (head[3] != 0).any():
+        tparts, mparts, o = [], [], 0
+        for r in range(d["n_rec"]):
+            n = int(counts[r])
+            if head[3][r] != 0:
+                redo = d["redo"](r)
+                tparts.append(torch.from_numpy(redo.times).to(dev))
+                mparts.append(torch.from_numpy(redo.meta).to(dev))
+                counts[r], invalid[r], dropped[r], total[r] = len(redo), redo.invalid, redo.dropped, redo.total_time
+            else:
+                tparts.append(times[o:o + n])
+                mparts.append(meta[o:o + n])
+            o += n
+        times, meta = torch.cat(tparts), torch.cat(mparts)
+    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dev).to(dt)
+    return DeviceNotes(times, meta, up(np.cumsum(counts) - counts, torch.int64), up(counts, torch.int64),
+                       up(invalid, torch.int32), up(dropped, torch.int32), up(total, torch.float64),
+                       up(head[3], torch.int32), counts)

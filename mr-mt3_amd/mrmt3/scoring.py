@@ -1,0 +1,430 @@
+"""Note-level scores from device-resident note tables: the pitch tables, the problem lists and the host
+restatement of `mrmt3_note_match_fwd` (include/mrmt3_hip.h), and `score_tables`, which reproduces `evaluate.py`'s numbers.
+
+The scores are BY DEFINITION those of `evaluate.compute_transcription_metrics` and `evaluate.mt3_program_aware_note_scores`
+(the mir_eval restatement in `contrib.transcription_metrics`).  Precision, recall and F1 depend only on the SIZE of a maximum
+matching, which is unique, so they are assembled from integers by the very expressions `evaluate.py` uses
+(`tm.scores_from_counts`, `evaluate.program_aware_result`): the results are equal with `==`.  The overlap ratio depends on
+WHICH maximum matching was found and may differ from the host's in the last digits, as the host's may from mir_eval's.
+
+`match_notes_host` is the kernel's contract on numpy arrays: window-based, never an n x m matrix.  It is the oracle of the
+kernel and runs without a GPU; tests hold it to `tm.match_notes`.
+"""
+from __future__ import annotations
+
+import dataclasses
+from typing import List
+
+import numpy as np
+
+from contrib import transcription_metrics as tm
+
+ONSET_TOLERANCE = 0.05
+OFFSET_RATIO = 0.2
+OFFSET_MIN_TOLERANCE = 0.05
+PITCH_TOLERANCE = 50.0
+STATUS_ORDER = 2         # a list of the problem is not in onset order
+TABLE_MIDI_AS_HZ = 0     # compute_transcription_metrics and "Onset F1": MIDI numbers go to the matcher as if they were Hz
+TABLE_HZ = 1             # the per-program scores: midi_to_hz values
+FAMILIES = ("onoff", "on", "flat", "midi_class", "full")
+GRANULARITIES = FAMILIES[2:]
+MIN_PITCH, MAX_PITCH = 21, 108       # tm.sequence_to_valued_intervals
+
+
+def pitch_tables():
+    """(lo, hi) int32 [2, 128]: reference pitch r and estimated pitch e are within the pitch tolerance iff
+    lo[t, r] <= e <= hi[t, r] (an empty range is lo > hi).  Each row comes from the expression of `tm.match_notes` on the
+    128 values the matcher would be handed: table 0 the MIDI numbers themselves, table 1 `tm.midi_to_hz` of them.  Pitch 0 of
+    table 0 has no edge (the host refuses a pitch <= 0)."""
+    lo, hi = np.ones((2, 128), np.int32), np.zeros((2, 128), np.int32)
+    midi = np.arange(128, dtype=np.float64)
+    for t, values in ((TABLE_MIDI_AS_HZ, midi), (TABLE_HZ, tm.midi_to_hz(midi))):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            cents = np.abs(1200.0 * np.subtract.outer(np.log2(values), np.log2(values)))
+            hit = np.less_equal(cents, PITCH_TOLERANCE)
+        if t == TABLE_MIDI_AS_HZ:
+            hit[0, :] = hit[:, 0] = False
+        for r in range(128):
+            at = np.flatnonzero(hit[r])
+            if len(at):
+                assert (np.diff(at) == 1).all()              # (a pitch's neighbours are a range)
+                lo[t, r], hi[t, r] = at[0], at[-1]
+    return lo, hi
+
+
+def _distance(a, b):
+    return np.around(np.abs(a - b), decimals=tm.N_DECIMALS)
+
+
+def _keys(times, idx):
+    """(valid bool [L], key f64 [L]) of one list: an entry is valid when its index lies in the table and its onset is a
+    number; the key is the onset of the nearest valid entry at or before it, -inf if there is none."""
+    idx = np.asarray(idx, np.int64)
+    n = len(times)
+    valid = (idx >= 0) & (idx < n)
+    onset = np.full(len(idx), np.nan)
+    onset[valid] = times[idx[valid], 0]
+    valid &= ~np.isnan(onset)
+    last = np.maximum.accumulate(np.where(valid, np.arange(len(idx)), -1))
+    key = np.where(last >= 0, onset[np.maximum(last, 0)], -np.inf)
+    return valid, key
+
+
+def _ordered(valid, key, idx) -> bool:
+    at = np.flatnonzero(valid)
+    k, i = key[at], np.asarray(idx, np.int64)[at]
+    return bool(((k[:-1] < k[1:]) | ((k[:-1] == k[1:]) & (i[:-1] < i[1:]))).all())
+
+
+def match_notes_host(ref_times, ref_meta, est_times, est_meta, ref_idx, ref_first, est_idx, est_first, prob_flags, pitch_lo,
+                     pitch_hi, onset_tol=ONSET_TOLERANCE, offset_ratio=OFFSET_RATIO, offset_min_tol=OFFSET_MIN_TOLERANCE):
+    """The contract of `mrmt3_note_match_fwd` on the host, the arguments of `lib.note_match` as numpy arrays ->
+    (matched int32 [n_prob], match int32 [Le], status int32 [n_prob]).  The same decomposition as the kernel (order, exact
+    windows, Kuhn's search from every estimated entry in list order, a free reference before a descent, the lowest
+    first), so the matching itself is the kernel's, not only its size."""
+    ref_times, est_times = np.asarray(ref_times, np.float64).reshape(-1, 2), np.asarray(est_times, np.float64).reshape(-1, 2)
+    ref_pitch, est_pitch = np.asarray(ref_meta).reshape(-1, 4)[:, 0], np.asarray(est_meta).reshape(-1, 4)[:, 0]
+    ref_idx, est_idx = np.asarray(ref_idx, np.int64), np.asarray(est_idx, np.int64)
+    pitch_lo, pitch_hi = np.asarray(pitch_lo).reshape(-1, 128), np.asarray(pitch_hi).reshape(-1, 128)
+    n_prob, Lr, Le = len(prob_flags), len(ref_idx), len(est_idx)
+    assert len(ref_first) == n_prob + 1 and len(est_first) == n_prob + 1
+    matched, status = np.zeros(n_prob, np.int32), np.zeros(n_prob, np.int32)
+    match = np.full(Le, -1, np.int32)
+    clamp = lambda v, lo, hi: min(max(int(v), lo), hi)
+    for p in range(n_prob):
+        r0 = clamp(ref_first[p], 0, Lr)
+        r1 = clamp(ref_first[p + 1], r0, Lr)
+        e0 = clamp(est_first[p], 0, Le)
+        e1 = clamp(est_first[p + 1], e0, Le)
+        offsets, table = bool(prob_flags[p] & 1), int(prob_flags[p]) >> 8
+        r_valid, r_key = _keys(ref_times, ref_idx[r0:r1])
+        e_valid, e_key = _keys(est_times, est_idx[e0:e1])
+        if not (_ordered(r_valid, r_key, ref_idx[r0:r1]) and _ordered(e_valid, e_key, est_idx[e0:e1])):
+            status[p] = STATUS_ORDER
+            continue
+        if not 0 <= table < len(pitch_lo):
+            continue
+        # the valid references' fields, by list position
+        rn = np.where(r_valid, ref_idx[r0:r1], 0)
+        r_on, r_off, r_pitch = ref_times[rn, 0], ref_times[rn, 1], ref_pitch[rn]
+        r_ok = r_valid & (r_pitch >= 0) & (r_pitch < 128)
+        r_lo, r_hi = pitch_lo[table][np.clip(r_pitch, 0, 127)], pitch_hi[table][np.clip(r_pitch, 0, 127)]
+        with np.errstate(invalid="ignore"):
+            r_tol = np.maximum(offset_ratio * (r_off - r_on), offset_min_tol)
+        # windows: a coarse bracket by the keys, the exact predicate inside it
+        margin = onset_tol + 1e-5
+        wlo, whi = np.zeros(e1 - e0, np.int64), np.zeros(e1 - e0, np.int64)
+        for k in range(e1 - e0):
+            a = int(np.searchsorted(r_key, e_key[k] - margin, "left"))
+            b = int(np.searchsorted(r_key, e_key[k] + margin, "right"))
+            with np.errstate(invalid="ignore"):
+                near = _distance(r_key[a:b], e_key[k]) <= onset_tol
+            wlo[k] = a + int(np.count_nonzero(~((r_key[a:b] >= e_key[k]) | near)))
+            whi[k] = b - int(np.count_nonzero((r_key[a:b] > e_key[k]) & ~near))
+        owner = np.full(r1 - r0, -1, np.int64)
+        stamp = np.zeros(r1 - r0, np.int64)
+
+        def candidates(k):
+            """(edge bool, free bool) over the window of estimated entry k"""
+            a, b = wlo[k], whi[k]
+            if not e_valid[k]:
+                return np.zeros(b - a, bool), np.zeros(b - a, bool)
+            en = est_idx[e0 + k]
+            on_e, off_e, pitch_e = est_times[en, 0], est_times[en, 1], est_pitch[en]
+            with np.errstate(invalid="ignore"):
+                edge = r_ok[a:b] & (_distance(r_on[a:b], on_e) <= onset_tol)
+                edge &= (r_lo[a:b] <= pitch_e) & (pitch_e <= r_hi[a:b])
+                if offsets:
+                    edge &= _distance(r_off[a:b], off_e) <= r_tol[a:b]
+            return edge, owner[a:b] < 0
+
+        for root in range(e1 - e0):
+            cur, stack = root, []
+            while True:
+                edge, free = candidates(cur)
+                a = wlo[cur]
+                hit = np.flatnonzero(edge & free)
+                if len(hit):
+                    e, r = cur, a + int(hit[0])
+                    while True:
+                        owner[r] = e
+                        match[e0 + e] = r0 + r
+                        if not stack:
+                            break
+                        e, r = stack.pop()
+                    matched[p] += 1
+                    break
+                down = np.flatnonzero(edge & ~free & (stamp[a:whi[cur]] != root + 1))
+                if len(down):
+                    r = a + int(down[0])
+                    stamp[r] = root + 1
+                    stack.append((cur, r))
+                    cur = int(owner[r])
+                elif stack:
+                    cur = stack.pop()[0]
+                else:
+                    break
+    return matched, match, status
+
+
+@dataclasses.dataclass
+class MidiTable:
+    """A MIDI file's notes as a table (instrument after instrument) and, for the program groups, every instrument's
+    (program, is_drum) in order: an instrument without notes still names a group in `evaluate.py`."""
+    times: np.ndarray
+    meta: np.ndarray
+    programs: list
+
+
+def table_from_midi(mid) -> MidiTable:
+    """`contrib.midi_io.MidiData` -> the note table `evaluate.py`'s scores are functions of."""
+    times = [(n.start, n.end) for inst in mid.instruments for n in inst.notes]
+    meta = [(n.pitch, n.velocity, int(inst.program) | int(bool(inst.is_drum)) << 8, 0)
+            for inst in mid.instruments for n in inst.notes]
+    return MidiTable(np.asarray(times, np.float64).reshape(-1, 2), np.asarray(meta, np.int32).reshape(-1, 4),
+                     [(int(inst.program), bool(inst.is_drum)) for inst in mid.instruments])
+
+
+@dataclasses.dataclass
+class Problems:
+    """What `build_problems` returns.  On the tables' device: ref_idx, ref_first, est_idx, est_first, prob_flags as
+    `lib.note_match` takes them.  On the host, per problem: pair (the recording pair), family (an index into FAMILIES), key
+    ((granular program, is_drum), None for the agnostic families), n_ref, n_est (the list lengths) and first_ref / first_est
+    (the lowest table row on each side, the order of first appearance)."""
+    ref_idx: "torch.Tensor"
+    ref_first: "torch.Tensor"
+    est_idx: "torch.Tensor"
+    est_first: "torch.Tensor"
+    prob_flags: "torch.Tensor"
+    pair: np.ndarray
+    family: np.ndarray
+    key: list
+    n_ref: np.ndarray
+    n_est: np.ndarray
+    first_ref: np.ndarray
+    first_est: np.ndarray
+    errors: list                                  # per pair: None, or the ValueError the host scorer would raise
+    families: tuple = FAMILIES                    # the families built
+
+
+_NO_ROW = 1 << 40
+
+
+def _side(notes, families):
+    """Per entry of one side: the table row, the recording, the problem key; and the [R, 4] validity counts."""
+    import torch
+    counts = notes.host_counts()
+    dev, R, total = notes.meta.device, len(counts), int(counts.sum())
+    count = notes.count.to(torch.int64)
+    rec = torch.repeat_interleave(torch.arange(R, device=dev), count, output_size=total)
+    begin = torch.cumsum(count, 0) - count
+    rows = notes.first.to(torch.int64)[rec] + (torch.arange(total, device=dev) - begin[rec])
+    start, end = notes.times[rows, 0], notes.times[rows, 1]
+    pitch, prog = notes.meta[rows, 0].to(torch.int64), notes.meta[rows, 2].to(torch.int64)
+    drum, prog = (prog >> 8) & 1, prog & 0xff
+    piano = (pitch >= MIN_PITCH) & (pitch <= MAX_PITCH) & (end != start)
+    ent_rows, ent_key = [], []
+    for name in families:
+        f = FAMILIES.index(name)
+        if f < 2:
+            keep, group = piano, torch.zeros_like(pitch)
+        elif name == "flat":
+            keep, group = None, drum | drum << 8
+        elif name == "midi_class":
+            keep, group = None, (prog // 8) * 8 | drum << 8
+        else:
+            keep, group = None, prog | drum << 8
+        key = ((rec * len(FAMILIES) + f) << 9) | group
+        ent_rows.append(rows if keep is None else rows[keep])
+        ent_key.append(key if keep is None else key[keep])
+    # tm._validate: a negative time, a duration <= 0 — among the piano-range notes, and among all
+    negative, short = (start < 0) | (end < 0), end <= start
+    bad = torch.stack([negative & piano, short & piano, negative, short], 1).to(torch.int64)
+    flags = torch.zeros(R, 4, dtype=torch.int64, device=dev).index_add_(0, rec, bad)
+    return torch.cat(ent_rows), torch.cat(ent_key), flags
+
+
+def build_problems(ref, est, families=FAMILIES) -> Problems:
+    """The lists of `evaluate.py`'s scores for every recording pair (ref recording r against est recording r; `ref`, `est`:
+    `mrmt3.notes.DeviceNotes` on one device, the host included).  Per pair:
+      - "onoff" and "on": the notes with pitch 21..108 and end != start (`tm.sequence_to_valued_intervals`), pitch table 0,
+        the offset criterion on and off;
+      - "flat", "midi_class", "full": one problem per (`evaluate.get_granular_program`, is_drum) key present on either side,
+        all notes, pitch table 1, offsets off.
+    Sorting and counting are torch operations on the tables' device; one tensor comes back: the problem keys, the list
+    lengths, and the counts that tell where `tm._validate` would raise (`errors`: the same ValueError, per pair)."""
+    import torch
+    families = tuple(families)
+    if not families or any(f not in FAMILIES for f in families):
+        raise ValueError("families must be a non-empty subset of %r, got %r" % (FAMILIES, families))
+    R = len(ref)
+    if len(est) != R:
+        raise ValueError("%d reference recordings against %d estimated ones" % (R, len(est)))
+    dev = ref.meta.device
+    r_rows, r_key, r_flags = _side(ref, families)
+    e_rows, e_key, e_flags = _side(est, families)
+    # the agnostic problems exist for every pair, the group problems where a key is present
+    forced = [(r * len(FAMILIES) + FAMILIES.index(f)) << 9 for r in range(R) for f in families if FAMILIES.index(f) < 2]
+    uniq = torch.unique(torch.cat([r_key, e_key, torch.tensor(forced, dtype=torch.int64, device=dev)]))
+    P = int(uniq.numel())
+    out, counts, firsts = [], [], []
+    for rows, key, notes in ((r_rows, r_key, ref), (e_rows, e_key, est)):
+        pid = torch.searchsorted(uniq, key)
+        by_onset = torch.sort(notes.times[rows, 0], stable=True).indices     # (entries of a problem are in row order)
+        order = by_onset[torch.sort(pid[by_onset], stable=True).indices]
+        n = torch.bincount(pid, minlength=P)
+        low = torch.full((P,), _NO_ROW, dtype=torch.int64, device=dev).scatter_reduce_(0, pid, rows, "amin")
+        out.append((rows[order].to(torch.int32), torch.cat([n.new_zeros(1), torch.cumsum(n, 0)]).to(torch.int32)))
+        counts.append(n)
+        firsts.append(low)
+    family_dev = (uniq >> 9) % len(FAMILIES)
+    flags = ((family_dev == 0).to(torch.int32) | (torch.where(family_dev < 2, TABLE_MIDI_AS_HZ, TABLE_HZ) << 8)).to(torch.int32)
+    home = torch.cat([uniq, counts[0], counts[1], firsts[0], firsts[1], r_flags.reshape(-1), e_flags.reshape(-1)]).cpu().numpy()
+    uniq_h, n_ref, n_est, first_ref, first_est = (home[i * P:(i + 1) * P] for i in range(5))
+    bad_ref, bad_est = home[5 * P:5 * P + 4 * R].reshape(R, 4), home[5 * P + 4 * R:].reshape(R, 4)
+    family = (uniq_h >> 9) % len(FAMILIES)
+    keys = [None if f < 2 else (int(k & 0xff), bool(k >> 8 & 1)) for f, k in zip(family, uniq_h & 0x1ff)]
+    piano_only = all(FAMILIES.index(f) < 2 for f in families)
+    errors = []
+    for r in range(R):
+        message = None
+        for bad, name in ((bad_ref[r], "reference"), (bad_est[r], "estimated")):
+            negative, short = (bad[0], bad[1]) if piano_only else (bad[2], bad[3])
+            if message is None and negative:
+                message = f"negative {name} interval time"
+            if message is None and short:
+                message = f"all {name} interval durations must be strictly positive"
+        errors.append(None if message is None else ValueError(message))
+    return Problems(out[0][0], out[0][1], out[1][0], out[1][1], flags, (uniq_h >> 9) // len(FAMILIES), family, keys,
+                    n_ref, n_est, first_ref, first_est, errors, families)
+
+
+def assemble_scores(problems: Problems, matched, programs_ref=None, programs_est=None, overlaps=None) -> List[dict]:
+    """One dict per recording pair from the matchings' sizes (`matched` [n_prob], host): the keys of
+    `evaluate.compute_transcription_metrics` (when "onoff" and "on" were built) and of
+    `evaluate.mt3_program_aware_note_scores` at every granularity built, whose "F1 by program" is kept per granularity as
+    "F1 by program (<granularity>)" and, for the last of flat / full / midi_class built, as "F1 by program" — what
+    `evaluate_main` is left with.  `programs_ref` / `programs_est`: per pair every instrument's (program, is_drum) in order
+    (None: the groups in order of first appearance in the table; the same unless an instrument has no notes).
+    `overlaps`: {problem: average overlap ratio} for the agnostic problems, or None: the overlap keys are absent."""
+    import evaluate
+    R = len(problems.errors)
+    by_pair = [dict() for _ in range(R)]
+    for p, (r, f) in enumerate(zip(problems.pair, problems.family)):
+        by_pair[int(r)].setdefault(int(f), []).append(p)
+    results = []
+    for r in range(R):
+        mine, res = by_pair[r], {}
+        scores = lambda p: tm.scores_from_counts(int(matched[p]), int(problems.n_ref[p]), int(problems.n_est[p]))
+        agnostic = {}
+        for f in (0, 1):
+            if f in mine:
+                p = mine[f][0]
+                agnostic[f] = scores(p) + (() if overlaps is None else (overlaps[p],))
+        if 0 in agnostic and 1 in agnostic:
+            p = mine[1][0]
+            res.update(evaluate.transcription_metrics_result(int(problems.n_ref[p]), int(problems.n_est[p]), agnostic[0],
+                                                             agnostic[1]))
+        for name in ("flat", "full", "midi_class"):
+            if name not in problems.families:
+                continue
+            f = FAMILIES.index(name)
+            at = {problems.key[p]: p for p in mine.get(f, [])}
+            sides = []
+            for programs, n, first in ((programs_ref, problems.n_ref, problems.first_ref),
+                                       (programs_est, problems.n_est, problems.first_est)):
+                if programs is not None and programs[r] is not None:
+                    seen = dict.fromkeys((evaluate.get_granular_program(pr, dr, name), bool(dr)) for pr, dr in programs[r])
+                    sides.append(list(seen))
+                else:
+                    sides.append(sorted((k for k, p in at.items() if n[p] > 0), key=lambda k: first[at[k]]))
+            groups = []
+            for key in evaluate.group_order(sides[0], sides[1]):
+                p = at.get(key)
+                if p is None:                    # an instrument without notes on either side
+                    groups.append((key, (0.0, 0.0, 0.0), 0, 0))
+                else:
+                    groups.append((key, scores(p), int(problems.n_ref[p]), int(problems.n_est[p])))
+            onset = agnostic[1][:3] if 1 in agnostic else (None, None, None)
+            got = evaluate.program_aware_result(onset, groups, name)
+            if 1 not in agnostic:
+                for k in ("Onset precision", "Onset recall", "Onset F1"):
+                    del got[k]
+            res["F1 by program (%s)" % name] = got["F1 by program"]
+            res.update(got)
+        results.append(res)
+    return results
+
+
+def upload(tables, device):
+    """`DeviceNotes` of a list of tables ((times, meta) pairs, `NoteArrays`, `MidiTable`s), or the argument itself."""
+    from mrmt3.notes import DeviceNotes
+    return tables if isinstance(tables, DeviceNotes) else DeviceNotes.from_arrays(tables, device)
+
+
+def score_tables(ref, est, with_overlap=False, families=FAMILIES, errors="raise", device=None, return_matching=False):
+    """ref, est: `mrmt3.notes.DeviceNotes` (or lists of tables, uploaded to `device`) -> one dict per recording pair with the
+    keys of `compute_transcription_metrics` and of `mt3_program_aware_note_scores` at the three granularities (see
+    `assemble_scores`), from ONE launch of the device matcher for all pairs and all problems.  Only `matched`, the list
+    lengths and `status` come back; with `with_overlap` also `match` and what `tm.average_overlap_ratio` of the kernel's
+    matching needs, and the overlap keys are present.  `families`: the scores to build (a subset of FAMILIES).
+    A pair the host scorer would refuse raises its ValueError (`errors="return"`: the pair's entry is the exception).
+    `return_matching` (with `with_overlap`): also returns, per pair, {"onoff": pairs, "on": pairs}, the kernel's matchings
+    as sorted (reference note, estimated note) numbers within the recording."""
+    import torch
+    from mrmt3 import lib
+    if device is None:
+        device = ref.meta.device if hasattr(ref, "first") else est.meta.device if hasattr(est, "first") else "cuda"
+    programs = [[getattr(t, "programs", None) for t in side] if isinstance(side, (list, tuple)) else None for side in (ref, est)]
+    ref, est = upload(ref, device), upload(est, device)
+    problems = build_problems(ref, est, families)
+    if errors == "raise":
+        for e in problems.errors:
+            if e is not None:
+                raise e
+    key = str(ref.meta.device)
+    if key not in _PITCH_TABLES:
+        _PITCH_TABLES[key] = tuple(torch.from_numpy(t).to(ref.meta.device) for t in pitch_tables())
+    lo, hi = _PITCH_TABLES[key]
+    matched, match, status = lib.note_match(ref.times, ref.meta, est.times, est.meta, problems.ref_idx, problems.ref_first,
+                                            problems.est_idx, problems.est_first, problems.prob_flags, lo, hi, ONSET_TOLERANCE,
+                                            OFFSET_RATIO, OFFSET_MIN_TOLERANCE)
+    head = torch.stack([matched, status]).cpu().numpy()
+    if head[1].any():
+        raise RuntimeError("note_match: status %r (the lists of build_problems are in order: a NaN onset?)" % head[1].tolist())
+    overlaps = matchings = None
+    if with_overlap:
+        overlaps, matchings = _overlaps(problems, ref, est, match)
+    out = assemble_scores(problems, head[0], programs[0], programs[1], overlaps)
+    out = [problems.errors[r] if problems.errors[r] is not None else out[r] for r in range(len(out))]
+    return (out, matchings) if return_matching else out
+
+
+_PITCH_TABLES = {}
+
+
+def _overlaps(problems, ref, est, match):
+    """({agnostic problem: `tm.average_overlap_ratio` of the kernel's matching}, per pair {"onoff" / "on": the matching}),
+    pairs in (reference row, estimated row) order as `tm.match_notes` returns them."""
+    match = match.cpu().numpy()
+    ref_idx, est_idx = problems.ref_idx.cpu().numpy(), problems.est_idx.cpu().numpy()
+    est_first = problems.est_first.cpu().numpy()
+    ref_times, est_times = ref.times.cpu().numpy(), est.times.cpu().numpy()
+    ref_at, est_at = ref.first.cpu().numpy(), est.first.cpu().numpy()
+    out, matchings = {}, [dict() for _ in problems.errors]
+    for p in np.flatnonzero(problems.family < 2):
+        pairs = matching_of(p, match, ref_idx, est_idx, est_first)
+        r = int(problems.pair[p])
+        matchings[r][FAMILIES[problems.family[p]]] = [(a - int(ref_at[r]), b - int(est_at[r])) for a, b in pairs]
+        if problems.n_ref[p] == 0 or problems.n_est[p] == 0:
+            out[p] = 0.0
+        else:
+            out[p] = tm.average_overlap_ratio(ref_times, est_times, pairs)
+    return out, matchings
+
+
+def matching_of(p, match, ref_idx, est_idx, est_first):
+    """Sorted (reference row, estimated row) pairs of problem p from the kernel's `match`."""
+    k = np.arange(int(est_first[p]), int(est_first[p + 1]))
+    k = k[match[k] >= 0]
+    return sorted(zip(ref_idx[match[k]].tolist(), est_idx[k].tolist()))

@@ -25,7 +25,10 @@ of a track's stems at random gains, mixed inside the log-mel kernel, labelled wi
 the least number that do, `+stem_gain_db=` (6) the gain range in dB.  Row geometry is the config's (`mel_length`,
 `event_length`, `num_rows_per_batch`, `split_frame_length`, `dataloader.train.batch_size` tracks per step); the track
 order is a function of (seed, epoch) and the ranks take disjoint shards of it.  `+stem_val_root=DIR` gives `val_loss` on
-the deterministic full mix of those tracks.  `+stem_device_labels=true` builds the targets on the device, one
+the deterministic full mix of those tracks; `+val_notes=true` adds the note-level numbers behind it: every rank
+transcribes the full mix of the first `+val_notes_tracks=K` tracks of its validation shard (0, the default: all of them) and
+scores the notes on the device against the tracks' note tables, rank 0 prints `epoch N val_onset_f1 X val_onset_program_f1 Y`
+(means over the tracks of all ranks; training weights).  `+stem_device_labels=true` builds the targets on the device, one
 launch per track visit, instead of tokenising whole tracks on the host: the same targets, and `targets_prev` with them,
 so a `*WithPrev` model trains from stems (without the option it is refused); the run then ends with `label_launches K`.
 `+stem_pitch_shift=N` (0) plays every track visit at 2^(k/12) times its speed, k drawn from [-N, N] semitones:
@@ -62,6 +65,7 @@ import argparse
 import os
 import sys
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -248,6 +252,74 @@ def stem_loaders(cfg, opts, device, world=1, rank=0, with_prev=False):
         val = StemLoader(stems.load_stem_folder(opts["val_root"], **native), StemMixBatcher(device, is_deterministic=True, **geom),
                          1, cfg.seed, rank, world, shuffle=False)
     return train, val
+
+
+def val_notes_options(cfg, stem):
+    """None without `+val_notes=true`; else the number of validation tracks each rank transcribes (`+val_notes_tracks=K`,
+    0: every track of its shard).  Needs `+stem_val_root`: the tracks' note tables are the reference."""
+    raw = cfg.get("val_notes")
+    if raw is None or str(raw).lower() not in _TRUTHY:
+        if raw is not None and str(raw).lower() not in ("false", "0", "no", "off"):
+            raise ValueError("val_notes must be true or false, got %r" % (raw,))
+        return None
+    if stem is None or stem.get("val_root") is None:
+        raise ValueError("+val_notes=true scores transcriptions of the validation tracks: it needs +stem_root and "
+                         "+stem_val_root")
+    k = cfg.get("val_notes_tracks", 0)
+    if isinstance(k, bool) or not isinstance(k, int) or k < 0:
+        raise ValueError("val_notes_tracks must be an int >= 0 (0: every track), got %r" % (k,))
+    return int(k)
+
+
+def full_mix(track, sample_rate=16000):
+    """The deterministic full mix of a stem track as one recording: every stem at gain 1, from sample 0."""
+    if track.rates is not None and any(int(r) != sample_rate for r in track.rates):
+        raise ValueError("val_notes transcribes stems at the model's %d Hz; track %s has %r" % (sample_rate, track.name,
+                                                                                                 track.rates))
+    mix = np.zeros(track.n_samples, np.float32)
+    for a in track.audio:
+        mix[:len(a)] += a
+    return mix
+
+
+def validate_notes(model, tracks, device, estimates=None, max_length=1024) -> dict:
+    """Note-level validation: the full mix of every track is transcribed by the model's inference path with the
+    notes decoded on the device (`InferenceHandler.inference_many(return_tables=True)`), and scored there against the
+    track's note table (`mrmt3.scoring.score_tables`, one launch for all tracks).  The NOTES THEMSELVES are scored, not a
+    MIDI round trip: no file is written and read back, so no time is quantised to MIDI ticks on the way.  The weights are
+    the model's as they stand (the training weights).
+    `estimates`: a `mrmt3.notes.DeviceNotes` with one recording per track to score instead of transcribing.
+    Returns {"tracks": n scored, "onset_f1": the SUM over the tracks of the instrument-agnostic onset F1,
+    "onset_program_f1": the sum of "Onset + program F1 (flat)", "per_track": the tracks' score dicts}: sums and a count,
+    so that ranks can be added like `val_loss`.  A track the host scorer would refuse (a reference note that does not
+    end after it starts) is left out of the sums and carries its ValueError in `per_track`."""
+    from mrmt3 import labels, scoring
+    from mrmt3.notes import DeviceNotes
+    tracks = list(tracks)
+    out = {"tracks": 0, "onset_f1": 0.0, "onset_program_f1": 0.0, "per_track": []}
+    if not tracks:
+        return out
+    if estimates is None:
+        import inference
+        was_training = model.training
+        model.eval()
+        try:
+            handler = inference.InferenceHandler(model=model, device=device)
+            estimates = handler.inference_many([full_mix(t) for t in tracks], max_length=max_length, return_tables=True)
+        finally:
+            model.train(was_training)
+    refs = []
+    for t in tracks:
+        table = labels.note_table(t)
+        refs.append(DeviceNotes.from_note_table(torch.from_numpy(table.times).to(device), torch.from_numpy(table.meta).to(device)))
+    out["per_track"] = scoring.score_tables(DeviceNotes.concat(refs), estimates, families=("on", "flat"), errors="return")
+    for got in out["per_track"]:
+        if isinstance(got, Exception):
+            continue
+        out["tracks"] += 1
+        out["onset_f1"] += got["Onset F1"]
+        out["onset_program_f1"] += got["Onset + program F1 (flat)"]
+    return out
 
 
 def accumulate_grad_batches(cfg) -> int:
@@ -441,6 +513,7 @@ def main(argv=None):
     max_steps = None if max_steps is None else int(max_steps)
     train_loader = val_loader = sampler = None
     stem = None if synthetic else stem_options(cfg, with_prev)
+    val_notes = val_notes_options(cfg, stem)
     if stem is not None:
         train_loader, val_loader = stem_loaders(cfg, stem, device, world, rank, with_prev)
         sampler = train_loader                   # (`set_epoch`: the track order is a function of (seed, epoch))
@@ -493,6 +566,17 @@ def main(argv=None):
                 dist.all_reduce(acc, op=dist.ReduceOp.SUM)
             if rank == 0 and acc[1].item() > 0:
                 print(f"epoch {ep} val_loss {(acc[0] / acc[1]).item():.4f}", flush=True)
+            if val_notes is not None:            # (+val_notes=true: the training weights, the first tracks of the shard)
+                shard = val_loader.shard()
+                got = validate_notes(task.model, [val_loader.tracks[t] for t in shard[:val_notes or len(shard)]], device,
+                                     max_length=int(cfg.get("event_length", 1024)))
+                notes_acc = torch.tensor([got["onset_f1"], got["onset_program_f1"], got["tracks"]], device=device,
+                                         dtype=torch.float64)
+                if world > 1:
+                    dist.all_reduce(notes_acc, op=dist.ReduceOp.SUM)
+                if rank == 0 and notes_acc[2].item() > 0:
+                    f1, pf1 = (notes_acc[:2] / notes_acc[2]).tolist()
+                    print(f"epoch {ep} val_onset_f1 {f1:.4f} val_onset_program_f1 {pf1:.4f}", flush=True)
             if ema_decay is None:
                 return
             acc.zero_()
