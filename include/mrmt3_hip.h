@@ -891,6 +891,36 @@ int mrmt3_note_match_fwd(const double* ref_times, const int* ref_meta, long long
 /* Launches of mrmt3_note_match_fwd since the process started (or since the last call with reset != 0). */
 unsigned long long mrmt3_note_match_launches(int reset);
 
+/* ---- frame counts and piano rolls ---------------------------------------------------------------------
+ * Both sides of every problem of one launch as time x pitch rolls at `fps` frames a second, and the counts of the frame
+ * score: tp = |ref & est|, n_ref = |ref|, n_est = |est| over all 128 pitch rows.  A restatement of the piano-roll
+ * convention MT3's frame score stands on (DESIGN 4o says what was and was not checked); the text below is the contract,
+ * mrmt3.scoring.frame_counts_host restates it on the host.
+ *
+ * Tables, lists and `first` arrays are mrmt3_note_match_fwd's (only the times and the pitch are read); the lists need not be
+ * in any order.  An entry with times (start, end) and pitch q sounds in frames [a, b) of pitch row q:
+ *   a = max(0, floor(start * fps)),  b = max(a + 1, ceil(end * fps)),  both then clamped to [0, n_frames];
+ * each product is ONE f64 multiplication (no fused multiply-add, no reciprocal).  A side's roll is the union of its entries.
+ * An entry is skipped (it contributes nothing and is counted in skipped[p][side]) when its index lies outside its table,
+ * either time is NaN, its pitch lies outside 0..127, or start * fps or end * fps is not below 2^31.  An entry whose b was
+ * cut by n_frames is counted in clipped[p][side].  side 0 = reference, 1 = estimate.
+ *
+ * Output (DEVICE): counts [n_prob][3] int64 (tp, n_ref, n_est), skipped and clipped [n_prob][2] int32, all zeroed on
+ * `stream` before the launch; roll: null, or [n_prob][2][128][W] 32-bit words, W = ceil(n_frames / 32), frame f of a row
+ * is bit f % 32 of word f / 32; every word is written, the bits at and beyond n_frames are 0.
+ * The workspace is not used: mrmt3_note_frames_workspace_bytes returns 0 and `workspace` may be null.
+ * Whatever the arrays hold, the kernel reads and writes nothing outside them (`first` clamped as in the matcher).
+ * MRMT3_ERR_INVALID_ARG before any launch: a null pointer (roll and the workspace excepted), n_prob <= 0, fps not finite
+ * or <= 0, n_frames outside [1, 2^31 - 64], a note count outside [0, 2^31), meta not 16-byte aligned. */
+size_t mrmt3_note_frames_workspace_bytes(int n_prob, long long n_frames);
+int mrmt3_note_frames_fwd(const double* ref_times, const int* ref_meta, long long n_ref_notes,
+                          const double* est_times, const int* est_meta, long long n_est_notes,
+                          const int* ref_idx, const int* ref_first, const int* est_idx, const int* est_first,
+                          int n_prob, double fps, long long n_frames,
+                          long long* counts, int* skipped, int* clipped, unsigned* roll, void* workspace, void* stream);
+/* Launches of mrmt3_note_frames_fwd since the process started (or since the last call with reset != 0). */
+unsigned long long mrmt3_note_frames_launches(int reset);
+
 /* ---- gradient exchange (data parallel, one process per GPU): RCCL communicators as opaque handles ----------------
  * Replaces what the reference gets from Lightning's `ddp_find_unused_parameters_false` strategy (config/config.yaml:45,
  * train.sh:6): torch DDP's bucketed NCCL all-reduce of the gradients.  The flat f32 gradient buffer is exchanged as a few

@@ -136,3 +136,63 @@ def sequence_to_valued_intervals(ns, min_midi_pitch=21, max_midi_pitch=108):
             if min_midi_pitch <= n.pitch <= max_midi_pitch and n.end_time != n.start_time]
     a = np.array(rows, dtype=np.float64).reshape(-1, 4)
     return a[:, :2], a[:, 2], a[:, 3]
+
+
+# ---- frame-level scores and instrument detection ----------------------------------------------------------------------
+# A restatement, from the description in DESIGN 4o, of the piano-roll convention MT3's frame score stands on (note_seq's
+# sequence_to_pianoroll at MT3's frame rate; neither package is in this build, so nothing here was checked against them).
+FRAMES_PER_SECOND = 62.5
+_FRAME_LIMIT = 2147483648.0                     # a note whose start or end frame is not below 2^31 is left out
+
+
+def note_frame_ranges(intervals, pitches, fps=FRAMES_PER_SECOND):
+    """(a int64 [m], b int64 [m], pitch int64 [m]) of the notes that sound: a note (start, end) of pitch q sounds in the
+    frames [a, b) of row q, a = max(0, floor(start * fps)), b = max(a + 1, ceil(end * fps)), each product one f64
+    multiplication.  A note with a NaN time, a pitch outside 0..127 or a product not below 2^31 is left out."""
+    iv = np.asarray(intervals, dtype=np.float64).reshape(-1, 2)
+    pitch = np.asarray(pitches, dtype=np.float64).reshape(-1)
+    if len(pitch) != len(iv):
+        raise ValueError("intervals and pitches have different lengths")
+    with np.errstate(invalid="ignore", over="ignore"):
+        ps, pe = iv[:, 0] * np.float64(fps), iv[:, 1] * np.float64(fps)
+        keep = ~np.isnan(iv).any(1) & (pitch >= 0) & (pitch <= 127) & (ps < _FRAME_LIMIT) & (pe < _FRAME_LIMIT)
+    ps, pe, pitch = ps[keep], pe[keep], pitch[keep]
+    a = np.maximum(np.floor(np.maximum(ps, 0.0)), 0.0).astype(np.int64)
+    b = np.maximum(np.ceil(np.maximum(pe, 0.0)).astype(np.int64), a + 1)
+    return a, b, pitch.astype(np.int64)
+
+
+def pianoroll(intervals, pitches, fps=FRAMES_PER_SECOND, n_frames=None):
+    """bool [n_frames, 128]: the union of the notes' frames; n_frames None: the largest b (0 without notes)."""
+    a, b, pitch = note_frame_ranges(intervals, pitches, fps)
+    if n_frames is None:
+        n_frames = int(b.max()) if len(b) else 0
+    roll = np.zeros((int(n_frames), 128), bool)
+    for lo, hi, q in zip(a.tolist(), b.tolist(), pitch.tolist()):
+        roll[lo:hi, q] = True
+    return roll
+
+
+def frame_counts(ref_intervals, ref_pitches, est_intervals, est_pitches, fps=FRAMES_PER_SECOND):
+    """(tp, n_ref, n_est): the frames of both rolls, of the reference's and of the estimate's, as Python ints."""
+    ref, est = note_frame_ranges(ref_intervals, ref_pitches, fps), note_frame_ranges(est_intervals, est_pitches, fps)
+    n_frames = max([int(s[1].max()) for s in (ref, est) if len(s[1])] or [0])
+    ref_roll = pianoroll(ref_intervals, ref_pitches, fps, n_frames)
+    est_roll = pianoroll(est_intervals, est_pitches, fps, n_frames)
+    return int((ref_roll & est_roll).sum()), int(ref_roll.sum()), int(est_roll.sum())
+
+
+def frame_scores(ref_intervals, ref_pitches, est_intervals, est_pitches, fps=FRAMES_PER_SECOND):
+    """(precision, recall, F1) of the estimate's piano roll against the reference's (pitches: MIDI numbers)."""
+    return scores_from_counts(*frame_counts(ref_intervals, ref_pitches, est_intervals, est_pitches, fps))
+
+
+def instrument_scores(ref_programs, est_programs):
+    """Instrument detection as MR-MT3 counts it: the two SETS of program numbers (a drum track is a member by its program
+    number) -> (n_ref, n_est, precision, recall, F1): matched / |est|, matched / |ref| and their harmonic mean, 0.0 where a
+    denominator is 0."""
+    ref, est = set(int(p) for p in ref_programs), set(int(p) for p in est_programs)
+    matched = len(ref & est)
+    precision = matched / len(est) if est else 0.0
+    recall = matched / len(ref) if ref else 0.0
+    return len(ref), len(est), precision, recall, f_measure(precision, recall)

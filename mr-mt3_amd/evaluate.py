@@ -74,45 +74,116 @@ def group_order(ref_keys, est_keys):
     return list(set(ref_keys) | set(est_keys))
 
 
-def _device_scores(pairs, device, families, with_overlap=True, errors="raise"):
+FRAME_KEYS = ("Frame precision", "Frame recall", "Frame F1")
+INSTRUMENT_KEYS = ("Num instruments ref", "Num instruments est", "Instrument precision", "Instrument recall", "Instrument F1")
+
+
+def frame_result(on, grouped):
+    """The frame keys from integer counts: `on` the (tp, n_ref, n_est) of the notes "Onset F1" is computed on
+    (or None), `grouped` {granularity: [(tp, n_ref, n_est) per program group]}: the counts are summed over the groups, so a
+    frame credited to the wrong instrument is one miss and one false alarm.  The host scorer and `mrmt3.scoring` both
+    assemble their result here."""
+    res = {}
+    if on is not None:
+        res.update(zip(FRAME_KEYS, tm.scores_from_counts(*on)))
+    for name, counts in grouped.items():
+        tp, n_ref, n_est = (sum(int(c[i]) for c in counts) for i in range(3))
+        res["Frame F1 (%s)" % name] = tm.scores_from_counts(tp, n_ref, n_est)[2]
+    return res
+
+
+def instrument_result(ref_programs, est_programs):
+    """The instrument-detection keys from the program numbers of the notes on each side (`tm.instrument_scores`)."""
+    return dict(zip(INSTRUMENT_KEYS, tm.instrument_scores(ref_programs, est_programs)))
+
+
+def host_frame_result(ref_mid, est_mid, granularities, on=True):
+    """`frame_result` of two MIDI files on the host: "on" from the notes of `tm.sequence_to_valued_intervals`, a
+    granularity's groups as `mt3_program_aware_note_scores` forms them, all of their notes."""
+    counts = None
+    if on:
+        iv_r, p_r, _ = tm.sequence_to_valued_intervals(midi_io.midi_to_note_sequence(ref_mid))
+        iv_e, p_e, _ = tm.sequence_to_valued_intervals(midi_io.midi_to_note_sequence(est_mid))
+        counts = tm.frame_counts(iv_r, p_r, iv_e, p_e)
+    grouped = {}
+    for g in granularities:
+        sides = []
+        for mid in (ref_mid, est_mid):
+            by_key = {}
+            for inst in mid.instruments:
+                key = (get_granular_program(inst.program, inst.is_drum, g), bool(inst.is_drum))
+                by_key.setdefault(key, []).extend(inst.notes)
+            sides.append(by_key)
+        arrays = lambda notes: (np.array([[n.start, n.end] for n in notes], dtype=np.float64).reshape(-1, 2),
+                                np.array([n.pitch for n in notes], dtype=np.float64))
+        grouped[g] = [tm.frame_counts(*arrays(sides[0].get(key, [])), *arrays(sides[1].get(key, [])))
+                      for key in sorted(set(sides[0]) | set(sides[1])) if sides[0].get(key) or sides[1].get(key)]
+    return frame_result(counts, grouped)
+
+
+def _host_instruments(ref_mid, est_mid):
+    programs = lambda mid: [inst.program for inst in mid.instruments if inst.notes]
+    return instrument_result(programs(ref_mid), programs(est_mid))
+
+
+def _device_scores(pairs, device, families, with_overlap=True, errors="raise", frames=False, instruments=False):
     from mrmt3 import scoring
     from mrmt3.notes import DeviceNotes
+    if instruments and "full" not in families:
+        families = tuple(families) + ("full",)
     ref = DeviceNotes.from_arrays([scoring.table_from_midi(_midi(r)) for r, _ in pairs], device)
     est = DeviceNotes.from_arrays([scoring.table_from_midi(_midi(e)) for _, e in pairs], device)
-    return scoring.score_tables(ref, est, with_overlap=with_overlap, families=families, errors=errors)
+    return scoring.score_tables(ref, est, with_overlap=with_overlap, families=families, errors=errors, frames=frames,
+                                instruments=instruments)
 
 
-def compute_transcription_metrics(ref_mid, est_mid, device=None):
+def _extra_keys(frames, instruments, granularities=()):
+    return ((FRAME_KEYS + tuple("Frame F1 (%s)" % g for g in granularities)) if frames else ()) + (
+        INSTRUMENT_KEYS if instruments else ())
+
+
+def compute_transcription_metrics(ref_mid, est_mid, device=None, frames=False, instruments=False):
     """evaluate.py:25-53: onset+offset and onset-only scores over all notes (pitches are passed to the matcher
     as MIDI numbers, exactly as the reference does).  `device`: the notes are uploaded and matched there
-    (`mrmt3.scoring.score_tables`); None is the host matcher."""
+    (`mrmt3.scoring.score_tables`); None is the host matcher.  `frames`: also FRAME_KEYS, the frame score of the same notes
+    (DESIGN 4o); `instruments`: also INSTRUMENT_KEYS.  Both paths assemble them from integers in `frame_result` and
+    `instrument_result`."""
+    ref_mid, est_mid = _midi(ref_mid), _midi(est_mid)
     if device is not None:
-        got = _device_scores([(ref_mid, est_mid)], device, ("onoff", "on"))[0]
-        return {k: got[k] for k in transcription_metrics_result(0, 0, (0,) * 4, (0,) * 4)}
-    ns_ref = midi_io.midi_to_note_sequence(_midi(ref_mid))
-    ns_est = midi_io.midi_to_note_sequence(_midi(est_mid))
+        got = _device_scores([(ref_mid, est_mid)], device, ("onoff", "on"), frames=frames, instruments=instruments)[0]
+        return {k: got[k] for k in tuple(transcription_metrics_result(0, 0, (0,) * 4, (0,) * 4)) + _extra_keys(frames, instruments)}
+    ns_ref = midi_io.midi_to_note_sequence(ref_mid)
+    ns_est = midi_io.midi_to_note_sequence(est_mid)
     iv_r, p_r, _ = tm.sequence_to_valued_intervals(ns_ref)
     iv_e, p_e, _ = tm.sequence_to_valued_intervals(ns_est)
     onoff = tm.precision_recall_f1_overlap(iv_r, p_r, iv_e, p_e)
     on = tm.precision_recall_f1_overlap(iv_r, p_r, iv_e, p_e, offset_ratio=None)
-    return transcription_metrics_result(len(iv_r), len(iv_e), onoff, on)
+    res = transcription_metrics_result(len(iv_r), len(iv_e), onoff, on)
+    if frames:
+        res.update(host_frame_result(ref_mid, est_mid, ()))
+    if instruments:
+        res.update(_host_instruments(ref_mid, est_mid))
+    return res
 
 
-def _program_aware_from_scores(got, granularity_type):
+def _program_aware_from_scores(got, granularity_type, frames=False, instruments=False):
     keys = ["Onset precision", "Onset recall", "Onset F1"] + [f"Onset + program {k} ({granularity_type})"
                                                               for k in ("precision", "recall", "F1")]
     res = {k: got[k] for k in keys}
     res["F1 by program"] = got["F1 by program (%s)" % granularity_type]
+    res.update({k: got[k] for k in _extra_keys(frames, instruments, (granularity_type,))})
     return res
 
 
-def mt3_program_aware_note_scores(fname1, fname2, granularity_type, device=None):
+def mt3_program_aware_note_scores(fname1, fname2, granularity_type, device=None, frames=False, instruments=False):
     """evaluate.py:56-237: instrument-agnostic onset F1 plus the program-aware onset F1 of MT3 at the given
-    program granularity (per-group scores weighted by note counts).  `device` as in `compute_transcription_metrics`."""
+    program granularity (per-group scores weighted by note counts).  `device` as in `compute_transcription_metrics`.
+    `frames`: also FRAME_KEYS and "Frame F1 (<granularity>)"; `instruments`: also INSTRUMENT_KEYS."""
     ref_mid, est_mid = _midi(fname1), _midi(fname2)
     if device is not None:
-        got = _device_scores([(ref_mid, est_mid)], device, ("on", granularity_type), with_overlap=False)[0]
-        return _program_aware_from_scores(got, granularity_type)
+        got = _device_scores([(ref_mid, est_mid)], device, ("on", granularity_type), with_overlap=False, frames=frames,
+                             instruments=instruments)[0]
+        return _program_aware_from_scores(got, granularity_type, frames, instruments)
     iv_r, p_r, _ = tm.sequence_to_valued_intervals(midi_io.midi_to_note_sequence(ref_mid))
     iv_e, p_e, _ = tm.sequence_to_valued_intervals(midi_io.midi_to_note_sequence(est_mid))
     precision, recall, f1, _ = tm.precision_recall_f1_overlap(iv_r, p_r, iv_e, p_e, offset_ratio=None)
@@ -138,7 +209,12 @@ def mt3_program_aware_note_scores(fname1, fname2, granularity_type, device=None)
             p, r, f, _ = tm.precision_recall_f1_overlap(r_iv, r_hz, e_iv, e_hz, offset_ratio=None)
             yield key, (p, r, f), len(r_iv), len(e_iv)
 
-    return program_aware_result((precision, recall, f1), scored(), granularity_type)
+    res = program_aware_result((precision, recall, f1), scored(), granularity_type)
+    if frames:
+        res.update(host_frame_result(ref_mid, est_mid, (granularity_type,)))
+    if instruments:
+        res.update(_host_instruments(ref_mid, est_mid))
+    return res
 
 
 def loop_transcription_eval(ref_mid, est_mid):
@@ -157,10 +233,11 @@ def loop_transcription_eval(ref_mid, est_mid):
 
 
 def evaluate_main(dataset_name, test_midi_dir, ground_truth_midi_dir, enable_instrument_eval=False, first_n=None,
-                  device=None):
+                  device=None, frames=False, instruments=False):
     """evaluate.py:275-330: pair every transcribed file with its ground truth, score at the three program
     granularities, print and return the means.  `device`: the files are read as before, their notes uploaded, and every
-    pair is scored in ONE launch of the device matcher (`mrmt3.scoring.score_tables`); None is the host matcher."""
+    pair is scored in ONE launch of the device matcher (`mrmt3.scoring.score_tables`); None is the host matcher.
+    `frames` / `instruments`: the means of the frame keys and of the instrument-detection keys too."""
     if dataset_name == "Slakh":
         est = sorted(glob.glob(f"{test_midi_dir}/*/mix.mid"))
         ref = [k.replace(test_midi_dir, ground_truth_midi_dir).replace("/mix.mid", "/all_src_v2.mid") for k in est]
@@ -175,7 +252,7 @@ def evaluate_main(dataset_name, test_midi_dir, ground_truth_midi_dir, enable_ins
     def score(pair):
         out = {}
         for granularity in ("flat", "full", "midi_class"):
-            out.update(mt3_program_aware_note_scores(pair[0], pair[1], granularity))
+            out.update(mt3_program_aware_note_scores(pair[0], pair[1], granularity, frames=frames, instruments=instruments))
         return out
 
     scores = collections.defaultdict(list)
@@ -187,13 +264,14 @@ def evaluate_main(dataset_name, test_midi_dir, ground_truth_midi_dir, enable_ins
             except Exception as exc:                      # one unreadable file must not end the run
                 print(str(exc))
         families = ("on", "flat", "full", "midi_class")
-        for got in (_device_scores(mids, device, families, with_overlap=False, errors="return") if mids else []):
+        for got in (_device_scores(mids, device, families, with_overlap=False, errors="return", frames=frames,
+                                   instruments=instruments) if mids else []):
             if isinstance(got, Exception):                # a pair the host matcher would refuse
                 print(str(got))
                 continue
             out = {}
             for granularity in ("flat", "full", "midi_class"):
-                out.update(_program_aware_from_scores(got, granularity))
+                out.update(_program_aware_from_scores(got, granularity, frames, instruments))
             for k, v in out.items():
                 scores[k].append(v)
     else:

@@ -107,7 +107,7 @@ def load():
     return lib
 
 
-MIN_VERSION = 127
+MIN_VERSION = 128
 COUNTER_NAMES = ("gemm_nt_tile", "gemm_nt8", "gemm_nt_geglu", "tn_group", "tn8", "tn_tile", "attn_fwd", "attn_bwd",
                  "attn_bwd_onepass", "attn_f32", "tn_f32", "gemm_nt_splitk", "gemm_nt_addnorm", "gemm_nt_normbwd",
                  "gemm_nt_geglubwd", "attn_fwd_varlen", "attn_bwd_varlen", "logmel_wave", "logmel_general")
@@ -394,6 +394,56 @@ def note_match(ref_times, ref_meta, est_times, est_meta, ref_idx, ref_first, est
 def note_match_launches(reset: bool = False) -> int:
     """Launches of `note_match` since the process started / the last reset (mrmt3_note_match_launches)."""
     return int(load().mrmt3_note_match_launches(int(reset)))
+
+
+FRAMES_MAX = (1 << 31) - 64      # the largest n_frames of mrmt3_note_frames_fwd
+
+
+def note_frames(ref_times, ref_meta, est_times, est_meta, ref_idx, ref_first, est_idx, est_first, fps, n_frames,
+                with_roll=False):
+    """Tables, lists and `first` arrays as `note_match` takes them (the lists in any order), fps frames a second, n_frames
+    the length of the rolls -> (counts [n_prob, 3] int64: tp, n_ref, n_est; skipped [n_prob, 2] int32; clipped [n_prob, 2]
+    int32) and, with `with_roll`, roll [n_prob, 2, 128, W] int32 (W = ceil(n_frames / 32) words of 32 frames, frame f is bit
+    f % 32 of word f // 32).  ONE launch for every problem, no read-back (include/mrmt3_hip.h: mrmt3_note_frames_fwd).
+    An argument the C library would refuse is a ValueError here, before anything is launched."""
+    import math
+    if isinstance(fps, bool) or not isinstance(fps, (int, float)) or not math.isfinite(fps) or fps <= 0:
+        raise ValueError(f"note_frames: fps must be finite and > 0, got {fps!r}")
+    if isinstance(n_frames, bool) or int(n_frames) != n_frames or not 1 <= int(n_frames) <= FRAMES_MAX:
+        raise ValueError(f"note_frames: n_frames must be a whole number in [1, 2^31 - 64], got {n_frames!r}")
+    for name, times, meta in (("ref", ref_times, ref_meta), ("est", est_times, est_meta)):
+        n = meta.shape[0]
+        if tuple(times.shape) != (n, 2) or times.dtype != torch.float64 or not times.is_contiguous():
+            raise ValueError(f"note_frames: {name}_times must be contiguous [n, 2] f64, got {tuple(times.shape)} {times.dtype}")
+        if meta.dim() != 2 or meta.shape[1] != 4 or meta.dtype != torch.int32 or not meta.is_contiguous():
+            raise ValueError(f"note_frames: {name}_meta must be contiguous [n, 4] int32, got {tuple(meta.shape)} {meta.dtype}")
+        if n >= 1 << 31:
+            raise ValueError(f"note_frames: {n} {name} notes, the note counts must be in [0, 2^31)")
+    for name, t in (("ref_idx", ref_idx), ("est_idx", est_idx), ("ref_first", ref_first), ("est_first", est_first)):
+        if t.dim() != 1 or t.dtype != torch.int32 or not t.is_contiguous():
+            raise ValueError(f"note_frames: {name} must be contiguous 1-D int32, got {tuple(t.shape)} {t.dtype}")
+    n_prob = ref_first.numel() - 1
+    if n_prob <= 0 or est_first.numel() != n_prob + 1:
+        raise ValueError(f"note_frames: ref_first and est_first must both be [n_prob + 1] with n_prob > 0, got "
+                         f"{ref_first.numel()} and {est_first.numel()} entries")
+    _dev(ref_times, ref_meta, est_times, est_meta, ref_idx, ref_first, est_idx, est_first)
+    dev, n_frames = ref_first.device, int(n_frames)
+    counts = torch.empty(n_prob, 3, device=dev, dtype=torch.int64)
+    skipped = torch.empty(n_prob, 2, device=dev, dtype=torch.int32)
+    clipped = torch.empty(n_prob, 2, device=dev, dtype=torch.int32)
+    roll = torch.empty(n_prob, 2, 128, -(-n_frames // 32), device=dev, dtype=torch.int32) if with_roll else None
+    spare = torch.empty(4, 4, device=dev, dtype=torch.int32)           # what an empty tensor's null pointer is replaced by
+    ptr = lambda t: _p(t) if t.numel() else _p(spare)
+    _check(load().mrmt3_note_frames_fwd(ptr(ref_times), ptr(ref_meta), ref_meta.shape[0], ptr(est_times), ptr(est_meta),
+                                        est_meta.shape[0], ptr(ref_idx), _p(ref_first), ptr(est_idx), _p(est_first), n_prob,
+                                        float(fps), n_frames, _p(counts), _p(skipped), _p(clipped), _p(roll), None, _stream()),
+           "note_frames_fwd")
+    return (counts, skipped, clipped, roll) if with_roll else (counts, skipped, clipped)
+
+
+def note_frames_launches(reset: bool = False) -> int:
+    """Launches of `note_frames` since the process started / the last reset (mrmt3_note_frames_launches)."""
+    return int(load().mrmt3_note_frames_launches(int(reset)))
 
 
 def gemm_nt(a, b, out=None, out_dtype=None, accumulate=False):

@@ -1,5 +1,7 @@
 """Note-level scores from device-resident note tables: the pitch tables, the problem lists and the host
-restatement of `mrmt3_note_match_fwd` (include/mrmt3_hip.h), and `score_tables`, which reproduces `evaluate.py`'s numbers.
+restatement of `mrmt3_note_match_fwd` (include/mrmt3_hip.h), and `score_tables`, which reproduces `evaluate.py`'s numbers;
+frame-level counts, piano rolls and instrument detection: the two host restatements of `mrmt3_note_frames_fwd`,
+`pianoroll`, and the `frames` / `instruments` options of `score_tables`.
 
 The scores are BY DEFINITION those of `evaluate.compute_transcription_metrics` and `evaluate.mt3_program_aware_note_scores`
 (the mir_eval restatement in `contrib.transcription_metrics`).  Precision, recall and F1 depend only on the SIZE of a maximum
@@ -167,6 +169,114 @@ def match_notes_host(ref_times, ref_meta, est_times, est_meta, ref_idx, ref_firs
     return matched, match, status
 
 
+# ---- frames ------------------------------------------------------------------------------------------------
+FRAMES_PER_SECOND = tm.FRAMES_PER_SECOND
+FRAME_LIMIT = 2147483648.0
+
+
+def _clamped(first, p, L):
+    a = min(max(int(first[p]), 0), L)
+    return a, min(max(int(first[p + 1]), a), L)
+
+
+def frame_counts_host(ref_times, ref_meta, est_times, est_meta, ref_idx, ref_first, est_idx, est_first, fps=FRAMES_PER_SECOND,
+                      n_frames=1, with_roll=False):
+    """The contract of `mrmt3_note_frames_fwd` on the host, the arguments of `lib.note_frames` as numpy arrays ->
+    (counts int64 [n_prob, 3], skipped int32 [n_prob, 2], clipped int32 [n_prob, 2]) and, with `with_roll`, roll uint32
+    [n_prob, 2, 128, W].  A dense bool roll per problem and side, packed into words at the end: the kernel's oracle."""
+    tables = ((np.asarray(ref_times, np.float64).reshape(-1, 2), np.asarray(ref_meta).reshape(-1, 4)[:, 0],
+               np.asarray(ref_idx, np.int64), ref_first),
+              (np.asarray(est_times, np.float64).reshape(-1, 2), np.asarray(est_meta).reshape(-1, 4)[:, 0],
+               np.asarray(est_idx, np.int64), est_first))
+    n_prob, n_frames, fps = len(ref_first) - 1, int(n_frames), np.float64(fps)
+    assert len(est_first) == n_prob + 1 and n_prob > 0 and n_frames >= 1 and np.isfinite(fps) and fps > 0
+    W = -(-n_frames // 32)
+    counts = np.zeros((n_prob, 3), np.int64)
+    skipped, clipped = np.zeros((n_prob, 2), np.int32), np.zeros((n_prob, 2), np.int32)
+    roll = np.zeros((n_prob, 2, 128, W), np.uint32) if with_roll else None
+    for p in range(n_prob):
+        dense = np.zeros((2, 128, W * 32), bool)
+        for s, (times, pitches, idx, first) in enumerate(tables):
+            L = max(int(first[n_prob]), 0)
+            lo, hi = _clamped(first, p, L)
+            for note in idx[lo:hi].tolist():
+                if not 0 <= note < len(times):
+                    skipped[p, s] += 1
+                    continue
+                start, end, pitch = times[note, 0], times[note, 1], int(pitches[note])
+                with np.errstate(over="ignore", invalid="ignore"):
+                    ps, pe = start * fps, end * fps
+                if np.isnan(start) or np.isnan(end) or not 0 <= pitch <= 127 or not ps < FRAME_LIMIT or not pe < FRAME_LIMIT:
+                    skipped[p, s] += 1
+                    continue
+                a = max(0, int(np.floor(max(ps, -1.0))))               # (max: -inf has no floor among the ints)
+                b = max(a + 1, int(np.ceil(max(pe, -1.0))))
+                if b > n_frames:
+                    clipped[p, s] += 1
+                dense[s, pitch, min(a, n_frames):min(b, n_frames)] = True
+        counts[p] = (dense[0] & dense[1]).sum(), dense[0].sum(), dense[1].sum()
+        if with_roll:
+            roll[p] = np.packbits(dense, axis=-1, bitorder="little").reshape(2, 128, W, 4).view("<u4")[..., 0]
+    return (counts, skipped, clipped, roll) if with_roll else (counts, skipped, clipped)
+
+
+def _union(intervals):
+    """Disjoint sorted [a, b) intervals with the same union."""
+    out = []
+    for a, b in sorted(intervals):
+        if out and a <= out[-1][1]:
+            out[-1][1] = max(out[-1][1], b)
+        else:
+            out.append([a, b])
+    return out
+
+
+def frame_counts_intervals(ref_times, ref_meta, est_times, est_meta, ref_idx, ref_first, est_idx, est_first,
+                           fps=FRAMES_PER_SECOND, n_frames=1):
+    """`frame_counts_host` without a roll, for the tests: per pitch the length of the union of each side's [a, b) intervals
+    and of the intersection of the two unions, in Python floats and ints -> (counts, skipped, clipped)."""
+    import math
+    n_prob, n_frames, fps = len(ref_first) - 1, int(n_frames), float(fps)
+    counts = np.zeros((n_prob, 3), np.int64)
+    skipped, clipped = np.zeros((n_prob, 2), np.int32), np.zeros((n_prob, 2), np.int32)
+    sides = ((np.asarray(ref_times, np.float64).reshape(-1, 2).tolist(), np.asarray(ref_meta).reshape(-1, 4)[:, 0].tolist(),
+              ref_idx, ref_first),
+             (np.asarray(est_times, np.float64).reshape(-1, 2).tolist(), np.asarray(est_meta).reshape(-1, 4)[:, 0].tolist(),
+              est_idx, est_first))
+    for p in range(n_prob):
+        rows = [dict(), dict()]                      # per side: pitch -> intervals
+        for s, (times, pitches, idx, first) in enumerate(sides):
+            lo, hi = _clamped(first, p, max(int(first[n_prob]), 0))
+            for note in (int(i) for i in idx[lo:hi]):
+                if note < 0 or note >= len(times):
+                    skipped[p, s] += 1
+                    continue
+                (start, end), pitch = times[note], pitches[note]
+                ps, pe = start * fps, end * fps
+                if start != start or end != end or pitch < 0 or pitch > 127 or not ps < FRAME_LIMIT or not pe < FRAME_LIMIT:
+                    skipped[p, s] += 1
+                    continue
+                a = 0 if ps < 0 else math.floor(ps)
+                b = max(a + 1, 0 if pe < 0 else math.ceil(pe))
+                if b > n_frames:
+                    clipped[p, s] += 1
+                    b = n_frames
+                if a < b:
+                    rows[s].setdefault(pitch, []).append((a, b))
+        for s in (0, 1):
+            rows[s] = {q: _union(iv) for q, iv in rows[s].items()}
+            counts[p, 1 + s] = sum(b - a for iv in rows[s].values() for a, b in iv)
+        for q in set(rows[0]) & set(rows[1]):
+            x, y, i, j = rows[0][q], rows[1][q], 0, 0
+            while i < len(x) and j < len(y):
+                counts[p, 0] += max(0, min(x[i][1], y[j][1]) - max(x[i][0], y[j][0]))
+                if x[i][1] <= y[j][1]:
+                    i += 1
+                else:
+                    j += 1
+    return counts, skipped, clipped
+
+
 @dataclasses.dataclass
 class MidiTable:
     """A MIDI file's notes as a table (instrument after instrument) and, for the program groups, every instrument's
@@ -190,7 +300,8 @@ class Problems:
     """What `build_problems` returns.  On the tables' device: ref_idx, ref_first, est_idx, est_first, prob_flags as
     `lib.note_match` takes them.  On the host, per problem: pair (the recording pair), family (an index into FAMILIES), key
     ((granular program, is_drum), None for the agnostic families), n_ref, n_est (the list lengths) and first_ref / first_est
-    (the lowest table row on each side, the order of first appearance)."""
+    (the lowest table row on each side, the order of first appearance).  max_end: the largest end time of any note of
+    either side (0.0 without notes; a NaN is passed over), what the length of the frame rolls is computed from."""
     ref_idx: "torch.Tensor"
     ref_first: "torch.Tensor"
     est_idx: "torch.Tensor"
@@ -205,6 +316,7 @@ class Problems:
     first_est: np.ndarray
     errors: list                                  # per pair: None, or the ValueError the host scorer would raise
     families: tuple = FAMILIES                    # the families built
+    max_end: float = 0.0
 
 
 _NO_ROW = 1 << 40
@@ -241,7 +353,8 @@ def _side(notes, families):
     negative, short = (start < 0) | (end < 0), end <= start
     bad = torch.stack([negative & piano, short & piano, negative, short], 1).to(torch.int64)
     flags = torch.zeros(R, 4, dtype=torch.int64, device=dev).index_add_(0, rec, bad)
-    return torch.cat(ent_rows), torch.cat(ent_key), flags
+    latest = torch.where(torch.isnan(end), torch.zeros_like(end), end).amax() if total else end.new_zeros(())
+    return torch.cat(ent_rows), torch.cat(ent_key), flags, latest
 
 
 def build_problems(ref, est, families=FAMILIES) -> Problems:
@@ -252,7 +365,8 @@ def build_problems(ref, est, families=FAMILIES) -> Problems:
       - "flat", "midi_class", "full": one problem per (`evaluate.get_granular_program`, is_drum) key present on either side,
         all notes, pitch table 1, offsets off.
     Sorting and counting are torch operations on the tables' device; one tensor comes back: the problem keys, the list
-    lengths, and the counts that tell where `tm._validate` would raise (`errors`: the same ValueError, per pair)."""
+    lengths, the counts that tell where `tm._validate` would raise (`errors`: the same ValueError, per pair), and the
+    largest end time (`max_end`)."""
     import torch
     families = tuple(families)
     if not families or any(f not in FAMILIES for f in families):
@@ -261,8 +375,8 @@ def build_problems(ref, est, families=FAMILIES) -> Problems:
     if len(est) != R:
         raise ValueError("%d reference recordings against %d estimated ones" % (R, len(est)))
     dev = ref.meta.device
-    r_rows, r_key, r_flags = _side(ref, families)
-    e_rows, e_key, e_flags = _side(est, families)
+    r_rows, r_key, r_flags, r_end = _side(ref, families)
+    e_rows, e_key, e_flags, e_end = _side(est, families)
     # the agnostic problems exist for every pair, the group problems where a key is present
     forced = [(r * len(FAMILIES) + FAMILIES.index(f)) << 9 for r in range(R) for f in families if FAMILIES.index(f) < 2]
     uniq = torch.unique(torch.cat([r_key, e_key, torch.tensor(forced, dtype=torch.int64, device=dev)]))
@@ -279,7 +393,9 @@ def build_problems(ref, est, families=FAMILIES) -> Problems:
         firsts.append(low)
     family_dev = (uniq >> 9) % len(FAMILIES)
     flags = ((family_dev == 0).to(torch.int32) | (torch.where(family_dev < 2, TABLE_MIDI_AS_HZ, TABLE_HZ) << 8)).to(torch.int32)
-    home = torch.cat([uniq, counts[0], counts[1], firsts[0], firsts[1], r_flags.reshape(-1), e_flags.reshape(-1)]).cpu().numpy()
+    home = torch.cat([uniq, counts[0], counts[1], firsts[0], firsts[1], r_flags.reshape(-1), e_flags.reshape(-1),
+                      torch.maximum(r_end, e_end).reshape(1).view(torch.int64)]).cpu().numpy()
+    home, max_end = home[:-1], float(home[-1:].view(np.float64)[0])       # (the f64's bits rode in the int64 tensor)
     uniq_h, n_ref, n_est, first_ref, first_est = (home[i * P:(i + 1) * P] for i in range(5))
     bad_ref, bad_est = home[5 * P:5 * P + 4 * R].reshape(R, 4), home[5 * P + 4 * R:].reshape(R, 4)
     family = (uniq_h >> 9) % len(FAMILIES)
@@ -296,7 +412,7 @@ def build_problems(ref, est, families=FAMILIES) -> Problems:
                 message = f"all {name} interval durations must be strictly positive"
         errors.append(None if message is None else ValueError(message))
     return Problems(out[0][0], out[0][1], out[1][0], out[1][1], flags, (uniq_h >> 9) // len(FAMILIES), family, keys,
-                    n_ref, n_est, first_ref, first_est, errors, families)
+                    n_ref, n_est, first_ref, first_est, errors, families, max_end)
 
 
 def assemble_scores(problems: Problems, matched, programs_ref=None, programs_est=None, overlaps=None) -> List[dict]:
@@ -362,7 +478,121 @@ def upload(tables, device):
     return tables if isinstance(tables, DeviceNotes) else DeviceNotes.from_arrays(tables, device)
 
 
-def score_tables(ref, est, with_overlap=False, families=FAMILIES, errors="raise", device=None, return_matching=False):
+def frames_for(max_end, fps=FRAMES_PER_SECOND) -> int:
+    """The roll length `score_tables` launches with: ceil(max_end * fps) + 1, within the kernel's [1, 2^31 - 64]."""
+    import math
+    from mrmt3 import lib
+    product = float(max_end) * float(fps)
+    if not product < lib.FRAMES_MAX:               # (also an infinite end: such notes are skipped, not clipped)
+        return lib.FRAMES_MAX
+    return max(1, math.ceil(product) + 1)
+
+
+def add_frame_scores(results, problems: Problems, counts) -> None:
+    """The frame keys of every pair's dict from the kernel's (or the host's) `counts` [n_prob, 3]: "Frame precision" /
+    "Frame recall" / "Frame F1" from the "on" problem (when built), "Frame F1 (<granularity>)" from the counts summed over
+    that granularity's groups (when built).  Assembled where `evaluate.py`'s host path assembles them."""
+    import evaluate
+    for r, res in enumerate(results):
+        if not isinstance(res, dict):
+            continue
+        mine = [p for p in range(len(problems.pair)) if problems.pair[p] == r]
+        on = None
+        grouped = {}
+        for name in problems.families:
+            f = FAMILIES.index(name)
+            at = [p for p in mine if problems.family[p] == f]
+            if name == "on":
+                on = tuple(int(v) for v in counts[at[0]])
+            elif f >= 2:
+                grouped[name] = [tuple(int(v) for v in counts[p]) for p in at]
+        res.update(evaluate.frame_result(on, grouped))
+
+
+def add_instrument_scores(results, problems: Problems) -> None:
+    """The instrument-detection keys of every pair's dict from the "full" problems' list lengths: no launch."""
+    import evaluate
+    f = FAMILIES.index("full")
+    for r, res in enumerate(results):
+        if not isinstance(res, dict):
+            continue
+        mine = [p for p in range(len(problems.pair)) if problems.pair[p] == r and problems.family[p] == f]
+        res.update(evaluate.instrument_result([problems.key[p][0] for p in mine if problems.n_ref[p] > 0],
+                                              [problems.key[p][0] for p in mine if problems.n_est[p] > 0]))
+
+
+def _program_key(notes, rows, by):
+    import torch
+    prog = notes.meta[rows, 2].to(torch.int64)
+    return (prog & 0x1ff) if by == "program" else torch.zeros_like(prog)
+
+
+def pianoroll(notes, fps=FRAMES_PER_SECOND, recording=None, by=None):
+    """The piano rolls of a `mrmt3.notes.DeviceNotes`: one bool tensor [frames_r, 128] per recording on the notes' device
+    (a list; `recording=r`: that recording's alone), frames_r the largest b of the recording, 0 for a recording
+    without notes.  Every note with a pitch in 0..127 is taken.  `by="program"`: per recording a dict
+    {(program, is_drum): roll}, every roll of a recording frames_r long.  ONE launch of the frame kernel with the rolls
+    written, one problem per roll, unpacked with torch operations; one tensor (the lengths and the keys) comes home."""
+    import torch
+    from mrmt3 import lib
+    if by not in (None, "program"):
+        raise ValueError("by must be None or 'program', got %r" % (by,))
+    R = len(notes)
+    if recording is not None and not 0 <= int(recording) < R:
+        raise ValueError("recording %r of %d" % (recording, R))
+    counts = notes.host_counts()
+    dev, total = notes.meta.device, int(counts.sum())
+    count = notes.count.to(torch.int64)
+    rec = torch.repeat_interleave(torch.arange(R, device=dev), count, output_size=total)
+    begin = torch.cumsum(count, 0) - count
+    rows = notes.first.to(torch.int64)[rec] + (torch.arange(total, device=dev) - begin[rec])
+    if recording is not None:
+        keep = rec == int(recording)
+        rec, rows = rec[keep], rows[keep]
+    start, end, pitch = notes.times[rows, 0], notes.times[rows, 1], notes.meta[rows, 0]
+    ps, pe = start * fps, end * fps                                   # (one f64 multiplication each, as in the kernel)
+    sounds = ~torch.isnan(start) & ~torch.isnan(end) & (pitch >= 0) & (pitch <= 127) & (ps < FRAME_LIMIT) & (pe < FRAME_LIMIT)
+    a = torch.floor(ps.clamp(min=0.0))
+    b = torch.where(sounds, torch.maximum(a + 1, torch.ceil(pe.clamp(min=0.0))), torch.zeros_like(a)).to(torch.int64)
+    key = (rec << 9) | _program_key(notes, rows, by)
+    wanted = range(R) if recording is None else [int(recording)]
+    forced = torch.tensor([r << 9 for r in wanted] if by is None else [], dtype=torch.int64, device=dev)
+    uniq = torch.unique(torch.cat([key, forced]))
+    P = int(uniq.numel())
+    if P == 0:                                       # by="program" without a single note
+        return [dict() for _ in wanted] if recording is None else dict()
+    pid = torch.searchsorted(uniq, key)
+    n = torch.bincount(pid, minlength=P)
+    order = torch.sort(pid, stable=True).indices
+    last = torch.zeros(P, dtype=torch.int64, device=dev).scatter_reduce_(0, pid, b, "amax")
+    home = torch.cat([uniq, last]).cpu().numpy()
+    uniq_h, last_h = home[:P], home[P:]
+    frames = {int(r): 0 for r in wanted}
+    for k, v in zip(uniq_h >> 9, last_h):
+        frames[int(k)] = max(frames[int(k)], int(v))
+    n_frames = max(1, max(frames.values()))
+    if n_frames > lib.FRAMES_MAX:
+        raise ValueError("a piano roll of %d frames is beyond the kernel's 2^31 - 64" % n_frames)
+    first = torch.cat([n.new_zeros(1), torch.cumsum(n, 0)]).to(torch.int32)
+    none = torch.zeros(P + 1, dtype=torch.int32, device=dev)
+    _, _, clipped, roll = lib.note_frames(notes.times, notes.meta, notes.times, notes.meta, rows[order].to(torch.int32), first,
+                                          none[:0], none, fps, n_frames, with_roll=True)
+    bits = (roll[:, 0].unsqueeze(-1) >> torch.arange(32, device=dev, dtype=torch.int32)) & 1      # [P, 128, W, 32]
+    dense = bits.reshape(P, 128, -1).transpose(1, 2).to(torch.bool)                                # [P, W * 32, 128]
+    out = {int(r): ({} if by else None) for r in wanted}
+    for p, k in enumerate(uniq_h.tolist()):
+        r = k >> 9
+        piece = dense[p, :frames[r]]
+        if by is None:
+            out[r] = piece
+        else:
+            out[r][(k & 0xff, bool(k >> 8 & 1))] = piece
+    got = [out[int(r)] for r in wanted]
+    return got if recording is None else got[0]
+
+
+def score_tables(ref, est, with_overlap=False, families=FAMILIES, errors="raise", device=None, return_matching=False,
+                 frames=False, instruments=False, fps=FRAMES_PER_SECOND):
     """ref, est: `mrmt3.notes.DeviceNotes` (or lists of tables, uploaded to `device`) -> one dict per recording pair with the
     keys of `compute_transcription_metrics` and of `mt3_program_aware_note_scores` at the three granularities (see
     `assemble_scores`), from ONE launch of the device matcher for all pairs and all problems.  Only `matched`, the list
@@ -370,9 +600,16 @@ def score_tables(ref, est, with_overlap=False, families=FAMILIES, errors="raise"
     matching needs, and the overlap keys are present.  `families`: the scores to build (a subset of FAMILIES).
     A pair the host scorer would refuse raises its ValueError (`errors="return"`: the pair's entry is the exception).
     `return_matching` (with `with_overlap`): also returns, per pair, {"onoff": pairs, "on": pairs}, the kernel's matchings
-    as sorted (reference note, estimated note) numbers within the recording."""
+    as sorted (reference note, estimated note) numbers within the recording.
+    `frames`: ONE launch more, of the frame kernel over the same problems at `fps`; its counts come home in the
+    tensor `matched` comes home in, and every pair's dict gains "Frame precision" / "Frame recall" / "Frame F1" (the lists
+    of the "on" problem) and "Frame F1 (<granularity>)" for the granularities built.  `instruments`: the instrument-detection
+    keys of `evaluate.instrument_result` from the "full" problems' list lengths, no launch.  Both off: what it always did."""
     import torch
     from mrmt3 import lib
+    families = tuple(families)
+    if instruments and "full" not in families:
+        raise ValueError("instruments=True counts the program sets of the 'full' problems: families %r lack them" % (families,))
     if device is None:
         device = ref.meta.device if hasattr(ref, "first") else est.meta.device if hasattr(est, "first") else "cuda"
     programs = [[getattr(t, "programs", None) for t in side] if isinstance(side, (list, tuple)) else None for side in (ref, est)]
@@ -389,13 +626,29 @@ def score_tables(ref, est, with_overlap=False, families=FAMILIES, errors="raise"
     matched, match, status = lib.note_match(ref.times, ref.meta, est.times, est.meta, problems.ref_idx, problems.ref_first,
                                             problems.est_idx, problems.est_first, problems.prob_flags, lo, hi, ONSET_TOLERANCE,
                                             OFFSET_RATIO, OFFSET_MIN_TOLERANCE)
-    head = torch.stack([matched, status]).cpu().numpy()
+    if frames:
+        counts, _, clipped = lib.note_frames(ref.times, ref.meta, est.times, est.meta, problems.ref_idx, problems.ref_first,
+                                             problems.est_idx, problems.est_first, fps, frames_for(problems.max_end, fps))
+        P = matched.numel()
+        home = torch.cat([matched.to(torch.int64), status.to(torch.int64), counts.reshape(-1),
+                          clipped.to(torch.int64).reshape(-1)]).cpu().numpy()
+        head, frame_counts, clipped = home[:2 * P].reshape(2, P), home[2 * P:5 * P].reshape(P, 3), home[5 * P:].reshape(P, 2)
+        # (a pair the host scorer refuses may hold a note that starts after the last end: its problems are not scored)
+        scored = np.asarray([problems.errors[int(r)] is None for r in problems.pair], bool)
+        if clipped[scored].any():
+            raise RuntimeError("note_frames: clipped %r although n_frames came from the same tables" % clipped.tolist())
+    else:
+        head = torch.stack([matched, status]).cpu().numpy()
     if head[1].any():
         raise RuntimeError("note_match: status %r (the lists of build_problems are in order: a NaN onset?)" % head[1].tolist())
     overlaps = matchings = None
     if with_overlap:
         overlaps, matchings = _overlaps(problems, ref, est, match)
     out = assemble_scores(problems, head[0], programs[0], programs[1], overlaps)
+    if frames:
+        add_frame_scores(out, problems, frame_counts)
+    if instruments:
+        add_instrument_scores(out, problems)
     out = [problems.errors[r] if problems.errors[r] is not None else out[r] for r in range(len(out))]
     return (out, matchings) if return_matching else out
 

@@ -27,7 +27,7 @@ the least number that do, `+stem_gain_db=` (6) the gain range in dB.  Row geomet
 order is a function of (seed, epoch) and the ranks take disjoint shards of it.  `+stem_val_root=DIR` gives `val_loss` on
 the deterministic full mix of those tracks; `+val_notes=true` adds the note-level numbers behind it: every rank
 transcribes the full mix of the first `+val_notes_tracks=K` tracks of its validation shard (0, the default: all of them) and
-scores the notes on the device against the tracks' note tables, rank 0 prints `epoch N val_onset_f1 X val_onset_program_f1 Y`
+scores the notes on the device against the tracks' note tables, rank 0 prints `epoch N val_onset_f1 X val_onset_program_f1 Y` (and, with `+val_frames=true`, a second line `epoch N val_frame_f1 Z`)
 (means over the tracks of all ranks; training weights).  `+stem_device_labels=true` builds the targets on the device, one
 launch per track visit, instead of tokenising whole tracks on the host: the same targets, and `targets_prev` with them,
 so a `*WithPrev` model trains from stems (without the option it is refused); the run then ends with `label_launches K`.
@@ -282,7 +282,19 @@ def full_mix(track, sample_rate=16000):
     return mix
 
 
-def validate_notes(model, tracks, device, estimates=None, max_length=1024) -> dict:
+def val_frames_option(cfg, val_notes) -> bool:
+    """`+val_frames=true`: the frame F1 beside the note-level numbers; it needs `+val_notes=true`."""
+    raw = cfg.get("val_frames")
+    if raw is None or str(raw).lower() in ("false", "0", "no", "off"):
+        return False
+    if str(raw).lower() not in _TRUTHY:
+        raise ValueError("val_frames must be true or false, got %r" % (raw,))
+    if val_notes is None:
+        raise ValueError("+val_frames=true scores the frames of the notes +val_notes=true transcribes: it needs +val_notes=true")
+    return True
+
+
+def validate_notes(model, tracks, device, estimates=None, max_length=1024, frames=False) -> dict:
     """Note-level validation: the full mix of every track is transcribed by the model's inference path with the
     notes decoded on the device (`InferenceHandler.inference_many(return_tables=True)`), and scored there against the
     track's note table (`mrmt3.scoring.score_tables`, one launch for all tracks).  The NOTES THEMSELVES are scored, not a
@@ -292,11 +304,14 @@ def validate_notes(model, tracks, device, estimates=None, max_length=1024) -> di
     Returns {"tracks": n scored, "onset_f1": the SUM over the tracks of the instrument-agnostic onset F1,
     "onset_program_f1": the sum of "Onset + program F1 (flat)", "per_track": the tracks' score dicts}: sums and a count,
     so that ranks can be added like `val_loss`.  A track the host scorer would refuse (a reference note that does not
-    end after it starts) is left out of the sums and carries its ValueError in `per_track`."""
+    end after it starts) is left out of the sums and carries its ValueError in `per_track`.
+    `frames`: one launch of the frame kernel more, and "frame_f1", the sum of the tracks' "Frame F1"."""
     from mrmt3 import labels, scoring
     from mrmt3.notes import DeviceNotes
     tracks = list(tracks)
     out = {"tracks": 0, "onset_f1": 0.0, "onset_program_f1": 0.0, "per_track": []}
+    if frames:
+        out["frame_f1"] = 0.0
     if not tracks:
         return out
     if estimates is None:
@@ -312,13 +327,16 @@ def validate_notes(model, tracks, device, estimates=None, max_length=1024) -> di
     for t in tracks:
         table = labels.note_table(t)
         refs.append(DeviceNotes.from_note_table(torch.from_numpy(table.times).to(device), torch.from_numpy(table.meta).to(device)))
-    out["per_track"] = scoring.score_tables(DeviceNotes.concat(refs), estimates, families=("on", "flat"), errors="return")
+    out["per_track"] = scoring.score_tables(DeviceNotes.concat(refs), estimates, families=("on", "flat"), errors="return",
+                                            frames=frames)
     for got in out["per_track"]:
         if isinstance(got, Exception):
             continue
         out["tracks"] += 1
         out["onset_f1"] += got["Onset F1"]
         out["onset_program_f1"] += got["Onset + program F1 (flat)"]
+        if frames:
+            out["frame_f1"] += got["Frame F1"]
     return out
 
 
@@ -514,6 +532,7 @@ def main(argv=None):
     train_loader = val_loader = sampler = None
     stem = None if synthetic else stem_options(cfg, with_prev)
     val_notes = val_notes_options(cfg, stem)
+    val_frames = val_frames_option(cfg, val_notes)
     if stem is not None:
         train_loader, val_loader = stem_loaders(cfg, stem, device, world, rank, with_prev)
         sampler = train_loader                   # (`set_epoch`: the track order is a function of (seed, epoch))
@@ -569,14 +588,16 @@ def main(argv=None):
             if val_notes is not None:            # (+val_notes=true: the training weights, the first tracks of the shard)
                 shard = val_loader.shard()
                 got = validate_notes(task.model, [val_loader.tracks[t] for t in shard[:val_notes or len(shard)]], device,
-                                     max_length=int(cfg.get("event_length", 1024)))
-                notes_acc = torch.tensor([got["onset_f1"], got["onset_program_f1"], got["tracks"]], device=device,
-                                         dtype=torch.float64)
+                                     max_length=int(cfg.get("event_length", 1024)), frames=val_frames)
+                notes_acc = torch.tensor([got["onset_f1"], got["onset_program_f1"], got["tracks"], got.get("frame_f1", 0.0)],
+                                         device=device, dtype=torch.float64)
                 if world > 1:
                     dist.all_reduce(notes_acc, op=dist.ReduceOp.SUM)
                 if rank == 0 and notes_acc[2].item() > 0:
                     f1, pf1 = (notes_acc[:2] / notes_acc[2]).tolist()
                     print(f"epoch {ep} val_onset_f1 {f1:.4f} val_onset_program_f1 {pf1:.4f}", flush=True)
+                    if val_frames:
+                        print(f"epoch {ep} val_frame_f1 {(notes_acc[3] / notes_acc[2]).item():.4f}", flush=True)
             if ema_decay is None:
                 return
             acc.zero_()
