@@ -2,6 +2,7 @@
 // MFMA 16x16x32 bf16, 160 KiB LDS.  No CUDA shims, no dual paths.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -74,6 +75,13 @@ int mrmt3_diag_env(const char* name);
       return MRMT3_ERR_HIP;                                                         \
     }                                                                               \
   } while (0)
+
+// launches of one entry point since the process started / the last reset: what a mrmt3_*_launches(int reset) returns
+struct MrLaunchCounter {
+  std::atomic<unsigned long long> n{0};
+  void hit() { n.fetch_add(1, std::memory_order_relaxed); }
+  unsigned long long read(int reset) { return reset ? n.exchange(0, std::memory_order_relaxed) : n.load(std::memory_order_relaxed); }
+};
 
 // ---- bf16 <-> f32 ------------------------------------------------------------------------------
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((unsigned)v) << 16); }

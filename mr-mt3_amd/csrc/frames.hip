@@ -12,11 +12,11 @@
 //      the tile's words are stored as they lie; every word of `roll` belongs to exactly one unit.
 // Work is O(entries x tiles) per problem: every unit reads the whole of both lists (profiles/r25_frame_scores.txt).
 //
+// The sides, the clamped list range of a problem and the test of an entry's index are notetab.h's, shared with match.hip.
+//
 // f64 work: the two products of the definition, floor and ceil; one rounding per operation (no fused multiply-add);
 // ordinary vector loads and stores.
-#include "common.h"
-
-#include <atomic>
+#include "notetab.h"
 
 #pragma clang fp contract(off)
 
@@ -26,22 +26,14 @@
 #define NF_WORDS (NF_TILE / 32)
 #define NF_MAX_BLOCKS (1 << 16)
 
-static std::atomic<unsigned long long> g_frames_launches{0};
-
-struct NfSide {
-  const double* times;
-  const int4* meta;
-  long long n_notes;
-  const int* idx;
-  const int* first;
-};
+static MrLaunchCounter g_frames_launches;
 
 __device__ __forceinline__ unsigned nf_wave_sum(unsigned v) {
   for (int d = NF_WAVE / 2; d > 0; d >>= 1) v += __shfl_xor(v, d);
   return v;
 }
 
-__global__ __launch_bounds__(NF_THREADS) void note_frames_kernel(NfSide ref, NfSide est, int n_prob, double fps,
+__global__ __launch_bounds__(NF_THREADS) void note_frames_kernel(NoteSide ref, NoteSide est, int n_prob, double fps,
                                                                   long long n_frames, long long n_tiles, long long W,
                                                                   unsigned long long* __restrict__ counts,
                                                                   int* __restrict__ skipped, int* __restrict__ clipped,
@@ -54,28 +46,19 @@ __global__ __launch_bounds__(NF_THREADS) void note_frames_kernel(NfSide ref, NfS
     const long long tile = unit - (long long)p * n_tiles;
     const long long f0 = tile * NF_TILE;
     const long long f1 = f0 + NF_TILE < n_frames ? f0 + NF_TILE : n_frames;
-    int lo[2], hi[2];
-    for (int s = 0; s < 2; ++s) {
-      const NfSide& side = s ? est : ref;
-      int L = side.first[n_prob];
-      L = L < 0 ? 0 : L;
-      int a = side.first[p], b = side.first[p + 1];
-      a = a < 0 ? 0 : (a > L ? L : a);
-      b = b < a ? a : (b > L ? L : b);
-      lo[s] = a;
-      hi[s] = b;
-    }
+    int lo[2], hi[2], L;
+    for (int s = 0; s < 2; ++s) note_range(s ? est : ref, n_prob, p, lo[s], hi[s], L);
     if (lo[0] == hi[0] && lo[1] == hi[1] && !roll) continue;       // (the same for every thread: no barrier is missed)
     // ---- 1. clear
     for (int i = tid; i < 2 * 128 * NF_WORDS; i += NF_THREADS) (&s_roll[0][0][0])[i] = 0u;
     __syncthreads();
     // ---- 2. the entries
     for (int s = 0; s < 2; ++s) {
-      const NfSide& side = s ? est : ref;
+      const NoteSide& side = s ? est : ref;
       int n_skip = 0, n_clip = 0;
       for (int q = lo[s] + tid; q < hi[s]; q += NF_THREADS) {
-        const int note = side.idx[q];
-        bool ok = note >= 0 && (long long)note < side.n_notes;
+        int note;
+        bool ok = note_at(side, q, note);
         double ps = 0.0, pe = 0.0;
         int pitch = 0;
         if (ok) {
@@ -166,10 +149,9 @@ extern "C" int mrmt3_note_frames_fwd(const double* ref_times, const int* ref_met
   MR_CHECK_ARG(fps > 0.0 && fps <= 1.7976931348623157e308, "note_frames_fwd: fps must be finite and > 0, got %g", fps);
   MR_CHECK_ARG(n_frames >= 1 && n_frames <= 0x7fffffffLL - 63,
                "note_frames_fwd: n_frames must be in [1, 2^31 - 64], got %lld", n_frames);
-  MR_CHECK_ARG(n_ref_notes >= 0 && n_est_notes >= 0 && n_ref_notes <= 0x7fffffffLL && n_est_notes <= 0x7fffffffLL,
-               "note_frames_fwd: the note counts must be in [0, 2^31), got %lld, %lld", n_ref_notes, n_est_notes);
-  MR_CHECK_ARG(((uintptr_t)ref_meta % 16) == 0 && ((uintptr_t)est_meta % 16) == 0,
-               "note_frames_fwd: meta must be 16-byte aligned");
+  NOTETAB_CHECK_COUNTS("note_frames_fwd", n_ref_notes, n_est_notes);
+  NOTETAB_CHECK_META("note_frames_fwd", "meta", ref_meta);
+  NOTETAB_CHECK_META("note_frames_fwd", "meta", est_meta);
   hipStream_t st = (hipStream_t)stream;
   MR_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)n_prob * 3 * sizeof(long long), st));
   MR_CHECK_HIP(hipMemsetAsync(skipped, 0, (size_t)n_prob * 2 * sizeof(int), st));
@@ -177,15 +159,13 @@ extern "C" int mrmt3_note_frames_fwd(const double* ref_times, const int* ref_met
   const long long n_tiles = (n_frames + NF_TILE - 1) / NF_TILE, W = (n_frames + 31) / 32;
   const long long units = (long long)n_prob * n_tiles;
   const unsigned blocks = (unsigned)(units < NF_MAX_BLOCKS ? units : NF_MAX_BLOCKS);
-  const NfSide ref{ref_times, (const int4*)ref_meta, n_ref_notes, ref_idx, ref_first};
-  const NfSide est{est_times, (const int4*)est_meta, n_est_notes, est_idx, est_first};
+  const NoteSide ref{ref_times, (const int4*)ref_meta, n_ref_notes, ref_idx, ref_first};
+  const NoteSide est{est_times, (const int4*)est_meta, n_est_notes, est_idx, est_first};
   hipLaunchKernelGGL(note_frames_kernel, dim3(blocks), dim3(NF_THREADS), 0, st, ref, est, n_prob, fps, n_frames, n_tiles, W,
                      (unsigned long long*)counts, skipped, clipped, roll);
   MR_CHECK_LAUNCH("note_frames_fwd");
-  g_frames_launches.fetch_add(1, std::memory_order_relaxed);
+  g_frames_launches.hit();
   return MRMT3_OK;
 }
 
-extern "C" unsigned long long mrmt3_note_frames_launches(int reset) {
-  return reset ? g_frames_launches.exchange(0, std::memory_order_relaxed) : g_frames_launches.load(std::memory_order_relaxed);
-}
+extern "C" unsigned long long mrmt3_note_frames_launches(int reset) { return g_frames_launches.read(reset); }

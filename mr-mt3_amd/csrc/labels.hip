@@ -1,5 +1,6 @@
 // Stem-mix labels on the device (mrmt3_label_rows_fwd): the padded target row of every training row, straight
-// from the track's note table — filter, trim, sort, walk; the contract is the header's.
+// from the track's note table (its layout and the alignment check: notetab.h) — filter, trim, sort, walk; the contract is
+// the header's.
 //
 // One workgroup per row.  Two scans over the table: the first finds the step of the subset's last event (the tie section
 // needs it, see the header's quirk), the second marks the sounding (program, pitch) pairs in an LDS bitmap — which is the
@@ -9,9 +10,7 @@
 // of its (pitch, program, is_drum) group over all stems, and a row follows the links to the first kept one.
 //
 // Integer and f64 work only, one rounding per operation (no fused multiply-add), ordinary vector stores.
-#include "common.h"
-
-#include <atomic>
+#include "notetab.h"
 
 #pragma clang fp contract(off)
 
@@ -25,7 +24,7 @@
 #define LB_ST_ORDER 4
 #define LB_ST_RANGE 8
 
-static std::atomic<unsigned long long> g_label_launches{0};
+static MrLaunchCounter g_label_launches;
 
 struct LbCodec {
   int pitch_base, velocity_base, tie_token, program_base, drum_base, max_shift_steps, sps, event_length, special;
@@ -284,17 +283,15 @@ extern "C" int mrmt3_label_rows_fwd(const double* note_times, const int* note_me
   MR_CHECK_ARG(pitch_base >= 0 && velocity_base >= 0 && tie_token >= 0 && program_base >= 0 && drum_base >= 0 &&
                    num_special_tokens >= 0,
                "label_rows_fwd: token bases and num_special_tokens must be >= 0");
-  MR_CHECK_ARG(((uintptr_t)note_meta % 16) == 0, "label_rows_fwd: note_meta must be 16-byte aligned");
+  NOTETAB_CHECK_META("label_rows_fwd", "note_meta", note_meta);
   const LbCodec c = {pitch_base, velocity_base, tie_token, program_base, drum_base, max_shift_steps, steps_per_second,
                      event_length, num_special_tokens, (double)sample_rate / (double)hop};
   hipLaunchKernelGGL(label_rows_kernel, dim3((unsigned)batch), dim3(LB_THREADS), 0, (hipStream_t)stream, note_times,
                      (const int4*)note_meta, n_notes, keep, start_frame, n_frames, total_frames, scale, shift, batch, c,
                      targets, status);
   MR_CHECK_LAUNCH("label_rows_fwd");
-  g_label_launches.fetch_add(1, std::memory_order_relaxed);
+  g_label_launches.hit();
   return MRMT3_OK;
 }
 
-extern "C" unsigned long long mrmt3_label_launches(int reset) {
-  return reset ? g_label_launches.exchange(0, std::memory_order_relaxed) : g_label_launches.load(std::memory_order_relaxed);
-}
+extern "C" unsigned long long mrmt3_label_launches(int reset) { return g_label_launches.read(reset); }

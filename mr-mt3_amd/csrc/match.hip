@@ -15,24 +15,17 @@
 // A run is matched by one wave from its first entry on and in list order, so the matching does not depend on which wave
 // drew it: the same bits on every run.
 //
+// The sides, the clamped list range of a problem and the test of an entry's index are notetab.h's, shared with frames.hip.
+//
 // f64 work only, one rounding per operation (no fused multiply-add); ordinary vector loads and stores.
-#include "common.h"
-
-#include <atomic>
+#include "notetab.h"
 
 #pragma clang fp contract(off)
 
 #define NM_THREADS 1024
 #define NM_WAVE 64
 
-static std::atomic<unsigned long long> g_match_launches{0};
-
-struct NmSide {
-  const double* times;
-  const int4* meta;
-  long long n_notes;
-  const int* idx;
-};
+static MrLaunchCounter g_match_launches;
 
 struct NmTol {
   double onset, ratio, offset_min;
@@ -48,17 +41,16 @@ __device__ __forceinline__ double nm_dist(double a, double b) {
   return __ddiv_rn(rint(__dmul_rn(fabs(__dsub_rn(a, b)), 1e6)), 1e6);
 }
 
-// entry `pos` of a list: is its index inside the table and its onset a number?
-__device__ __forceinline__ bool nm_entry(const NmSide& s, int pos, int& note, double& on) {
-  note = s.idx[pos];
-  if (note < 0 || (long long)note >= s.n_notes) return false;
+// entry `pos` of a list: does it name a note of the table (note_at) whose onset is a number?
+__device__ __forceinline__ bool nm_entry(const NoteSide& s, int pos, int& note, double& on) {
+  if (!note_at(s, pos, note)) return false;
   on = s.times[2 * (size_t)note];
   return on == on;
 }
 
 // the onset the order and the windows see at `pos`: the entry's, or that of the nearest valid entry before it (an entry
 // without a valid index or onset is transparent), -inf if there is none.  `note` receives that entry's index, -1 for none.
-__device__ __forceinline__ double nm_key(const NmSide& s, int first, int pos, int& note) {
+__device__ __forceinline__ double nm_key(const NoteSide& s, int first, int pos, int& note) {
   for (int q = pos; q >= first; --q) {
     double on;
     if (nm_entry(s, q, note, on)) return on;
@@ -67,7 +59,7 @@ __device__ __forceinline__ double nm_key(const NmSide& s, int first, int pos, in
   return -__builtin_huge_val();
 }
 
-__device__ __forceinline__ bool nm_ordered(const NmSide& s, int first, int pos) {
+__device__ __forceinline__ bool nm_ordered(const NoteSide& s, int first, int pos) {
   int note, before;
   double on;
   if (pos <= first || !nm_entry(s, pos, note, on)) return true;
@@ -76,21 +68,16 @@ __device__ __forceinline__ bool nm_ordered(const NmSide& s, int first, int pos) 
 }
 
 __global__ __launch_bounds__(NM_THREADS) void note_match_kernel(
-    NmSide ref, NmSide est, const int* __restrict__ ref_first, const int* __restrict__ est_first,
-    const int* __restrict__ prob_flags, int n_prob, const int* __restrict__ pitch_lo, const int* __restrict__ pitch_hi,
-    int n_tables, NmTol tol, int* __restrict__ matched, int* match, int* __restrict__ status, int* ws) {
+    NoteSide ref, NoteSide est, const int* __restrict__ prob_flags, int n_prob, const int* __restrict__ pitch_lo,
+    const int* __restrict__ pitch_hi, int n_tables, NmTol tol, int* __restrict__ matched, int* match,
+    int* __restrict__ status, int* ws) {
   __shared__ int s_bad, s_next, s_matched;
   const int tid = threadIdx.x, lane = tid & (NM_WAVE - 1);
   const int p = blockIdx.x;
   if (p >= n_prob) return;
-  int Lr = ref_first[n_prob], Le = est_first[n_prob];
-  Lr = Lr < 0 ? 0 : Lr;
-  Le = Le < 0 ? 0 : Le;
-  int r0 = ref_first[p], r1 = ref_first[p + 1], e0 = est_first[p], e1 = est_first[p + 1];
-  r0 = r0 < 0 ? 0 : (r0 > Lr ? Lr : r0);
-  r1 = r1 < r0 ? r0 : (r1 > Lr ? Lr : r1);
-  e0 = e0 < 0 ? 0 : (e0 > Le ? Le : e0);
-  e1 = e1 < e0 ? e0 : (e1 > Le ? Le : e1);
+  int r0, r1, Lr, e0, e1, Le;
+  note_range(ref, n_prob, p, r0, r1, Lr);
+  note_range(est, n_prob, p, e0, e1, Le);
   const int flags = prob_flags[p];
   const bool offsets = flags & 1;
   const int table = flags >> 8;
@@ -287,25 +274,21 @@ extern "C" int mrmt3_note_match_fwd(const double* ref_times, const int* ref_meta
                "note_match_fwd: null pointer (the workspace too: its size is known to the caller alone)");
   MR_CHECK_ARG(n_prob > 0 && n_tables > 0, "note_match_fwd: n_prob and n_tables must be > 0, got %d, %d", n_prob, n_tables);
   MR_CHECK_ARG(n_tables <= (1 << 22), "note_match_fwd: at most %d pitch tables, got %d", 1 << 22, n_tables);
-  MR_CHECK_ARG(n_ref_notes >= 0 && n_est_notes >= 0 && n_ref_notes <= 0x7fffffffLL && n_est_notes <= 0x7fffffffLL,
-               "note_match_fwd: the note counts must be in [0, 2^31), got %lld, %lld", n_ref_notes, n_est_notes);
+  NOTETAB_CHECK_COUNTS("note_match_fwd", n_ref_notes, n_est_notes);
   MR_CHECK_ARG(onset_tol >= 0.0 && offset_ratio >= 0.0 && offset_min_tol >= 0.0,
                "note_match_fwd: the tolerances must be >= 0 (a NaN is not), got %g, %g, %g", onset_tol, offset_ratio,
                offset_min_tol);
-  MR_CHECK_ARG(((uintptr_t)ref_meta % 16) == 0 && ((uintptr_t)est_meta % 16) == 0,
-               "note_match_fwd: meta must be 16-byte aligned");
+  NOTETAB_CHECK_META("note_match_fwd", "meta", ref_meta);
+  NOTETAB_CHECK_META("note_match_fwd", "meta", est_meta);
   MR_CHECK_ARG(((uintptr_t)workspace % 4) == 0, "note_match_fwd: the workspace must be 4-byte aligned");
-  const NmSide ref{ref_times, (const int4*)ref_meta, n_ref_notes, ref_idx};
-  const NmSide est{est_times, (const int4*)est_meta, n_est_notes, est_idx};
+  const NoteSide ref{ref_times, (const int4*)ref_meta, n_ref_notes, ref_idx, ref_first};
+  const NoteSide est{est_times, (const int4*)est_meta, n_est_notes, est_idx, est_first};
   const NmTol tol{onset_tol, offset_ratio, offset_min_tol};
-  hipLaunchKernelGGL(note_match_kernel, dim3((unsigned)n_prob), dim3(NM_THREADS), 0, (hipStream_t)stream, ref, est, ref_first,
-                     est_first, prob_flags, n_prob, pitch_lo, pitch_hi, n_tables, tol, matched, match, status,
-                     (int*)workspace);
+  hipLaunchKernelGGL(note_match_kernel, dim3((unsigned)n_prob), dim3(NM_THREADS), 0, (hipStream_t)stream, ref, est,
+                     prob_flags, n_prob, pitch_lo, pitch_hi, n_tables, tol, matched, match, status, (int*)workspace);
   MR_CHECK_LAUNCH("note_match_fwd");
-  g_match_launches.fetch_add(1, std::memory_order_relaxed);
+  g_match_launches.hit();
   return MRMT3_OK;
 }
 
-extern "C" unsigned long long mrmt3_note_match_launches(int reset) {
-  return reset ? g_match_launches.exchange(0, std::memory_order_relaxed) : g_match_launches.load(std::memory_order_relaxed);
-}
+extern "C" unsigned long long mrmt3_note_match_launches(int reset) { return g_match_launches.read(reset); }

@@ -1,6 +1,6 @@
 // Token rows -> notes on the device (mrmt3_notes_decode_fwd): the cut at the first EOS, the run-length decoder and
 // the note state machine of contrib/note_sequences.py for every segment of every recording in one launch; the contract is the
-// header's.
+// header's.  What it writes is a note table (its layout and the alignment check: notetab.h).
 //
 // One workgroup per recording; it takes the recording's rows in order.  Per row the cut is a strided minimum; then the
 // tokens go through LDS in chunks of NT_THREADS: every thread classifies one token, a segmented scan gives the step count
@@ -11,9 +11,7 @@
 // compacts it first, and only if every slot is alive is the recording over capacity.
 //
 // Integer and f64 work only, one rounding per operation (no fused multiply-add), ordinary vector stores.
-#include "common.h"
-
-#include <atomic>
+#include "notetab.h"
 
 #pragma clang fp contract(off)
 
@@ -32,7 +30,7 @@
 
 static_assert(NT_CAP < NT_DEAD, "slot indices are 16-bit");
 
-static std::atomic<unsigned long long> g_notes_launches{0};
+static MrLaunchCounter g_notes_launches;
 
 // one token of a chunk as the walk reads it: one 16-byte LDS load
 struct __attribute__((aligned(16))) NtRec {
@@ -340,15 +338,13 @@ extern "C" int mrmt3_notes_decode_fwd(const mrmt3_grammar* g, const long long* i
                g->n_pitch, g->n_program);
   MR_CHECK_ARG(g->n_drum <= 65536 && g->n_velocity <= 65536, "notes_decode_fwd: n_drum and n_velocity must be <= 65536");
   MR_CHECK_ARG(g->steps_per_second > 0, "notes_decode_fwd: steps_per_second must be > 0, got %d", g->steps_per_second);
-  MR_CHECK_ARG(((uintptr_t)meta % 16) == 0, "notes_decode_fwd: meta must be 16-byte aligned");
+  NOTETAB_CHECK_META("notes_decode_fwd", "meta", meta);
   hipLaunchKernelGGL(notes_decode_kernel, dim3((unsigned)n_rec), dim3(NT_THREADS), 0, (hipStream_t)stream, *g, ids, logp, rows,
                      ld, seg_first, n_rec, start_time, limit, velocity_of_bin, n_notes, invalid, dropped, status, total_time,
                      times, (int4*)meta, logc);
   MR_CHECK_LAUNCH("notes_decode_fwd");
-  g_notes_launches.fetch_add(1, std::memory_order_relaxed);
+  g_notes_launches.hit();
   return MRMT3_OK;
 }
 
-extern "C" unsigned long long mrmt3_notes_launches(int reset) {
-  return reset ? g_notes_launches.exchange(0, std::memory_order_relaxed) : g_notes_launches.load(std::memory_order_relaxed);
-}
+extern "C" unsigned long long mrmt3_notes_launches(int reset) { return g_notes_launches.read(reset); }

@@ -12,8 +12,6 @@
 // packed f32 (csrc/Makefile), and a tap outside the stem is not added at all (a select, never a product with zero).
 #include "common.h"
 
-#include <atomic>
-
 #pragma clang fp contract(off)
 
 #define RS_THREADS 256
@@ -24,7 +22,7 @@
 #define RS_PHASES 512                            // ABI constant: a table has RS_PHASES + 1 rows
 #define RS_SPAN (RS_TILE * 4 + RS_MAX_TAPS)      // floats of LDS: the span of a full tile at step 4
 
-static std::atomic<unsigned long long> g_resample_launches{0};
+static MrLaunchCounter g_resample_launches;
 
 typedef float rs_f4 __attribute__((ext_vector_type(4)));
 typedef rs_f4 rs_f4a8 __attribute__((aligned(8)));   // a table row starts on 8 bytes (n_taps is even), not on 16
@@ -224,11 +222,8 @@ extern "C" int mrmt3_resample_mix_fwd(const float* pool, long long pool_samples,
                      src_begin, src_end, src_step, src_gain, src_filt, n_src, batch, n_samples, filt, n_filt, n_taps,
                      valid_samples, out, stage);
   MR_CHECK_LAUNCH("resample_mix_fwd");
-  g_resample_launches.fetch_add(1, std::memory_order_relaxed);
+  g_resample_launches.hit();
   return MRMT3_OK;
 }
 
-extern "C" unsigned long long mrmt3_resample_launches(int reset) {
-  return reset ? g_resample_launches.exchange(0, std::memory_order_relaxed)
-               : g_resample_launches.load(std::memory_order_relaxed);
-}
+extern "C" unsigned long long mrmt3_resample_launches(int reset) { return g_resample_launches.read(reset); }

@@ -97,6 +97,22 @@ def instrument_result(ref_programs, est_programs):
     return dict(zip(INSTRUMENT_KEYS, tm.instrument_scores(ref_programs, est_programs)))
 
 
+def _groups(mid, granularity):
+    """{(granular program, is_drum): the notes of a file's instruments of that group}, keys in order of first appearance (an
+    instrument without notes still names its group)."""
+    groups = {}
+    for inst in mid.instruments:
+        key = (get_granular_program(inst.program, inst.is_drum, granularity), bool(inst.is_drum))
+        groups.setdefault(key, []).extend(inst.notes)
+    return groups
+
+
+def _interval_arrays(notes):
+    """(intervals f64 [n, 2], MIDI pitches f64 [n]) of a list of notes."""
+    return (np.array([[n.start, n.end] for n in notes], dtype=np.float64).reshape(-1, 2),
+            np.array([n.pitch for n in notes], dtype=np.float64))
+
+
 def host_frame_result(ref_mid, est_mid, granularities, on=True):
     """`frame_result` of two MIDI files on the host: "on" from the notes of `tm.sequence_to_valued_intervals`, a
     granularity's groups as `mt3_program_aware_note_scores` forms them, all of their notes."""
@@ -107,17 +123,9 @@ def host_frame_result(ref_mid, est_mid, granularities, on=True):
         counts = tm.frame_counts(iv_r, p_r, iv_e, p_e)
     grouped = {}
     for g in granularities:
-        sides = []
-        for mid in (ref_mid, est_mid):
-            by_key = {}
-            for inst in mid.instruments:
-                key = (get_granular_program(inst.program, inst.is_drum, g), bool(inst.is_drum))
-                by_key.setdefault(key, []).extend(inst.notes)
-            sides.append(by_key)
-        arrays = lambda notes: (np.array([[n.start, n.end] for n in notes], dtype=np.float64).reshape(-1, 2),
-                                np.array([n.pitch for n in notes], dtype=np.float64))
-        grouped[g] = [tm.frame_counts(*arrays(sides[0].get(key, [])), *arrays(sides[1].get(key, [])))
-                      for key in sorted(set(sides[0]) | set(sides[1])) if sides[0].get(key) or sides[1].get(key)]
+        ref_g, est_g = _groups(ref_mid, g), _groups(est_mid, g)
+        grouped[g] = [tm.frame_counts(*_interval_arrays(ref_g.get(key, [])), *_interval_arrays(est_g.get(key, [])))
+                      for key in sorted(set(ref_g) | set(est_g)) if ref_g.get(key) or est_g.get(key)]
     return frame_result(counts, grouped)
 
 
@@ -187,26 +195,13 @@ def mt3_program_aware_note_scores(fname1, fname2, granularity_type, device=None,
     iv_r, p_r, _ = tm.sequence_to_valued_intervals(midi_io.midi_to_note_sequence(ref_mid))
     iv_e, p_e, _ = tm.sequence_to_valued_intervals(midi_io.midi_to_note_sequence(est_mid))
     precision, recall, f1, _ = tm.precision_recall_f1_overlap(iv_r, p_r, iv_e, p_e, offset_ratio=None)
-
-    def group(mid):
-        g = collections.OrderedDict()
-        for inst in mid.instruments:
-            key = (get_granular_program(inst.program, inst.is_drum, granularity_type), inst.is_drum)
-            g.setdefault(key, []).extend(inst.notes)
-        return g
-
-    ref_g, est_g = group(ref_mid), group(est_mid)
+    ref_g, est_g = _groups(ref_mid, granularity_type), _groups(est_mid, granularity_type)
 
     def scored():
         for key in group_order(ref_g, est_g):
-
-            def arrays(notes):
-                iv = np.array([[n.start, n.end] for n in notes], dtype=np.float64).reshape(-1, 2)
-                return iv, tm.midi_to_hz([n.pitch for n in notes])
-
-            r_iv, r_hz = arrays(ref_g.get(key, []))
-            e_iv, e_hz = arrays(est_g.get(key, []))
-            p, r, f, _ = tm.precision_recall_f1_overlap(r_iv, r_hz, e_iv, e_hz, offset_ratio=None)
+            (r_iv, r_pitch), (e_iv, e_pitch) = _interval_arrays(ref_g.get(key, [])), _interval_arrays(est_g.get(key, []))
+            p, r, f, _ = tm.precision_recall_f1_overlap(r_iv, tm.midi_to_hz(r_pitch), e_iv, tm.midi_to_hz(e_pitch),
+                                                        offset_ratio=None)
             yield key, (p, r, f), len(r_iv), len(e_iv)
 
     res = program_aware_result((precision, recall, f1), scored(), granularity_type)

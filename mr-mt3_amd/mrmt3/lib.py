@@ -353,6 +353,34 @@ def notes_launches(reset: bool = False) -> int:
     return int(load().mrmt3_notes_launches(int(reset)))
 
 
+def _note_lists(who, ref_times, ref_meta, est_times, est_meta, ref_idx, ref_first, est_idx, est_first) -> int:
+    """The check `note_match` and `note_frames` share, before anything touches the device: two note tables, two lists, two
+    `first` arrays.  A ValueError that names the wrapper `who`; returns n_prob."""
+    for name, times, meta in (("ref", ref_times, ref_meta), ("est", est_times, est_meta)):
+        n = meta.shape[0]
+        if tuple(times.shape) != (n, 2) or times.dtype != torch.float64 or not times.is_contiguous():
+            raise ValueError(f"{who}: {name}_times must be contiguous [n, 2] f64, got {tuple(times.shape)} {times.dtype}")
+        if meta.dim() != 2 or meta.shape[1] != 4 or meta.dtype != torch.int32 or not meta.is_contiguous():
+            raise ValueError(f"{who}: {name}_meta must be contiguous [n, 4] int32, got {tuple(meta.shape)} {meta.dtype}")
+        if n >= 1 << 31:
+            raise ValueError(f"{who}: {n} {name} notes, the note counts must be in [0, 2^31)")
+    for name, t in (("ref_idx", ref_idx), ("est_idx", est_idx), ("ref_first", ref_first), ("est_first", est_first)):
+        if t.dim() != 1 or t.dtype != torch.int32 or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be contiguous 1-D int32, got {tuple(t.shape)} {t.dtype}")
+    n_prob = ref_first.numel() - 1
+    if n_prob <= 0 or est_first.numel() != n_prob + 1:
+        raise ValueError(f"{who}: ref_first and est_first must both be [n_prob + 1] with n_prob > 0, got "
+                         f"{ref_first.numel()} and {est_first.numel()} entries")
+    return n_prob
+
+
+def _or_spare(dev):
+    """t -> its pointer, or that of a spare block where t is empty (an empty tensor's pointer is null, which the C library
+    refuses)."""
+    spare = torch.empty(4, 4, device=dev, dtype=torch.int32)
+    return lambda t: _p(t) if t.numel() else _p(spare)
+
+
 def note_match(ref_times, ref_meta, est_times, est_meta, ref_idx, ref_first, est_idx, est_first, prob_flags, pitch_lo,
                pitch_hi, onset_tol=0.05, offset_ratio=0.2, offset_min_tol=0.05):
     """ref_times / est_times [n, 2] f64 and ref_meta / est_meta [n, 4] int32 (note tables: a `mrmt3.labels.NoteTable` on the
@@ -360,18 +388,15 @@ def note_match(ref_times, ref_meta, est_times, est_meta, ref_idx, ref_first, est
     in onset order; ref_first / est_first [n_prob + 1] int32; prob_flags [n_prob] int32 (bit 0: offsets on, bits 8..: the
     pitch table); pitch_lo / pitch_hi [n_tables, 128] int32, all on the device -> (matched [n_prob] int32, match [Le] int32,
     status [n_prob] int32).  ONE launch for every problem; Lr and Le are taken from the list tensors' lengths, no read-back
-    (include/mrmt3_hip.h: mrmt3_note_match_fwd)."""
+    (include/mrmt3_hip.h: mrmt3_note_match_fwd).  A malformed argument is a ValueError, before anything is launched."""
+    n_prob = _note_lists("note_match", ref_times, ref_meta, est_times, est_meta, ref_idx, ref_first, est_idx, est_first)
+    if prob_flags.dim() != 1 or prob_flags.dtype != torch.int32 or not prob_flags.is_contiguous() or prob_flags.numel() != n_prob:
+        raise ValueError(f"note_match: prob_flags must be contiguous [n_prob = {n_prob}] int32, got "
+                         f"{tuple(prob_flags.shape)} {prob_flags.dtype}")
+    for name, t in (("pitch_lo", pitch_lo), ("pitch_hi", pitch_hi)):
+        if t.dim() != 2 or t.shape[1] != 128 or t.shape != pitch_lo.shape or t.dtype != torch.int32 or not t.is_contiguous():
+            raise ValueError(f"note_match: {name} must be contiguous [n_tables, 128] int32, got {tuple(t.shape)} {t.dtype}")
     _dev(ref_times, ref_meta, est_times, est_meta, ref_idx, ref_first, est_idx, est_first, prob_flags, pitch_lo, pitch_hi)
-    for times, meta in ((ref_times, ref_meta), (est_times, est_meta)):
-        n = meta.shape[0]
-        assert times.shape == (n, 2) and times.dtype == torch.float64 and times.is_contiguous()
-        assert meta.shape == (n, 4) and meta.dtype == torch.int32 and meta.is_contiguous()
-    for t in (ref_idx, est_idx, ref_first, est_first, prob_flags):
-        assert t.dim() == 1 and t.dtype == torch.int32 and t.is_contiguous()
-    n_prob = prob_flags.numel()
-    assert ref_first.numel() == n_prob + 1 and est_first.numel() == n_prob + 1
-    assert pitch_lo.dim() == 2 and pitch_lo.shape[1] == 128 and pitch_lo.dtype == torch.int32 and pitch_lo.is_contiguous()
-    assert pitch_hi.shape == pitch_lo.shape and pitch_hi.dtype == torch.int32 and pitch_hi.is_contiguous()
     dev, Lr, Le = prob_flags.device, ref_idx.numel(), est_idx.numel()
     matched = torch.empty(n_prob, device=dev, dtype=torch.int32)
     status = torch.empty(n_prob, device=dev, dtype=torch.int32)
@@ -381,8 +406,7 @@ def note_match(ref_times, ref_meta, est_times, est_meta, ref_idx, ref_first, est
     if words == 0 and (Lr or Le):
         raise ValueError(f"note_match: list lengths {Lr}, {Le} are beyond the kernel's 2^30 entries")
     ws = torch.empty(max(words, 1), device=dev, dtype=torch.int32)
-    spare = torch.empty(4, 4, device=dev, dtype=torch.int32)           # what an empty tensor's null pointer is replaced by
-    ptr = lambda t: _p(t) if t.numel() else _p(spare)
+    ptr = _or_spare(dev)
     _check(lib.mrmt3_note_match_fwd(ptr(ref_times), ptr(ref_meta), ref_meta.shape[0], ptr(est_times), ptr(est_meta),
                                     est_meta.shape[0], ptr(ref_idx), _p(ref_first), ptr(est_idx), _p(est_first),
                                     ptr(prob_flags), n_prob, _p(pitch_lo), _p(pitch_hi), pitch_lo.shape[0], float(onset_tol),
@@ -411,29 +435,14 @@ def note_frames(ref_times, ref_meta, est_times, est_meta, ref_idx, ref_first, es
         raise ValueError(f"note_frames: fps must be finite and > 0, got {fps!r}")
     if isinstance(n_frames, bool) or int(n_frames) != n_frames or not 1 <= int(n_frames) <= FRAMES_MAX:
         raise ValueError(f"note_frames: n_frames must be a whole number in [1, 2^31 - 64], got {n_frames!r}")
-    for name, times, meta in (("ref", ref_times, ref_meta), ("est", est_times, est_meta)):
-        n = meta.shape[0]
-        if tuple(times.shape) != (n, 2) or times.dtype != torch.float64 or not times.is_contiguous():
-            raise ValueError(f"note_frames: {name}_times must be contiguous [n, 2] f64, got {tuple(times.shape)} {times.dtype}")
-        if meta.dim() != 2 or meta.shape[1] != 4 or meta.dtype != torch.int32 or not meta.is_contiguous():
-            raise ValueError(f"note_frames: {name}_meta must be contiguous [n, 4] int32, got {tuple(meta.shape)} {meta.dtype}")
-        if n >= 1 << 31:
-            raise ValueError(f"note_frames: {n} {name} notes, the note counts must be in [0, 2^31)")
-    for name, t in (("ref_idx", ref_idx), ("est_idx", est_idx), ("ref_first", ref_first), ("est_first", est_first)):
-        if t.dim() != 1 or t.dtype != torch.int32 or not t.is_contiguous():
-            raise ValueError(f"note_frames: {name} must be contiguous 1-D int32, got {tuple(t.shape)} {t.dtype}")
-    n_prob = ref_first.numel() - 1
-    if n_prob <= 0 or est_first.numel() != n_prob + 1:
-        raise ValueError(f"note_frames: ref_first and est_first must both be [n_prob + 1] with n_prob > 0, got "
-                         f"{ref_first.numel()} and {est_first.numel()} entries")
+    n_prob = _note_lists("note_frames", ref_times, ref_meta, est_times, est_meta, ref_idx, ref_first, est_idx, est_first)
     _dev(ref_times, ref_meta, est_times, est_meta, ref_idx, ref_first, est_idx, est_first)
     dev, n_frames = ref_first.device, int(n_frames)
     counts = torch.empty(n_prob, 3, device=dev, dtype=torch.int64)
     skipped = torch.empty(n_prob, 2, device=dev, dtype=torch.int32)
     clipped = torch.empty(n_prob, 2, device=dev, dtype=torch.int32)
     roll = torch.empty(n_prob, 2, 128, -(-n_frames // 32), device=dev, dtype=torch.int32) if with_roll else None
-    spare = torch.empty(4, 4, device=dev, dtype=torch.int32)           # what an empty tensor's null pointer is replaced by
-    ptr = lambda t: _p(t) if t.numel() else _p(spare)
+    ptr = _or_spare(dev)
     _check(load().mrmt3_note_frames_fwd(ptr(ref_times), ptr(ref_meta), ref_meta.shape[0], ptr(est_times), ptr(est_meta),
                                         est_meta.shape[0], ptr(ref_idx), _p(ref_first), ptr(est_idx), _p(est_first), n_prob,
                                         float(fps), n_frames, _p(counts), _p(skipped), _p(clipped), _p(roll), None, _stream()),

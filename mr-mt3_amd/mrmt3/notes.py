@@ -254,6 +254,7 @@ def _decode_launch(ids_dev, frame_times, codec, logp, recordings, eos_token_id, 
     regions whole).  Returns a dict; `redo(r)` decodes recording r on the host (a recording over the kernel's capacity)."""
     import torch
     from mrmt3 import lib
+    from mrmt3.scoring import _home
     check_codec(codec)
     if not ids_dev.is_cuda or (logp is not None and not logp.is_cuda):
         raise RuntimeError("decode_notes needs device tensors (no CPU fallback of the kernel): decode_notes_host is the host's")
@@ -282,8 +283,7 @@ def _decode_launch(ids_dev, frame_times, codec, logp, recordings, eos_token_id, 
     out = lib.notes_decode(grammar, ids_dev, torch.from_numpy(seg_first).to(dev), scalars[:rows], scalars[rows:], _TABLES[key],
                            sps, logp)
     n_rec = len(seg_first) - 1
-    head = torch.stack([out[k] for k in ("n_notes", "invalid", "dropped", "status")]).cpu().numpy()
-    total = out["total_time"].cpu().numpy()
+    *head, total = _home(*(out[k] for k in ("n_notes", "invalid", "dropped", "status", "total_time")))
     counts = np.where(head[3] == 0, head[0], 0)
     pick = np.concatenate([int(seg_first[r]) * (ld - 1) + np.arange(counts[r]) for r in range(n_rec)] or [np.zeros(0, int)])
     at = torch.from_numpy(pick.astype(np.int64)).to(dev)
@@ -299,25 +299,27 @@ def _decode_launch(ids_dev, frame_times, codec, logp, recordings, eos_token_id, 
                 logc=None if logp is None else out["logc"][at])
 
 
+def _recordings(d, *tables):
+    """The walk over a launch's recordings: per recording (r, slices, redo) with `slices` its rows of each of `tables`
+    (laid end to end in recording order, as `_decode_launch` gathers them; None stays None) and `redo` None, or, for a
+    recording over the kernel's capacity, its `NoteArrays` decoded on the host (`slices` is then empty)."""
+    o = 0
+    for r in range(d["n_rec"]):
+        n = int(d["counts"][r])
+        yield r, [None if t is None else t[o:o + n] for t in tables], d["redo"](r) if d["head"][3][r] != 0 else None
+        o += n
+
+
 def decode_notes(ids_dev, frame_times, codec, logp=None, recordings=None, eos_token_id=1, pad_token_id=0) -> List[NoteArrays]:
     """ids_dev [rows, ld] int64 on the device as the decoder returned them (every row of every recording, a recording's rows
     together), frame_times [rows, frames] on the host, `codec` of `vocabularies.build_codec`, logp [rows, ld] f32 on the
     device or None, `recordings` the row count of each recording (None: one) -> one `NoteArrays` per recording.  One launch;
     only the notes written come back.  A recording over the kernel's capacity is decoded by `decode_notes_host`."""
     d = _decode_launch(ids_dev, frame_times, codec, logp, recordings, eos_token_id, pad_token_id)
-    head, total, counts = d["head"], d["total"], d["counts"]
-    times, meta = d["times"].cpu().numpy(), d["meta"].cpu().numpy()
-    logc = None if d["logc"] is None else d["logc"].cpu().numpy()
-    result, o = [], 0
-    for r in range(d["n_rec"]):
-        if head[3][r] != 0:                      # over capacity: this recording alone goes to the host
-            result.append(d["redo"](r))
-            continue
-        n = int(counts[r])
-        result.append(NoteArrays(times[o:o + n], meta[o:o + n], None if logc is None else logc[o:o + n], int(head[1][r]),
-                                 int(head[2][r]), float(total[r])))
-        o += n
-    return result
+    head, total = d["head"], d["total"]
+    host = [None if t is None else t.cpu().numpy() for t in (d["times"], d["meta"], d["logc"])]
+    return [redo if redo is not None else NoteArrays(*mine, int(head[1][r]), int(head[2][r]), float(total[r]))
+            for r, mine, redo in _recordings(d, *host)]
 
 
 @dataclasses.dataclass
@@ -345,6 +347,29 @@ class DeviceNotes:
             self.counts = self.count.cpu().numpy().astype(np.int64)
         return self.counts
 
+    def entries(self, recording=None):
+        """(rec, rows): per entry the recording and the table row, int64 on the notes' device, recording after recording;
+        `recording=r`: the entries of that recording alone."""
+        import torch
+        dev, R, total = self.meta.device, len(self), int(self.host_counts().sum())
+        count = self.count.to(torch.int64)
+        rec = torch.repeat_interleave(torch.arange(R, device=dev), count, output_size=total)
+        begin = torch.cumsum(count, 0) - count
+        rows = self.first.to(torch.int64)[rec] + (torch.arange(total, device=dev) - begin[rec])
+        if recording is not None:
+            keep = rec == int(recording)
+            rec, rows = rec[keep], rows[keep]
+        return rec, rows
+
+    @classmethod
+    def _undecoded(cls, times, meta, counts, total_time) -> "DeviceNotes":
+        """Tables that were not decoded: `times` and `meta` on their device, `counts` the host's rows per recording, laid end
+        to end; invalid, dropped and status are zeros, `total_time` a list of floats."""
+        import torch
+        dev, zeros = meta.device, lambda: torch.zeros(len(counts), dtype=torch.int32, device=meta.device)
+        return cls(times, meta, torch.from_numpy(np.cumsum(counts) - counts).to(dev), torch.from_numpy(counts).to(dev), zeros(),
+                   zeros(), torch.tensor(total_time, dtype=torch.float64, device=dev), zeros(), counts)
+
     @classmethod
     def from_arrays(cls, tables, device) -> "DeviceNotes":
         """`tables`: one (times [n, 2], meta [n, 4]) pair of numpy arrays (or a `NoteArrays`) per recording, uploaded."""
@@ -353,25 +378,16 @@ class DeviceNotes:
         counts = np.asarray([len(m) for _, m in pairs], np.int64)
         times = np.concatenate([np.asarray(t, np.float64).reshape(-1, 2) for t, _ in pairs] or [np.zeros((0, 2))])
         meta = np.concatenate([np.asarray(m, np.int32).reshape(-1, 4) for _, m in pairs] or [np.zeros((0, 4), np.int32)])
-        R = len(pairs)
-        zeros = torch.zeros(R, dtype=torch.int32, device=device)
-        total = [float(t.total_time) if hasattr(t, "total_time") else 0.0 for t in tables]
-        return cls(torch.from_numpy(times).to(device), torch.from_numpy(meta).to(device),
-                   torch.from_numpy(np.cumsum(counts) - counts).to(device), torch.from_numpy(counts).to(device), zeros,
-                   zeros.clone(), torch.tensor(total, dtype=torch.float64, device=device), zeros.clone(), counts)
+        return cls._undecoded(torch.from_numpy(times).to(device), torch.from_numpy(meta).to(device), counts,
+                              [float(t.total_time) if hasattr(t, "total_time") else 0.0 for t in tables])
 
     @classmethod
     def from_note_table(cls, times, meta=None) -> "DeviceNotes":
         """One recording: a track's reference, `mrmt3.labels.NoteTable` tensors already on a device (`times`, `meta`, or an
         object that has both).  No copy."""
-        import torch
         if meta is None:
             times, meta = times.times, times.meta
-        n, dev = meta.shape[0], meta.device
-        zeros = torch.zeros(1, dtype=torch.int32, device=dev)
-        return cls(times, meta, torch.zeros(1, dtype=torch.int64, device=dev), torch.full((1,), n, dtype=torch.int64, device=dev),
-                   zeros, zeros.clone(), torch.zeros(1, dtype=torch.float64, device=dev), zeros.clone(),
-                   np.asarray([n], np.int64))
+        return cls._undecoded(times, meta, np.asarray([meta.shape[0]], np.int64), [0.0])
 
     @classmethod
     def concat(cls, parts) -> "DeviceNotes":
@@ -395,18 +411,13 @@ def decode_notes_device(ids_dev, frame_times, codec, recordings=None, eos_token_
     times, meta, total = d["times"], d["meta"], d["total"].copy()
     invalid, dropped = head[1].copy(), head[2].copy()
     if (head[3] != 0).any():
-        tparts, mparts, o = [], [], 0
-        for r in range(d["n_rec"]):
-            n = int(counts[r])
-            if head[3][r] != 0:
-                redo = d["redo"](r)
-                tparts.append(torch.from_numpy(redo.times).to(dev))
-                mparts.append(torch.from_numpy(redo.meta).to(dev))
+        tparts, mparts = [], []
+        for r, (t, m), redo in _recordings(d, times, meta):
+            if redo is not None:
+                t, m = torch.from_numpy(redo.times).to(dev), torch.from_numpy(redo.meta).to(dev)
                 counts[r], invalid[r], dropped[r], total[r] = len(redo), redo.invalid, redo.dropped, redo.total_time
-            else:
-                tparts.append(times[o:o + n])
-                mparts.append(meta[o:o + n])
-            o += n
+            tparts.append(t)
+            mparts.append(m)
         times, meta = torch.cat(tparts), torch.cat(mparts)
     up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dev).to(dt)
     return DeviceNotes(times, meta, up(np.cumsum(counts) - counts, torch.int64), up(counts, torch.int64),

@@ -1,7 +1,8 @@
 """Note-level scores from device-resident note tables: the pitch tables, the problem lists and the host
 restatement of `mrmt3_note_match_fwd` (include/mrmt3_hip.h), and `score_tables`, which reproduces `evaluate.py`'s numbers;
-frame-level counts, piano rolls and instrument detection: the two host restatements of `mrmt3_note_frames_fwd`,
-`pianoroll`, and the `frames` / `instruments` options of `score_tables`.
+frame-level counts, piano rolls and instrument detection: the host restatement of `mrmt3_note_frames_fwd`,
+`pianoroll`, and the `frames` / `instruments` options of `score_tables`.  Both paths go from entry keys to lists in `_lists`
+and bring their small tensors home in `_home`.
 
 The scores are BY DEFINITION those of `evaluate.compute_transcription_metrics` and `evaluate.mt3_program_aware_note_scores`
 (the mir_eval restatement in `contrib.transcription_metrics`).  Precision, recall and F1 depend only on the SIZE of a maximum
@@ -15,6 +16,7 @@ kernel and runs without a GPU; tests hold it to `tm.match_notes`.
 from __future__ import annotations
 
 import dataclasses
+import functools
 from typing import List
 
 import numpy as np
@@ -78,6 +80,12 @@ def _ordered(valid, key, idx) -> bool:
     return bool(((k[:-1] < k[1:]) | ((k[:-1] == k[1:]) & (i[:-1] < i[1:]))).all())
 
 
+def _clamped(first, p, L):
+    """The list range of problem p as the kernels clamp it (csrc/notetab.h: note_range): a in [0, L], b in [a, L]."""
+    a = min(max(int(first[p]), 0), L)
+    return a, min(max(int(first[p + 1]), a), L)
+
+
 def match_notes_host(ref_times, ref_meta, est_times, est_meta, ref_idx, ref_first, est_idx, est_first, prob_flags, pitch_lo,
                      pitch_hi, onset_tol=ONSET_TOLERANCE, offset_ratio=OFFSET_RATIO, offset_min_tol=OFFSET_MIN_TOLERANCE):
     """The contract of `mrmt3_note_match_fwd` on the host, the arguments of `lib.note_match` as numpy arrays ->
@@ -92,12 +100,8 @@ def match_notes_host(ref_times, ref_meta, est_times, est_meta, ref_idx, ref_firs
     assert len(ref_first) == n_prob + 1 and len(est_first) == n_prob + 1
     matched, status = np.zeros(n_prob, np.int32), np.zeros(n_prob, np.int32)
     match = np.full(Le, -1, np.int32)
-    clamp = lambda v, lo, hi: min(max(int(v), lo), hi)
     for p in range(n_prob):
-        r0 = clamp(ref_first[p], 0, Lr)
-        r1 = clamp(ref_first[p + 1], r0, Lr)
-        e0 = clamp(est_first[p], 0, Le)
-        e1 = clamp(est_first[p + 1], e0, Le)
+        (r0, r1), (e0, e1) = _clamped(ref_first, p, Lr), _clamped(est_first, p, Le)
         offsets, table = bool(prob_flags[p] & 1), int(prob_flags[p]) >> 8
         r_valid, r_key = _keys(ref_times, ref_idx[r0:r1])
         e_valid, e_key = _keys(est_times, est_idx[e0:e1])
@@ -174,11 +178,6 @@ FRAMES_PER_SECOND = tm.FRAMES_PER_SECOND
 FRAME_LIMIT = 2147483648.0
 
 
-def _clamped(first, p, L):
-    a = min(max(int(first[p]), 0), L)
-    return a, min(max(int(first[p + 1]), a), L)
-
-
 def frame_counts_host(ref_times, ref_meta, est_times, est_meta, ref_idx, ref_first, est_idx, est_first, fps=FRAMES_PER_SECOND,
                       n_frames=1, with_roll=False):
     """The contract of `mrmt3_note_frames_fwd` on the host, the arguments of `lib.note_frames` as numpy arrays ->
@@ -218,63 +217,6 @@ def frame_counts_host(ref_times, ref_meta, est_times, est_meta, ref_idx, ref_fir
         if with_roll:
             roll[p] = np.packbits(dense, axis=-1, bitorder="little").reshape(2, 128, W, 4).view("<u4")[..., 0]
     return (counts, skipped, clipped, roll) if with_roll else (counts, skipped, clipped)
-
-
-def _union(intervals):
-    """Disjoint sorted [a, b) intervals with the same union."""
-    out = []
-    for a, b in sorted(intervals):
-        if out and a <= out[-1][1]:
-            out[-1][1] = max(out[-1][1], b)
-        else:
-            out.append([a, b])
-    return out
-
-
-def frame_counts_intervals(ref_times, ref_meta, est_times, est_meta, ref_idx, ref_first, est_idx, est_first,
-                           fps=FRAMES_PER_SECOND, n_frames=1):
-    """`frame_counts_host` without a roll, for the tests: per pitch the length of the union of each side's [a, b) intervals
-    and of the intersection of the two unions, in Python floats and ints -> (counts, skipped, clipped)."""
-    import math
-    n_prob, n_frames, fps = len(ref_first) - 1, int(n_frames), float(fps)
-    counts = np.zeros((n_prob, 3), np.int64)
-    skipped, clipped = np.zeros((n_prob, 2), np.int32), np.zeros((n_prob, 2), np.int32)
-    sides = ((np.asarray(ref_times, np.float64).reshape(-1, 2).tolist(), np.asarray(ref_meta).reshape(-1, 4)[:, 0].tolist(),
-              ref_idx, ref_first),
-             (np.asarray(est_times, np.float64).reshape(-1, 2).tolist(), np.asarray(est_meta).reshape(-1, 4)[:, 0].tolist(),
-              est_idx, est_first))
-    for p in range(n_prob):
-        rows = [dict(), dict()]                      # per side: pitch -> intervals
-        for s, (times, pitches, idx, first) in enumerate(sides):
-            lo, hi = _clamped(first, p, max(int(first[n_prob]), 0))
-            for note in (int(i) for i in idx[lo:hi]):
-                if note < 0 or note >= len(times):
-                    skipped[p, s] += 1
-                    continue
-                (start, end), pitch = times[note], pitches[note]
-                ps, pe = start * fps, end * fps
-                if start != start or end != end or pitch < 0 or pitch > 127 or not ps < FRAME_LIMIT or not pe < FRAME_LIMIT:
-                    skipped[p, s] += 1
-                    continue
-                a = 0 if ps < 0 else math.floor(ps)
-                b = max(a + 1, 0 if pe < 0 else math.ceil(pe))
-                if b > n_frames:
-                    clipped[p, s] += 1
-                    b = n_frames
-                if a < b:
-                    rows[s].setdefault(pitch, []).append((a, b))
-        for s in (0, 1):
-            rows[s] = {q: _union(iv) for q, iv in rows[s].items()}
-            counts[p, 1 + s] = sum(b - a for iv in rows[s].values() for a, b in iv)
-        for q in set(rows[0]) & set(rows[1]):
-            x, y, i, j = rows[0][q], rows[1][q], 0, 0
-            while i < len(x) and j < len(y):
-                counts[p, 0] += max(0, min(x[i][1], y[j][1]) - max(x[i][0], y[j][0]))
-                if x[i][1] <= y[j][1]:
-                    i += 1
-                else:
-                    j += 1
-    return counts, skipped, clipped
 
 
 @dataclasses.dataclass
@@ -318,19 +260,57 @@ class Problems:
     families: tuple = FAMILIES                    # the families built
     max_end: float = 0.0
 
+    @functools.cached_property
+    def by_pair(self) -> list:
+        """Per recording pair {family: [its problems, ascending]}, built once."""
+        index = [dict() for _ in self.errors]
+        for p, (r, f) in enumerate(zip(self.pair, self.family)):
+            index[int(r)].setdefault(int(f), []).append(p)
+        return index
+
 
 _NO_ROW = 1 << 40
+
+
+def _home(*tensors):
+    """Several small tensors of one device (int32, int64, f64) to the host in ONE copy: concatenated as int64 (an f64's
+    bits ride as they are), copied, and cut up again -> one numpy array per tensor, with its dtype and shape."""
+    import torch
+    flat = [t.reshape(-1).view(torch.int64) if t.dtype == torch.float64 else t.reshape(-1).to(torch.int64) for t in tensors]
+    data, out, o = torch.cat(flat).cpu().numpy(), [], 0
+    for t in tensors:
+        piece = data[o:o + t.numel()]
+        piece = piece.view(np.float64) if t.dtype == torch.float64 else piece.astype(np.int32 if t.dtype == torch.int32 else np.int64)
+        out.append(piece.reshape(tuple(t.shape)))
+        o += t.numel()
+    return out
+
+
+def _lists(sides, forced):
+    """Entry keys -> problems and their lists.  `sides`: per side (key, rows, pre, reduce): the int64 key and table row of
+    every entry, `pre` None or a permutation of the entries that a problem's entries keep among themselves (None: the
+    order they come in), `reduce` [(values, op, fill)], per-problem reductions of per-entry values; `forced`: keys that are
+    a problem even without an entry.  -> (uniq, per side (n, idx int32, first int32, the reductions)): the sorted problem
+    keys, and per side the list lengths, the lists end to end in problem order and where each begins."""
+    import torch
+    uniq = torch.unique(torch.cat([key for key, _, _, _ in sides] + [forced]))
+    P, out = int(uniq.numel()), []
+    for key, rows, pre, reduce in sides:
+        pid = torch.searchsorted(uniq, key)
+        order = torch.sort(pid, stable=True).indices if pre is None else pre[torch.sort(pid[pre], stable=True).indices]
+        n = torch.bincount(pid, minlength=P)
+        first = torch.cat([n.new_zeros(1), torch.cumsum(n, 0)]).to(torch.int32)
+        reduced = [torch.full((P,), fill, dtype=torch.int64, device=key.device).scatter_reduce_(0, pid, values, op)
+                   for values, op, fill in reduce]
+        out.append((n, rows[order].to(torch.int32), first, reduced))
+    return uniq, out
 
 
 def _side(notes, families):
     """Per entry of one side: the table row, the recording, the problem key; and the [R, 4] validity counts."""
     import torch
-    counts = notes.host_counts()
-    dev, R, total = notes.meta.device, len(counts), int(counts.sum())
-    count = notes.count.to(torch.int64)
-    rec = torch.repeat_interleave(torch.arange(R, device=dev), count, output_size=total)
-    begin = torch.cumsum(count, 0) - count
-    rows = notes.first.to(torch.int64)[rec] + (torch.arange(total, device=dev) - begin[rec])
+    rec, rows = notes.entries()
+    dev, R, total = notes.meta.device, len(notes), int(rows.numel())
     start, end = notes.times[rows, 0], notes.times[rows, 1]
     pitch, prog = notes.meta[rows, 0].to(torch.int64), notes.meta[rows, 2].to(torch.int64)
     drum, prog = (prog >> 8) & 1, prog & 0xff
@@ -379,25 +359,16 @@ def build_problems(ref, est, families=FAMILIES) -> Problems:
     e_rows, e_key, e_flags, e_end = _side(est, families)
     # the agnostic problems exist for every pair, the group problems where a key is present
     forced = [(r * len(FAMILIES) + FAMILIES.index(f)) << 9 for r in range(R) for f in families if FAMILIES.index(f) < 2]
-    uniq = torch.unique(torch.cat([r_key, e_key, torch.tensor(forced, dtype=torch.int64, device=dev)]))
-    P = int(uniq.numel())
-    out, counts, firsts = [], [], []
-    for rows, key, notes in ((r_rows, r_key, ref), (e_rows, e_key, est)):
-        pid = torch.searchsorted(uniq, key)
-        by_onset = torch.sort(notes.times[rows, 0], stable=True).indices     # (entries of a problem are in row order)
-        order = by_onset[torch.sort(pid[by_onset], stable=True).indices]
-        n = torch.bincount(pid, minlength=P)
-        low = torch.full((P,), _NO_ROW, dtype=torch.int64, device=dev).scatter_reduce_(0, pid, rows, "amin")
-        out.append((rows[order].to(torch.int32), torch.cat([n.new_zeros(1), torch.cumsum(n, 0)]).to(torch.int32)))
-        counts.append(n)
-        firsts.append(low)
+    # (entries of a problem are in row order: a stable sort by onset leaves onset, then row)
+    uniq, ((n_r, r_idx, r_first, (r_low,)), (n_e, e_idx, e_first, (e_low,))) = _lists(
+        [(key, rows, torch.sort(notes.times[rows, 0], stable=True).indices, [(rows, "amin", _NO_ROW)])
+         for rows, key, notes in ((r_rows, r_key, ref), (e_rows, e_key, est))],
+        torch.tensor(forced, dtype=torch.int64, device=dev))
     family_dev = (uniq >> 9) % len(FAMILIES)
     flags = ((family_dev == 0).to(torch.int32) | (torch.where(family_dev < 2, TABLE_MIDI_AS_HZ, TABLE_HZ) << 8)).to(torch.int32)
-    home = torch.cat([uniq, counts[0], counts[1], firsts[0], firsts[1], r_flags.reshape(-1), e_flags.reshape(-1),
-                      torch.maximum(r_end, e_end).reshape(1).view(torch.int64)]).cpu().numpy()
-    home, max_end = home[:-1], float(home[-1:].view(np.float64)[0])       # (the f64's bits rode in the int64 tensor)
-    uniq_h, n_ref, n_est, first_ref, first_est = (home[i * P:(i + 1) * P] for i in range(5))
-    bad_ref, bad_est = home[5 * P:5 * P + 4 * R].reshape(R, 4), home[5 * P + 4 * R:].reshape(R, 4)
+    uniq_h, n_ref, n_est, first_ref, first_est, bad_ref, bad_est, max_end = _home(
+        uniq, n_r, n_e, r_low, e_low, r_flags, e_flags, torch.maximum(r_end, e_end).reshape(1))
+    max_end = float(max_end[0])
     family = (uniq_h >> 9) % len(FAMILIES)
     keys = [None if f < 2 else (int(k & 0xff), bool(k >> 8 & 1)) for f, k in zip(family, uniq_h & 0x1ff)]
     piano_only = all(FAMILIES.index(f) < 2 for f in families)
@@ -411,7 +382,7 @@ def build_problems(ref, est, families=FAMILIES) -> Problems:
             if message is None and short:
                 message = f"all {name} interval durations must be strictly positive"
         errors.append(None if message is None else ValueError(message))
-    return Problems(out[0][0], out[0][1], out[1][0], out[1][1], flags, (uniq_h >> 9) // len(FAMILIES), family, keys,
+    return Problems(r_idx, r_first, e_idx, e_first, flags, (uniq_h >> 9) // len(FAMILIES), family, keys,
                     n_ref, n_est, first_ref, first_est, errors, families, max_end)
 
 
@@ -424,13 +395,9 @@ def assemble_scores(problems: Problems, matched, programs_ref=None, programs_est
     (None: the groups in order of first appearance in the table; the same unless an instrument has no notes).
     `overlaps`: {problem: average overlap ratio} for the agnostic problems, or None: the overlap keys are absent."""
     import evaluate
-    R = len(problems.errors)
-    by_pair = [dict() for _ in range(R)]
-    for p, (r, f) in enumerate(zip(problems.pair, problems.family)):
-        by_pair[int(r)].setdefault(int(f), []).append(p)
     results = []
-    for r in range(R):
-        mine, res = by_pair[r], {}
+    for r, mine in enumerate(problems.by_pair):
+        res = {}
         scores = lambda p: tm.scores_from_counts(int(matched[p]), int(problems.n_ref[p]), int(problems.n_est[p]))
         agnostic = {}
         for f in (0, 1):
@@ -496,12 +463,11 @@ def add_frame_scores(results, problems: Problems, counts) -> None:
     for r, res in enumerate(results):
         if not isinstance(res, dict):
             continue
-        mine = [p for p in range(len(problems.pair)) if problems.pair[p] == r]
         on = None
         grouped = {}
         for name in problems.families:
             f = FAMILIES.index(name)
-            at = [p for p in mine if problems.family[p] == f]
+            at = problems.by_pair[r].get(f, [])
             if name == "on":
                 on = tuple(int(v) for v in counts[at[0]])
             elif f >= 2:
@@ -516,7 +482,7 @@ def add_instrument_scores(results, problems: Problems) -> None:
     for r, res in enumerate(results):
         if not isinstance(res, dict):
             continue
-        mine = [p for p in range(len(problems.pair)) if problems.pair[p] == r and problems.family[p] == f]
+        mine = problems.by_pair[r].get(f, [])
         res.update(evaluate.instrument_result([problems.key[p][0] for p in mine if problems.n_ref[p] > 0],
                                               [problems.key[p][0] for p in mine if problems.n_est[p] > 0]))
 
@@ -540,15 +506,8 @@ def pianoroll(notes, fps=FRAMES_PER_SECOND, recording=None, by=None):
     R = len(notes)
     if recording is not None and not 0 <= int(recording) < R:
         raise ValueError("recording %r of %d" % (recording, R))
-    counts = notes.host_counts()
-    dev, total = notes.meta.device, int(counts.sum())
-    count = notes.count.to(torch.int64)
-    rec = torch.repeat_interleave(torch.arange(R, device=dev), count, output_size=total)
-    begin = torch.cumsum(count, 0) - count
-    rows = notes.first.to(torch.int64)[rec] + (torch.arange(total, device=dev) - begin[rec])
-    if recording is not None:
-        keep = rec == int(recording)
-        rec, rows = rec[keep], rows[keep]
+    dev = notes.meta.device
+    rec, rows = notes.entries(recording)
     start, end, pitch = notes.times[rows, 0], notes.times[rows, 1], notes.meta[rows, 0]
     ps, pe = start * fps, end * fps                                   # (one f64 multiplication each, as in the kernel)
     sounds = ~torch.isnan(start) & ~torch.isnan(end) & (pitch >= 0) & (pitch <= 127) & (ps < FRAME_LIMIT) & (pe < FRAME_LIMIT)
@@ -557,25 +516,19 @@ def pianoroll(notes, fps=FRAMES_PER_SECOND, recording=None, by=None):
     key = (rec << 9) | _program_key(notes, rows, by)
     wanted = range(R) if recording is None else [int(recording)]
     forced = torch.tensor([r << 9 for r in wanted] if by is None else [], dtype=torch.int64, device=dev)
-    uniq = torch.unique(torch.cat([key, forced]))
+    uniq, ((_, idx, first, (last,)),) = _lists([(key, rows, None, [(b, "amax", 0)])], forced)
     P = int(uniq.numel())
     if P == 0:                                       # by="program" without a single note
         return [dict() for _ in wanted] if recording is None else dict()
-    pid = torch.searchsorted(uniq, key)
-    n = torch.bincount(pid, minlength=P)
-    order = torch.sort(pid, stable=True).indices
-    last = torch.zeros(P, dtype=torch.int64, device=dev).scatter_reduce_(0, pid, b, "amax")
-    home = torch.cat([uniq, last]).cpu().numpy()
-    uniq_h, last_h = home[:P], home[P:]
+    uniq_h, last_h = _home(uniq, last)
     frames = {int(r): 0 for r in wanted}
     for k, v in zip(uniq_h >> 9, last_h):
         frames[int(k)] = max(frames[int(k)], int(v))
     n_frames = max(1, max(frames.values()))
     if n_frames > lib.FRAMES_MAX:
         raise ValueError("a piano roll of %d frames is beyond the kernel's 2^31 - 64" % n_frames)
-    first = torch.cat([n.new_zeros(1), torch.cumsum(n, 0)]).to(torch.int32)
     none = torch.zeros(P + 1, dtype=torch.int32, device=dev)
-    _, _, clipped, roll = lib.note_frames(notes.times, notes.meta, notes.times, notes.meta, rows[order].to(torch.int32), first,
+    _, _, clipped, roll = lib.note_frames(notes.times, notes.meta, notes.times, notes.meta, idx, first,
                                           none[:0], none, fps, n_frames, with_roll=True)
     bits = (roll[:, 0].unsqueeze(-1) >> torch.arange(32, device=dev, dtype=torch.int32)) & 1      # [P, 128, W, 32]
     dense = bits.reshape(P, 128, -1).transpose(1, 2).to(torch.bool)                                # [P, W * 32, 128]
@@ -629,22 +582,19 @@ def score_tables(ref, est, with_overlap=False, families=FAMILIES, errors="raise"
     if frames:
         counts, _, clipped = lib.note_frames(ref.times, ref.meta, est.times, est.meta, problems.ref_idx, problems.ref_first,
                                              problems.est_idx, problems.est_first, fps, frames_for(problems.max_end, fps))
-        P = matched.numel()
-        home = torch.cat([matched.to(torch.int64), status.to(torch.int64), counts.reshape(-1),
-                          clipped.to(torch.int64).reshape(-1)]).cpu().numpy()
-        head, frame_counts, clipped = home[:2 * P].reshape(2, P), home[2 * P:5 * P].reshape(P, 3), home[5 * P:].reshape(P, 2)
+        matched, status, frame_counts, clipped = _home(matched, status, counts, clipped)
         # (a pair the host scorer refuses may hold a note that starts after the last end: its problems are not scored)
         scored = np.asarray([problems.errors[int(r)] is None for r in problems.pair], bool)
         if clipped[scored].any():
             raise RuntimeError("note_frames: clipped %r although n_frames came from the same tables" % clipped.tolist())
     else:
-        head = torch.stack([matched, status]).cpu().numpy()
-    if head[1].any():
-        raise RuntimeError("note_match: status %r (the lists of build_problems are in order: a NaN onset?)" % head[1].tolist())
+        matched, status = _home(matched, status)
+    if status.any():
+        raise RuntimeError("note_match: status %r (the lists of build_problems are in order: a NaN onset?)" % status.tolist())
     overlaps = matchings = None
     if with_overlap:
         overlaps, matchings = _overlaps(problems, ref, est, match)
-    out = assemble_scores(problems, head[0], programs[0], programs[1], overlaps)
+    out = assemble_scores(problems, matched, programs[0], programs[1], overlaps)
     if frames:
         add_frame_scores(out, problems, frame_counts)
     if instruments:

@@ -151,3 +151,62 @@ def dense_roll(notes, fps, n_frames):
         b = max(a + 1, math.ceil(end * fps) if end * fps > -1e18 else 0)
         roll[min(a, n_frames):min(b, n_frames), pitch] = True
     return roll
+
+
+def _union(intervals):
+    """Disjoint sorted [a, b) intervals with the same union."""
+    out = []
+    for a, b in sorted(intervals):
+        if out and a <= out[-1][1]:
+            out[-1][1] = max(out[-1][1], b)
+        else:
+            out.append([a, b])
+    return out
+
+
+def frame_counts_intervals(ref_times, ref_meta, est_times, est_meta, ref_idx, ref_first, est_idx, est_first,
+                           fps=62.5, n_frames=1):
+    """`scoring.frame_counts_host` without a roll, a second, independent form: per pitch the length of the union of each
+    side's [a, b) intervals and of the intersection of the two unions, in Python floats and ints -> (counts, skipped,
+    clipped).  Only the range clamp is the product's."""
+    import math
+    from mrmt3.scoring import FRAME_LIMIT, _clamped
+    n_prob, n_frames, fps = len(ref_first) - 1, int(n_frames), float(fps)
+    counts = np.zeros((n_prob, 3), np.int64)
+    skipped, clipped = np.zeros((n_prob, 2), np.int32), np.zeros((n_prob, 2), np.int32)
+    sides = ((np.asarray(ref_times, np.float64).reshape(-1, 2).tolist(), np.asarray(ref_meta).reshape(-1, 4)[:, 0].tolist(),
+              ref_idx, ref_first),
+             (np.asarray(est_times, np.float64).reshape(-1, 2).tolist(), np.asarray(est_meta).reshape(-1, 4)[:, 0].tolist(),
+              est_idx, est_first))
+    for p in range(n_prob):
+        rows = [dict(), dict()]                      # per side: pitch -> intervals
+        for s, (times, pitches, idx, first) in enumerate(sides):
+            lo, hi = _clamped(first, p, max(int(first[n_prob]), 0))
+            for note in (int(i) for i in idx[lo:hi]):
+                if note < 0 or note >= len(times):
+                    skipped[p, s] += 1
+                    continue
+                (start, end), pitch = times[note], pitches[note]
+                ps, pe = start * fps, end * fps
+                if start != start or end != end or pitch < 0 or pitch > 127 or not ps < FRAME_LIMIT or not pe < FRAME_LIMIT:
+                    skipped[p, s] += 1
+                    continue
+                a = 0 if ps < 0 else math.floor(ps)
+                b = max(a + 1, 0 if pe < 0 else math.ceil(pe))
+                if b > n_frames:
+                    clipped[p, s] += 1
+                    b = n_frames
+                if a < b:
+                    rows[s].setdefault(pitch, []).append((a, b))
+        for s in (0, 1):
+            rows[s] = {q: _union(iv) for q, iv in rows[s].items()}
+            counts[p, 1 + s] = sum(b - a for iv in rows[s].values() for a, b in iv)
+        for q in set(rows[0]) & set(rows[1]):
+            x, y, i, j = rows[0][q], rows[1][q], 0, 0
+            while i < len(x) and j < len(y):
+                counts[p, 0] += max(0, min(x[i][1], y[j][1]) - max(x[i][0], y[j][0]))
+                if x[i][1] <= y[j][1]:
+                    i += 1
+                else:
+                    j += 1
+    return counts, skipped, clipped

@@ -20,7 +20,7 @@ TILE = 2048
 def _both(packed, fps, n_frames):
     from mrmt3 import scoring
     dense = scoring.frame_counts_host(*packed.arrays(), fps, n_frames, with_roll=True)
-    union = scoring.frame_counts_intervals(*packed.arrays(), fps, n_frames)
+    union = F.frame_counts_intervals(*packed.arrays(), fps, n_frames)
     for a, b in zip(dense[:3], union):
         assert a.dtype == b.dtype and (a == b).all(), np.argwhere(a != b)[:5]
     return dense

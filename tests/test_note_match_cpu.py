@@ -214,6 +214,26 @@ def test_abi_declares_the_matcher_and_refuses_bad_arguments():
     assert lib.note_match_launches() == before
 
 
+def test_malformed_arguments_are_value_errors():
+    """The wrapper refuses what `note_frames` refuses, by the same check and before it asks for device tensors."""
+    import torch
+    times, meta = torch.zeros(4, 2, dtype=torch.float64), torch.zeros(4, 4, dtype=torch.int32)
+    idx, first = torch.arange(4, dtype=torch.int32), torch.tensor([0, 4], dtype=torch.int32)
+    lo, hi = (torch.from_numpy(t) for t in scoring.pitch_tables())
+    good = dict(ref_times=times, ref_meta=meta, est_times=times, est_meta=meta, ref_idx=idx, ref_first=first, est_idx=idx,
+                est_first=first, prob_flags=torch.zeros(1, dtype=torch.int32), pitch_lo=lo, pitch_hi=hi)
+    before = lib.note_match_launches()
+    for change in (dict(ref_times=torch.zeros(4, 4, dtype=torch.float64)[:, ::2]), dict(est_meta=meta[:, :3]),
+                   dict(ref_idx=idx.long()), dict(est_first=first[:1]), dict(ref_first=first[:1], est_first=first[:1]),
+                   dict(prob_flags=torch.zeros(2, dtype=torch.int32)), dict(pitch_lo=lo[:, :127].contiguous()),
+                   dict(pitch_hi=hi[:1])):
+        with pytest.raises(ValueError, match="note_match"):
+            lib.note_match(**{**good, **change})
+    with pytest.raises(RuntimeError):                # host tensors: no CPU fallback of the kernel
+        lib.note_match(**good)
+    assert lib.note_match_launches() == before
+
+
 def test_val_notes_options():
     import train
     stem = dict(val_root="somewhere")

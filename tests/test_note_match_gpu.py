@@ -152,6 +152,27 @@ def test_unordered_lists_and_edge_less_entries(dev, tables):
     assert matched.tolist() == [0] and (match == -1).all()
 
 
+def test_hostile_first_arrays_give_the_hosts_clamp(dev, tables):
+    """`first` entries below 0, above the list length and decreasing: the ranges are those of the contract's clamp
+    (csrc/notetab.h: note_range; `scoring._clamped`), no two problems share an entry, and matched, match and status are the
+    host's with ==.  Three problems, at most 8 entries a list."""
+    from mrmt3 import scoring
+    cases = [M.chain(3, True, True, False)[0], M.chain(4, False, True, False)[0], M.chain(3, True, False, True)[0]]
+    packed = M.pack(cases)
+    (_, r1, _, Lr), (_, _, e2, Le) = packed.ref_first.tolist(), packed.est_first.tolist()
+    packed.ref_first[:] = [-3, r1, Lr + 100, Lr]             # [0, r1), [r1, Lr), nothing
+    packed.est_first[:] = [Le + 50, -5, e2, Le]              # nothing, [0, e2), [e2, Le)
+    for idx, times, (a, b) in ((packed.ref_idx, packed.ref_times, (r1, Lr)), (packed.est_idx, packed.est_times, (0, e2))):
+        part = idx[a:b].copy()                               # the lists of two cases as one, in onset order
+        idx[a:b] = part[np.lexsort((part, times[part, 0]))]
+    assert max(Lr - r1, e2) <= 8
+    want = scoring.match_notes_host(*packed.arrays(), *tables, onset_tol=M.CHAIN_TOL)
+    assert want[2].tolist() == [0, 0, 0] and want[0].tolist()[0] == want[0].tolist()[2] == 0 and want[0][1] >= 4
+    got = _launch(packed, tables, dev, onset_tol=M.CHAIN_TOL)
+    for name, a, b in zip(("matched", "match", "status"), got, want):
+        assert (a == b).all(), (name, a.tolist(), b.tolist())
+
+
 def _midi_pairs():
     return [M.synthetic_midi(s) for s in (1, 2, 3)]
 
