@@ -153,12 +153,10 @@ class Engine:
         """lib.add_rmsnorm_bwd with the norm-weight gradient deferred to one batched reduction (flush_norm_dw).
         fp32 path: the kernel's second output (the masked gradient of the sublayer output below) is bf16-only, so it is
         formed from dx1 here — dx1 itself without dropout, one mask-and-copy launch with it."""
-        if self.dt == torch.bfloat16:
-            return lib.add_rmsnorm_bwd(*a, defer=self.norm_dw, **kw)
-        want_dy = kw.pop("want_dy", True)
-        dx1, _ = lib.add_rmsnorm_bwd(*a, defer=self.norm_dw, want_dy=False, **kw)
-        if not want_dy:
-            return dx1, None
+        want_dy, bf16 = kw.pop("want_dy", True), self.dt == torch.bfloat16
+        dx1, dy = lib.add_rmsnorm_bwd(*a, defer=self.norm_dw, want_dy=want_dy and bf16, **kw)
+        if bf16 or not want_dy:
+            return dx1, dy
         p = kw.get("p", 0.0)
         if p <= 0.0:
             return dx1, dx1
@@ -169,13 +167,13 @@ class Engine:
         """add_rmsnorm_fwd(x, y, ...) where y is the pending projection `pend` = (a, W) of the sublayer above (None: the
         stack's first norm, nothing to add): one fused launch when the shape allows, else the product then the row kernel."""
         xn_dtype = xn_dtype or self.dt
-        if pend is None:
-            return lib.add_rmsnorm_fwd(x, None, w_norm, self.eps, xn_dtype, **kw)
-        a, w = pend
-        if ((self.fuse_rows & 1) and self.y_dtype == torch.bfloat16 and xn_dtype == torch.bfloat16 and x.shape[1] == 512 and
-                lib.gemm_rows_ok(a, w)):
-            return lib.gemm_nt_addnorm(a, w, x, w_norm, self.eps, **kw)
-        y = lib.gemm_nt(a, w, out_dtype=self.y_dtype)
+        y = None
+        if pend is not None:
+            a, w = pend
+            if ((self.fuse_rows & 1) and self.y_dtype == torch.bfloat16 and xn_dtype == torch.bfloat16 and x.shape[1] == 512 and
+                    lib.gemm_rows_ok(a, w)):
+                return lib.gemm_nt_addnorm(a, w, x, w_norm, self.eps, **kw)
+            y = lib.gemm_nt(a, w, out_dtype=self.y_dtype)
         return lib.add_rmsnorm_fwd(x, y, w_norm, self.eps, xn_dtype, **kw)
 
     def _proj_norm_bwd(self, a, wt, dres, x1, rstd, w_norm, dw, **kw):
@@ -196,6 +194,88 @@ class Engine:
         dg = lib.gemm_nt(dy, wt)
         return lib.geglu_bwd(h, dg, **kw)
 
+    # ---- sublayer pieces: each stated once; the stacks and the one-layer memory-encoder shortcut are made of them ----------
+    # Dropout site ids always come from the caller: the stack loop draws them (`_sid()`) in a fixed order, the shortcut (which
+    # never drops) passes 0 and draws none — the masks of every later site depend on how many were drawn.
+    def _rng(self, p):
+        """The dropout arguments every site of a step shares (its own stream id is added by the piece)."""
+        return dict(p=p, seed=self.seed, step=self.step_dev)
+
+    def _addnorm(self, x, pend, key, p, s_in, keep, **kw):
+        """The add + norm in front of a sublayer: `pend` (the projection the sublayer above left pending, dropped at site
+        s_in) is added to the residual stream x — in place when nothing is kept for a backward.  Returns (x1, xn, rstd)."""
+        return self._proj_addnorm(x, pend, self.ln(key), stream_y=s_in, x1=None if keep else x, **self._rng(p), **kw)
+
+    def _addnorm_bwd(self, t, a, wname, dx, p, **kw):
+        """Backward of the `_addnorm` of record t through the projection `wname` that read its output (a: the gradient of that
+        projection's output); dx: the residual gradient, updated in place unless `dx1=` says otherwise.  Returns (dx, dy)."""
+        kw.setdefault("dx1", dx)
+        return self._proj_norm_bwd(a, self.WT(wname), dx, t["x1"], t["rstd"], self.ln(t["ln"]), self.ndw(t["ln"]),
+                                   stream_y=t["s_in"], **self._rng(p), **kw)
+
+    def _attn_fwd(self, q, k, v, B, Lq, Lk, causal, pack, sid, p, keep, want_lo):
+        """One attention site: (o, lse, o_lo).  Lk = 0: self-attention, the keys are the query rows.  pack (a lib.PackPlan): the
+        query rows are packed end to end (the keys too when Lk = 0, else dense [B*Lk]) — the varlen kernels."""
+        kw = dict(stream_id=sid, want_lse=keep, want_lo=keep and want_lo, **self._rng(p))
+        if pack is not None:
+            return lib.attn_fwd_varlen(q, k, v, pack, self.H, Lk, causal, **kw)
+        return lib.attn_fwd(q, k, v, B, self.H, Lq, Lk or Lq, causal, **kw)
+
+    def _attn_bwd(self, t, q, k, v, do, dq, dk, dv, B, Lq, Lk, causal, pack, p):
+        """Backward of the `_attn_fwd` whose outputs record t holds, into the caller's dq / dk / dv."""
+        kw = dict(stream_id=t["s_att"], o_lo=t["o_lo"], **self._rng(p))
+        if pack is not None:
+            return lib.attn_bwd_varlen(q, k, v, t["o"], do, t["lse"], dq, dk, dv, pack, self.H, Lk, causal, **kw)
+        return lib.attn_bwd(q, k, v, t["o"], do, t["lse"], dq, dk, dv, B, self.H, Lq, Lk or Lq, causal, **kw)
+
+    def _oproj_bwd(self, dy, o, wname):
+        """Backward of an attention output projection that was left pending into the next add + norm (dy: that norm's masked
+        gradient): the weight gradient, and the gradient of the attention output."""
+        self.wgrad(dy, o, self.flat.GW(wname))
+        return lib.gemm_nt(dy, self.WT(wname))
+
+    def _ff_fwd(self, x, pend, pre, i, key, p, s_in, s_g, keep):
+        """Gated-GELU feed-forward sublayer of layer i of stack `pre`: add + norm, wi and the gate (one launch in bf16: K2 + K7,
+        same bits as the two kernels); wo is left pending.  Returns (x1, the tape record, the pending (g, wo))."""
+        x, xn, rstd = self._addnorm(x, pend, key, p, s_in, keep)
+        wi = self.W(f"{pre}.{i}.wi")
+        if xn.dtype == torch.bfloat16:
+            h, g = lib.gemm_nt_geglu(xn, wi, stream_id=s_g, **self._rng(p))
+        else:
+            h = lib.gemm_nt(xn, wi)
+            g = lib.geglu_fwd(h, stream_id=s_g, **self._rng(p))
+        return x, dict(kind="ff", i=i, ln=key, x1=x, xn=xn, rstd=rstd, h=h, g=g, s_in=s_in, s_g=s_g), (g, self.W(f"{pre}.{i}.wo"))
+
+    def _ff_bwd(self, t, pre, dx, dy, p):
+        """Backward of `_ff_fwd` (dy: the masked gradient of the pending wo projection): (dx, dy) below the sublayer."""
+        wi, wo = f"{pre}.{t['i']}.wi", f"{pre}.{t['i']}.wo"
+        self.wgrad(dy, t["g"], self.flat.GW(wo))
+        dh = self._proj_geglu_bwd(dy, self.WT(wo), t["h"], stream_id=t["s_g"], **self._rng(p))
+        self.wgrad(dh, t["xn"], self.flat.GW(wi))
+        return self._addnorm_bwd(t, dh, wi, dx, p)
+
+    def _final_fwd(self, x, pend, pre, p, s_in, s_out, keep, xn_dtype=None):
+        """The closing norm of stack `pre` (its output dropped at site s_out): (out, the tape record)."""
+        key = f"{pre}.final_layer_norm.weight"
+        x, out, rstd = self._addnorm(x, pend, key, p, s_in, keep, xn_dtype=xn_dtype, stream_out=s_out, out_drop=True)
+        return out, dict(kind="final", ln=key, x1=x, rstd=rstd, s_in=s_in, s_out=s_out)
+
+    def _final_bwd(self, t, d_out, p, want_dy, dx_dtype):
+        """Backward of `_final_fwd`: (dx in `dx_dtype`, dy or None)."""
+        return self._norm_bwd(d_out, None, t["x1"], t["rstd"], self.ln(t["ln"]), self.ndw(t["ln"]), want_dy=want_dy,
+                              stream_y=t["s_in"], stream_out=t["s_out"], out_drop=True, dx1_dtype=dx_dtype, **self._rng(p))
+
+    def _input_fwd(self, a, wname, L, p, s_emb):
+        """Input prologue of the encoder and the memory encoder: projection `wname` of a, + sinusoid, dropout at site s_emb."""
+        src = lib.gemm_nt(a, self.W(wname), out_dtype=self.y_dtype)
+        return lib.addpos_fwd(src, self.pos(a.device), L, stream_id=s_emb, **self._rng(p))
+
+    def _input_bwd(self, dx, a, wname, p, s_emb):
+        """Backward of `_input_fwd`: the projection's weight gradient; returns the masked gradient of its output."""
+        dsrc = lib.dropmask_cast(dx, stream_id=s_emb, out_dtype=self.dt, **self._rng(p))
+        self.wgrad(dsrc, a, self.flat.GW(wname))
+        return dsrc
+
     def flush_norm_dw(self):
         if self.norm_dw is not None:
             self.norm_dw.flush()
@@ -213,9 +293,15 @@ class Engine:
         name tensors of work that never ran — a later flush would accumulate uninitialised memory into the gradients
         (ADVICE r2)."""
         if self.tn_group is not None:
-            self.tn_group._sites.clear()
+            self.tn_group.clear()
         if self.norm_dw is not None:
-            self.norm_dw._queue.clear()
+            self.norm_dw.clear()
+
+    def begin_step(self):
+        """Start of a training step: nothing deferred by an aborted capture / a failed step leaks into this one, and the
+        dropout site ids restart (they are per-step: step_dev salts them)."""
+        self.reset_deferred()
+        self._stream_ctr = 0
 
     def prepare(self, training: bool):
         if self.dt == torch.bfloat16:
@@ -229,74 +315,42 @@ class Engine:
         enc: [B*Le, d] compute-dtype encoder states for cross-attention.  Returns the final-normed
         (and dropped) states [B*L, d] in the compute dtype.  pack (a lib.PackPlan): x is [Tcap, d], rows packed end to end —
         every row-wise kernel runs on the Tcap rows, the attention sites on the varlen kernels (encoder states stay dense)."""
-        f, dt, H, inner, eps = self.flat, self.dt, self.H, self.inner, self.eps
+        inner = self.inner
         keep = tape is not None
+        push = tape.push if keep else (lambda **kw: None)
+        cross = is_decoder and enc is not None
         pend = None          # the projection of the sublayer above, not yet added to the residual stream: (operand, weight)
-        sy = 0
+        sy = 0               # ... and the dropout site of its output
         # cross-attention K | V of every layer in one projection of the encoder output: [B*Le, n_layers * 768]
         kv_all = lib.gemm_nt(enc, self.W(f"{prefix}.ckv_all")) if is_decoder and n_layers > 0 else None
         for i in range(n_layers):
             b = f"{prefix}.block.{i}.layer"
             # -- self attention
-            s_in = sy
-            x, xn, rstd = self._proj_addnorm(x, pend, self.ln(f"{b}.0.layer_norm.weight"), write_x1=True,
-                                             p=p, seed=self.seed, step=self.step_dev, stream_y=s_in, x1=None if keep else x)
+            ln = f"{b}.0.layer_norm.weight"
+            x, xn, rstd = self._addnorm(x, pend, ln, p, sy, keep)
             qkv = lib.gemm_nt(xn, self.W(f"{prefix}.{i}.qkv"))
             s_att = self._sid()
-            if pack is not None:
-                o, lse, o_lo = lib.attn_fwd_varlen(qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:], pack, H, 0,
-                                                   is_decoder, p=p, seed=self.seed, step=self.step_dev, stream_id=s_att,
-                                                   want_lse=keep, want_lo=keep and self.lo_sites == "all")
-            else:
-                o, lse, o_lo = lib.attn_fwd(qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:], B, H, L, L,
-                                            is_decoder, p=p, seed=self.seed, step=self.step_dev, stream_id=s_att,
-                                            want_lse=keep, want_lo=keep and self.lo_sites == "all")
-            pend = (o, self.W(f"{prefix}.{i}.o"))
-            sy = self._sid()
-            if keep:
-                tape.push(kind="self", i=i, x1=x, xn=xn, rstd=rstd, qkv=qkv, o=o, o_lo=o_lo, lse=lse, s_in=s_in,
-                          s_att=s_att)
-            ff = 1
-            if is_decoder and enc is not None:
-                s_in = sy
-                x, xn, rstd = self._proj_addnorm(x, pend, self.ln(f"{b}.1.layer_norm.weight"),
-                                                 p=p, seed=self.seed, step=self.step_dev, stream_y=s_in, x1=None if keep else x)
+            o, lse, o_lo = self._attn_fwd(qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:], B, L, 0, is_decoder,
+                                          pack, s_att, p, keep, self.lo_sites == "all")
+            push(kind="self", i=i, ln=ln, x1=x, xn=xn, rstd=rstd, qkv=qkv, o=o, o_lo=o_lo, lse=lse, s_in=sy, s_att=s_att)
+            pend, sy = (o, self.W(f"{prefix}.{i}.o")), self._sid()
+            if cross:
+                ln = f"{b}.1.layer_norm.weight"
+                x, xn, rstd = self._addnorm(x, pend, ln, p, sy, keep)
                 q = lib.gemm_nt(xn, self.W(f"{prefix}.{i}.cq"))
                 kv = kv_all[:, i * 2 * inner:(i + 1) * 2 * inner]        # this layer's K | V columns (row stride n_layers * 768)
                 s_att = self._sid()
-                if pack is not None:
-                    o, lse, o_lo = lib.attn_fwd_varlen(q, kv[:, :inner], kv[:, inner:], pack, H, Le, False, p=p, seed=self.seed,
-                                                       step=self.step_dev, stream_id=s_att, want_lse=keep, want_lo=keep)
-                else:
-                    o, lse, o_lo = lib.attn_fwd(q, kv[:, :inner], kv[:, inner:], B, H, L, Le, False, p=p, seed=self.seed,
-                                                step=self.step_dev, stream_id=s_att, want_lse=keep, want_lo=keep)
-                pend = (o, self.W(f"{prefix}.{i}.co"))
-                sy = self._sid()
-                if keep:
-                    tape.push(kind="cross", i=i, x1=x, xn=xn, rstd=rstd, q=q, kv=kv, o=o, o_lo=o_lo, lse=lse,
-                              s_in=s_in, s_att=s_att)
-                ff = 2
+                o, lse, o_lo = self._attn_fwd(q, kv[:, :inner], kv[:, inner:], B, L, Le, False, pack, s_att, p, keep, True)
+                push(kind="cross", i=i, ln=ln, x1=x, xn=xn, rstd=rstd, q=q, kv=kv, o=o, o_lo=o_lo, lse=lse, s_in=sy, s_att=s_att)
+                pend, sy = (o, self.W(f"{prefix}.{i}.co")), self._sid()
             # -- gated-GELU feed forward
-            s_in = sy
-            x, xn, rstd = self._proj_addnorm(x, pend, self.ln(f"{b}.{ff}.layer_norm.weight"),
-                                             p=p, seed=self.seed, step=self.step_dev, stream_y=s_in, x1=None if keep else x)
-            s_g = self._sid()
-            if xn.dtype == torch.bfloat16:         # K2 + K7 in one launch (same bits as the two kernels)
-                h, g = lib.gemm_nt_geglu(xn, self.W(f"{prefix}.{i}.wi"), p=p, seed=self.seed, step=self.step_dev, stream_id=s_g)
-            else:
-                h = lib.gemm_nt(xn, self.W(f"{prefix}.{i}.wi"))
-                g = lib.geglu_fwd(h, p=p, seed=self.seed, step=self.step_dev, stream_id=s_g)
-            pend = (g, self.W(f"{prefix}.{i}.wo"))
+            ln = f"{b}.{2 if cross else 1}.layer_norm.weight"
+            x, rec, pend = self._ff_fwd(x, pend, prefix, i, ln, p, sy, self._sid(), keep)
+            push(**rec)
             sy = self._sid()
-            if keep:
-                tape.push(kind="ff", i=i, ff=ff, x1=x, xn=xn, rstd=rstd, h=h, g=g, s_in=s_in, s_g=s_g)
-        s_out = self._sid()
-        x, out, rstd = self._proj_addnorm(x, pend, self.ln(f"{prefix}.final_layer_norm.weight"), xn_dtype=out_dtype or dt, p=p,
-                                          seed=self.seed, step=self.step_dev, stream_y=sy, stream_out=s_out, out_drop=True,
-                                          x1=None if keep else x)
-        if keep:
-            tape.push(kind="final", x1=x, rstd=rstd, s_in=sy, s_out=s_out, prefix=prefix, n_layers=n_layers,
-                      is_decoder=is_decoder, B=B, L=L, Le=Le, enc=enc, p=p, pack=pack)
+        out, rec = self._final_fwd(x, pend, prefix, p, sy, self._sid(), keep, xn_dtype=out_dtype)
+        push(prefix=prefix, n_layers=n_layers, is_decoder=is_decoder, cross=cross, B=B, L=L, Le=Le, enc=enc, p=p, pack=pack,
+             **rec)
         return out
 
     def stack_bwd(self, tape, d_out, d_enc=None, on_layer_done=None):
@@ -307,70 +361,41 @@ class Engine:
         fin = tape.pop()
         assert fin["kind"] == "final"
         prefix, n_layers, is_dec = fin["prefix"], fin["n_layers"], fin["is_decoder"]
-        B, L, Le, enc, p, pack = fin["B"], fin["L"], fin["Le"], fin["enc"], fin["p"], fin.get("pack")
-        H, inner, seed = self.H, self.inner, self.seed
+        B, L, Le, enc, p, pack = fin["B"], fin["L"], fin["Le"], fin["enc"], fin["p"], fin["pack"]
+        inner = self.inner
         has_y = n_layers > 0
-        rg = self.res_grad_dtype if has_y else torch.float32
-        dx, dy = self._norm_bwd(d_out, None, fin["x1"], fin["rstd"], self.ln(f"{prefix}.final_layer_norm.weight"),
-                                     self.ndw(f"{prefix}.final_layer_norm.weight"), want_dy=has_y, p=p, seed=seed, step=self.step_dev,
-                                     stream_y=fin["s_in"], stream_out=fin["s_out"], out_drop=True, dx1_dtype=rg)
+        dx, dy = self._final_bwd(fin, d_out, p, has_y, self.res_grad_dtype if has_y else torch.float32)
         # gradient of the cross-attention K | V of every layer, side by side like the forward's kv_all: the gradient of
         # the encoder output is then ONE product with K = n_layers * 768 after the loop instead of n_layers f32 accumulations
         dkv_all = (torch.empty(B * Le, n_layers * 2 * inner, device=d_out.device, dtype=self.dt)
                    if is_dec and n_layers > 0 else None)
         for i in reversed(range(n_layers)):
-            b = f"{prefix}.block.{i}.layer"
             t = tape.pop()
             assert t["kind"] == "ff" and t["i"] == i
-            ff = t["ff"]
-            self.wgrad(dy, t["g"], f.GW(f"{prefix}.{i}.wo"))
-            dh = self._proj_geglu_bwd(dy, self.WT(f"{prefix}.{i}.wo"), t["h"], p=p, seed=seed, step=self.step_dev,
-                                      stream_id=t["s_g"])
-            self.wgrad(dh, t["xn"], f.GW(f"{prefix}.{i}.wi"))
-            dx, dy = self._proj_norm_bwd(dh, self.WT(f"{prefix}.{i}.wi"), dx, t["x1"], t["rstd"],
-                                         self.ln(f"{b}.{ff}.layer_norm.weight"), self.ndw(f"{b}.{ff}.layer_norm.weight"),
-                                         p=p, seed=seed, step=self.step_dev, stream_y=t["s_in"], dx1=dx)
-            if ff == 2:
+            dx, dy = self._ff_bwd(t, prefix, dx, dy, p)
+            if fin["cross"]:
                 t = tape.pop()
                 assert t["kind"] == "cross"
-                self.wgrad(dy, t["o"], f.GW(f"{prefix}.{i}.co"))
-                do = lib.gemm_nt(dy, self.WT(f"{prefix}.{i}.co"))
+                do = self._oproj_bwd(dy, t["o"], f"{prefix}.{i}.co")
                 dq = torch.empty_like(t["q"])
                 dkv = dkv_all[:, i * 2 * inner:(i + 1) * 2 * inner]
                 kv = t["kv"]
-                if pack is not None:
-                    lib.attn_bwd_varlen(t["q"], kv[:, :inner], kv[:, inner:], t["o"], do, t["lse"], dq, dkv[:, :inner],
-                                        dkv[:, inner:], pack, H, Le, False, p=p, seed=seed, step=self.step_dev,
-                                        stream_id=t["s_att"], o_lo=t["o_lo"])
-                else:
-                    lib.attn_bwd(t["q"], kv[:, :inner], kv[:, inner:], t["o"], do, t["lse"], dq, dkv[:, :inner],
-                                 dkv[:, inner:], B, H, L, Le, False, p=p, seed=seed, step=self.step_dev,
-                                 stream_id=t["s_att"], o_lo=t["o_lo"])
+                self._attn_bwd(t, t["q"], kv[:, :inner], kv[:, inner:], do, dq, dkv[:, :inner], dkv[:, inner:], B, L, Le, False,
+                               pack, p)
                 self.wgrad(dq, t["xn"], f.GW(f"{prefix}.{i}.cq"))
                 self.wgrad(dkv, enc, f.GW(f"{prefix}.{i}.ckv"))
-                dx, dy = self._proj_norm_bwd(dq, self.WT(f"{prefix}.{i}.cq"), dx, t["x1"], t["rstd"],
-                                             self.ln(f"{b}.1.layer_norm.weight"), self.ndw(f"{b}.1.layer_norm.weight"),
-                                             p=p, seed=seed, step=self.step_dev, stream_y=t["s_in"], dx1=dx)
+                dx, dy = self._addnorm_bwd(t, dq, f"{prefix}.{i}.cq", dx, p)
             t = tape.pop()
             assert t["kind"] == "self" and t["i"] == i
-            self.wgrad(dy, t["o"], f.GW(f"{prefix}.{i}.o"))
-            do = lib.gemm_nt(dy, self.WT(f"{prefix}.{i}.o"))
+            do = self._oproj_bwd(dy, t["o"], f"{prefix}.{i}.o")
             qkv = t["qkv"]
             dqkv = torch.empty_like(qkv)
-            if pack is not None:
-                lib.attn_bwd_varlen(qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:], t["o"], do, t["lse"],
-                                    dqkv[:, :inner], dqkv[:, inner:2 * inner], dqkv[:, 2 * inner:], pack, H, 0, is_dec, p=p,
-                                    seed=seed, step=self.step_dev, stream_id=t["s_att"], o_lo=t["o_lo"])
-            else:
-                lib.attn_bwd(qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:], t["o"], do, t["lse"],
-                             dqkv[:, :inner], dqkv[:, inner:2 * inner], dqkv[:, 2 * inner:], B, H, L, L, is_dec, p=p,
-                             seed=seed, step=self.step_dev, stream_id=t["s_att"], o_lo=t["o_lo"])
+            self._attn_bwd(t, qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:], do, dqkv[:, :inner],
+                           dqkv[:, inner:2 * inner], dqkv[:, 2 * inner:], B, L, 0, is_dec, pack, p)
             self.wgrad(dqkv, t["xn"], f.GW(f"{prefix}.{i}.qkv"))
             last = i == 0                                     # the stack's input gradient leaves in f32
-            dx, dy = self._proj_norm_bwd(dqkv, self.WT(f"{prefix}.{i}.qkv"), dx, t["x1"], t["rstd"],
-                                         self.ln(f"{b}.0.layer_norm.weight"), self.ndw(f"{b}.0.layer_norm.weight"),
-                                         want_dy=(i > 0), p=p, seed=seed, step=self.step_dev, stream_y=t["s_in"],
-                                         dx1=None if (last and dx.dtype != torch.float32) else dx)
+            dx, dy = self._addnorm_bwd(t, dqkv, f"{prefix}.{i}.qkv", dx, p, want_dy=not last,
+                                       dx1=None if (last and dx.dtype != torch.float32) else dx)
             if on_layer_done is not None:
                 on_layer_done(prefix, i)
         if dkv_all is not None and d_enc is not None:      # (None: everything below the cross k|v projections is frozen)
@@ -391,9 +416,8 @@ class Engine:
         """proj -> + sinusoid -> dropout -> encoder stack (models/t5.py:122-136).  mel [B,Le,d]."""
         B, Le, d = mel.shape
         mel2 = self._act(mel.reshape(B * Le, d))
-        src = lib.gemm_nt(mel2, self.W("proj"), out_dtype=self.y_dtype)
         s_emb = self._sid()
-        x = lib.addpos_fwd(src, self.pos(mel.device), Le, p=p, seed=self.seed, step=self.step_dev, stream_id=s_emb)
+        x = self._input_fwd(mel2, "proj", Le, p, s_emb)
         if tape is not None:
             tape.push(kind="enc_in", mel=mel2, s_emb=s_emb, p=p)
         return self.stack_fwd("encoder", x, B, Le, self.cfg["num_layers"], False, p=p, tape=tape)
@@ -402,8 +426,7 @@ class Engine:
         dx = self.stack_bwd(tape, d_enc_out, on_layer_done=on_layer_done)
         t = tape.pop()
         assert t["kind"] == "enc_in"
-        dsrc = lib.dropmask_cast(dx, p=t["p"], seed=self.seed, step=self.step_dev, stream_id=t["s_emb"], out_dtype=self.dt)
-        self.wgrad(dsrc, t["mel"], self.flat.GW("proj"))
+        self._input_bwd(dx, t["mel"], "proj", t["p"], t["s_emb"])
 
     def segmem(self, ids, B, L, tape=None):
         """embed -> segmem_proj -> 1-layer bidirectional encoder, dropout 0
@@ -411,49 +434,42 @@ class Engine:
         `self.segmem_encoder(segmem_embeds)` routes the embeddings through `embed_tokens` =
         segmem_proj).  Returns the first `segmem_length` positions [B, Ls, d] in the compute dtype.
 
-        Only those Ls outputs are ever used (`[:, :self.segmem_length]`), so for the reference's
-        one-layer memory encoder the computation is restricted EXACTLY: keys/values need all L
-        positions, but queries, the O projection, the feed-forward and the final norm only the first
-        Ls rows (6.4 -> ~1 GFLOP per segment, SURVEY §7 "segmem-encoder shortcut")."""
-        f, dt, d, H, inner, eps = self.flat, self.dt, self.d, self.H, self.inner, self.eps
+        Only those Ls outputs are ever used (`[:, :self.segmem_length]`), so the reference's one-layer memory encoder is
+        restricted EXACTLY (6.4 -> ~1 GFLOP per segment, SURVEY §7 "segmem-encoder shortcut"): its self-attention — the one
+        part written out here — takes keys / values from all L rows and queries from the first Ls; the sublayers behind it
+        are the stacks' own pieces on Ls rows.  No dropout, so no site id is drawn (the generic path draws the stack's)."""
+        f, d, inner = self.flat, self.d, self.inner
+        keep = tape is not None
         Ls = min(self.segmem_length, L)
         emb = lib.embed_fwd(ids.reshape(-1), f.master("decoder_embed_tokens.weight"), None, L, shift=False,
                             pad_id=self.cfg["pad_token_id"])
         emb_a = self._act(emb)
-        src = lib.gemm_nt(emb_a, self.W("segmem_proj"), out_dtype=self.y_dtype)
-        x = lib.addpos_fwd(src, self.pos(ids.device), L)
+        x = self._input_fwd(emb_a, "segmem_proj", L, 0.0, 0)
+        rec = dict(kind="seg_in", ids=ids.reshape(-1), emb=emb_a, L=L, Ls=Ls, B=B)
         if self.segmem_num_layers != 1:
-            if tape is not None:
-                tape.push(kind="seg_in", ids=ids.reshape(-1), emb=emb_a, L=L, short=False, Ls=Ls, B=B)
+            if keep:
+                tape.push(short=False, **rec)
             full = self.stack_fwd("segmem_encoder", x, B, L, self.segmem_num_layers, False, p=0.0, tape=tape)
             return full.view(B, L, d)[:, :Ls]
         pre, b = "segmem_encoder", "segmem_encoder.block.0.layer"
         Wqkv = self.W(f"{pre}.0.qkv")
-        _, xn_full, rstd_full = lib.add_rmsnorm_fwd(x, None, self.ln(f"{b}.0.layer_norm.weight"), eps, dt, write_x1=False)
+        _, xn_full, rstd_full = self._proj_addnorm(x, None, self.ln(f"{b}.0.layer_norm.weight"), write_x1=False)
         kv = lib.gemm_nt(xn_full, Wqkv[inner:])                                     # [B*L, 2*inner]
         xs = x.view(B, L, d)[:, :Ls].contiguous().view(B * Ls, d)
         xns = xn_full.view(B, L, d)[:, :Ls].contiguous().view(B * Ls, d)
         q = lib.gemm_nt(xns, Wqkv[:inner])
-        o, lse, o_lo = lib.attn_fwd(q, kv[:, :inner], kv[:, inner:], B, H, Ls, L, False, want_lse=tape is not None,
-                                    want_lo=tape is not None)
-        y = lib.gemm_nt(o, self.W(f"{pre}.0.o"), out_dtype=self.y_dtype)
-        x1, xn1, rstd1 = lib.add_rmsnorm_fwd(xs, y, self.ln(f"{b}.1.layer_norm.weight"), eps, dt)
-        if xn1.dtype == torch.bfloat16:
-            h, g = lib.gemm_nt_geglu(xn1, self.W(f"{pre}.0.wi"))
-        else:
-            h = lib.gemm_nt(xn1, self.W(f"{pre}.0.wi"))
-            g = lib.geglu_fwd(h)
-        y2 = lib.gemm_nt(g, self.W(f"{pre}.0.wo"), out_dtype=self.y_dtype)
-        x2, out, rstd2 = lib.add_rmsnorm_fwd(x1, y2, self.ln(f"{pre}.final_layer_norm.weight"), eps, dt)
-        if tape is not None:
-            tape.push(kind="seg_in", ids=ids.reshape(-1), emb=emb_a, L=L, short=True, Ls=Ls, B=B, x=x,
-                      xn_full=xn_full, rstd_full=rstd_full, kv=kv, xns=xns, q=q, o=o, o_lo=o_lo, lse=lse, x1=x1, xn1=xn1,
-                      rstd1=rstd1, h=h, g=g, x2=x2, rstd2=rstd2)
+        o, lse, o_lo = self._attn_fwd(q, kv[:, :inner], kv[:, inner:], B, Ls, L, False, None, 0, 0.0, keep, True)
+        # (keep = True also without a tape: B*Ls rows, and xs is x itself when L = Ls — nothing is updated in place)
+        x1, ff, pend = self._ff_fwd(xs, (o, self.W(f"{pre}.0.o")), pre, 0, f"{b}.1.layer_norm.weight", 0.0, 0, 0, True)
+        out, fin = self._final_fwd(x1, pend, pre, 0.0, 0, 0, True)
+        if keep:
+            tape.push(short=True, x=x, xn_full=xn_full, rstd_full=rstd_full, kv=kv, xns=xns, q=q, o=o, o_lo=o_lo, lse=lse,
+                      s_att=0, ff=ff, fin=fin, **rec)
         return out.view(B, Ls, d)
 
     def segmem_bwd(self, tape, d_mem):
         """d_mem: fp32 [B, Ls, d] gradient w.r.t. the memory vectors."""
-        f, d, H, inner = self.flat, self.d, self.H, self.inner
+        f, d, inner = self.flat, self.d, self.inner
         if tape.ops[-1]["kind"] != "seg_in":                    # generic multi-layer path
             fin = next(o for o in reversed(tape.ops) if o["kind"] == "seg_in")
             B, L, Ls = fin["B"], fin["L"], fin["Ls"]
@@ -466,35 +482,27 @@ class Engine:
             B, L, Ls = t["B"], t["L"], t["Ls"]
             pre, b = "segmem_encoder", "segmem_encoder.block.0.layer"
             GW, WT = f.GW(f"{pre}.0.qkv"), self.WT(f"{pre}.0.qkv")
-            d_out = d_mem.contiguous().view(B * Ls, d)
-            dx2, dy2 = self._norm_bwd(d_out, None, t["x2"], t["rstd2"], self.ln(f"{pre}.final_layer_norm.weight"),
-                                           self.ndw(f"{pre}.final_layer_norm.weight"))
-            self.wgrad(dy2, t["g"], f.GW(f"{pre}.0.wo"))
-            dg = lib.gemm_nt(dy2, self.WT(f"{pre}.0.wo"))
-            dh = lib.geglu_bwd(t["h"], dg)
-            self.wgrad(dh, t["xn1"], f.GW(f"{pre}.0.wi"))
-            dxn1 = lib.gemm_nt(dh, self.WT(f"{pre}.0.wi"), out_dtype=self.y_dtype)
-            dx1, dy = self._norm_bwd(dxn1, dx2, t["x1"], t["rstd1"], self.ln(f"{b}.1.layer_norm.weight"),
-                                          self.ndw(f"{b}.1.layer_norm.weight"), dx1=dx2)
-            self.wgrad(dy, t["o"], f.GW(f"{pre}.0.o"))
-            do = lib.gemm_nt(dy, self.WT(f"{pre}.0.o"))
+            # (the residual gradient stays f32 on these B*Ls rows: it is scattered into the zero-padded f32 one below)
+            dx1, dy = self._final_bwd(t["fin"], d_mem.contiguous().view(B * Ls, d), 0.0, True, torch.float32)
+            dx1, dy = self._ff_bwd(t["ff"], pre, dx1, dy, 0.0)
+            do = self._oproj_bwd(dy, t["o"], f"{pre}.0.o")
             kv = t["kv"]
             dq, dkv = torch.empty_like(t["q"]), torch.empty_like(kv)
-            lib.attn_bwd(t["q"], kv[:, :inner], kv[:, inner:], t["o"], do, t["lse"], dq, dkv[:, :inner],
-                         dkv[:, inner:], B, H, Ls, L, False, o_lo=t["o_lo"])
+            self._attn_bwd(t, t["q"], kv[:, :inner], kv[:, inner:], do, dq, dkv[:, :inner], dkv[:, inner:], B, Ls, L, False,
+                           None, 0.0)
             self.wgrad(dq, t["xns"], GW[:inner])
             self.wgrad(dkv, t["xn_full"], GW[inner:])
+            # the input gradient of the row-restricted attention: two products (keys / values on all L rows, queries on the
+            # first Ls) summed, under the residual gradient zero-padded from Ls to L rows
             dxn_full = lib.gemm_nt(dkv, WT[:, inner:], out_dtype=torch.float32)          # [B*L, d]
             dxns = lib.gemm_nt(dq, WT[:, :inner], out_dtype=torch.float32)               # [B*Ls, d]
             dxn_full.view(B, L, d)[:, :Ls] += dxns.view(B, Ls, d)
             dres = torch.zeros(B, L, d, device=dx1.device, dtype=torch.float32)
             dres[:, :Ls] = dx1.view(B, Ls, d)
             dx, _ = self._norm_bwd(dxn_full, dres.view(B * L, d), t["x"], t["rstd_full"],
-                                        self.ln(f"{b}.0.layer_norm.weight"), self.ndw(f"{b}.0.layer_norm.weight"),
-                                        want_dy=False)
+                                   self.ln(f"{b}.0.layer_norm.weight"), self.ndw(f"{b}.0.layer_norm.weight"), want_dy=False)
         assert t["kind"] == "seg_in"
-        dsrc = lib.dropmask_cast(dx, out_dtype=self.dt)
-        self.wgrad(dsrc, t["emb"], f.GW("segmem_proj"))
+        dsrc = self._input_bwd(dx, t["emb"], "segmem_proj", 0.0, 0)
         if "decoder_embed_tokens.weight" in f.frozen:
             return
         demb = lib.gemm_nt(dsrc, self.WT("segmem_proj"), out_dtype=torch.float32)

@@ -569,6 +569,10 @@ class TnGroup:
     def __len__(self):
         return len(self._sites)
 
+    def clear(self):
+        """Forget what was recorded without launching it (the operands of work that never ran); plans and spares stay."""
+        self._sites.clear()
+
     def _host_table(self, nbytes, capturing):
         if not capturing:
             return _PinnedTable(nbytes)         # (the spares are for captures only: an eager plan must not use one up)
@@ -700,6 +704,10 @@ class NormDwBatch:
             self._ws[key] = ws
         self._queue.append((key, dw))
         return ws
+
+    def clear(self):
+        """Forget the queued sites without reducing them (their partial rows were never written); workspaces and tables stay."""
+        self._queue.clear()
 
     def flush(self):
         if not self._queue:

@@ -262,8 +262,7 @@ class Trainer:
         under capture it closes the current graph segment.  tcap: packed decoder rows.  Returns (objective, plain NLL): one
         tensor twice when no loss option is on."""
         eng, flat = self.engine, self.flat
-        eng.reset_deferred()                                 # nothing of an aborted capture / failed step leaks into this one
-        eng._stream_ctr = 0                                  # dropout site ids are per-step (step_dev salts them)
+        eng.begin_step()                                     # nothing deferred leaks in; dropout site ids are per-step
         mel = self.mel_from_audio(inputs) if audio else inputs
         plan = self._pack_plan(labels, tcap)
         targets = labels.reshape(-1) if plan is None else plan.targets
@@ -594,8 +593,7 @@ class Trainer:
         if pending:
             left.append("pending HIP error %s" % pending)
         self._drop_capture_stream()                          # a later capture (another input shape) gets a fresh stream
-        self.engine.reset_deferred()
-        self.engine._stream_ctr = 0
+        self.engine.begin_step()
         log = os.environ.get("MRMT3_CAPTURE_LOG")
         if log:
             objs = gc.get_objects()
