@@ -278,6 +278,9 @@ extern "C" int mrmt3_gemm_nt(const void* A, int lda, const void* B, int ldb, voi
   const int esz = in_dtype == MRMT3_BF16 ? 2 : 4;
   MR_CHECK_ARG((K * esz) % 64 == 0, "gemm_nt: K*elem_size must be a multiple of 64 bytes (K=%d)", K);
   MR_CHECK_ARG((lda * esz) % 16 == 0 && (ldb * esz) % 16 == 0, "gemm_nt: row strides must be 16-byte multiples");
+  // (a single row has no stride to speak of: torch reports any value for a dimension of size 1)
+  MR_CHECK_ARG((M == 1 || lda >= K) && (N == 1 || ldb >= K) && (M == 1 || ldc >= N),
+               "gemm_nt: a row stride is smaller than the row (lda=%d ldb=%d K=%d ldc=%d N=%d)", lda, ldb, K, ldc, N);
   {
     const int osz = out_dtype == MRMT3_BF16 ? 2 : 4;
     MR_CHECK_ARG((ldc * osz) % 16 == 0 && (N * osz) % 16 == 0 && ((uintptr_t)C % 16) == 0,
@@ -311,6 +314,7 @@ extern "C" int mrmt3_gemm_nt_ws(const void* A, int lda, const void* B, int ldb, 
   if (workspace && A && B && C && M > 0 && N > 0 && K > 0 && in_dtype == MRMT3_BF16 &&
       (out_dtype == MRMT3_BF16 || out_dtype == MRMT3_F32) && !(accumulate && out_dtype != MRMT3_F32) &&
       (lda * 2) % 16 == 0 && (ldb * 2) % 16 == 0 && (ldc * (out_dtype == MRMT3_BF16 ? 2 : 4)) % 16 == 0 &&
+      lda >= K && ldb >= K && ldc >= N &&
       ((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0 && ((uintptr_t)C % 16) == 0 && use_gemm8()) {
     if (mrmt3_gemm_nt8_splitk_try(A, lda, B, ldb, C, ldc, M, N, K, in_dtype, out_dtype, accumulate, workspace,
                                   workspace_bytes, (hipStream_t)stream)) {
@@ -526,6 +530,8 @@ extern "C" int mrmt3_gemm_tn(const void* A, int lda, const void* B, int ldb, flo
   MR_CHECK_ARG(M > 0 && N1 >= 8 && N2 >= 8, "gemm_tn: bad sizes");
   MR_CHECK_ARG(N1 % 8 == 0 && N2 % 4 == 0 && lda % 8 == 0 && ldb % 8 == 0 && ldc % 4 == 0,
                "gemm_tn: N1/lda/ldb must be multiples of 8, N2/ldc of 4");
+  MR_CHECK_ARG((M == 1 || (lda >= N1 && ldb >= N2)) && ldc >= N2,
+               "gemm_tn: a row stride is smaller than the row (lda=%d N1=%d ldb=%d N2=%d ldc=%d)", lda, N1, ldb, N2, ldc);
   int tiles, splits, rps;
   tn_plan(M, N1, N2, &tiles, &splits, &rps);
   MR_CHECK_ARG(workspace_bytes >= (size_t)splits * N1 * N2 * sizeof(float), "gemm_tn: workspace too small");

@@ -567,6 +567,9 @@ int mrmt3_gemm_nt8_splitk_try(const void* A, int lda, const void* B, int ldb, vo
 // Saves the GEGLU kernel's read of h (rows x 2 dff bf16) and one launch per feed-forward block; h is still written
 // (the backward needs it).  Shapes the fused kernel does not take run as the two separate kernels: same results bit for
 // bit either way (the epilogue rounds h to bf16 first and applies the element-wise kernel's arithmetic and mask).
+// rowops.hip: mrmt3_geglu_fwd on rows of ldh / ldg elements
+int mrmt3_geglu_fwd_ld(const void* h, int ldh, void* g, int ldg, int rows, int dff, int dtype, float p_drop, uint64_t seed,
+                       const int32_t* step_dev, uint32_t stream_id, void* stream);
 extern "C" int mrmt3_gemm_nt_geglu(const void* x, int ldx, const void* wi, int ldw, void* h, int ldh, void* g, int ldg,
                                    int rows, int dff, int K, float p_drop, uint64_t seed, const int32_t* step_dev,
                                    uint32_t stream_id, void* stream) {
@@ -583,10 +586,12 @@ extern "C" int mrmt3_gemm_nt_geglu(const void* x, int ldx, const void* wi, int l
                ((uintptr_t)g % 16) == 0 && g8_operands_fit(rows, ldx, 2 * dff, ldw, K);
   if (MR_KNOB("MRMT3_GEGLU_FUSED", 1) == 0) fused = false;
   if (!fused) {
+    // (h and g may be views of wider buffers here as in the fused launch; what the row kernel cannot take is refused
+    // before the product is launched, so that a refused call has written nothing)
+    MR_CHECK_ARG(ldg % 8 == 0 && ((uintptr_t)g % 16) == 0, "gemm_nt_geglu: g rows must be 16-byte aligned (ldg=%d)", ldg);
     int rc = mrmt3_gemm_nt(x, ldx, wi, ldw, h, ldh, rows, 2 * dff, K, MRMT3_BF16, MRMT3_BF16, 0, stream);
     if (rc != MRMT3_OK) return rc;
-    MR_CHECK_ARG(ldh == 2 * dff && ldg == dff, "gemm_nt_geglu: the unfused path needs dense h and g");
-    return mrmt3_geglu_fwd(h, g, rows, dff, MRMT3_BF16, p_drop, seed, step_dev, stream_id, stream);
+    return mrmt3_geglu_fwd_ld(h, ldh, g, ldg, rows, dff, MRMT3_BF16, p_drop, seed, step_dev, stream_id, stream);
   }
   G8Params P = g8_params_base(x, ldx, wi, ldw, h, ldh, rows, 2 * dff, K);
   P.C2 = g; P.ldc2 = ldg; P.dff = dff;

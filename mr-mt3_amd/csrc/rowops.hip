@@ -335,7 +335,7 @@ extern "C" int mrmt3_add_rmsnorm_bwd(const void* dxn, int dxn_dtype, const void*
 // ------------------------------------------------------------------------------------------------
 // Both kernels move 8 elements (two dropout quads) per thread and iteration: 16-byte accesses for bf16.
 template <typename T>
-__global__ void geglu_fwd_kernel(const T* __restrict__ h, T* __restrict__ g, int rows, int dff, DropCfg d) {
+__global__ void geglu_fwd_kernel(const T* __restrict__ h, int ldh, T* __restrict__ g, int ldg, int rows, int dff, DropCfg d) {
   DROP_STEP(d);
   const size_t n8 = (size_t)rows * dff / 8;
   const int dff8 = dff / 8;
@@ -343,13 +343,13 @@ __global__ void geglu_fwd_kernel(const T* __restrict__ h, T* __restrict__ g, int
     const size_t row = i / dff8;
     const int col = (int)(i % dff8) * 8;
     float a[8], b[8], o[8];
-    load4<T>(h + row * 2 * dff + col, a);
-    load4<T>(h + row * 2 * dff + col + 4, a + 4);
-    load4<T>(h + row * 2 * dff + dff + col, b);
-    load4<T>(h + row * 2 * dff + dff + col + 4, b + 4);
-    geglu_fwd8(d, 2 * i, a, b, o);
-    store4<T>(g + row * dff + col, o);
-    store4<T>(g + row * dff + col + 4, o + 4);
+    load4<T>(h + row * ldh + col, a);
+    load4<T>(h + row * ldh + col + 4, a + 4);
+    load4<T>(h + row * ldh + dff + col, b);
+    load4<T>(h + row * ldh + dff + col + 4, b + 4);
+    geglu_fwd8(d, 2 * i, a, b, o);                 // (the mask index is the element's index in a dense [rows][dff])
+    store4<T>(g + row * ldg + col, o);
+    store4<T>(g + row * ldg + col + 4, o + 4);
   }
 }
 
@@ -384,18 +384,26 @@ __global__ void geglu_bwd_kernel(const T* __restrict__ h, const T* __restrict__ 
   }
 }
 
-extern "C" int mrmt3_geglu_fwd(const void* h, void* g, int rows, int dff, int dtype, float p_drop, uint64_t seed, const int32_t* step_dev,
-                               uint32_t stream_id, void* stream) {
+// h [rows][ldh] and g [rows][ldg] as views of wider buffers (ldh, ldg in elements): the second half of the unfused
+// mrmt3_gemm_nt_geglu (gemm8.hip).  Same arithmetic and the same mask as the dense form: the mask follows (row, feature).
+int mrmt3_geglu_fwd_ld(const void* h, int ldh, void* g, int ldg, int rows, int dff, int dtype, float p_drop, uint64_t seed,
+                       const int32_t* step_dev, uint32_t stream_id, void* stream) {
   MR_CHECK_ARG(h && g && rows > 0 && dff % 8 == 0, "geglu_fwd: bad args");
   MR_CHECK_DTYPE("geglu_fwd", dtype);
+  MR_CHECK_ARG(ldh >= 2 * dff && ldg >= dff && ldh % 8 == 0 && ldg % 8 == 0, "geglu_fwd: ldh >= 2 dff, ldg >= dff, both multiples of 8");
   DropCfg d = make_drop(p_drop, seed, stream_id, step_dev);
   const int blocks = ew_blocks((size_t)rows * dff / 8);
   mr_dtype(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    hipLaunchKernelGGL(geglu_fwd_kernel<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const T*)h, (T*)g, rows, dff, d);
+    hipLaunchKernelGGL(geglu_fwd_kernel<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const T*)h, ldh, (T*)g, ldg, rows, dff, d);
   });
   MR_CHECK_LAUNCH("geglu_fwd");
   return MRMT3_OK;
+}
+
+extern "C" int mrmt3_geglu_fwd(const void* h, void* g, int rows, int dff, int dtype, float p_drop, uint64_t seed, const int32_t* step_dev,
+                               uint32_t stream_id, void* stream) {
+  return mrmt3_geglu_fwd_ld(h, 2 * dff, g, dff, rows, dff, dtype, p_drop, seed, step_dev, stream_id, stream);
 }
 
 extern "C" int mrmt3_geglu_bwd(const void* h, const void* dg, void* dh, int rows, int dff, int dtype, float p_drop,
