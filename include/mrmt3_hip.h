@@ -709,6 +709,8 @@ int mrmt3_decoder_begin_beam(mrmt3_decoder* dec, const mrmt3_decoder_weights* w,
  * backpointers into out_ids [groups][ld] int64: start token, tokens, eos_id when the hypothesis is
  * shorter than 1 + max_length, pad_id to ld.  hyps[g][3] receives the hypothesis length (start token
  * included, EOS excluded): the caller's output width is min(max over groups + 1, 1 + max_length).
+ * A NaN score compares false both ways: a group's first hypothesis stays chosen when its score is NaN, and a NaN
+ * further down the list is never chosen.
  * Needs ld >= 1 + max_length and max_length = the number of steps run when a group is not done. */
 int mrmt3_decoder_beam_finalize(mrmt3_decoder* dec, int64_t* out_ids, int ld, int max_length, void* stream);
 /* The same, and out_logp [groups][ld] f32 (nullable) receives the log-probability of every token of the chosen

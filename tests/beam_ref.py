@@ -54,7 +54,8 @@ class BeamRef:
             if self.done[g]:
                 continue
             flat = s[g * k:(g + 1) * k].reshape(-1)
-            order = np.lexsort((np.arange(flat.size), -flat))[:2 * k + 1]   # score descending, then flat index
+            # score descending (a NaN above every number, as torch.topk ranks it), then flat index
+            order = np.lexsort((np.arange(flat.size), -flat, ~np.isnan(flat)))[:2 * k + 1]
             top = flat[order]
             fin = top[np.isfinite(top)]
             if len(fin) > 1:
@@ -100,7 +101,13 @@ class BeamRef:
             for j in range(self.k):
                 r = g * self.k + j
                 self._add(g, self.scores[r] / (1 + T) ** self.lp, T, r)
-        best = [sorted(h, key=lambda e: e[0])[-1] for h in self.hyps]   # stable sort + pop(): last of equal maxima
+        best = []
+        for h in self.hyps:                     # stable sort + pop(): the last of equal maxima, written as the scan the kernel
+            b = 0                               # runs so that a NaN score has a place: it compares false both ways, so the
+            for i in range(1, len(h)):          # list's first entry stays chosen if it is NaN and a later NaN never is
+                if h[i][0] >= h[b][0]:
+                    b = i
+            best.append(h[b])
         seqs = [self.history(e, r) for _, e, r in best]
         W = min(max(len(q) for q in seqs) + 1, 1 + max_length)
         out = np.full((self.G, W), self.pad, dtype=np.int64)
