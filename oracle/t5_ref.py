@@ -49,10 +49,11 @@ def gelu_new(x):
     return 0.5 * x * (1.0 + torch.tanh(math.sqrt(2.0 / math.pi) * (x + 0.044715 * torch.pow(x, 3.0))))
 
 
-def attention(xq, xkv, wq, wk, wv, wo, n_heads, mask=None):
+def attention(xq, xkv, wq, wk, wv, wo, n_heads, mask=None, drop=None):
     """T5Attention without relative bias (reference builds every block with
     has_relative_attention_bias=False, `models/t5.py:487-490`): scores are UNSCALED q.k^T plus an
-    additive mask, softmax in fp32."""
+    additive mask, softmax in fp32.  `drop` (None = eval mode): a callable applied to the softmax probabilities
+    [B, H, Lq, Lk], HF's `nn.functional.dropout(attn_weights)` under a mask the caller chooses."""
     B, Lq, _ = xq.shape
     Lk = xkv.shape[1]
     dk = wq.shape[0] // n_heads
@@ -63,12 +64,18 @@ def attention(xq, xkv, wq, wk, wv, wo, n_heads, mask=None):
     if mask is not None:
         scores = scores + mask
     p = F.softmax(_f32(scores), dim=-1).type_as(scores)
+    if drop is not None:
+        p = drop(p)
     o = (p @ v).transpose(1, 2).reshape(B, Lq, n_heads * dk)
     return o @ wo.t()
 
 
-def ff_gated_gelu(x, wi0, wi1, wo):
-    return (gelu_new(x @ wi0.t()) * (x @ wi1.t())) @ wo.t()
+def ff_gated_gelu(x, wi0, wi1, wo, drop=None):
+    """T5DenseGatedGeluDense; `drop` (None = eval mode): a callable applied to gelu(wi_0 x) * (wi_1 x) before wo."""
+    g = gelu_new(x @ wi0.t()) * (x @ wi1.t())
+    if drop is not None:
+        g = drop(g)
+    return g @ wo.t()
 
 
 def pos_emb(seq, dim, offset=0, max_length=5000):
@@ -96,11 +103,21 @@ def shift_right(labels, start_id=0, pad_id=0):
     return out.masked_fill(out == -100, pad_id)
 
 
-def t5_stack(sd, prefix, cfg, x, is_decoder, enc=None, n_layers=None):
-    """`T5Stack.forward` (`models/t5.py:507-702`), eval mode (dropout = identity), all-ones masks."""
+def t5_stack(sd, prefix, cfg, x, is_decoder, enc=None, n_layers=None, drop=None):
+    """`T5Stack.forward` (`models/t5.py:507-702`), all-ones masks; eval mode (dropout = identity) unless `drop` is given.
+
+    `drop` (tests/_dropout_grads.py builds one): `drop.stack(prefix, n_layers)` returns the dropout sites of this stack, an
+    object with `rows(x, name)` and `probs(p, name)` that return their argument under the mask of the next site.  They are
+    asked in the order HF's T5Stack drops: "emb" (embeddings + sinusoid), then per layer "att" (self-attention
+    probabilities), "o" (its output, before the residual add), in a decoder with cross-attention "catt" and "co", then "g"
+    (gelu(wi_0 x) * (wi_1 x)) and "wo", and "out" (the closing norm's output).  With `drop=None` nothing here changes."""
     H, eps = cfg["num_heads"], cfg["layer_norm_epsilon"]
     L = x.shape[1]
     x = x + pos_emb(L, x.shape[-1])
+    if drop is not None:
+        if n_layers is None:
+            n_layers = cfg["num_decoder_layers"] if is_decoder else cfg["num_layers"]
+        return _t5_stack_dropped(sd, prefix, cfg, x, is_decoder, enc, n_layers, drop.stack(prefix, n_layers))
     mask = causal_additive_mask(L) if is_decoder else None
     if n_layers is None:
         n_layers = cfg["num_decoder_layers"] if is_decoder else cfg["num_layers"]
@@ -122,21 +139,47 @@ def t5_stack(sd, prefix, cfg, x, is_decoder, enc=None, n_layers=None):
     return rms_norm(x, sd[f"{prefix}.final_layer_norm.weight"], eps)
 
 
+def _t5_stack_dropped(sd, prefix, cfg, x, is_decoder, enc, n_layers, sites):
+    """The loop of `t5_stack` in training mode: `x` already holds embeddings + sinusoid; `sites` as described there."""
+    H, eps = cfg["num_heads"], cfg["layer_norm_epsilon"]
+    mask = causal_additive_mask(x.shape[1]) if is_decoder else None
+    x = sites.rows(x, "emb")
+    for i in range(n_layers):
+        b = f"{prefix}.block.{i}.layer"
+        g = lambda n: sd[f"{b}.{n}.weight"]
+        xn = rms_norm(x, g("0.layer_norm"), eps)
+        y = attention(xn, xn, g("0.SelfAttention.q"), g("0.SelfAttention.k"), g("0.SelfAttention.v"),
+                      g("0.SelfAttention.o"), H, mask, drop=lambda p: sites.probs(p, "att"))
+        x = x + sites.rows(y, "o")
+        ff = 1
+        if is_decoder and enc is not None:
+            xn = rms_norm(x, g("1.layer_norm"), eps)
+            y = attention(xn, enc, g("1.EncDecAttention.q"), g("1.EncDecAttention.k"), g("1.EncDecAttention.v"),
+                          g("1.EncDecAttention.o"), H, None, drop=lambda p: sites.probs(p, "catt"))
+            x = x + sites.rows(y, "co")
+            ff = 2
+        xn = rms_norm(x, g(f"{ff}.layer_norm"), eps)
+        y = ff_gated_gelu(xn, g(f"{ff}.DenseReluDense.wi_0"), g(f"{ff}.DenseReluDense.wi_1"),
+                          g(f"{ff}.DenseReluDense.wo"), drop=lambda t: sites.rows(t, "g"))
+        x = x + sites.rows(y, "wo")
+    return sites.rows(rms_norm(x, sd[f"{prefix}.final_layer_norm.weight"], eps), "out")
+
+
 # ----------------------------------------------------------------------------------------------
 # model variants
 # ----------------------------------------------------------------------------------------------
 
-def encode(sd, cfg, mel):
-    return t5_stack(sd, "encoder", cfg, mel @ sd["proj.weight"].t(), False)
+def encode(sd, cfg, mel, drop=None):
+    return t5_stack(sd, "encoder", cfg, mel @ sd["proj.weight"].t(), False, drop=drop)
 
 
-def decode_logits(sd, cfg, dec_ids, enc, dec_embeds=None):
+def decode_logits(sd, cfg, dec_ids, enc, dec_embeds=None, drop=None):
     x = sd["decoder_embed_tokens.weight"][dec_ids] if dec_embeds is None else dec_embeds
-    y = t5_stack(sd, "decoder", cfg, x, True, enc=enc)
+    y = t5_stack(sd, "decoder", cfg, x, True, enc=enc, drop=drop)
     return y
 
 
-def segmem_memory(sd, cfg, ids, segmem_length, n_layers=1):
+def segmem_memory(sd, cfg, ids, segmem_length, n_layers=1, drop=None):
     """embed -> segmem_proj -> 1-layer bidirectional segmem_encoder over ALL positions -> first segmem_length
     (`models/t5_segmem_v2_with_prev.py:121-123`)."""
     emb = sd["decoder_embed_tokens.weight"][ids]
@@ -146,7 +189,7 @@ def segmem_memory(sd, cfg, ids, segmem_length, n_layers=1):
     # at `models/t5.py:539-540`.  (SURVEY.md §8a row S1 says segmem_proj is never applied; the
     # reference's recorded outputs show it is.)
     emb = emb @ sd["segmem_proj.weight"].t()
-    return t5_stack(sd, "segmem_encoder", cfg, emb, False, n_layers=n_layers)[:, :segmem_length]
+    return t5_stack(sd, "segmem_encoder", cfg, emb, False, n_layers=n_layers, drop=drop)[:, :segmem_length]
 
 
 def _prev_row_ids(dec_ids):
@@ -159,23 +202,27 @@ def _prev_row_ids(dec_ids):
     return torch.cat([dummy, seg[:-1]], dim=0).long()
 
 
-def forward_logits(sd, cfg, mel, labels, variant="t5", targets_prev=None, segmem_length=64):
-    """Returns lm_logits [B,Ld,V] for variant in {t5, segmem_v1, segmem_v2, segmem_v2_with_prev}."""
-    enc = encode(sd, cfg, mel)
+def forward_logits(sd, cfg, mel, labels, variant="t5", targets_prev=None, segmem_length=64, segmem_num_layers=1,
+                   drop=None):
+    """Returns lm_logits [B,Ld,V] for variant in {t5, segmem_v1, segmem_v2, segmem_v2_with_prev}.  `drop` (None = eval
+    mode): the dropout sites of a training step, see `t5_stack`; the stacks ask it in the order encoder, memory encoder,
+    decoder."""
+    enc = encode(sd, cfg, mel, drop=drop)
     dec_ids = shift_right(labels, cfg["decoder_start_token_id"], cfg["pad_token_id"])
+    memory = lambda ids: segmem_memory(sd, cfg, ids, segmem_length, n_layers=segmem_num_layers, drop=drop)
     if variant == "t5":
-        y = decode_logits(sd, cfg, dec_ids, enc)
+        y = decode_logits(sd, cfg, dec_ids, enc, drop=drop)
     elif variant == "segmem_v1":
-        mem = segmem_memory(sd, cfg, _prev_row_ids(dec_ids), segmem_length)
+        mem = memory(_prev_row_ids(dec_ids))
         emb = torch.cat([mem, sd["decoder_embed_tokens.weight"][dec_ids]], dim=1)
-        y = decode_logits(sd, cfg, None, enc, dec_embeds=emb)[:, segmem_length:]
+        y = decode_logits(sd, cfg, None, enc, dec_embeds=emb, drop=drop)[:, segmem_length:]
     elif variant == "segmem_v2":
-        mem = segmem_memory(sd, cfg, _prev_row_ids(dec_ids), segmem_length)
-        y = decode_logits(sd, cfg, dec_ids, torch.cat([enc, mem], dim=1))
+        mem = memory(_prev_row_ids(dec_ids))
+        y = decode_logits(sd, cfg, dec_ids, torch.cat([enc, mem], dim=1), drop=drop)
     elif variant == "segmem_v2_with_prev":
         tp = targets_prev.masked_fill(targets_prev == -100, cfg["pad_token_id"])
-        mem = segmem_memory(sd, cfg, tp, segmem_length)
-        y = decode_logits(sd, cfg, dec_ids, torch.cat([enc, mem], dim=1))
+        mem = memory(tp)
+        y = decode_logits(sd, cfg, dec_ids, torch.cat([enc, mem], dim=1), drop=drop)
     else:
         raise ValueError(variant)
     return y @ sd["lm_head.weight"].t()
