@@ -234,8 +234,44 @@ int mrmt3_label_rows_fwd(const double* note_times, const int* note_meta, int n_n
                          int pitch_base, int velocity_base, int tie_token, int program_base, int drum_base,
                          int max_shift_steps, int steps_per_second, int sample_rate, int hop, int event_length,
                          int num_special_tokens, long long* targets, int* status, void* stream);
-/* Launches of mrmt3_label_rows_fwd since the process started (or since the last call with reset != 0); kept apart from
- * mrmt3_dispatch_counts like the resampler's. */
+/* Labels of cross-track rows: the row of a VIRTUAL track of up to 4 parts (LB_MAX_PARTS, an ABI constant),
+ * each part a track's note table with its own stem mask, speed factor, transposition and delay.  A row's targets are by
+ * definition Tokenizer.row_targets of the tokenisation of mrmt3.stems.virtual_note_sequence(parts);
+ * mrmt3.labels.label_rows_parts_host restates this entry on the host.
+ *
+ * The note arena (DEVICE): note_times [n_notes][2] f64 and note_meta [n_notes][4] int32, 16-byte aligned, the note tables
+ * of every cached track one after the other, each as mrmt3_label_rows_fwd takes it — but `next` counts from the table's
+ * first note, so a table may lie anywhere in the arena.
+ * Per (row, part), DEVICE arrays [batch][n_parts]: note_first, note_count (int32: the part's table is notes
+ * [note_first, note_first + note_count) of the arena), keep (uint64 stem mask), delay_frames (int64, >= 0; a negative
+ * value counts as 0), scale (f64), shift (int32).  Per row, [batch]: start_frame (the virtual track's frame F), n_frames,
+ * total_frames (int64, of the virtual track).  The codec by value, as above.  A part with note_count <= 0 or keep == 0
+ * contributes nothing.
+ *
+ * The row is the row of mrmt3_label_rows_fwd over the notes of all parts, with these additions:
+ *  - Time of a note of part p: t if shift_p == 0, else fl(t * scale_p); then, if delay_p != 0, fl(that + fl(delay_p / fps)).
+ *    One rounding per operation.  Pitch: pitch + shift_p for notes that are not drum notes.
+ *  - Trim: the successor of a note is the first kept note along the links of the note's OWN part.  This is the definition's
+ *    trim as long as no (program, is_drum) pair is kept in two parts of the row (status 16 otherwise).
+ *  - S_last, the tie section and the event list are the row's, over all parts.  In the event order the part index comes
+ *    before the index in the part's table.
+ *  - status: 1, 2, 4 and 8 as above, the capacities (2048 events, 2048 tie pairs) per row over all parts, 4 also where a
+ *    delay made two start times of a group equal; 16: two parts hold kept notes of one (program, is_drum).  The caller
+ *    rebuilds a row with status != 0 on the host.
+ *  - A one-part row with delay 0 is the row mrmt3_label_rows_fwd writes for that table, integer for integer.
+ * Bounds: whatever the arrays and the tables hold, nothing outside [0, n_notes) of the arena is read (a part's range is cut
+ * to the arena), a part never follows a link outside its own range, and a note follows at most note_count links.
+ * MRMT3_ERR_INVALID_ARG before any launch: a null pointer (the arena's two excepted when n_notes == 0), n_parts outside
+ * [1, 4], n_notes < 0, batch <= 0, the codec checks of mrmt3_label_rows_fwd, note_meta not 16-byte aligned. */
+int mrmt3_label_rows_parts_fwd(const double* note_times, const int* note_meta, int n_notes, int n_parts,
+                               const int* note_first, const int* note_count, const unsigned long long* keep,
+                               const long long* delay_frames, const double* scale, const int* shift,
+                               const long long* start_frame, const long long* n_frames, const long long* total_frames,
+                               int batch, int pitch_base, int velocity_base, int tie_token, int program_base,
+                               int drum_base, int max_shift_steps, int steps_per_second, int sample_rate, int hop,
+                               int event_length, int num_special_tokens, long long* targets, int* status, void* stream);
+/* Launches of mrmt3_label_rows_fwd and mrmt3_label_rows_parts_fwd since the process started (or since the last call with
+ * reset != 0); kept apart from mrmt3_dispatch_counts like the resampler's. */
 unsigned long long mrmt3_label_launches(int reset);
 
 /* ---- K2/K4/K6/K7/K9: bias-free Linear layers (nn.Linear(bias=False) inside HF T5Block,

@@ -100,7 +100,7 @@ extern "C" int mrmt3_reset_knobs(void) {
   return MRMT3_OK;
 }
 
-extern "C" int mrmt3_version(void) { return 128; /* 0.1.28: mrmt3_note_frames_fwd + mrmt3_note_frames_workspace_bytes + mrmt3_note_frames_launches (frame counts and piano rolls from note tables); 127: mrmt3_note_match_fwd + mrmt3_note_match_workspace_bytes + mrmt3_note_match_launches (note matching on the device); 126: mrmt3_notes_decode_fwd + mrmt3_notes_launches (token rows -> notes on the device), mrmt3_grammar gains steps_per_second; 125: mrmt3_label_rows_fwd + mrmt3_label_launches (stem-mix labels built on the device); 124: mrmt3_resample_mix_fwd + mrmt3_resample_launches (windowed-sinc resampler that mixes); 123: mrmt3_logmel_mix_fwd (stems mixed inside the log-mel load); 122: dispatch counters of the two log-mel kernels (MRMT3_CNT_LOGMEL_*); 121: one optimizer tail (mrmt3_adamw_step takes the stat / range-table / EMA arguments, mrmt3_grad_norm the range table; mrmt3_adamw_step_clipped, mrmt3_adamw_step_groups and mrmt3_grad_norm_ranges removed); 120: grammar-constrained decoding (mrmt3_grammar_*, mrmt3_decoder_set_grammar, mrmt3_decoder_grammar_active; the tails' ban pointer takes a row stride); 119: optimizer parameter groups (mrmt3_opt_ranges_plan, mrmt3_adamw_step_groups, mrmt3_grad_norm_ranges); 118: label smoothing + z-loss in the cross-entropy kernels (mrmt3_ce_fwd_bwd_reg, mrmt3_lmhead_ce_fwd_bwd_reg); 117: sampled decoding (mrmt3_decoder_set_sampling, mrmt3_sample_logits); 116: per-token log-probabilities (mrmt3_decoder_set_logprobs, mrmt3_decoder_beam_finalize_logprobs, mrmt3_token_logprob, mrmt3_lmhead_logprob); 115: mrmt3_grad_norm + mrmt3_adamw_step_clipped (global-norm / value gradient clipping and the non-finite guard inside the captured step); 114: the slabs-only weight-gradient GEMM and its batched slab reduce removed (the one fallback of the grouped launch is mrmt3_gemm_tn); 113: mrmt3_counter_add (per-micro-batch dropout salt of gradient accumulation); 112: packed decoder rows (mrmt3_pack_*, mrmt3_embed_fwd_packed, mrmt3_attn_*_varlen); 111: mrmt3_decoder_logits, torch.argmax NaN order in the decoder; 110: round 6 (capture hygiene entry points, owned streams, abort trace, pair bf16 conversion); 108: round 5 (knobs read once per process + mrmt3_set_knob; kernel diagnostics only in the -DMRMT3_DIAG build); 107: round 4 */ }
+extern "C" int mrmt3_version(void) { return 129; /* 0.1.29: mrmt3_label_rows_parts_fwd (labels of cross-track rows); 128: mrmt3_note_frames_fwd + mrmt3_note_frames_workspace_bytes + mrmt3_note_frames_launches (frame counts and piano rolls from note tables); 127: mrmt3_note_match_fwd + mrmt3_note_match_workspace_bytes + mrmt3_note_match_launches (note matching on the device); 126: mrmt3_notes_decode_fwd + mrmt3_notes_launches (token rows -> notes on the device), mrmt3_grammar gains steps_per_second; 125: mrmt3_label_rows_fwd + mrmt3_label_launches (stem-mix labels built on the device); 124: mrmt3_resample_mix_fwd + mrmt3_resample_launches (windowed-sinc resampler that mixes); 123: mrmt3_logmel_mix_fwd (stems mixed inside the log-mel load); 122: dispatch counters of the two log-mel kernels (MRMT3_CNT_LOGMEL_*); 121: one optimizer tail (mrmt3_adamw_step takes the stat / range-table / EMA arguments, mrmt3_grad_norm the range table; mrmt3_adamw_step_clipped, mrmt3_adamw_step_groups and mrmt3_grad_norm_ranges removed); 120: grammar-constrained decoding (mrmt3_grammar_*, mrmt3_decoder_set_grammar, mrmt3_decoder_grammar_active; the tails' ban pointer takes a row stride); 119: optimizer parameter groups (mrmt3_opt_ranges_plan, mrmt3_adamw_step_groups, mrmt3_grad_norm_ranges); 118: label smoothing + z-loss in the cross-entropy kernels (mrmt3_ce_fwd_bwd_reg, mrmt3_lmhead_ce_fwd_bwd_reg); 117: sampled decoding (mrmt3_decoder_set_sampling, mrmt3_sample_logits); 116: per-token log-probabilities (mrmt3_decoder_set_logprobs, mrmt3_decoder_beam_finalize_logprobs, mrmt3_token_logprob, mrmt3_lmhead_logprob); 115: mrmt3_grad_norm + mrmt3_adamw_step_clipped (global-norm / value gradient clipping and the non-finite guard inside the captured step); 114: the slabs-only weight-gradient GEMM and its batched slab reduce removed (the one fallback of the grouped launch is mrmt3_gemm_tn); 113: mrmt3_counter_add (per-micro-batch dropout salt of gradient accumulation); 112: packed decoder rows (mrmt3_pack_*, mrmt3_embed_fwd_packed, mrmt3_attn_*_varlen); 111: mrmt3_decoder_logits, torch.argmax NaN order in the decoder; 110: round 6 (capture hygiene entry points, owned streams, abort trace, pair bf16 conversion); 108: round 5 (knobs read once per process + mrmt3_set_knob; kernel diagnostics only in the -DMRMT3_DIAG build); 107: round 4 */ }
 extern "C" const char* mrmt3_last_error(void) { return g_err; }
 
 int mrmt3_cu_count() {

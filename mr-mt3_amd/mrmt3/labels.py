@@ -141,20 +141,33 @@ def first_step(frame: int, codec: LabelCodec) -> int:
     return s
 
 
-def _row_tokens(table: NoteTable, mask: int, start_frame: int, n_frames: int, total_frames: int, scale: float, shift: int,
-                codec: LabelCodec) -> list:
-    """The row contract, token ids before `pad_targets`."""
-    sps = codec.steps_per_second
-    notes = []                                   # [start, end, pitch, vbin, program, is_drum, merged index]
+def _kept_notes(table: NoteTable, mask: int, scale: float, shift: int, delay: float = 0.0, part: int = 0) -> list:
+    """[start, end, pitch, vbin, program, is_drum, (part, table index)] of the notes the mask keeps, as the row sees them:
+    times scaled when shift != 0, then delayed when delay != 0, one rounding each."""
+    notes = []
     for i in range(len(table.meta)):
         pitch, vbin, packed, _ = (int(v) for v in table.meta[i])
-        if not mask >> (packed >> 16) & 1:
+        if not mask >> (packed >> 16 & 63) & 1:
             continue
         st, en, drum = float(table.times[i, 0]), float(table.times[i, 1]), bool(packed >> 8 & 1)
         if shift != 0:
             st, en = st * scale, en * scale
             pitch = pitch if drum else pitch + shift
-        notes.append([st, en, pitch, vbin, packed & 0xff, drum, i])
+        if delay != 0.0:
+            st, en = st + delay, en + delay
+        notes.append([st, en, pitch, vbin, packed & 0xff, drum, (part, i)])
+    return notes
+
+
+def _row_tokens(table: NoteTable, mask: int, start_frame: int, n_frames: int, total_frames: int, scale: float, shift: int,
+                codec: LabelCodec) -> list:
+    """The row contract, token ids before `pad_targets`."""
+    return _tokens_of_notes(_kept_notes(table, mask, scale, shift), start_frame, n_frames, total_frames, codec)[0]
+
+
+def _tokens_of_notes(notes: list, start_frame: int, n_frames: int, total_frames: int, codec: LabelCodec):
+    """Trim, sort, walk over `_kept_notes` lists -> (token ids, events in the window, tie pairs)."""
+    sps = codec.steps_per_second
     groups = {}
     for n in notes:
         groups.setdefault((n[2], n[4], n[5]), []).append(n)
@@ -172,7 +185,7 @@ def _row_tokens(table: NoteTable, mask: int, start_frame: int, n_frames: int, to
         events.append((st, 1, drum, program, pitch, i, vbin))
     events.sort()
     if not events:
-        return [codec.tie_token]                 # (the definition raises IndexError here)
+        return [codec.tie_token], 0, 0           # (the definition raises IndexError here)
     steps = [round(e[0] * sps) for e in events]  # half to even, like rint
     lo = first_step(start_frame, codec)
     hi = first_step(start_frame + n_frames, codec) if start_frame + n_frames < total_frames else None
@@ -182,7 +195,9 @@ def _row_tokens(table: NoteTable, mask: int, start_frame: int, n_frames: int, to
         if s < bound and not e[2]:
             state[(e[3], e[4])] = e[1]
     out, cur_program, cur_velocity = [], None, None
-    for program, pitch in sorted(k for k, on in state.items() if on):
+    ties = sorted(k for k, on in state.items() if on)
+    in_window = 0
+    for program, pitch in ties:
         if program != cur_program:
             out.append(codec.program_base + program)
             cur_program = program
@@ -192,6 +207,7 @@ def _row_tokens(table: NoteTable, mask: int, start_frame: int, n_frames: int, to
     for e, s in zip(events, steps):
         if s < lo or (hi is not None and s >= hi):
             continue
+        in_window += 1
         _, on, drum, program, pitch, _, vbin = e
         if s - lo > flushed:                     # every event emits its pitch or drum token: the shift comes first
             left = flushed = s - lo
@@ -205,7 +221,7 @@ def _row_tokens(table: NoteTable, mask: int, start_frame: int, n_frames: int, to
             out.append(codec.velocity_base + vbin)
             cur_velocity = vbin
         out.append((codec.drum_base if drum else codec.pitch_base) + pitch)
-    return out
+    return out, in_window, len(ties)
 
 
 def label_rows_host(table: NoteTable, keep, start_frame, n_frames, total_frames, scale, shift, codec: LabelCodec,
@@ -222,3 +238,89 @@ def label_rows_host(table: NoteTable, keep, start_frame, n_frames, total_frames,
         if len(row) < event_length:
             out[b, len(row)] = 1
     return out, np.zeros(B, np.int32)
+
+
+# ---- rows of virtual tracks -----------------------------------------------------------------------------------
+
+MAX_PARTS = 4            # parts of one cross-track row (LB_MAX_PARTS, an ABI constant)
+STATUS_SHARED = 16       # two parts of the row hold kept notes of one (program, is_drum): the per-part trim does not serve
+CAPACITY = 2048          # events of a row's window, and tie pairs, that the kernels hold (mrmt3.lib.LABEL_CAPACITY)
+
+
+def note_arena(tables):
+    """Note tables one after the other, as `mrmt3_label_rows_parts_fwd` takes them: (NoteTable of all notes — its `next`
+    links count from each table's own first note, so they are the tables' own —, first note of every table)."""
+    first = np.concatenate([[0], np.cumsum([len(t.meta) for t in tables])]).astype(np.int64)
+    times = np.concatenate([t.times.reshape(-1, 2) for t in tables]) if tables else np.zeros((0, 2), np.float64)
+    meta = np.concatenate([t.meta.reshape(-1, 4) for t in tables]) if tables else np.zeros((0, 4), np.int32)
+    return NoteTable(np.ascontiguousarray(times), np.ascontiguousarray(meta), max([t.n_stems for t in tables] + [1])), first[:-1]
+
+
+def _part_status(table: NoteTable, mask: int, scale: float, shift: int, delay: float) -> int:
+    """STATUS_RANGE and STATUS_ORDER of one part, found the way the kernel finds them: along the table's links."""
+    n, flags = len(table.meta), 0
+    kept = lambda i: bool(mask >> (int(table.meta[i, 2]) >> 16 & 63) & 1)
+
+    def start(i):
+        t = float(table.times[i, 0])
+        t = t * scale if shift != 0 else t
+        return t + delay if delay != 0.0 else t
+
+    for i in range(n):
+        if not kept(i):
+            continue
+        pitch, vbin, packed, j = (int(v) for v in table.meta[i])
+        pitch = pitch + shift if shift != 0 and not packed >> 8 & 1 else pitch
+        if not (0 <= pitch <= 127 and 0 <= (packed & 0xff) <= 127 and 0 <= vbin <= 127):
+            flags |= STATUS_RANGE
+            continue
+        hops = 0
+        while hops < n and 0 <= j < n and not kept(j):
+            j, hops = int(table.meta[j, 3]), hops + 1
+        if (shift != 0 or delay != 0.0) and 0 <= j < n and kept(j):
+            if start(j) < start(i) or (start(j) == start(i) and j < i):
+                flags |= STATUS_ORDER
+    return flags
+
+
+def label_rows_parts_host(arena: NoteTable, note_first, note_count, keep, delay_frames, scale, shift, start_frame, n_frames,
+                          total_frames, codec: LabelCodec, event_length: int = 1024):
+    """The contract of `mrmt3_label_rows_parts_fwd` on the host: (targets int64 [B, event_length] in `pad_targets` form,
+    status int32 [B], the kernel's status words).  `arena`: the tables one after the other (`note_arena`); note_first,
+    note_count, keep (uint64), delay_frames, scale, shift [B, P]; start_frame, n_frames, total_frames [B].  The tokens are
+    the definition's — the trim runs over the whole row — so a row with status 16 is still the row the batcher wants; the
+    kernel's tokens equal them wherever the status is 0."""
+    keep = np.asarray(keep)
+    B, P = keep.shape
+    if not 1 <= P <= MAX_PARTS:
+        raise ValueError("a row has 1 to %d parts, got %d" % (MAX_PARTS, P))
+    N = len(arena.meta)
+    fps = np.float64(codec.frames_per_second)
+    out = np.full((B, event_length), -100, np.int64)
+    status = np.zeros(B, np.int32)
+    for b in range(B):
+        notes, owners, flags = [], {}, 0
+        for p in range(P):
+            first, count, mask = int(note_first[b][p]), int(note_count[b][p]), int(keep[b][p])
+            if first < 0 or first > N:
+                first, count = 0, 0
+            count = max(0, min(count, N - first))
+            if mask == 0 or count == 0:
+                continue
+            d = int(delay_frames[b][p])
+            delay = float(np.float64(d) / fps) if d > 0 else 0.0
+            table = NoteTable(arena.times[first:first + count], arena.meta[first:first + count], arena.n_stems)
+            flags |= _part_status(table, mask, float(scale[b][p]), int(shift[b][p]), delay)
+            part = _kept_notes(table, mask, float(scale[b][p]), int(shift[b][p]), delay, p)
+            for n in part:
+                if owners.setdefault((n[4] & 0x7f, n[5]), p) != p:
+                    flags |= STATUS_SHARED
+            notes += part
+        row, events, ties = _tokens_of_notes(notes, int(start_frame[b]), int(n_frames[b]), int(total_frames[b]), codec)
+        flags |= (STATUS_EVENTS if events > CAPACITY else 0) | (STATUS_TIES if ties > CAPACITY else 0)
+        row = row[:event_length]
+        out[b, :len(row)] = np.asarray(row, np.int64) + codec.num_special_tokens
+        if len(row) < event_length:
+            out[b, len(row)] = 1
+        status[b] = flags
+    return out, status

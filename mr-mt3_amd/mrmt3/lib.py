@@ -107,7 +107,7 @@ def load():
     return lib
 
 
-MIN_VERSION = 128
+MIN_VERSION = 129
 COUNTER_NAMES = ("gemm_nt_tile", "gemm_nt8", "gemm_nt_geglu", "tn_group", "tn8", "tn_tile", "attn_fwd", "attn_bwd",
                  "attn_bwd_onepass", "attn_f32", "tn_f32", "gemm_nt_splitk", "gemm_nt_addnorm", "gemm_nt_normbwd",
                  "gemm_nt_geglubwd", "attn_fwd_varlen", "attn_bwd_varlen", "logmel_wave", "logmel_general")
@@ -306,8 +306,39 @@ def label_rows(note_times, note_meta, n_stems, keep, start_frame, n_frames, tota
     return targets, status
 
 
+LABEL_MAX_PARTS = 4          # parts of one row of mrmt3_label_rows_parts_fwd (LB_MAX_PARTS, an ABI constant)
+
+
+def label_rows_parts(note_times, note_meta, note_first, note_count, keep, delay_frames, scale, shift, start_frame, n_frames,
+                     total_frames, codec, event_length=1024):
+    """Rows of virtual tracks (DESIGN 4q).  note_times [N, 2] f64 and note_meta [N, 4] int32: the note arena on the device;
+    note_first / note_count [B, P] int32, keep (uint64 masks) / delay_frames [B, P] int64, scale [B, P] f64, shift [B, P]
+    int32, 1 <= P <= LABEL_MAX_PARTS; start_frame / n_frames / total_frames [B] int64 -> (targets [B, event_length] int64,
+    status [B] int32) as `label_rows` (include/mrmt3_hip.h: mrmt3_label_rows_parts_fwd)."""
+    _dev(note_times, note_meta, note_first, note_count, keep, delay_frames, scale, shift, start_frame, n_frames, total_frames)
+    N = note_meta.shape[0]
+    assert note_times.shape == (N, 2) and note_times.dtype == torch.float64 and note_times.is_contiguous()
+    assert note_meta.shape == (N, 4) and note_meta.dtype == torch.int32 and note_meta.is_contiguous()
+    assert keep.dim() == 2
+    B, P = keep.shape
+    for t, dt in ((note_first, torch.int32), (note_count, torch.int32), (keep, torch.int64), (delay_frames, torch.int64),
+                  (scale, torch.float64), (shift, torch.int32)):
+        assert t.shape == (B, P) and t.dtype == dt and t.is_contiguous()
+    for t in (start_frame, n_frames, total_frames):
+        assert t.shape == (B,) and t.dtype == torch.int64 and t.is_contiguous()
+    targets = torch.empty(B, int(event_length), device=keep.device, dtype=torch.int64)
+    status = torch.empty(B, device=keep.device, dtype=torch.int32)
+    _check(load().mrmt3_label_rows_parts_fwd(
+        _p(note_times) if N else None, _p(note_meta) if N else None, N, P, _p(note_first), _p(note_count), _p(keep),
+        _p(delay_frames), _p(scale), _p(shift), _p(start_frame), _p(n_frames), _p(total_frames), B, codec.pitch_base,
+        codec.velocity_base, codec.tie_token, codec.program_base, codec.drum_base, codec.max_shift_steps,
+        codec.steps_per_second, codec.sample_rate, codec.hop, int(event_length), codec.num_special_tokens, _p(targets),
+        _p(status), _stream()), "label_rows_parts_fwd")
+    return targets, status
+
+
 def label_launches(reset: bool = False) -> int:
-    """Launches of `label_rows` since the process started / the last reset (mrmt3_label_launches)."""
+    """Launches of `label_rows` and `label_rows_parts` since the process started / the last reset (mrmt3_label_launches)."""
     return int(load().mrmt3_label_launches(int(reset)))
 
 

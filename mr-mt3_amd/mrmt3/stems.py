@@ -75,6 +75,47 @@ def speed_note_sequence(ns: NoteSequence, shift: int, step: int) -> NoteSequence
     return out
 
 
+@dataclasses.dataclass
+class VirtualPart:
+    """One part of a cross-track row: the stems `kept` (indices, ascending) of `track`, played at
+    step / 2^32 times its speed and transposed by `shift` semitones, then delayed by `delay_frames` whole frames."""
+    track: StemTrack
+    kept: tuple
+    shift: int = 0
+    step: int = 1 << 32
+    delay_frames: int = 0
+
+
+def _stretched_samples(track: StemTrack, step: int, sample_rate: int) -> int:
+    from mrmt3.resample import out_length
+    return max(n if step == 1 << 32 else out_length(n, step) for n in track.lengths(sample_rate))
+
+
+def virtual_n_samples(parts, sample_rate: int = 16000, hop: int = 128) -> int:
+    """The virtual track's length in samples: the longest (stretched) part behind its delay."""
+    return max(_stretched_samples(p.track, int(p.step), sample_rate) + int(p.delay_frames) * hop for p in parts)
+
+
+def virtual_note_sequence(parts, sample_rate: int = 16000, hop: int = 128) -> NoteSequence:
+    """The DEFINITION of a cross-track row's label: the notes of every part in part order, each part
+    `speed_note_sequence(merged_note_sequence(track, kept), shift, step)` (untouched when shift == 0) with
+    fl(delay_frames / fps) added to every start and end — one f64 rounding for the quotient, one for the sum, and no
+    change at all when delay_frames == 0.  fps = sample_rate / hop.  The sequence is tokenised at `virtual_n_samples`."""
+    fps = float(sample_rate) / float(hop)
+    out = NoteSequence()
+    for p in parts:
+        ns = merged_note_sequence(p.track, tuple(p.kept))
+        if int(p.shift) != 0:
+            ns = speed_note_sequence(ns, int(p.shift), int(p.step))
+        delay = float(int(p.delay_frames)) / fps
+        for n in ns.notes:
+            if int(p.delay_frames) != 0:
+                n = dataclasses.replace(n, start_time=n.start_time + delay, end_time=n.end_time + delay)
+            out.notes.append(n)
+        out.total_time = max(out.total_time, ns.total_time + delay)
+    return out
+
+
 def shift_range(track: StemTrack):
     """(lowest, highest) pitch shift in semitones that keeps every non-drum note of the track inside the codec's 0..127:
     (-min_pitch, 127 - max_pitch); (-127, 127) for a track without pitched notes.  A function of the track alone."""

@@ -31,6 +31,9 @@ scores the notes on the device against the tracks' note tables, rank 0 prints `e
 (means over the tracks of all ranks; training weights).  `+stem_device_labels=true` builds the targets on the device, one
 launch per track visit, instead of tokenising whole tracks on the host: the same targets, and `targets_prev` with them,
 so a `*WithPrev` model trains from stems (without the option it is refused); the run then ends with `label_launches K`.
+`+stem_cross=K` (0, at most 3; needs `+stem_device_labels=true`) gives every track visit the next K tracks of the
+rank's epoch order as partners, whose stems a row borrows with probability `+stem_cross_prob=` (0.5) each;
+`+stem_shift_per_row=true` draws the pitch shift per row and part instead of per visit.
 `+stem_pitch_shift=N` (0) plays every track visit at 2^(k/12) times its speed, k drawn from [-N, N] semitones:
 audio resampled on the device, labels transposed and rescaled in time; `+stem_native_rate=true` accepts stems at a quarter
 to four times the config's rate (Slakh's 44.1 kHz) and resamples them on the device when a track is uploaded.  Validation
@@ -147,7 +150,9 @@ def stem_options(cfg, with_prev=False):
     and `native_rate` when `+stem_pitch_shift=` (semitones, default 0) / `+stem_native_rate=` (default false) are given,
     validated like the other options: a ValueError names the key; likewise `device_labels` when
     `+stem_device_labels=` (default false) is given.  Only the label kernel builds `targets_prev`: without
-    `+stem_device_labels=true` a `*WithPrev` model is refused."""
+    `+stem_device_labels=true` a `*WithPrev` model is refused.  `+stem_cross=K` (partner tracks per visit, 0 to 3),
+    `+stem_cross_prob=` (0.5, in [0, 1]) and `+stem_shift_per_row=` (false) appear as `cross`, `cross_prob` and
+    `shift_per_row` when given; cross-track rows and per-row shifts need `+stem_device_labels=true`."""
     root = cfg.get("stem_root")
     if root is None or str(root).lower() in ("", "none", "null"):
         return None
@@ -184,6 +189,35 @@ def stem_options(cfg, with_prev=False):
         out["native_rate"] = native
     if labels is not None:
         out["device_labels"] = labels
+    cross, prob, per_row = cfg.get("stem_cross"), cfg.get("stem_cross_prob"), cfg.get("stem_shift_per_row")
+    if cross is not None:
+        if isinstance(cross, str) and cross.lstrip("+-").isdigit():
+            cross = int(cross)
+        if isinstance(cross, bool) or not isinstance(cross, int) or not 0 <= cross <= 3:
+            raise ValueError("stem_cross must be an int in [0, 3] (partner tracks per visit), got %r" % (cross,))
+        out["cross"] = cross
+    if prob is not None:
+        try:
+            if isinstance(prob, bool):
+                raise ValueError
+            prob = float(prob)
+        except (TypeError, ValueError):
+            raise ValueError("stem_cross_prob must be a number, got %r" % (prob,)) from None
+        if not 0.0 <= prob <= 1.0:
+            raise ValueError("stem_cross_prob must be in [0, 1], got %r" % (prob,))
+        out["cross_prob"] = prob
+    if per_row is not None:
+        if isinstance(per_row, str) and per_row.lower() in ("true", "false"):
+            per_row = per_row.lower() == "true"
+        if not isinstance(per_row, bool):
+            raise ValueError("stem_shift_per_row must be true or false, got %r" % (per_row,))
+        out["shift_per_row"] = per_row
+    if (out.get("cross") or out.get("shift_per_row")) and not labels:
+        raise ValueError("stem_cross and stem_shift_per_row need +stem_device_labels=true: the rows of a virtual track "
+                         "are labelled by the label kernel only (DESIGN 4q)")
+    if out.get("cross") and out.get("pitch_shift") and not out.get("shift_per_row"):
+        raise ValueError("stem_cross with stem_pitch_shift needs +stem_shift_per_row=true: every part has its own shift "
+                         "range")
     if not 0.0 <= out["keep"] <= 1.0:
         raise ValueError("stem_keep must be in [0, 1], got %r" % (out["keep"],))
     if not 0.0 <= out["gain_db"] < float("inf"):
@@ -200,11 +234,15 @@ class StemLoader:
     `tracks_per_step` per batch, every track one `StemMixBatcher.build` — `(mel [rows, mel_length, 512], targets
     [rows, event_length])`, and `targets_prev` behind them when the batcher builds it, already on the device.  The track order is `mrmt3.stems.epoch_order(seed, epoch)`, the ranks
     take disjoint shards of it (`rank_shard`), and the batcher's draws restart from (seed, epoch, rank) with every
-    epoch.  `shuffle=False` (validation: the deterministic full mix) keeps the folder's order.  Has what
+    epoch.  `shuffle=False` (validation: the deterministic full mix) keeps the folder's order.  `partners=K`
+    hands every visit the next K tracks of this rank's epoch order as partner tracks, cyclic and without the visited one —
+    a function of (seed, epoch, rank) like the order itself; partners are dropped from the end while the stems of all
+    tracks exceed the 64 sources of a row.  Has what
     `loader_batches` asks of a loader and of a sampler: `len()`, iteration, `set_epoch`."""
 
-    def __init__(self, tracks, batcher, tracks_per_step, seed, rank=0, world=1, shuffle=True):
+    def __init__(self, tracks, batcher, tracks_per_step, seed, rank=0, world=1, shuffle=True, partners=0):
         from mrmt3 import stems
+        self.n_partners = int(partners)
         self.tracks, self.batcher, self.per = tracks, batcher, max(1, int(tracks_per_step))
         self.seed, self.rank, self.world, self.shuffle, self.epoch = int(seed), rank, world, shuffle, 0
         self._stems = stems
@@ -222,11 +260,28 @@ class StemLoader:
     def __len__(self):
         return -(-len(self.shard()) // self.per)
 
+    def partners_of(self, shard, j):
+        """The partner tracks of the visit at place j of the shard."""
+        ids = []
+        for k in range(1, len(shard)):
+            t = shard[(j + k) % len(shard)]
+            if t != shard[j] and t not in ids and len(ids) < self.n_partners:
+                ids.append(t)
+        out = [self.tracks[t] for t in ids]
+        while out and len(self.tracks[shard[j]].audio) + sum(len(t.audio) for t in out) > 64:
+            out.pop()
+        return out
+
     def __iter__(self):
         import random
         shard = self.shard()
         self.batcher.rng = random.Random((self.seed * 1000003 + self.epoch) * 4099 + self.rank)
         for i in range(0, len(shard), self.per):
+            if self.n_partners:
+                built = [self.batcher.build(self.tracks[shard[j]], partners=self.partners_of(shard, j))
+                         for j in range(i, min(i + self.per, len(shard)))]
+                yield tuple(torch.cat([b[k] for b in built]) for k in range(len(built[0])))
+                continue
             built = [self.batcher.build(self.tracks[t]) for t in shard[i:i + self.per]]
             yield tuple(torch.cat([b[k] for b in built]) for k in range(len(built[0])))
 
@@ -245,8 +300,10 @@ def stem_loaders(cfg, opts, device, world=1, rank=0, with_prev=False):
         geom.update(device_labels=True, with_prev=with_prev)
     train = StemLoader(stems.load_stem_folder(opts["root"], **native),
                        StemMixBatcher(device, keep_prob=opts["keep"], min_stems=opts["min_stems"], gain_db=opts["gain_db"],
-                                      pitch_shift=opts.get("pitch_shift", 0), **geom),
-                       per, cfg.seed, rank, world)
+                                      pitch_shift=opts.get("pitch_shift", 0), cross_track=bool(opts.get("cross")),
+                                      cross_prob=opts.get("cross_prob", 0.5), per_row_shift=bool(opts.get("shift_per_row")),
+                                      **geom),
+                       per, cfg.seed, rank, world, partners=opts.get("cross", 0))
     val = None
     if opts["val_root"] is not None:
         val = StemLoader(stems.load_stem_folder(opts["val_root"], **native), StemMixBatcher(device, is_deterministic=True, **geom),
